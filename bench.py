@@ -33,12 +33,6 @@ sys.path.insert(0, ROOT)
 np = torch = _lib = synth = EnginePeer = Exchange = shard_range = Engine = plan_parameters = None
 
 
-# The ROCm runtime spreads a process's streams over four hardware queues unless told otherwise; with torch's and RCCL's streams
-# beside the engine's three, two of the engine's can share one and then run in order (seen in the command line: DESIGN.md
-# section 4, "Hardware queues").  Read by the runtime at the first HIP call, so it is set before torch is imported.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
-
 def _imports():
     global np, torch, _lib, synth, EnginePeer, Exchange, shard_range, Engine, plan_parameters
     import numpy as np_
@@ -114,7 +108,7 @@ def run_step(e, xch, batches, ordinals, out_buf, hints, pass_ms=None):
     for b in batches:
         e.get_covariatedata(b)
     xch.histograms_done()
-    xch.train_and_share()
+    dq = xch.train_and_share()
     mark(wait=True)
     for b in batches:
         e.recalibrate(b, out_buf.data_ptr())
@@ -122,7 +116,57 @@ def run_step(e, xch, batches, ordinals, out_buf, hints, pass_ms=None):
     mark()
     if pass_ms is not None:
         pass_ms[:] = [round((marks[i + 1] - marks[i]) * 1e3, 1) for i in range(4)]
-    return dict(sampled_inserted=sampled, trusted_inserted=trusted, fpr=fpr, fpr_too_high=too_high)
+    return dict(sampled_inserted=sampled, trusted_inserted=trusted, fpr=fpr, fpr_too_high=too_high, thresholds=thr, dq=dq)
+
+
+DUMP_SAMPLE_READS = 1 << 16      # reads whose recalibrated qualities --dump-outputs writes (150 bp: 39 MB in float32)
+DUMP_SAMPLE_SEED = 2718
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, e, info, batches, first_read, out_buf):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy in float32 / float64.
+
+    The delta-Q model, the thresholds and the counts come from that step's return value, the covariate histograms from
+    the engine as the step left them.  The recalibrated qualities are those of a fixed, seeded sample of whole reads:
+    the step writes every batch into the same output buffer, so pass 4 of the step is run again, untimed, batch by
+    batch with the step's model, and the sampled reads are kept (global read indices in recal_sample_reads.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_reads = sum(b.n_reads for b in batches)
+    n_sample = min(DUMP_SAMPLE_READS, n_reads)
+    # one read drawn from each of n_sample equal strata: sorted, distinct, and the same for the same arguments
+    rng = np.random.RandomState(DUMP_SAMPLE_SEED)
+    edges = np.arange(n_sample + 1, dtype=np.int64) * n_reads // n_sample
+    picks = edges[:-1] + (rng.random_sample(n_sample) * (edges[1:] - edges[:-1])).astype(np.int64)
+    recal = np.empty((n_sample, READ_LEN), dtype=np.float32)
+    start, done = 0, 0
+    for bt in batches:
+        lo, hi = np.searchsorted(picks, [start, start + bt.n_reads])
+        if hi > lo:
+            e.recalibrate(bt, out_buf.data_ptr())
+            e.sync()
+            rows = torch.from_numpy(picks[lo:hi] - start).to(out_buf.device)
+            recal[lo:hi] = out_buf[:bt.n_reads * READ_LEN].view(bt.n_reads, READ_LEN)[rows].cpu().numpy()
+            done += hi - lo
+        start += bt.n_reads
+    assert done == n_sample
+    cov = e.covariates()
+    st = e.stats()
+    arrays = {"recal_qual_sample": recal, "recal_sample_reads": (first_read + picks).astype(np.float64),
+              "thresholds": np.asarray(info["thresholds"], dtype=np.float64),
+              "counts": np.array([info["sampled_inserted"], info["trusted_inserted"], st["corrected_reads"], st["correction_queries"]],
+                                 dtype=np.float64),
+              "fpr": np.array([info["fpr"]], dtype=np.float64)}
+    for k in ("meanq", "rg", "q", "cycle", "dinuc"):
+        arrays["dq_" + k] = np.asarray(info["dq"][k], dtype=np.float64)
+    for k in ("rg", "q", "cycle", "dinuc"):
+        arrays["covariates_" + k] = cov[k].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("[dump] %d arrays, %.1f MB, in %s (counts: sampled_inserted, trusted_inserted, corrected_reads, correction_queries)"
+        % (len(arrays), total / 1e6, out_dir))
 
 
 def exchange_one_rank(e, xch, steps, device):
@@ -532,10 +576,18 @@ def main():
                          "resident reads (--ab-rounds times each, in turn): wall time of an overlapped step and of its four passes per "
                          "setting; a knob a setting does not name has its default; prints one JSON object and exits")
     ap.add_argument("--ab-rounds", type=int, default=2)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, under 64 MB: "
+                         "the delta-Q model, thresholds, counts, covariate histograms and the recalibrated qualities of a fixed, "
+                         "seeded sample of reads); one rank only")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus != 1 or args.emulate_shard or args.ab_set is not None or args.ab_tune):
+        raise SystemExit("--dump-outputs goes with a plain one-rank run (--gpus 1, no --emulate-shard / --ab-set / --ab-tune)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has not imported torch or the
         # engine library and never touches a GPU; the ranks are fresh CHILD processes (no exec of this one).
@@ -719,6 +771,8 @@ def main():
 
     prof = e.profile()
     stats = e.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e, info, batches, a, out_buf)
     # Untimed, same process, same resident reads: one more step with every kernel in order on one stream.  In the timed
     # region passes 1-3 keep two streams busy, so a kernel's event duration there includes time it shared the chip; the
     # roofline line of the dominant kernel is quoted on its EXCLUSIVE duration from this step (both are printed).

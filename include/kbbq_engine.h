@@ -158,8 +158,8 @@ int kbbq_engine_sync(kbbq_engine *e);
  * "scan_blocks" / "walk_blocks" / "infer_blocks" = workgroups per CU of the kernels that stay resident for a whole batch while
  * the other stream has work (0 = as many as fit ... 16, 17 = the engine's own choice; KBBQ_SCAN_BLOCKS, KBBQ_WALK_BLOCKS,
  * KBBQ_INFER_BLOCKS).  KBBQ_EINVAL for an unknown name or a value out of range.
- * The engine runs kernels of neighbouring batches on two streams of its own: a host process with many streams should set
- * GPU_MAX_HW_QUEUES >= 8 in its environment before its first HIP call, or the two may share a hardware queue. */
+ * The engine runs kernels of neighbouring batches on two streams of its own: in a host process with more streams than the
+ * runtime's hardware queues (GPU_MAX_HW_QUEUES) the two may share a queue and then run in order. */
 int kbbq_engine_tune(kbbq_engine *e, const char *name, uint64_t value);
 /* hipStream_t of the engine, as void*. */
 void *kbbq_engine_stream(kbbq_engine *e);

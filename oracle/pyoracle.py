@@ -119,15 +119,13 @@ def lib():
 
 
 def ref_lib():
-    """oracle/_ref/libref.so (stand-alone parts of the reference) or None."""
+    """oracle/_ref/libref.so (stand-alone parts of the reference, built by `make -C oracle ref` where the reference tree is
+    present) or None."""
     global _REF
     if _REF is None:
         so = os.path.join(_HERE, "_ref", "libref.so")
         if not os.path.exists(so):
-            if os.path.isdir("/root/reference/include/minionrng"):
-                subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
-            if not os.path.exists(so):
-                return None
+            return None
         R = ctypes.CDLL(so)
         R.ref_rng_outputs.argtypes = [c_u32, c_u64, u64p]
         R.ref_bernoulli_count.restype = c_u64

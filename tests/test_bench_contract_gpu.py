@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import common
@@ -87,3 +88,30 @@ def test_bench_exchange_in_the_library_gives_the_same_answer():
         assert a["result"][key] == b["result"][key], key
     x = b["exchange_one_rank"]
     assert x["exchange_by"].startswith("library") and x["exchange_ms_per_step"]["filter0"] > 0 and x["exchange_ms_per_step"]["filter1"] > 0
+
+
+def test_bench_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as .npy files in float32 / float64 under 64 MB, the same from run to
+    run for the same workload whatever the number of steps, and consistent with the line's own counts."""
+    common_args = ["--gpus", "1", "--genome-len", "30000000", "--no-cpu-baseline", "--no-pcie", "--no-exclusive-step"]
+    lines, dumps = [], []
+    for i, steps in enumerate((["--steps", "1", "--warmup", "0"], ["--steps", "3", "--warmup", "1"])):
+        d = tmp_path / ("run%d" % i)
+        out = subprocess.run([sys.executable, "bench.py"] + common_args + steps + ["--dump-outputs", str(d)], cwd=common.ROOT,
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    assert [ln["steps"] for ln in lines] == [1, 3]
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"recal_qual_sample", "recal_sample_reads", "dq_cycle", "thresholds", "counts"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    r = lines[0]["result"]
+    assert list(a["counts"][:2]) == [r["sampled_inserted"], r["trusted_inserted"]] and a["fpr"][0] == r["fpr"]
+    reads = a["recal_sample_reads"]
+    assert len(reads) == 1 << 16 and np.all(np.diff(reads) > 0) and reads[-1] < lines[0]["config"]["reads"]
+    q = a["recal_qual_sample"]
+    assert q.shape == (len(reads), 150) and q.any() and np.array_equal(q, np.round(q))

@@ -312,3 +312,14 @@ def test_bench_refuses_a_rank_count_it_was_not_launched_with():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, env=env, timeout=120)
     assert out.returncode != 0 and "WORLD_SIZE=3" in out.stderr and not out.stdout.strip()
+
+
+def test_bench_refuses_arguments_it_cannot_honour():
+    """No timed step, or a dump of outputs from a run that is not a plain one-rank run: refused before any GPU use."""
+    import subprocess
+    import sys
+    for args, text in ((["--steps", "0"], "--steps"), (["--warmup", "-1"], "--warmup"),
+                       (["--gpus", "2", "--dump-outputs", "out"], "--dump-outputs"),
+                       (["--emulate-shard", "0/2", "--dump-outputs", "out"], "--dump-outputs")):
+        out = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=120)
+        assert out.returncode != 0 and text in out.stderr and not out.stdout.strip(), args

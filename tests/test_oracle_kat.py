@@ -4,11 +4,13 @@ Two kinds of evidence:
   * the known-answer values SURVEY.md section 8c records from the reference itself;
   * oracle/_ref -- the reference's own minionrng and bloom_filter.hpp, compiled in place (they are
     the only parts of the path that build without htslib) -- plus real libstdc++-11
-    std::shuffle / uniform_int_distribution / bernoulli_distribution.
+    std::shuffle / uniform_int_distribution / bernoulli_distribution.  Its answers are stored in
+    tests/golden/ref_kat.npz, so these checks run where the reference tree is absent too.
 The read-level functions (infer_read_errors, get_errors, ...) have no reference fixture:
 "parity unpinned" beyond these anchors.
 """
 import ctypes
+import importlib.util
 import os
 
 import numpy as np
@@ -16,8 +18,12 @@ import pytest
 
 from oracle import pyoracle
 
+_spec = importlib.util.spec_from_file_location(
+    "make_ref_kat", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_ref_kat.py"))
+KAT = importlib.util.module_from_spec(_spec)      # tests/golden/make_ref_kat.py: the inputs and the stored known answers
+_spec.loader.exec_module(KAT)
+
 u64, u32 = ctypes.c_uint64, ctypes.c_uint32
-SEED = pyoracle.DEFAULT_BLOOM_SEED
 
 
 @pytest.fixture(scope="module")
@@ -31,6 +37,11 @@ def R():
     if r is None:
         pytest.skip("oracle/_ref not built (reference tree absent)")
     return r
+
+
+@pytest.fixture(scope="module")
+def K():
+    return KAT.load()
 
 
 @pytest.fixture(scope="module")
@@ -155,62 +166,65 @@ def test_base_codes(L):
         assert L.ko_base_code(ch[0]) == code
 
 
-# ---------------------------------------------------------------- against oracle/_ref
+# ---------------------------------------------------------------- against the reference's own code
+# tests/golden/ref_kat.npz holds what oracle/_ref/libref.so computes on these inputs (tests/golden/make_ref_kat.py): the
+# oracle is compared with it everywhere, and the file with the library itself wherever oracle/_ref is built.
 
-def test_rng_stream_equals_minion(L, R):
-    for seed in (0, 1, 777, 0xFFFFFFFF, 3061464579):
-        a, b = (u64 * 2000)(), (u64 * 2000)()
-        L.ko_rng_outputs(seed, 2000, a)
-        R.ref_rng_outputs(seed, 2000, b)
-        assert list(a) == list(b)
-
-
-def test_bernoulli_equals_libstdcxx_draw_by_draw(L, R):
-    n = 200000
-    for seed, p in ((777, 0.35), (1, 7.0 / 30.0), (5, 0.05), (9, 0.999999), (3, 1e-9)):
-        ref = np.zeros(n, dtype=np.uint8)
-        R.ref_bernoulli_bits(seed, p, n, ref.ctypes.data_as(pyoracle.u8p))
-        outs = (u64 * n)()
-        L.ko_rng_outputs(seed, n, outs)
-        mine = np.array([L.ko_bernoulli_one(u, p) for u in list(outs)[:20000]], dtype=np.uint8)
-        assert np.array_equal(mine, ref[:20000])
-        assert L.ko_bernoulli_count(seed, p, n) == int(ref.sum())
+def test_ref_kat_fixture_equals_the_reference(R):
+    want = KAT.collect(R)
+    got = KAT.load()
+    assert sorted(want) == sorted(got)
+    for key in want:
+        assert want[key].dtype == got[key].dtype and np.array_equal(want[key], got[key]), key
 
 
-def test_optimal_parameters_equal_reference(L, R):
-    rng = np.random.RandomState(4)
-    for _ in range(40):
-        n = int(rng.randint(1000, 2 ** 31 - 1)) * int(rng.choice([1, 7, 100]))
-        p = float(rng.choice([0.01, 0.0005, 0.05, 0.2, 1e-6]))
-        a, b, c, d = u32(), u64(), u32(), u64()
-        L.ko_optimal_parameters(n, p, ctypes.byref(a), ctypes.byref(b))
-        assert R.ref_optimal_parameters(n, p, SEED, ctypes.byref(c), ctypes.byref(d)) == 0
-        assert (a.value, b.value) == (c.value, d.value)
+def test_rng_stream_equals_minion(L, K):
+    for seed, ref in zip(KAT.RNG_SEEDS, K["rng_outputs"]):
+        a = (u64 * KAT.RNG_N)()
+        L.ko_rng_outputs(seed, KAT.RNG_N, a)
+        assert list(a) == [int(x) for x in ref]
 
 
-def test_salts_equal_reference(R):
-    for approx, fpr in ((700000, 0.01), (700000, 0.0005), (10 ** 9, 0.05), (5000, 0.2)):
+def test_bernoulli_equals_libstdcxx_draw_by_draw(L, K):
+    n, m = KAT.BERNOULLI_N, KAT.BERNOULLI_DRAWS
+    for (seed, p), bits, count in zip(KAT.BERNOULLI, K["bernoulli_bits"], K["bernoulli_counts"]):
+        ref = np.unpackbits(bits, bitorder="little")[:m]
+        outs = (u64 * m)()
+        L.ko_rng_outputs(seed, m, outs)
+        mine = np.array([L.ko_bernoulli_one(u, p) for u in list(outs)], dtype=np.uint8)
+        assert np.array_equal(mine, ref)
+        assert L.ko_bernoulli_count(seed, p, n) == int(count)
+
+
+def test_optimal_parameters_equal_reference(L, K):
+    ns, ps = KAT.optimal_parameter_inputs()
+    for n, p, nh, bits in zip(ns, ps, K["optimal_nhash"], K["optimal_bits"]):
+        a, b = u32(), u64()
+        L.ko_optimal_parameters(int(n), float(p), ctypes.byref(a), ctypes.byref(b))
+        assert (a.value, b.value) == (int(nh), int(bits))
+
+
+def test_salts_equal_reference(K):
+    for i, (approx, fpr) in enumerate(KAT.SALT_CASES):
         o = pyoracle.Oracle(32, 0.35, 1, approx, fpr, fpr)
         info = o.filter_info(0)
-        out, rs = (u32 * 128)(), u64()
-        n = R.ref_salts(info["nsalt"], SEED, out, ctypes.byref(rs))
-        assert n == info["nsalt"] and rs.value == info["random_seed"]
-        assert list(out[:n]) == [int(x) for x in info["salts"]]
+        n = int(K["salt_counts"][i])
+        assert info["nsalt"] == int(K["salt_nsalt_in"][i]) == n and int(K["salt_random_seeds"][i]) == info["random_seed"]
+        assert [int(x) for x in K["salts"][i][:n]] == [int(x) for x in info["salts"]]
 
 
-def test_hash_ap_equals_reference(L, R):
-    rng = np.random.RandomState(7)
-    for _ in range(2000):
-        key = int(rng.randint(0, 2 ** 62)) * 4 + int(rng.randint(0, 4))
-        salt = int(rng.randint(0, 2 ** 32))
-        assert L.ko_hash_ap8(key, salt) == R.ref_hash_ap(key.to_bytes(8, "little"), 8, salt)
+def test_hash_ap_equals_reference(L, K):
+    keys, salts = KAT.hash_ap_inputs()
+    for key, salt, want in zip(keys, salts, K["hash_ap"]):
+        assert L.ko_hash_ap8(int(key), int(salt)) == int(want)
 
 
-def test_pattern_table_equals_real_libstdcxx(filters, R):
-    for which, nsalt in ((0, 7), (1, 11)):
-        ref = np.zeros(65536 * 8, dtype=np.uint64)
-        R.ref_pattern_table(3061464579, nsalt, ref.ctypes.data_as(pyoracle.u64p))
-        assert np.array_equal(filters.filter_patterns(which), ref)
+def test_pattern_table_equals_real_libstdcxx(filters, K):
+    # (the fixture's tables come from a salt seed of 3061464579: the random seed of both filters here, test_blocked_sizes_and_seed)
+    assert filters.filter_info(0)["random_seed"] & 0xFFFFFFFF == KAT.PATTERN_SEED
+    for which, nsalt, digest in zip((0, 1), KAT.PATTERN_NSALT, K["pattern_table_sha256"]):
+        assert filters.filter_info(which)["nsalt"] == nsalt
+        assert np.array_equal(KAT.table_digest(filters.filter_patterns(which)), digest)
 
 
 def test_native_build_of_the_oracle_equals_the_portable_one(tmp_path):

@@ -444,7 +444,7 @@ print("rccl one-rank exchange ok")
     assert out.returncode == 0 and "rccl one-rank exchange ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
 
 
-def test_exchange_steps_over_rccl_with_two_ranks():
+def test_exchange_steps_over_rccl_with_two_ranks(tmp_path):
     """Two ranks over RCCL, one GPU each (runs where two devices are visible; the driver's one-GPU box skips it): each rank
     works through its shard of the reads, the filters are OR-ed through the pipelined slab loop (several slabs and a ragged
     last one: slab_words = 2^14), histograms summed, delta-Q broadcast -- filters, inserted counts, covariates and the
@@ -497,8 +497,7 @@ dist.barrier()
 dist.destroy_process_group()
 print("rccl two-rank exchange ok", rank)
 '''
-    script = os.path.join(common.ROOT, "gpurun_out", "rccl_two_ranks.py")
-    os.makedirs(os.path.dirname(script), exist_ok=True)
+    script = str(tmp_path / "rccl_two_ranks.py")
     with open(script, "w") as f:
         f.write(code)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
