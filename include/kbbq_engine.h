@@ -305,10 +305,19 @@ typedef struct kbbq_dq {
 int kbbq_train(kbbq_engine *e);
 int kbbq_dq_get(kbbq_engine *e, kbbq_dq *out);      /* caller-allocated arrays */
 int kbbq_set_dq(kbbq_engine *e, const kbbq_dq *dq); /* e.g. tables computed on another rank */
+/* The ranges kbbq_set_dq accepts: the device keeps the cycle and dinucleotide deltas as int8 and
+ * meanq + rgdq + qdq as int16, and the apply kernel adds a cycle delta to the latter in int16.  A table with any
+ * value outside them is refused with KBBQ_EINVAL (the message names the table) and the engine keeps the tables it
+ * had.  Trained tables lie in [-93, 93] and always fit. */
+#define KBBQ_DQ_DELTA_MIN (-128)     /* cycledq, dinucdq */
+#define KBBQ_DQ_DELTA_MAX 127
+#define KBBQ_DQ_BASE_MIN (-32640)    /* meanq[rg] + rgdq[rg] + qdq[rg][q], summed exactly: INT16_MIN - KBBQ_DQ_DELTA_MIN */
+#define KBBQ_DQ_BASE_MAX 32640       /* INT16_MAX - KBBQ_DQ_DELTA_MAX */
 
 /* ---- pass 4: CReadData::recalibrate (readutils.cc:572-595) ---------------- */
 
-/* qual_out: n_bases bytes, device or host like the batch.  A device output is queued on the engine's stream
+/* qual_out: n_bases bytes, device or host like the batch; neither it nor the batch's qual needs any particular
+ * alignment.  A device output is queued on the engine's stream
  * (complete after kbbq_engine_sync, or order your own work behind kbbq_engine_stream); a host output is complete
  * when the call returns. */
 int kbbq_recalibrate_batch(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qual_out);

@@ -2216,6 +2216,22 @@ int kbbq_set_dq(kbbq_engine *e, const kbbq_dq *in) {
     if (!e || !in || !in->meanq || !in->rgdq || !in->qdq || !in->cycledq || !in->dinucdq) return fail(KBBQ_EINVAL, "null argument");
     if (in->n_rg != (uint64_t)e->p.n_rg || in->n_cycle != (uint64_t)e->p.max_read_len)
         return fail(KBBQ_EINVAL, "delta-Q tables must be [%d rg][%d cycles]", e->p.n_rg, e->p.max_read_len);
+    // The device holds the cycle and dinucleotide deltas as int8 and meanq + rgdq + qdq as int16, and the apply
+    // kernel's LDS tables add a cycle delta to the latter in int16 (upload_dq, k_recalibrate): refuse what they
+    // cannot hold exactly instead of wrapping it.  The engine keeps its tables on a refusal.
+    const uint64_t nq = in->n_rg * kNQ, nc = nq * 2 * in->n_cycle, nd = nq * 16;
+    for (uint64_t i = 0; i < nc; ++i)
+        if (in->cycledq[i] < KBBQ_DQ_DELTA_MIN || in->cycledq[i] > KBBQ_DQ_DELTA_MAX)
+            return fail(KBBQ_EINVAL, "cycledq[%llu] = %d is outside [%d, %d]", (unsigned long long)i, in->cycledq[i], KBBQ_DQ_DELTA_MIN, KBBQ_DQ_DELTA_MAX);
+    for (uint64_t i = 0; i < nd; ++i)
+        if (in->dinucdq[i] < KBBQ_DQ_DELTA_MIN || in->dinucdq[i] > KBBQ_DQ_DELTA_MAX)
+            return fail(KBBQ_EINVAL, "dinucdq[%llu] = %d is outside [%d, %d]", (unsigned long long)i, in->dinucdq[i], KBBQ_DQ_DELTA_MIN, KBBQ_DQ_DELTA_MAX);
+    for (uint64_t i = 0; i < nq; ++i) {
+        const int64_t base = (int64_t)in->meanq[i / kNQ] + in->rgdq[i / kNQ] + in->qdq[i];
+        if (base < KBBQ_DQ_BASE_MIN || base > KBBQ_DQ_BASE_MAX)
+            return fail(KBBQ_EINVAL, "meanq + rgdq + qdq of read group %llu, quality %d = %lld is outside [%d, %d]",
+                        (unsigned long long)(i / kNQ), (int)(i % kNQ), (long long)base, KBBQ_DQ_BASE_MIN, KBBQ_DQ_BASE_MAX);
+    }
     DqTables &d = e->dq;
     d.n_rg = in->n_rg;
     d.n_cycle = in->n_cycle;
