@@ -69,21 +69,32 @@ int kbbq_bgzf_kernel_ms(kbbq_bgzf *z, double *format_ms, double *deflate_ms, dou
  * file's bytes in chunks; the device inflates every BGZF block (one wavefront each), finds the lines, checks that the
  * records have kseq's four-line shape, and packs them into the engine's read layout.  The same chunks fed again in pass 4
  * give the output: the records' text re-assembled on the device around the new qualities and deflated by a kbbq_bgzf.
+ * Three containers are read, decided by the first bytes after create or rewind: BGZF (every block inflated by one wavefront);
+ * any other gzip stream -- one member or several, as gzip and pigz write them (the blocks found and decoded speculatively
+ * in parallel, csrc/gzip_inflate.h; every member's CRC-32 and ISIZE checked, a mismatch is KBBQ_EIO); and uncompressed
+ * text (a leading '@', kbbq_fastq_reader_take_text).  What htslib's bgzf_read / kseq_read take for the reference (htsiter.cc:49-60).
  * Shapes this path does not take -- multi-line records, FASTA, empty reads, carriage returns, "RG:" fields in read names,
- * a file that is not BGZF -- are reported (flags bit 0) and left to the caller's serial reader, which stays the definition. */
+ * bytes behind a gzip member that are not another member, a gzip stream that ends inside a member -- are reported
+ * (flags bit 0) and left to the caller's serial reader, which stays the definition. */
 typedef struct kbbq_fastq_reader kbbq_fastq_reader;
 typedef struct kbbq_fastq_chunk {
-    uint64_t consumed;      /* bytes of the input that were taken: whole BGZF blocks (feed the rest again with the next chunk) */
+    uint64_t consumed;      /* bytes of the input that were taken: whole BGZF blocks (feed the rest again with the next chunk);
+                             * a gzip or text stream: all of them (the reader keeps what it cannot decode yet) */
     uint64_t n_records;     /* complete records of this chunk (a record cut by the chunk's end is carried into the next one) */
     uint64_t n_bases;
     uint32_t longest, shortest;
     uint32_t flags;         /* bit 0: a shape the device path does not take; bit 1: a read name shorter than 2 characters
                              * (readutils.cc:90 throws); bit 2: the input ended inside a record */
-    uint32_t n_blocks;      /* BGZF blocks inflated */
+    uint32_t n_blocks;      /* BGZF blocks inflated; a gzip stream: segments accepted (decoded in parallel) */
     uint64_t text_bytes;    /* inflated bytes of this chunk */
+    uint32_t n_redecoded;   /* a gzip stream: segments decoded again because the block the finder offered was not where the
+                             * segment in front of them ended (a false start: it costs time, never bytes) */
 } kbbq_fastq_chunk;
 int kbbq_fastq_reader_create(int32_t device, kbbq_fastq_reader **out);
 void kbbq_fastq_reader_destroy(kbbq_fastq_reader *r);
+/* Uncompressed FASTQ (a leading '@') is the text itself; with on == 0 -- the default, the reader's contract before it read
+ * anything but BGZF -- it is reported (flags bit 0) instead.  Before the first chunk of a stream. */
+int kbbq_fastq_reader_take_text(kbbq_fastq_reader *r, int32_t on);
 /* Restart at the beginning of a file (pass 4 feeds the same chunks again). */
 int kbbq_fastq_reader_rewind(kbbq_fastq_reader *r);
 /* Keep what the first scan inflates: with on != 0 (before the scan's first chunk) the text and record index of every chunk
@@ -103,8 +114,9 @@ int kbbq_fastq_reader_kept(kbbq_fastq_reader *r, uint64_t *n_chunks, uint64_t *n
 int kbbq_fastq_reader_select(kbbq_fastq_reader *r, uint64_t i, kbbq_fastq_chunk *info);
 int kbbq_fastq_reader_attach(kbbq_fastq_reader *r, const kbbq_reads *batch);
 /* The next bytes of the file (host memory; page-locked memory is copied by DMA).  last != 0: nothing follows.
- * Every block's CRC-32 and ISIZE are checked as bgzf_read checks them; a block that does not inflate to them is
- * KBBQ_EIO ("CRC32 checksum mismatch" / "does not inflate"). */
+ * Every block's (gzip: member's) CRC-32 and ISIZE are checked as bgzf_read checks them; a block that does not inflate to
+ * them is KBBQ_EIO ("CRC32 checksum mismatch" / "does not inflate").  A gzip or text stream may be fed in pieces of any
+ * size; a chunk call may then give no records (its text waits for the next one). */
 int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, int32_t last, kbbq_fastq_chunk *info);
 /* Optional: start copying a piece of the file to the device AHEAD of the kbbq_fastq_reader_chunk call that will take it --
  * from the caller's I/O thread, the moment the piece has been read (page-locked memory) -- so that the host link moves piece
@@ -120,7 +132,12 @@ int kbbq_reads_upload_text(kbbq_engine *e, const kbbq_reads *host, const uint8_t
  * BGZF blocks at the front of file_bytes[0, n_bytes) whose inflated bytes fit in `capacity` are inflated on the device,
  * checked (CRC-32, ISIZE) and copied to host_out (page-locked memory makes the copy DMA).  *consumed: bytes of the input
  * taken (feed the rest again in front of the next piece), *produced: bytes written.  What bgzf_read does under
- * sam_read1 / kseq_read (htsiter.hh:64-66,101-126), at the device's rate instead of a thread pool's. */
+ * sam_read1 / kseq_read (htsiter.hh:64-66,101-126), at the device's rate instead of a thread pool's.
+ * A plain gzip stream (the container is decided by the first call's bytes, as for kbbq_fastq_reader_chunk) is decoded
+ * statefully: *consumed = n_bytes (the reader keeps what it cannot decode yet), *produced <= capacity bytes of the inflated
+ * stream in order (what does not fit is held back on the device and comes first in the next call); n_bytes == 0 means
+ * the end of the input -- call it until *produced is 0.  Bytes behind a member that are not another member end the stream,
+ * as gzread takes them; a stream that ends inside a member is KBBQ_EIO.  Uncompressed text: copied, *consumed = *produced. */
 int kbbq_fastq_reader_inflate(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint8_t *host_out, uint64_t capacity,
                               uint64_t *consumed, uint64_t *produced);
 /* The current chunk's records as a device batch (arrays owned by the library: kbbq_reads_free): bases, N mask, qualities,
@@ -130,8 +147,11 @@ int kbbq_fastq_reader_batch(kbbq_fastq_reader *r, kbbq_reads *dev);
  * d_qual (device: the batch's new qualities, in the batch's base order) on the quality lines, submitted to writer z
  * (kbbq_bgzf_collect returns the blocks).  after_stream as in kbbq_bgzf_submit. */
 int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, void *after_stream);
-/* Milliseconds the device spent inflating / indexing + packing since creation. */
+/* Milliseconds the device spent inflating / indexing + packing since creation (a gzip stream's stages are in inflate_ms). */
 int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms);
+/* A gzip stream's stages since creation, in milliseconds of wall time (each stage waits for its kernels): block finding,
+ * speculative decode with the re-decodes of false starts, the window chain, resolve + CRC-32. */
+int kbbq_fastq_reader_gzip_ms(kbbq_fastq_reader *r, double *find_ms, double *decode_ms, double *chain_ms, double *resolve_ms);
 
 /* ---- the input side: a BAM file read on the device (round 4) ----------------------------------------------------------
  * What it replaces: sam_read1 (BamFile::next, htsiter.cc:5), the BAM constructor of CReadData (readutils.cc:13-61, with

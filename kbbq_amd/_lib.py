@@ -69,7 +69,8 @@ class SynthParams(ctypes.Structure):
 
 class FastqChunk(ctypes.Structure):
     _fields_ = [("consumed", c_u64), ("n_records", c_u64), ("n_bases", c_u64), ("longest", ctypes.c_uint32),
-                ("shortest", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32), ("text_bytes", c_u64)]
+                ("shortest", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32), ("text_bytes", c_u64),
+                ("n_redecoded", ctypes.c_uint32)]
 
 
 class ProfileEntry(ctypes.Structure):
@@ -167,6 +168,8 @@ SYMBOLS = {
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "kbbq_fastq_reader_attach": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
     "kbbq_fastq_reader_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "kbbq_fastq_reader_gzip_ms": (ctypes.c_int, [c_vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
+    "kbbq_fastq_reader_take_text": (ctypes.c_int, [c_vp, ctypes.c_int32]),
     "kbbq_reads_clone": (ctypes.c_int, [ctypes.POINTER(Reads), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Reads)]),
     "kbbq_engine_dims": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "kbbq_group_rccl_unique_id": (ctypes.c_int, [ctypes.c_void_p]),

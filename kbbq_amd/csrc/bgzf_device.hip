@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -13,8 +14,10 @@
 #include "bgzf_device.h"
 #include "bgzf_inflate.h"
 #include "bam_device.h"
+#include "gzip_inflate.h"
 
 using namespace kbbq::dfl;
+using namespace kbbq::gz;
 
 #define fail kbbq_fail
 #define HIP_TRY(expr)                                                                                  \
@@ -438,6 +441,24 @@ struct kbbq_fastq_reader {
     bool keeping = false;
     int64_t selected = -1;      // the kept chunk that is the current one (pass 4), or -1: the live buffers
     uint64_t kept_bytes = 0;
+    // The container, decided by the first bytes after create / rewind: BGZF blocks, another gzip stream (gzip_inflate.h),
+    // or the text itself.  The state of a gzip stream between chunk calls:
+    enum { C_UNKNOWN, C_BGZF, C_GZIP, C_TEXT } container = C_UNKNOWN;
+    enum { GZ_HEADER, GZ_DEFLATE, GZ_TRAILER } gz_phase = GZ_HEADER;
+    std::vector<uint8_t> gz_pending;        // compressed bytes not decoded yet (from the byte that holds the next block)
+    uint32_t gz_bit0 = 0;                   // bit of gz_pending[0] where the next block starts (GZ_DEFLATE)
+    uint32_t gz_win = 0;                    // bytes of the member's output in the window (at most GZ_WINDOW)
+    uint32_t gz_crc = 0;                    // the member's CRC-32 so far and its length mod 2^32
+    uint32_t gz_isize = 0;
+    bool take_text = false;                 // kbbq_fastq_reader_take_text
+    bool gz_failed = false;                 // kbbq_fastq_reader_inflate: the stream cannot go on (reported once its bytes are out)
+    bool gz_members = false;                // a member header was met (bytes behind a trailer that are not one: flags bit 0)
+    Buf gz_in, gz_out, gz_win_buf, gz_slots, gz_scratch, gz_segs, gz_lo, gz_cand, gz_placed, gz_crcs;
+    Buf gz_hold;                            // kbbq_fastq_reader_inflate: inflated bytes that did not fit in the caller's buffer
+    uint64_t gz_hold_bytes = 0, gz_hold_off = 0;
+    uint64_t gz_redecoded = 0;              // segments decoded again after a false start, this chunk call
+    uint64_t gz_lanes = 0;                  // decoding lanes the device keeps resident (the segment count's ceiling)
+    double ms_gz_find = 0, ms_gz_decode = 0, ms_gz_chain = 0, ms_gz_resolve = 0;
 };
 
 namespace {
@@ -543,6 +564,301 @@ void stash_current(kbbq_fastq_reader *r) {
     r->packed_is_exact = false;
 }
 
+// ---- a plain gzip stream (gzip_inflate.h): the host's part -- members, segments, linking -- around the kernels ----------
+// grow a device buffer, keeping its first `used` bytes
+int grow_keep(Buf &b, size_t need, size_t used, hipStream_t st) {
+    if (b.bytes >= need) return KBBQ_OK;
+    Buf nb;
+    int rc = nb.reserve(need);
+    if (rc) return rc;
+    if (used) HIP_TRY(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    b.release();
+    b = nb;
+    return KBBQ_OK;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+enum { R_MORE, R_FINAL, R_NEED_INPUT, R_BIG, R_GIVE_UP };
+constexpr uint32_t GZ_SEG_FLOOR = 32768;            // compressed bytes per segment at least
+constexpr uint32_t GZ_BIG_SLOT = 1u << 26;          // entries of the slot of a lone segment whose first block fills a normal one
+
+// One round over the member's compressed bytes from bit *pos of r->gz_in (n bytes): segments, candidates, speculative
+// decode, linking, then the accepted segments' bytes into r->gz_out[GZ_WINDOW + *P, ...) and their CRC-32 into the member's.
+int gz_round(kbbq_fastq_reader *r, uint64_t n, uint64_t *pos, uint64_t *P, bool big, int *outcome, uint32_t *n_acc) {
+    const uint64_t start = *pos;
+    if (start >= n * 8) { *outcome = R_NEED_INPUT; return KBBQ_OK; }
+    const uint64_t first_byte = start >> 3, avail = n - first_byte;
+    const uint8_t *d_in = (const uint8_t *)r->gz_in.p;
+    int rc;
+    // segments: as many as the device keeps decoding lanes resident (one segment each), never below GZ_SEG_FLOOR bytes
+    if (!r->gz_lanes) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, r->device));
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gz_inflate, 64, 0));
+        r->gz_lanes = (uint64_t)std::max(1, prop.multiProcessorCount) * (uint64_t)std::max(1, per_cu) * 64;
+        if (getenv("KBBQ_DEBUG_CODEC")) fprintf(stderr, "k_gz_inflate: %d wavefronts per CU on %d CUs\n", per_cu, prop.multiProcessorCount);
+    }
+    const uint64_t seg_bytes = std::max<uint64_t>(GZ_SEG_FLOOR, (avail + r->gz_lanes - 1) / r->gz_lanes);
+    const uint32_t S = big ? 1u : (uint32_t)std::max<uint64_t>(1, (avail + seg_bytes - 1) / seg_bytes);
+    std::vector<uint64_t> L(1, start);
+    auto t = std::chrono::steady_clock::now();
+    if (S > 1) {
+        const uint32_t nf = S - 1;
+        if ((rc = r->gz_lo.reserve((size_t)nf * 16 + 64))) return rc;
+        if ((rc = r->gz_cand.reserve((size_t)nf * 8 + 64))) return rc;
+        std::vector<uint64_t> lohi(2 * (size_t)nf), cand(nf);
+        for (uint32_t k = 1; k < S; ++k) {
+            lohi[k - 1] = (first_byte + k * seg_bytes) * 8;
+            lohi[nf + k - 1] = std::min<uint64_t>(first_byte + (k + 1) * seg_bytes, n) * 8;
+        }
+        HIP_TRY(hipMemcpyAsync(r->gz_lo.p, lohi.data(), (size_t)nf * 16, hipMemcpyHostToDevice, r->st));
+        const uint64_t *lo = (const uint64_t *)r->gz_lo.p;
+        hipLaunchKernelGGL(k_gz_find, dim3(std::min<uint32_t>(nf, 65535)), dim3(256), 0, r->st, d_in, n, lo, lo + nf, (uint64_t *)r->gz_cand.p, nf);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(cand.data(), r->gz_cand.p, (size_t)nf * 8, hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipStreamSynchronize(r->st));
+        for (uint64_t c : cand) if (c != GZ_NONE && c > L.back()) L.push_back(c);
+        r->ms_gz_find += ms_since(t);
+        t = std::chrono::steady_clock::now();
+    }
+    const uint32_t m = (uint32_t)L.size();
+    std::vector<GzSeg> segs(m);
+    uint64_t slot_total = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+        GzSeg &g = segs[i];
+        memset(&g, 0, sizeof g);
+        g.start_bit = L[i];
+        g.stop_bit = i + 1 < m ? L[i + 1] : ~0ull;
+        g.window = i == 0 ? r->gz_win : GZ_WINDOW;
+        const uint64_t range = ((i + 1 < m ? L[i + 1] : n * 8) - L[i]) / 8 + 1;
+        g.slot_cap = big ? GZ_BIG_SLOT : (uint32_t)std::min<uint64_t>(5 * range + 131072, 1u << 30);
+        g.slot_off = slot_total;
+        slot_total += g.slot_cap;
+    }
+    if ((rc = r->gz_slots.reserve(slot_total * 2 + 64))) return rc;
+    if ((rc = r->gz_scratch.reserve((size_t)m * sizeof(GzScratch)))) return rc;
+    if ((rc = r->gz_segs.reserve((size_t)m * sizeof(GzSeg)))) return rc;
+    GzSeg *d_segs = (GzSeg *)r->gz_segs.p;
+    uint16_t *d_slots = (uint16_t *)r->gz_slots.p;
+    GzScratch *d_scr = (GzScratch *)r->gz_scratch.p;
+    HIP_TRY(hipMemcpyAsync(d_segs, segs.data(), (size_t)m * sizeof(GzSeg), hipMemcpyHostToDevice, r->st));
+    hipLaunchKernelGGL(k_gz_inflate, dim3((m + 63) / 64), dim3(64), 0, r->st, d_in, n, d_segs, m, (const uint32_t *)nullptr, d_slots, d_scr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(segs.data(), d_segs, (size_t)m * sizeof(GzSeg), hipMemcpyDeviceToHost, r->st));
+    HIP_TRY(hipStreamSynchronize(r->st));
+    // Every segment whose start is not where the one in front of it ended is decoded again from there, all at once: the
+    // one in front may itself be unconfirmed, so this is speculation too, but it usually settles the chain in one pass
+    // (a false positive of the finder is an isolated candidate) where the walk below would decode them one after another.
+    std::vector<uint32_t> which;
+    for (int pass = 0; pass < 4; ++pass) {
+        which.clear();
+        for (uint32_t i = 0; i + 1 < m; ++i) {
+            const GzSeg &g = segs[i];
+            if (g.status == GZ_BAD || g.status == GZ_FINAL || g.status == GZ_IN_END || !g.n_blocks || segs[i + 1].start_bit == g.end_bit) continue;
+            segs[i + 1].start_bit = g.end_bit;
+            which.push_back(i + 1);
+        }
+        if (which.empty()) break;
+        if ((rc = r->gz_cand.reserve(which.size() * 4 + 64))) return rc;      // (the candidates have been read)
+        HIP_TRY(hipMemcpyAsync(d_segs, segs.data(), (size_t)m * sizeof(GzSeg), hipMemcpyHostToDevice, r->st));
+        HIP_TRY(hipMemcpyAsync(r->gz_cand.p, which.data(), which.size() * 4, hipMemcpyHostToDevice, r->st));
+        hipLaunchKernelGGL(k_gz_inflate, dim3((unsigned)(which.size() + 63) / 64), dim3(64), 0, r->st, d_in, n, d_segs, (uint32_t)which.size(),
+                           (const uint32_t *)r->gz_cand.p, d_slots, d_scr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(segs.data(), d_segs, (size_t)m * sizeof(GzSeg), hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipStreamSynchronize(r->st));
+        r->gz_redecoded += which.size();
+    }
+    // ---- linking: from the confirmed start, segment i + 1 counts only when segment i ended exactly where it started
+    std::vector<GzPlaced> acc;
+    const uint64_t out_base = *P;
+    uint32_t hist = r->gz_win;      // bytes of the member in front of the current segment (at most GZ_WINDOW)
+    *outcome = R_MORE;
+    for (uint32_t i = 0;;) {
+        const GzSeg &g = segs[i];
+        if (g.status == GZ_BAD) return fail(KBBQ_EIO, "the gzip stream does not inflate (a block at bit %llu of the piece)", (unsigned long long)g.start_bit);
+        if (g.n_blocks == 0) {
+            *outcome = g.status == GZ_IN_END ? R_NEED_INPUT : big ? R_GIVE_UP : R_BIG;
+            break;
+        }
+        if (g.min_marker < GZ_WINDOW && GZ_WINDOW - g.min_marker > hist) return fail(KBBQ_EIO, "the gzip stream does not inflate (a distance too far back)");
+        GzPlaced p;
+        p.slot_off = g.slot_off;
+        p.out_off = *P;
+        p.out_len = g.out_len;
+        p.pad = 0;
+        acc.push_back(p);
+        *P += g.out_len;
+        hist = (uint32_t)std::min<uint64_t>(GZ_WINDOW, (uint64_t)hist + g.out_len);
+        r->gz_isize += g.out_len;
+        *pos = g.end_bit;
+        ++*n_acc;
+        if (g.status == GZ_FINAL) { *outcome = R_FINAL; break; }
+        if (g.status == GZ_IN_END) { *outcome = R_NEED_INPUT; break; }
+        if (i + 1 >= m) break;      // a full slot: the next round goes on from here
+        GzSeg &h = segs[i + 1];
+        if (h.start_bit != g.end_bit) {
+            // a false start (or a segment that ended early): decode it again from where this one ended
+            h.start_bit = g.end_bit;
+            h.window = hist;
+            HIP_TRY(hipMemcpyAsync(d_segs + i + 1, &h, sizeof h, hipMemcpyHostToDevice, r->st));
+            hipLaunchKernelGGL(k_gz_inflate, dim3(1), dim3(64), 0, r->st, d_in, n, d_segs + i + 1, 1u, (const uint32_t *)nullptr, d_slots, d_scr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&h, d_segs + i + 1, sizeof h, hipMemcpyDeviceToHost, r->st));
+            HIP_TRY(hipStreamSynchronize(r->st));
+            ++r->gz_redecoded;
+        }
+        ++i;
+    }
+    r->gz_win = hist;
+    r->ms_gz_decode += ms_since(t);
+    if (acc.empty()) return KBBQ_OK;
+    // ---- the accepted segments' bytes: their last 32 KB in order, then the rest in parallel; the CRC-32 of the round
+    t = std::chrono::steady_clock::now();
+    if ((rc = grow_keep(r->gz_out, GZ_WINDOW + *P + 4096, GZ_WINDOW + out_base, r->st))) return rc;
+    const uint32_t na = (uint32_t)acc.size();
+    if ((rc = r->gz_placed.reserve((size_t)na * sizeof(GzPlaced)))) return rc;
+    HIP_TRY(hipMemcpyAsync(r->gz_placed.p, acc.data(), (size_t)na * sizeof(GzPlaced), hipMemcpyHostToDevice, r->st));
+    uint8_t *out = (uint8_t *)r->gz_out.p;
+    const GzPlaced *d_pl = (const GzPlaced *)r->gz_placed.p;
+    hipLaunchKernelGGL(k_gz_chain, dim3(1), dim3(1024), 0, r->st, (const uint16_t *)d_slots, d_pl, na, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r->st));
+    r->ms_gz_chain += ms_since(t);
+    t = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL(k_gz_resolve, dim3(8, std::min<uint32_t>(na, 8192)), dim3(256), 0, r->st, (const uint16_t *)d_slots, d_pl, na, out);
+    HIP_TRY(hipGetLastError());
+    const uint64_t bytes = *P - out_base;
+    constexpr uint32_t piece = 1u << 20;
+    const uint32_t n_pieces = (uint32_t)((bytes + piece - 1) / piece);
+    std::vector<uint32_t> crcs(n_pieces);
+    if (n_pieces) {
+        if ((rc = r->gz_crcs.reserve((size_t)n_pieces * 4 + 64))) return rc;
+        hipLaunchKernelGGL(k_gz_crc, dim3(std::min<uint32_t>((n_pieces + 3) / 4, 4096)), dim3(256), 0, r->st, (const uint8_t *)out + GZ_WINDOW + out_base, bytes,
+                           piece, (uint32_t *)r->gz_crcs.p, n_pieces);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(crcs.data(), r->gz_crcs.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, r->st));
+    }
+    HIP_TRY(hipStreamSynchronize(r->st));
+    // crc32_combine: crc(AB) = crc(A) x^(8 |B|) + crc(B)
+    const uint32_t x_piece = crc_xpow8(piece);
+    for (uint32_t i = 0; i < n_pieces; ++i) {
+        const uint64_t len = std::min<uint64_t>(piece, bytes - (uint64_t)i * piece);
+        r->gz_crc = crc_mulmod(r->gz_crc, len == piece ? x_piece : crc_xpow8(len)) ^ crcs[i];
+    }
+    r->ms_gz_resolve += ms_since(t);
+    return KBBQ_OK;
+}
+
+// The gzip stream's bytes of this call behind what earlier calls left (r->gz_pending) inflated into
+// r->gz_out[GZ_WINDOW, GZ_WINDOW + *produced); what cannot be decoded yet stays pending.  last: nothing follows (a member
+// that does not end then is flagged).  Bytes behind a trailer that are not a member header: flags bit 0 (or, with
+// garbage_ends, the end of the stream, as gzread takes them).
+int gz_decode(kbbq_fastq_reader *r, const uint8_t *bytes, uint64_t n_bytes, bool last, bool garbage_ends, uint64_t *produced, uint32_t *flags, uint32_t *n_acc) {
+    using R = kbbq_fastq_reader;
+    auto &pend = r->gz_pending;
+    uint64_t pos = r->gz_phase == R::GZ_DEFLATE ? r->gz_bit0 : 0;
+    pend.insert(pend.end(), bytes, bytes + n_bytes);
+    const uint8_t *buf = pend.data();
+    const uint64_t n = pend.size();
+    uint64_t P = 0;
+    *produced = 0;
+    *n_acc = 0;
+    r->gz_redecoded = 0;
+    int rc;
+    if ((rc = r->gz_out.reserve(GZ_WINDOW + 4096))) return rc;
+    if ((rc = r->gz_win_buf.reserve(GZ_WINDOW))) return rc;
+    if (r->gz_win) HIP_TRY(hipMemcpyAsync(r->gz_out.p, r->gz_win_buf.p, GZ_WINDOW, hipMemcpyDeviceToDevice, r->st));
+    bool uploaded = false;
+    bool big = false;
+    for (;;) {
+        if (r->gz_phase == R::GZ_HEADER) {
+            const uint64_t at = pos >> 3;
+            if (at >= n) break;
+            const int64_t h = member_header(buf + at, n - at);
+            if (h < 0) {
+                if (!(garbage_ends && r->gz_members)) *flags |= 1;
+                pos = n * 8;
+                break;
+            }
+            if (h == 0) { if (last) *flags |= 1; break; }
+            pos += (uint64_t)h * 8;
+            r->gz_phase = R::GZ_DEFLATE;
+            r->gz_win = 0;
+            r->gz_crc = 0;
+            r->gz_isize = 0;
+            r->gz_members = true;
+            continue;
+        }
+        if (r->gz_phase == R::GZ_TRAILER) {
+            const uint64_t at = pos >> 3;
+            if (at + 8 > n) { if (last) *flags |= 1; break; }
+            const uint8_t *t = buf + at;
+            const uint32_t crc = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
+            const uint32_t isize = t[4] | (t[5] << 8) | (t[6] << 16) | ((uint32_t)t[7] << 24);
+            if (crc != r->gz_crc) return fail(KBBQ_EIO, "gzip member: CRC32 checksum mismatch");
+            if (isize != r->gz_isize) return fail(KBBQ_EIO, "gzip member: ISIZE mismatch (%u against %u bytes inflated)", isize, r->gz_isize);
+            pos += 64;
+            r->gz_phase = R::GZ_HEADER;
+            continue;
+        }
+        if (!uploaded) {
+            if ((rc = r->gz_in.reserve(n + 4096))) return rc;
+            HIP_TRY(hipMemcpyAsync(r->gz_in.p, buf, n, hipMemcpyHostToDevice, r->st));
+            HIP_TRY(hipMemsetAsync((char *)r->gz_in.p + n, 0, 64, r->st));
+            uploaded = true;
+        }
+        int outcome = R_MORE;
+        if ((rc = gz_round(r, n, &pos, &P, big, &outcome, n_acc))) return rc;
+        big = outcome == R_BIG;
+        if (outcome == R_FINAL) { r->gz_phase = R::GZ_TRAILER; pos = (pos + 7) & ~7ull; continue; }
+        if (outcome == R_NEED_INPUT) { if (last) *flags |= 1; break; }
+        if (outcome == R_GIVE_UP) { *flags |= 1; break; }
+    }
+    // what was not decoded waits for the next call; the window for it is the last GZ_WINDOW bytes of gz_out[0, GZ_WINDOW + P)
+    const uint64_t keep_from = std::min<uint64_t>(pos >> 3, n);
+    r->gz_bit0 = (uint32_t)(pos & 7);
+    pend.erase(pend.begin(), pend.begin() + (ptrdiff_t)keep_from);
+    if (P) HIP_TRY(hipMemcpyAsync(r->gz_win_buf.p, (const char *)r->gz_out.p + P, GZ_WINDOW, hipMemcpyDeviceToDevice, r->st));
+    *produced = P;
+    return KBBQ_OK;
+}
+
+void gz_reset(kbbq_fastq_reader *r) {
+    r->container = kbbq_fastq_reader::C_UNKNOWN;
+    r->gz_phase = kbbq_fastq_reader::GZ_HEADER;
+    r->gz_pending.clear();
+    r->gz_bit0 = r->gz_win = r->gz_crc = r->gz_isize = 0;
+    r->gz_members = false;
+    r->gz_failed = false;
+    r->gz_hold_bytes = 0;
+    r->gz_redecoded = 0;
+}
+
+// The container from the first bytes of a stream: 1 decided, 0 more bytes are needed
+int detect_container(kbbq_fastq_reader *r, const uint8_t *p, uint64_t n, bool last) {
+    using R = kbbq_fastq_reader;
+    if (n >= 1 && p[0] == '@') { r->container = r->take_text ? R::C_TEXT : R::C_BGZF; return 1; }
+    if (n >= 1 && p[0] != 0x1f) { r->container = R::C_BGZF; return 1; }      // (the BGZF path flags it)
+    if (n < 12) { if (!last) return 0; r->container = R::C_BGZF; return 1; }
+    if (p[1] != 0x8b || p[2] != 8) { r->container = R::C_BGZF; return 1; }
+    if (!(p[3] & 4)) { r->container = R::C_GZIP; return 1; }
+    const uint32_t xlen = p[10] | (p[11] << 8);
+    if (12 + (uint64_t)xlen > n) { if (!last) return 0; r->container = R::C_GZIP; return 1; }
+    bool bc = false;
+    for (uint32_t x = 0; x + 4 <= xlen;) {
+        const uint8_t *sf = p + 12 + x;
+        const uint32_t slen = sf[2] | (sf[3] << 8);
+        if (sf[0] == 66 && sf[1] == 67 && slen == 2 && x + 6 <= xlen) bc = true;      // (fastq_io.cc: bgzf_block_size's rule)
+        x += 4 + slen;
+    }
+    r->container = bc ? R::C_BGZF : R::C_GZIP;
+    return 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -574,7 +890,9 @@ void kbbq_fastq_reader_destroy(kbbq_fastq_reader *r) {
     KbbqDeviceGuard guard(r->device);
     if (r->st) (void)hipStreamSynchronize(r->st);
     Buf *all[] = {&r->comp, &r->text, &r->status, &r->blk_meta, &r->h_meta, &r->tile_counts, &r->tile_sums, &r->nl_pos, &r->idx_u32,
-                  &r->idx_second, &r->base_sz, &r->text_sz, &r->flags, &r->carry, &r->h_small, &r->seq_text, &r->counter};
+                  &r->idx_second, &r->base_sz, &r->text_sz, &r->flags, &r->carry, &r->h_small, &r->seq_text, &r->counter,
+                  &r->gz_in, &r->gz_out, &r->gz_win_buf, &r->gz_slots, &r->gz_scratch, &r->gz_segs, &r->gz_lo, &r->gz_cand, &r->gz_placed,
+                  &r->gz_crcs, &r->gz_hold};
     for (Buf *b : all) b->release();
     r->pre.release();
     release_kept(r);
@@ -593,6 +911,7 @@ int kbbq_fastq_reader_rewind(kbbq_fastq_reader *r) {
     r->selected = -1;
     r->carry_bytes = 0;
     r->have_chunk = false;
+    gz_reset(r);
     return KBBQ_OK;
 }
 
@@ -649,11 +968,51 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     r->selected = -1;
     r->have_chunk = false;
     r->packed_is_exact = false;
+    uint64_t text = r->carry_bytes;
+    const uint64_t text_cap = 3500000000ull;      // record offsets travel in 32 bits
+    uint32_t nb = 0;
+    int rc;
+    // (while chunks are kept, a buffer that no longer fits gives up the kept ones: pass 4 then inflates the file again)
+    auto reserve_or_drop = [&](Buf &b, size_t need) -> int {
+        int rc2 = b.reserve(need);
+        if (rc2 == KBBQ_ENOMEM && (r->keeping || !r->kept.empty())) {
+            (void)hipGetLastError();
+            release_kept(r);
+            r->keeping = false;
+            rc2 = b.reserve(need);
+        }
+        return rc2;
+    };
+    if (r->container == kbbq_fastq_reader::C_UNKNOWN && !detect_container(r, file_bytes, n_bytes, last != 0)) return KBBQ_OK;      // (consumed 0)
+    if (r->container != kbbq_fastq_reader::C_BGZF) {
+        // ---- plain gzip (gzip_inflate.h) or the text itself: every byte is taken, the reader keeps what it cannot decode yet
+        HIP_TRY(hipEventRecord(r->t0, r->st));
+        (void)r->pre.take(file_bytes, n_bytes, r->st);      // (a piece copied ahead is not used: the stream's state comes first)
+        uint64_t produced = 0;
+        const void *from = nullptr;
+        if (r->container == kbbq_fastq_reader::C_TEXT) {
+            produced = n_bytes;
+        } else {
+            if ((rc = gz_decode(r, file_bytes, n_bytes, last != 0, false, &produced, &info->flags, &info->n_blocks))) return rc;
+            info->n_redecoded = (uint32_t)r->gz_redecoded;
+            from = (const char *)r->gz_out.p + GZ_WINDOW;
+        }
+        info->consumed = n_bytes;
+        if (text + produced > text_cap) info->flags |= 1;
+        if (info->flags & 1) return KBBQ_OK;
+        if ((rc = reserve_or_drop(r->text, text + produced + 4096))) return rc;
+        if ((rc = r->h_small.reserve(4096))) return rc;
+        if (r->carry_bytes) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, r->carry_bytes, hipMemcpyDeviceToDevice, r->st));
+        if (produced) {
+            if (from) HIP_TRY(hipMemcpyAsync((char *)r->text.p + text, from, produced, hipMemcpyDeviceToDevice, r->st));
+            else HIP_TRY(hipMemcpyAsync((char *)r->text.p + text, file_bytes, produced, hipMemcpyHostToDevice, r->st));
+        }
+        text += produced;
+    } else {
     // ---- the block boundaries: hop from header to header (RFC 1952 member with the 'BC' extra subfield, SAM spec 4.1)
     std::vector<uint64_t> c_off, o_off;
     std::vector<uint32_t> c_len, o_len;
-    uint64_t at = 0, text = r->carry_bytes;
-    const uint64_t text_cap = 3500000000ull;      // record offsets travel in 32 bits
+    uint64_t at = 0;
     while (at + 18 <= n_bytes) {
         const uint8_t *h = file_bytes + at;
         if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) { info->flags |= 1; break; }      // not BGZF
@@ -685,19 +1044,7 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     info->n_blocks = (uint32_t)c_off.size();
     if (info->flags & 1) return KBBQ_OK;
     if (at == 0 && n_bytes && !last && c_off.empty()) return fail(KBBQ_EINVAL, "the chunk holds no complete BGZF block");
-    const uint32_t nb = (uint32_t)c_off.size();
-    int rc;
-    // (while chunks are kept, a buffer that no longer fits gives up the kept ones: pass 4 then inflates the file again)
-    auto reserve_or_drop = [&](Buf &b, size_t need) -> int {
-        int rc2 = b.reserve(need);
-        if (rc2 == KBBQ_ENOMEM && (r->keeping || !r->kept.empty())) {
-            (void)hipGetLastError();
-            release_kept(r);
-            r->keeping = false;
-            rc2 = b.reserve(need);
-        }
-        return rc2;
-    };
+    nb = (uint32_t)c_off.size();
     // ---- compressed bytes and block table to the device, inflate
     void *d_comp = r->pre.take(file_bytes, n_bytes, r->st);      // copied ahead by the caller's I/O thread?
     if (!d_comp && (rc = r->comp.reserve(at + 4096))) return rc;
@@ -743,6 +1090,7 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
         // the blocks' checksums, as bgzf_read verifies them
         hipLaunchKernelGGL(k_block_crc, dim3(std::min<unsigned>((nb + 3) / 4, 256 * 16)), dim3(256), 0, r->st, A);
         HIP_TRY(hipGetLastError());
+    }
     }
     HIP_TRY(hipMemsetAsync((char *)r->text.p + text, 0, 64, r->st));
     HIP_TRY(hipEventRecord(r->t1, r->st));
@@ -836,6 +1184,45 @@ int kbbq_fastq_reader_inflate(kbbq_fastq_reader *r, const uint8_t *file_bytes, u
     r->selected = -1;
     r->have_chunk = false;
     *consumed = *produced = 0;
+    if (r->container == kbbq_fastq_reader::C_UNKNOWN && n_bytes && !detect_container(r, file_bytes, n_bytes, false)) return KBBQ_OK;
+    if (r->container == kbbq_fastq_reader::C_TEXT) {      // the bytes are the text
+        const uint64_t n = std::min(n_bytes, capacity);
+        memcpy(host_out, file_bytes, n);
+        *consumed = *produced = n;
+        return KBBQ_OK;
+    }
+    if (r->container == kbbq_fastq_reader::C_GZIP) {
+        // Every byte is taken (the reader keeps what it cannot decode yet); what does not fit in `capacity` is held back on the
+        // device and comes first in the next call.  n_bytes == 0: the end of the input.
+        *consumed = n_bytes;
+        int rc;
+        if (!r->gz_hold_bytes) {
+            HIP_TRY(hipEventRecord(r->t0, r->st));
+            uint64_t got = 0;
+            uint32_t flags = 0, n_acc = 0;
+            if (r->gz_failed) return fail(KBBQ_EIO, "the gzip stream ends inside a member, or a member is too large for the device decoder");
+            if ((rc = gz_decode(r, file_bytes, n_bytes, n_bytes == 0, true, &got, &flags, &n_acc))) return rc;
+            HIP_TRY(hipEventRecord(r->t1, r->st));
+            // (what was decoded in front of the trouble comes out first, as gzread gives it; the error with the next call)
+            if (flags & 1) r->gz_failed = true;
+            if ((rc = grow_keep(r->gz_hold, got + 64, 0, r->st))) return rc;
+            if (got) HIP_TRY(hipMemcpyAsync(r->gz_hold.p, (const char *)r->gz_out.p + GZ_WINDOW, got, hipMemcpyDeviceToDevice, r->st));
+            r->gz_hold_bytes = got;
+            r->gz_hold_off = 0;
+            HIP_TRY(hipStreamSynchronize(r->st));
+            float a = 0;
+            if (hipEventElapsedTime(&a, r->t0, r->t1) == hipSuccess) r->ms_inflate += a;
+        } else if (n_bytes) {
+            r->gz_pending.insert(r->gz_pending.end(), file_bytes, file_bytes + n_bytes);
+        }
+        const uint64_t n = std::min(r->gz_hold_bytes, capacity);
+        if (!n && r->gz_failed) return fail(KBBQ_EIO, "the gzip stream ends inside a member, or a member is too large for the device decoder");
+        if (n) HIP_TRY(hipMemcpy(host_out, (const char *)r->gz_hold.p + r->gz_hold_off, n, hipMemcpyDeviceToHost));
+        r->gz_hold_off += n;
+        r->gz_hold_bytes -= n;
+        *produced = n;
+        return KBBQ_OK;
+    }
     // whole blocks while their inflated bytes fit
     std::vector<uint64_t> c_off, o_off;
     std::vector<uint32_t> c_len, o_len;
@@ -1084,8 +1471,23 @@ int kbbq_fastq_reader_preload(kbbq_fastq_reader *r, const uint8_t *file_bytes, u
 
 int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (inflate_ms) *inflate_ms = r->ms_inflate;
+    if (inflate_ms) *inflate_ms = r->ms_inflate;      // (a gzip stream's stages included: kbbq_fastq_reader_gzip_ms splits them)
     if (index_ms) *index_ms = r->ms_index;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_take_text(kbbq_fastq_reader *r, int32_t on) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    r->take_text = on != 0;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_gzip_ms(kbbq_fastq_reader *r, double *find_ms, double *decode_ms, double *chain_ms, double *resolve_ms) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (find_ms) *find_ms = r->ms_gz_find;
+    if (decode_ms) *decode_ms = r->ms_gz_decode;
+    if (chain_ms) *chain_ms = r->ms_gz_chain;
+    if (resolve_ms) *resolve_ms = r->ms_gz_resolve;
     return KBBQ_OK;
 }
 

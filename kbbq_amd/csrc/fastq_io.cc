@@ -20,6 +20,8 @@ private:
     gzFile f_;
 };
 
+}  // namespace
+
 // size of the BGZF block that starts with this gzip header, or 0 if it is not one
 size_t bgzf_block_size(const unsigned char *h, size_t have) {
     if (have < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return 0;
@@ -32,6 +34,8 @@ size_t bgzf_block_size(const unsigned char *h, size_t have) {
     }
     return 0;
 }
+
+namespace {
 
 class BgzfSource : public ByteSource {
 public:
@@ -242,6 +246,11 @@ std::unique_ptr<ByteSource> open_bytes(const std::string &path, int threads) {
             return std::unique_ptr<ByteSource>(new BgzfSource(f, threads));
         }
         fclose(f);
+        // a plain gzip stream: the installed source decodes it on the device too (it takes both containers)
+        if (got >= 3 && head[0] == 0x1f && head[1] == 0x8b && head[2] == 8 && g_bgzf_factory) {
+            std::unique_ptr<ByteSource> dev = g_bgzf_factory(path);
+            if (dev) return dev;
+        }
     }
     gzFile g = path == "-" ? gzdopen(0, "rb") : gzopen(path.c_str(), "rb");
     if (!g) return nullptr;

@@ -34,8 +34,13 @@ public:
     virtual int read(void *dst, unsigned n) = 0;   // bytes delivered (short only at the end), 0 at EOF, < 0 on error
 };
 std::unique_ptr<ByteSource> open_bytes(const std::string &path, int threads);
+// The size of the BGZF block whose gzip header starts h[0, have) -- FEXTRA with a 'BC' subfield of two bytes among its
+// subfields -- or 0 if it is not one: what decides "BGZF" for every reader of this program (the device reader's own test
+// in kbbq_fastq_reader_chunk is the same rule).
+size_t bgzf_block_size(const unsigned char *h, size_t have);
 // Another inflater for BGZF files (the command line installs the one on the GPU, kbbq_cli.cc: DeviceBgzfSource): called by
-// open_bytes for a regular BGZF file; a null result falls back to the thread pool.
+// open_bytes for a regular BGZF file, and for a regular file that is another gzip stream; a null result falls back to the
+// thread pool (BGZF) or to zlib.
 typedef std::unique_ptr<ByteSource> (*BgzfSourceFactory)(const std::string &path);
 void set_bgzf_source_factory(BgzfSourceFactory f);
 

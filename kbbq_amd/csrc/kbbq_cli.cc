@@ -413,7 +413,7 @@ private:
     bool sink_stop_ = false, sink_failed_ = false;
 };
 
-// BGZF input for the host parsers (BAM; FASTQ that the device's record kernels do not take) inflated on the GPU
+// BGZF or plain gzip input for the host parsers (BAM; FASTQ that the device's record kernels do not take) inflated on the GPU
 // (kbbq_fastq_reader_inflate): a thread reads the file in 32 MB pieces, the device inflates and checks their blocks and
 // copies the bytes into one of two page-locked buffers, read() hands them on.  What bgzf_mt's thread pool does for the
 // reference (htsiter.hh:64-66,110-112) -- the pool's cores go to the parsers instead.  Installed as fastq_io's BGZF source;
@@ -496,14 +496,17 @@ private:
                 if (r == 0) { file_end = true; break; }
                 left += (uint64_t)r;
             }
-            if (left == 0) break;
+            // (at the end of the file the calls go on with no bytes until nothing more comes out: a gzip stream that is not
+            // BGZF is decoded statefully, and its last bytes -- or the news that it ends inside a member -- come then;
+            // for BGZF the first such call gives nothing)
             uint64_t consumed = 0, produced = 0;
             if (kbbq_fastq_reader_inflate(reader_, in_, left, out_[k], kOut, &consumed, &produced) < 0) {
                 std::cerr << "BGZF input: " << kbbq_last_error() << std::endl;
                 fail();
                 return;
             }
-            if (consumed == 0) {      // no whole block in what is left: a truncated file
+            if (left == 0 && produced == 0) break;
+            if (consumed == 0 && left) {      // no whole block in what is left: a truncated file
                 if (file_end) { std::cerr << "BGZF input: the file ends inside a block." << std::endl; fail(); return; }
                 fail();
                 return;
@@ -559,8 +562,10 @@ public:
     kbbq_bam_reader *bam = nullptr;
     bool oq_unwritable = false;               // some record's OQ tag bam_aux_update_str could not update (--set-oq: host path)
     double wait_s = 0, device_s = 0, batch_s = 0;
+    const char *container = "BGZF";           // what the file is: BGZF, gzip (other gzip streams) or text
 
     bool open_bam(const std::string &path, bool use_oq, int32_t n_ref, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
+        bam_mode_ = true;
         if (!open_file(path)) return false;
         std::vector<const char *> ids;
         for (auto &id : rg_ids) ids.push_back(id.c_str());
@@ -570,7 +575,7 @@ public:
     }
     bool open(const std::string &path) {
         if (!open_file(path)) return false;
-        if (kbbq_fastq_reader_create(0, &reader) < 0) return false;
+        if (kbbq_fastq_reader_create(0, &reader) < 0 || kbbq_fastq_reader_take_text(reader, 1) < 0) return false;
         start_pass();
         return true;
     }
@@ -580,8 +585,18 @@ public:
         struct stat st;
         if (fstat(fd_, &st) != 0 || !S_ISREG(st.st_mode)) return false;      // a pipe cannot be read twice
         size_ = (uint64_t)st.st_size;
-        unsigned char magic[4] = {0, 0, 0, 0};
-        if (pread(fd_, magic, 4, 0) != 4 || magic[0] != 0x1f || magic[1] != 0x8b || magic[2] != 8 || !(magic[3] & 4)) return false;      // not BGZF
+        // BGZF, another gzip stream (one member or several) or the text itself (include/kbbq_bgzf.h: the reader decides the
+        // same way); BAM is BGZF
+        std::vector<unsigned char> head(12 + 65535);      // (a gzip header's fixed part and the longest extra field)
+        const ssize_t got = pread(fd_, head.data(), head.size(), 0);
+        if (got < 4) return false;
+        const unsigned char *magic = head.data();
+        const bool gz = magic[0] == 0x1f && magic[1] == 0x8b && magic[2] == 8;
+        bgzf_ = bgzf_block_size(magic, (size_t)got) != 0;      // (fastq_io.h: the one rule for "this is BGZF")
+        container = bgzf_ ? "BGZF" : gz ? "gzip" : "text";
+        const bool bgzf = bgzf_;
+        if (!gz && magic[0] != '@') return false;
+        if (bam_mode_ && !bgzf) return false;
         for (int i = 0; i < 2; ++i) {
             void *p = nullptr;
             if (kbbq_host_alloc(kFront + kPiece, &p) < 0) return false;
@@ -629,7 +644,8 @@ public:
                     got += (uint64_t)r;
                 }
                 // the piece starts for the device at once: its copy overlaps the kernels of the piece before it
-                if (ok && !(getenv("KBBQ_PRELOAD") && atoi(getenv("KBBQ_PRELOAD")) == 0)) {
+                // (BGZF only: the reader decodes another gzip stream from the bytes it kept, and text is copied as it is)
+                if (ok && bgzf_ && !(getenv("KBBQ_PRELOAD") && atoi(getenv("KBBQ_PRELOAD")) == 0)) {
                     if (bam) (void)kbbq_bam_reader_preload(bam, buf_[b] + kFront, n, kFront);
                     else if (reader) (void)kbbq_fastq_reader_preload(reader, buf_[b] + kFront, n, kFront);
                 }
@@ -699,6 +715,7 @@ private:
     std::mutex mu_;
     std::condition_variable cv_;
     bool filled_[2] = {false, false}, io_error_ = false, quit_ = false;
+    bool bam_mode_ = false, bgzf_ = false;
 };
 
 // What the output pass needs of one batch besides the new qualities, kept from the first scan when it fits in
@@ -1201,9 +1218,9 @@ int main(int argc, char *argv[]) {
     // The first scan parses its input with a pool: BAM always (bam_io.h: BamChunkParser), FASTQ when it is strictly
     // four-line (fastq_io.h: FastqChunkParser) -- anything else, found out while parsing, starts the scan over with the
     // serial reader.  KBBQ_SERIAL_PARSE=1: the serial readers at once.
-    // A BGZF-compressed FASTQ file is read on the GPU (DeviceFastqInput): the compressed bytes go to the device, which
-    // inflates, finds the records and packs them; every chunk of the file is one resident batch.  Anything that path does
-    // not take -- another container, records that are not four lines, read groups in the names, reads that do not fit in HBM
+    // A FASTQ file -- BGZF, any other gzip stream or uncompressed -- is read on the GPU (DeviceFastqInput): the file's bytes
+    // go to the device, which inflates, finds the records and packs them; every chunk of the file is one resident batch.
+    // Anything that path does not take -- standard input, records that are not four lines, read groups in the names, reads that do not fit in HBM
     // -- starts over with the host parsers below.  KBBQ_DEVICE_READER=0: the host parsers at once.
     DeviceFastqInput dev_in;
     // (KBBQ_HOST_DEFLATE=1, the zlib writer of rounds 1-2, goes with the host readers: the A/B of the whole host I/O path)
@@ -2089,7 +2106,7 @@ int main(int argc, char *argv[]) {
     if (clock.on && dev_in.active) {
         double inf = 0, idx = 0;
         if (dev_in.bam) kbbq_bam_reader_kernel_ms(dev_in.bam, &inf, &idx); else kbbq_fastq_reader_kernel_ms(dev_in.reader, &inf, &idx);
-        std::cerr << "[timing] " << (dev_in.bam ? "BAM" : "FASTQ") << " reader on the GPU (" << (dev_in.text_kept ? "one scan, the text kept in HBM: " : "both scans: ")
+        std::cerr << "[timing] " << (dev_in.bam ? "BAM" : "FASTQ") << " reader on the GPU (" << dev_in.container << "; " << (dev_in.text_kept ? "one scan, the text kept in HBM: " : "both scans: ")
                   << (dev_in.text_kept ? std::to_string(dev_in.kept_bytes) + " bytes; " : std::string()) << "waiting for file reads " << dev_in.wait_s
                   << " s, device calls " << dev_in.device_s << " s, packing + batch arrays " << dev_in.batch_s << " s; kernels: inflate " << inf << " ms, index + pack " << idx << " ms" << std::endl;
     }
