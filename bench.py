@@ -14,9 +14,15 @@ With N > 1 ranks (torchrun, one per GPU) the reads are sharded by contiguous
 ranges (strong scaling: the data set is fixed) and the three exchange steps of
 kbbq_amd/dist.py run over RCCL.
 
-Prints ONE JSON line on rank 0.  The `cpu_baseline` leg (N=1 only) times the
-oracle -- the single-threaded CPU restatement of the reference -- on a bounded
-sample of the same workload; it is a reported baseline, never the product path.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps,
+writes --dump-outputs if asked and prints the line: the headline and what the
+timed steps themselves yield (counts, exchange times, per-kernel event times).
+--full adds what the headline does not need: an untimed in-order step on both
+sides of the timed region and the roofline object quoted on it, the digest of
+the recalibrated qualities, the PCIe-inclusive leg and the `cpu_baseline` leg
+(N=1 only), which times the oracle -- the single-threaded CPU restatement of
+the reference -- on a bounded sample of the same workload; it is a reported
+baseline, never the product path.
 """
 import argparse
 import ctypes
@@ -548,6 +554,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the untimed in-order steps and the roofline object quoted on them, "
+                         "the digest of the recalibrated qualities (result.recal_qual_sum), the CPU baseline and the PCIe-inclusive "
+                         "leg; --no-exclusive-step, --no-cpu-baseline and --no-pcie still leave out their part")
     ap.add_argument("--genome-len", type=int, default=int(os.environ.get("KBBQ_BENCH_GENOME", 3_000_000_000)))
     ap.add_argument("--coverage", type=int, default=30)
     ap.add_argument("--cpu-genome-len", type=int, default=8_000_000)
@@ -753,7 +763,7 @@ def main():
         return
     # (the card slows down under sustained load -- the same kernel measures 9.0 ms on a cold card and 9.8-10.3 ms a
     # minute later -- so the exclusive step is taken on both sides of the timed region: the roofline quotes the one behind)
-    want_excl = not os.environ.get("KBBQ_NO_OVERLAP") and not args.no_exclusive_step
+    want_excl = args.full and not os.environ.get("KBBQ_NO_OVERLAP") and not args.no_exclusive_step
     prof_excl_before = exclusive_step() if want_excl and args.warmup > 0 else None
     e.profile_reset()
     xch.reset_timers()
@@ -777,16 +787,17 @@ def main():
     # region passes 1-3 keep two streams busy, so a kernel's event duration there includes time it shared the chip; the
     # roofline line of the dominant kernel is quoted on its EXCLUSIVE duration from this step (both are printed).
     prof_excl = exclusive_step() if want_excl else None
-    # untimed: digest of the recalibrated qualities (rank-count invariant)
-    digest = 0
-    for bt in batches:
-        e.recalibrate(bt, out_buf.data_ptr())
-        e.sync()
-        digest += int(out_buf[:bt.n_bases].to(torch.int64).sum().item())
-    if world > 1:
-        dg = torch.tensor([digest], dtype=torch.int64, device=coll_dev)
-        dist.all_reduce(dg)
-        digest = int(dg.item())
+    # untimed (--full): digest of the recalibrated qualities (rank-count invariant)
+    if args.full:
+        digest = 0
+        for bt in batches:
+            e.recalibrate(bt, out_buf.data_ptr())
+            e.sync()
+            digest += int(out_buf[:bt.n_bases].to(torch.int64).sum().item())
+        if world > 1:
+            dg = torch.tensor([digest], dtype=torch.int64, device=coll_dev)
+            dist.all_reduce(dg)
+            digest = int(dg.item())
 
     if rank == 0:
         bases_total = n_reads_total * READ_LEN
@@ -819,58 +830,60 @@ def main():
                     kernels[name]["exclusive_avg_ms"] = round(ms / launches, 4)
                     if "alg_bytes_per_launch" in kernels[name]:
                         kernels[name]["exclusive_GBps"] = round(kernels[name]["alg_bytes_per_launch"] / (ms / launches) / 1e6, 1)
-            dom = max((k for k in kernels if "exclusive_GBps" in kernels[k]), key=lambda k: kernels[k]["exclusive_avg_ms"] * kernels[k]["launches"])
-            dom_ms, dom_GBps = kernels[dom]["exclusive_avg_ms"], kernels[dom]["exclusive_GBps"]
-            dom_how = ("exclusive: an untimed in-order step of this same run behind the timed region (kbbq_engine_tune no_overlap), HIP events on "
-                       "the engine's stream; avg_launch_ms_before_timed_region: the same step taken behind the warm-up, on a cooler card")
-        else:
-            dom = max((k for k in kernels if "achieved_GBps" in kernels[k] and not kernels[k].get("overlapped")),
-                      key=lambda k: kernels[k]["total_ms"])
-            dom_ms, dom_GBps = kernels[dom]["avg_ms"], kernels[dom]["achieved_GBps"]
-            dom_how = "the timed region (every kernel in order on one stream: KBBQ_NO_OVERLAP)"
-        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the figure
-        # is the committed rocprofv3 --pmc summary of this same command at the same launch size
-        traffic, traffic_note = None, "no PMC summary for this launch size"
-        try:
-            pmc = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r04_pmc_latest.json")))
-            k = pmc["kernels"].get(dom)
-            launches_per_step = kernels[dom]["launches"] // args.steps
-            full_launches = (n_local // BATCH_READS) >= 1 and READ_LEN == 150 and BATCH_READS == 1 << 22
-            if pmc.get("kernel_source_sha16") != kernel_source_sha16():
-                traffic_note = ("the committed PMC summary (%s) was taken on other kernel sources than the ones this run was built from: "
-                                "not quoted" % pmc.get("summary_file"))
-            elif k and full_launches:
-                # gfx950: FETCH_SIZE tallies the L2's 128-byte memory requests at 64 bytes each (MI355X_MICROARCH.md, HBM
-                # section; tools/probe_req: every random lookup is one TCC_EA0_RDREQ_128B) -- doubled here
-                traffic = round((2.0 * k["FETCH_SIZE"] + k["WRITE_SIZE"]) * 1024.0)
-                traffic_note = ("2 x FETCH_SIZE + WRITE_SIZE per launch of %d reads, %s (rocprofv3 --pmc of this command on these kernel sources; "
-                                "%d launches per step here, the last one partial); FETCH_SIZE counts the 128-byte requests of gfx950's L2 as "
-                                "64 bytes" % (BATCH_READS, pmc["summary_file"], launches_per_step))
-        except (OSError, ValueError, KeyError):
-            pass
-        # bytes the dominant kernel NEEDS: its share of the reads plus 16 bytes (one 128-bit block) per Bloom lookup it
-        # really issued (counted by the kernel); the L2 fetches a 128-byte line for each, which is what `traffic` shows
-        useful = None
-        if dom == "k_infer" and stats.get("infer_lookups"):
-            per_launch = kernels[dom]["launches"] // args.steps
-            useful = round(n_local * READ_LEN * 1.25 / per_launch + 16.0 * stats["infer_lookups"] / per_launch)
-        roof = dict(bound="hbm", kernel=dom, useful_bytes=useful, achieved=dom_GBps, peak=HBM_PEAK_GBPS, unit="GB/s",
-                    frac=round(dom_GBps / HBM_PEAK_GBPS, 4), traffic=traffic,
-                    algorithmic_bytes_per_launch=kernels[dom]["alg_bytes_per_launch"], avg_launch_ms=dom_ms,
-                    duration_measured_in=dom_how,
-                    timed_region_avg_launch_ms=kernels[dom]["avg_ms"],
-                    avg_launch_ms_before_timed_region=(round(prof_excl_before[dom][1] / prof_excl_before[dom][0], 4)
-                                                       if prof_excl and prof_excl_before and prof_excl_before.get(dom, (0, 0))[0] else None),
-                    timed_region_note="in the timed region the kernel shares the chip with the insert side of pass 2 on the side stream; "
-                                      "its event duration there is not its own cost",
-                    traffic_note=traffic_note,
-                    traffic_GBps=None if traffic is None else round(traffic / dom_ms / 1e6, 1),
-                    note="achieved = SURVEY 8d's algorithmic bytes (64 per Bloom query) over the launch time.  The engine's blocks are 16 bytes, "
-                         "but the L2 fetches a whole 128-byte line per random lookup (tools/probe_req: TCC_EA0_RDREQ_128B = lookups), so the "
-                         "HBM traffic is above the algorithmic figure although 23 % of the queries are answered by hint bits; in those real "
-                         "bytes the kernel runs at traffic / avg_launch_ms of HBM bandwidth, and the probe's ceiling for this access pattern is "
-                         "54 G lookups/s = 6.9 TB/s.  dominant = largest total among the kernels that run alone (pass-3 kernels overlap on "
-                         "two streams, flagged `overlapped`)")
+        if args.full:
+            if prof_excl:
+                dom = max((k for k in kernels if "exclusive_GBps" in kernels[k]), key=lambda k: kernels[k]["exclusive_avg_ms"] * kernels[k]["launches"])
+                dom_ms, dom_GBps = kernels[dom]["exclusive_avg_ms"], kernels[dom]["exclusive_GBps"]
+                dom_how = ("exclusive: an untimed in-order step of this same run behind the timed region (kbbq_engine_tune no_overlap), HIP events on "
+                           "the engine's stream; avg_launch_ms_before_timed_region: the same step taken behind the warm-up, on a cooler card")
+            else:
+                dom = max((k for k in kernels if "achieved_GBps" in kernels[k] and not kernels[k].get("overlapped")),
+                          key=lambda k: kernels[k]["total_ms"])
+                dom_ms, dom_GBps = kernels[dom]["avg_ms"], kernels[dom]["achieved_GBps"]
+                dom_how = "the timed region (every kernel in order on one stream: KBBQ_NO_OVERLAP)"
+            # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the figure
+            # is the committed rocprofv3 --pmc summary of this same command at the same launch size
+            traffic, traffic_note = None, "no PMC summary for this launch size"
+            try:
+                pmc = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r04_pmc_latest.json")))
+                k = pmc["kernels"].get(dom)
+                launches_per_step = kernels[dom]["launches"] // args.steps
+                full_launches = (n_local // BATCH_READS) >= 1 and READ_LEN == 150 and BATCH_READS == 1 << 22
+                if pmc.get("kernel_source_sha16") != kernel_source_sha16():
+                    traffic_note = ("the committed PMC summary (%s) was taken on other kernel sources than the ones this run was built from: "
+                                    "not quoted" % pmc.get("summary_file"))
+                elif k and full_launches:
+                    # gfx950: FETCH_SIZE tallies the L2's 128-byte memory requests at 64 bytes each (MI355X_MICROARCH.md, HBM
+                    # section; tools/probe_req: every random lookup is one TCC_EA0_RDREQ_128B) -- doubled here
+                    traffic = round((2.0 * k["FETCH_SIZE"] + k["WRITE_SIZE"]) * 1024.0)
+                    traffic_note = ("2 x FETCH_SIZE + WRITE_SIZE per launch of %d reads, %s (rocprofv3 --pmc of this command on these kernel sources; "
+                                    "%d launches per step here, the last one partial); FETCH_SIZE counts the 128-byte requests of gfx950's L2 as "
+                                    "64 bytes" % (BATCH_READS, pmc["summary_file"], launches_per_step))
+            except (OSError, ValueError, KeyError):
+                pass
+            # bytes the dominant kernel NEEDS: its share of the reads plus 16 bytes (one 128-bit block) per Bloom lookup it
+            # really issued (counted by the kernel); the L2 fetches a 128-byte line for each, which is what `traffic` shows
+            useful = None
+            if dom == "k_infer" and stats.get("infer_lookups"):
+                per_launch = kernels[dom]["launches"] // args.steps
+                useful = round(n_local * READ_LEN * 1.25 / per_launch + 16.0 * stats["infer_lookups"] / per_launch)
+            roof = dict(bound="hbm", kernel=dom, useful_bytes=useful, achieved=dom_GBps, peak=HBM_PEAK_GBPS, unit="GB/s",
+                        frac=round(dom_GBps / HBM_PEAK_GBPS, 4), traffic=traffic,
+                        algorithmic_bytes_per_launch=kernels[dom]["alg_bytes_per_launch"], avg_launch_ms=dom_ms,
+                        duration_measured_in=dom_how,
+                        timed_region_avg_launch_ms=kernels[dom]["avg_ms"],
+                        avg_launch_ms_before_timed_region=(round(prof_excl_before[dom][1] / prof_excl_before[dom][0], 4)
+                                                           if prof_excl and prof_excl_before and prof_excl_before.get(dom, (0, 0))[0] else None),
+                        timed_region_note="in the timed region the kernel shares the chip with the insert side of pass 2 on the side stream; "
+                                          "its event duration there is not its own cost",
+                        traffic_note=traffic_note,
+                        traffic_GBps=None if traffic is None else round(traffic / dom_ms / 1e6, 1),
+                        note="achieved = SURVEY 8d's algorithmic bytes (64 per Bloom query) over the launch time.  The engine's blocks are 16 bytes, "
+                             "but the L2 fetches a whole 128-byte line per random lookup (tools/probe_req: TCC_EA0_RDREQ_128B = lookups), so the "
+                             "HBM traffic is above the algorithmic figure although 23 % of the queries are answered by hint bits; in those real "
+                             "bytes the kernel runs at traffic / avg_launch_ms of HBM bandwidth, and the probe's ceiling for this access pattern is "
+                             "54 G lookups/s = 6.9 TB/s.  dominant = largest total among the kernels that run alone (pass-3 kernels overlap on "
+                             "two streams, flagged `overlapped`)")
         line = {
             "metric": "recalibrated Gbases/sec", "value": round(value, 4), "unit": "Gbases/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
@@ -883,22 +896,23 @@ def main():
                        "reads": n_reads_total, "bases": bases_total, "batch_reads": BATCH_READS,
                        "parallelism": "reads sharded x%d, Bloom OR all-reduce + histogram sum over RCCL" % world
                        if world > 1 else "1 GPU, reads resident in HBM"},
-            "roofline": roof,
             "kernels": kernels,
             "result": {"sampled_inserted": info["sampled_inserted"], "trusted_inserted": info["trusted_inserted"],
                        "fpr": info["fpr"], "corrected_reads_per_step": stats["corrected_reads"],
-                       "correction_queries_per_step": stats["correction_queries"],
-                       "recal_qual_sum": digest},
+                       "correction_queries_per_step": stats["correction_queries"]},
             # slice-bucketed inserts (kbbq_amd/csrc/bucket.h): records gathered per flush, flushes per step and filter,
             # records that overflowed a region and were inserted directly
             "bucketed_inserts": {"records_per_flush": stats["bucket_capacity"], "flushes_per_step": list(stats["bucket_flushes"]),
                                  "direct_fallback_records": stats["bucket_direct"]},
         }
+        if args.full:
+            line["roofline"] = roof
+            line["result"]["recal_qual_sum"] = digest
         if args.force_exchange:
             line["exchange_one_rank"] = exchange_one_rank(e, xch, args.steps, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(e, args.cpu_genome_len, cov)
-        if world == 1 and not args.no_pcie:
+        if args.full and world == 1 and not args.no_pcie:
             shard.free()      # the leg needs HBM for its own resident copy
             shard = None
             line["pcie_inclusive"] = pcie_inclusive(args.pcie_genome_len, cov, local_rank)

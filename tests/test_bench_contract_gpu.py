@@ -1,5 +1,5 @@
-"""bench.py keeps the driver's contract: one JSON line with the agreed keys, the roofline object for a kernel
-that runs alone, the CPU baseline leg -- checked on a small configuration."""
+"""bench.py keeps the driver's contract: one JSON line with the agreed keys; with --full also the roofline object for a
+kernel that runs alone, the digest and the CPU baseline and PCIe-inclusive legs -- checked on a small configuration."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--genome-len", "30000000",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--genome-len", "30000000",
                           "--cpu-genome-len", "300000", "--pcie-genome-len", "10000000"], cwd=common.ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -50,10 +50,10 @@ def test_bench_prints_one_contract_line():
 
 
 def test_bench_two_ranks_reproduce_one_rank():
-    """The N > 1 path of bench.py launched the plain way -- `python bench.py --gpus 2`, no torchrun: the script
+    """The N > 1 path of bench.py launched directly -- `python bench.py --gpus 2`, no torchrun: the script
     spawns its own ranks before it touches a GPU -- here with both ranks on the one GPU of the box and gloo instead
     of RCCL: shards, ordinals, the three exchange steps and the digest must give the N = 1 answer."""
-    common_args = ["--steps", "1", "--warmup", "0", "--genome-len", "30000000", "--no-cpu-baseline", "--no-pcie"]
+    common_args = ["--full", "--steps", "1", "--warmup", "0", "--genome-len", "30000000", "--no-cpu-baseline", "--no-pcie"]
     one = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + common_args, cwd=common.ROOT, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
     env = dict(os.environ, KBBQ_BENCH_BACKEND="gloo", KBBQ_BENCH_ONE_GPU="1")
@@ -74,9 +74,9 @@ def test_bench_two_ranks_reproduce_one_rank():
 
 def test_bench_exchange_in_the_library_gives_the_same_answer():
     """bench.py --exchange lib --force-exchange: every exchange step of a step runs through the library's own RCCL calls
-    (include/kbbq_exchange.h; a group of one rank on this box) at the bench's launch sizes; counts, fpr and digest must be the
-    plain run's, and the line says who exchanged."""
-    common_args = ["--steps", "1", "--warmup", "0", "--genome-len", "30000000", "--no-cpu-baseline", "--no-pcie", "--no-exclusive-step"]
+    (include/kbbq_exchange.h; a group of one rank on this box) at the bench's launch sizes; counts, fpr and digest must be those
+    of the run without it, and the line says who exchanged."""
+    common_args = ["--full", "--steps", "1", "--warmup", "0", "--genome-len", "30000000", "--no-cpu-baseline", "--no-pcie", "--no-exclusive-step"]
     one = subprocess.run([sys.executable, "bench.py"] + common_args, cwd=common.ROOT, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
     lib = subprocess.run([sys.executable, "bench.py", "--force-exchange", "--exchange", "lib"] + common_args, cwd=common.ROOT, capture_output=True, text=True,
@@ -91,9 +91,10 @@ def test_bench_exchange_in_the_library_gives_the_same_answer():
 
 
 def test_bench_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
-    """--dump-outputs DIR: the last timed step's outputs as .npy files in float32 / float64 under 64 MB, the same from run to
-    run for the same workload whatever the number of steps, and consistent with the line's own counts."""
-    common_args = ["--gpus", "1", "--genome-len", "30000000", "--no-cpu-baseline", "--no-pcie", "--no-exclusive-step"]
+    """--dump-outputs DIR on a plain run (no --full): the last timed step's outputs as .npy files in float32 / float64 under
+    64 MB, the same from run to run for the same workload whatever the number of steps, and consistent with the line's own
+    counts; the line holds the headline and none of what --full adds."""
+    common_args = ["--gpus", "1", "--genome-len", "30000000"]
     lines, dumps = [], []
     for i, steps in enumerate((["--steps", "1", "--warmup", "0"], ["--steps", "3", "--warmup", "1"])):
         d = tmp_path / ("run%d" % i)
@@ -103,6 +104,11 @@ def test_bench_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
         lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
         dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
     assert [ln["steps"] for ln in lines] == [1, 3]
+    for ln in lines:
+        assert ln["metric"] == "recalibrated Gbases/sec" and ln["unit"] == "Gbases/s" and ln["higher_is_better"] is True and ln["dtype"] == "u64"
+        assert abs(ln["value"] - ln["config"]["bases"] / (ln["ms_per_step"] / 1e3) / 1e9) < 1e-3 * ln["value"]
+        assert not {"roofline", "cpu_baseline", "pcie_inclusive", "ingest_inclusive_value"} & set(ln) and "recal_qual_sum" not in ln["result"]
+        assert not any("exclusive_avg_ms" in k for k in ln["kernels"].values())
     a, b = dumps
     assert sorted(a) == sorted(b) and {"recal_qual_sample", "recal_sample_reads", "dq_cycle", "thresholds", "counts"} <= set(a)
     assert sum(x.nbytes for x in a.values()) <= 64 << 20

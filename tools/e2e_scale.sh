@@ -28,6 +28,6 @@ while True:
     recs += a.shape[0]
 print("cli_records %d cli_qual_sum %d" % (recs, total))
 PY
-python bench.py --genome-len $G --no-cpu-baseline --steps 1 2>/dev/null | python -c "
+python bench.py --full --genome-len $G --no-cpu-baseline --steps 1 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench_qual_sum', d['result']['recal_qual_sum'], 'reads', d['config']['reads'])" | tee -a gpurun_out/e2e_scale.log
 rm -rf $D
