@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <deque>
 #include <cstdio>
@@ -58,10 +59,106 @@ static std::ostream &put_now(std::ostream &os) {   // kbbq.cc:49-53
     return os << std::put_time(&tm, "[%F %T %Z]");
 }
 
+// a stamped line on stderr and the exit status that goes with it
+static int give_up(const std::string &text) {
+    std::cerr << put_now << text << std::endl;
+    return 1;
+}
+
 static struct option long_options[] = {   // kbbq.cc:66-79
     {"ksize", required_argument, 0, 'k'},    {"use-oq", no_argument, 0, 'u'},     {"set-oq", no_argument, 0, 's'},
     {"genomelen", required_argument, 0, 'g'}, {"coverage", required_argument, 0, 'c'}, {"fixed", required_argument, 0, 'f'},
     {"alpha", required_argument, 0, 'a'},     {"threads", required_argument, 0, 't'},  {0, 0, 0, 0}};
+
+enum class Format { fastq, bam, cram, unknown };
+
+// The value of an environment switch (what getenv returned): a number, or "set to this text"
+static long long env_num(const char *s, long long unset) { return s ? strtoll(s, nullptr, 10) : unset; }
+static bool env_is(const char *s, const char *text) { return s && !strcmp(s, text); }
+
+// What the user asked for: the command line (kbbq.cc:81-150) and every KBBQ_* switch of the environment (README.md), each
+// read in one place -- here, when main() makes its CliOptions, before the first file is opened -- with its default beside it.
+struct CliOptions {
+    int k = 32;
+    long double alpha = 0;
+    uint64_t genomelen = 0;
+    unsigned coverage = 0;
+    bool set_oq = false, use_oq = false;
+    int nthreads = 0;
+    std::string filename = "-", fixedinput;
+    int out_threads = 1;      // --threads, or "pick" (parse())
+    int io_threads = 1;       // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
+    bool is_bam = false;      // what sniff() found
+    bool timing = getenv("KBBQ_TIMING") != nullptr;                          // set to anything: wall-clock per phase on stderr at the end
+    int write_threads = (int)env_num(getenv("KBBQ_WRITE_THREADS"), 4);       // threads writing ranges of a regular output file; 1: sequential always
+    bool preload = env_num(getenv("KBBQ_PRELOAD"), 1) != 0;                  // =0: a piece of the device reader is not copied ahead of its chunk call
+    // bytes of the file per chunk of the device reader, reads per engine call: shrunk so that tests cross many boundaries with small files
+    uint64_t reader_piece = std::max<uint64_t>(64, (uint64_t)env_num(getenv("KBBQ_READER_PIECE_KB"), 256 << 10)) << 10;
+    size_t batch_reads = std::max<size_t>(1, (size_t)env_num(getenv("KBBQ_BATCH_READS"), 1 << 20));
+    long long host_cache_mb = env_num(getenv("KBBQ_HOST_CACHE_MB"), LLONG_MIN);   // host memory for the records of resident batches; unset: host_cache_budget()
+    int test_io_threads = (int)env_num(getenv("KBBQ_IO_THREADS"), 1);        // reader threads of the --io-test helpers
+    bool host_deflate = env_num(getenv("KBBQ_HOST_DEFLATE"), 0) != 0;        // =1: the zlib writer with the host readers, the A/B of the whole host I/O path
+    bool device_inflate = env_num(getenv("KBBQ_DEVICE_INFLATE"), 1) != 0;    // =0: the host parsers' BGZF input is inflated by their thread pool
+    bool resident = !env_is(getenv("KBBQ_RESIDENT"), "0");                   // =0: every pass reads the file again, nothing stays in HBM
+    bool device_reader = env_num(getenv("KBBQ_DEVICE_READER"), 1) != 0;      // =0: the host parsers at once
+    bool serial_parse = env_num(getenv("KBBQ_SERIAL_PARSE"), 0) != 0;        // =1: the serial readers at once
+    bool keep_text = env_num(getenv("KBBQ_KEEP_TEXT"), 1) != 0;              // =0: pass 4 of the device reader reads the file again
+    uint32_t seed = (uint32_t)env_num(getenv("KBBQ_SEED"), 0);               // the sampler's seed; 0: from time and pid like the reference
+    const char *devices = getenv("KBBQ_DEVICES");                            // 0,1,...: passes 1-3 sharded over these devices (run_on_devices)
+    bool exchange_local = env_is(getenv("KBBQ_EXCHANGE"), "local");          // in-process copies even between distinct devices
+    bool qual_digest = env_num(getenv("KBBQ_QUAL_DIGEST"), 0) != 0;          // =1: "[digest]" lines (bench.py's trusted_inserted and recal_qual_sum)
+    bool release = env_num(getenv("KBBQ_RELEASE"), 0) != 0;                  // =1: everything is freed in order at the end, no exit(0)
+
+    bool fixed_mode() const { return !fixedinput.empty(); }
+    bool host_io() const { return host_deflate; }
+    // BGZF input that the host parsers read (BAM always) is inflated on the GPU as well
+    bool inflate_on_device() const { return !host_deflate && device_inflate; }
+    // The device reader (DeviceFastqInput) may be tried: it makes resident batches of a regular file
+    bool may_read_on_device(bool resident_on) const {
+        return !fixed_mode() && !host_io() && resident_on && filename != "-" && device_reader && !serial_parse;
+    }
+    uint64_t host_cache_budget() const {
+        if (host_cache_mb != LLONG_MIN) return (uint64_t)host_cache_mb << 20;
+        const long pages = sysconf(_SC_PHYS_PAGES), psize = sysconf(_SC_PAGE_SIZE);
+        const uint64_t ram = pages > 0 && psize > 0 ? (uint64_t)pages * (uint64_t)psize : 0;
+        return std::min<uint64_t>(ram / 4, 64ULL << 30);
+    }
+    // false: the message is on stderr, exit status 1
+    bool parse(int argc, char *argv[]) {
+        int opt = 0, opt_idx = 0;
+        while ((opt = getopt_long(argc, argv, "k:usg:c:f:a:t:", long_options, &opt_idx)) != -1) {
+            switch (opt) {
+                case 'k':
+                    k = std::stoi(std::string(optarg));
+                    // (the reference only prints this and goes on, kbbq.cc:102-104)
+                    if (k <= 0 || k > KBBQ_MAX_KMER) return !give_up("  Error: k must be <= " + std::to_string(KBBQ_MAX_KMER) + " and > 0.");
+                    break;
+                case 'u': use_oq = true; break;
+                case 's': set_oq = true; break;
+                case 'g': genomelen = std::stoull(std::string(optarg)); break;
+                case 'c': coverage = (unsigned)std::stoul(std::string(optarg)); break;
+                case 'f': fixedinput = std::string(optarg); break;
+                case 'a': alpha = std::stold(std::string(optarg)); break;
+                case 't':
+                    nthreads = std::stoi(std::string(optarg));
+                    if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
+                    break;
+                case '?':
+                default:
+                    return !give_up(std::string("  Unknown argument ") + (char)opt);
+            }
+        }
+        // --threads sizes the BGZF compression pool like the reference's htslib pool (kbbq.cc:159-168); unlike the
+        // reference, 0 does not mean "single-threaded" but "pick": the writer is the end-to-end bottleneck
+        out_threads = nthreads > 0 ? nthreads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        io_threads = out_threads;
+        if (optind < argc) {
+            filename = std::string(argv[optind]);
+            while (++optind < argc) std::cerr << put_now << " Warning: Extra argument " << argv[optind] << " ignored." << std::endl;
+        }
+        return true;
+    }
+};
 
 // minion::create_seed_seq().GenerateOne() (minion.hpp:320-345, 377-408; the chrono/random_device branch
 // is disabled there by the __cpluscplus typo, so the inputs are time(nullptr), getpid() and two constants)
@@ -82,7 +179,6 @@ static uint32_t time_pid_seed() {
     return (uint32_t)(sum >> 32);
 }
 
-enum class Format { fastq, bam, cram, unknown };
 static Format sniff(const std::string &path) {   // hts_detect_format, as far as this tool needs it
     gzFile f = path == "-" ? nullptr : gzopen(path.c_str(), "rb");
     if (!f) return Format::unknown;
@@ -162,7 +258,8 @@ private:
 struct PhaseClock {
     std::vector<std::pair<std::string, double>> phases;
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    bool on = getenv("KBBQ_TIMING") != nullptr;
+    bool on;
+    explicit PhaseClock(bool timing) : on(timing) {}
     void mark(const char *name) {
         const auto t1 = std::chrono::steady_clock::now();
         phases.emplace_back(name, std::chrono::duration<double>(t1 - t0).count());
@@ -180,10 +277,9 @@ struct PhaseClock {
     }
 };
 
-static int g_io_threads = 1;   // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
-static std::unique_ptr<Source> open_source(const std::string &path, bool is_bam, bool use_oq) {   // open_file, kbbq.cc:55-64
-    if (is_bam) return std::unique_ptr<Source>(new BamSource(path, use_oq, g_io_threads));
-    return std::unique_ptr<Source>(new FastqSource(path, g_io_threads));
+static std::unique_ptr<Source> open_source(const CliOptions &o, const std::string &path) {   // open_file, kbbq.cc:55-64
+    if (o.is_bam) return std::unique_ptr<Source>(new BamSource(path, o.use_oq, o.io_threads));
+    return std::unique_ptr<Source>(new FastqSource(path, o.io_threads));
 }
 
 // BGZF output through the encoder on the GPU (include/kbbq_bgzf.h): what the reference leaves to htslib's bgzf_write /
@@ -193,7 +289,7 @@ static std::unique_ptr<Source> open_source(const std::string &path, bool is_bam,
 // itself around the recalibrated qualities it already holds.  The decompressed stream is the host writer's, byte for byte.
 class DeviceBgzfWriter : public ByteSink {
 public:
-    DeviceBgzfWriter(FILE *out, int device) : out_(out) {
+    DeviceBgzfWriter(FILE *out, int device, int want /* CliOptions::write_threads */) : out_(out) {
         if (kbbq_bgzf_create(device, &z_) < 0) { z_ = nullptr; failed_ = true; return; }
         // Output that lands in a regular file (kbbq ... > out.fq.gz) is written by several threads at once, each its own
         // range with pwrite: one thread fills the page cache at ~5 GB/s, which at BASELINE size is longer than the GPU
@@ -203,7 +299,6 @@ public:
         const int fd = fileno(out_);
         struct stat st;
         const int fl = fd >= 0 ? fcntl(fd, F_GETFL) : -1;
-        int want = getenv("KBBQ_WRITE_THREADS") ? atoi(getenv("KBBQ_WRITE_THREADS")) : 4;
 #ifdef F_SETPIPE_SZ
         // a pipe: as much buffer as the system grants (64 KB by default, 1 MB usually allowed): fewer hand-overs to the reader
         if (fd >= 0 && fstat(fd, &st) == 0 && S_ISFIFO(st.st_mode)) (void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);
@@ -240,50 +335,28 @@ public:
         }
         return !failed_;
     }
-    // One batch of FASTQ records (RecordStore layout) whose quality lines come from device memory.
-    bool fastq_batch(const char *blob, const uint32_t *lens, uint64_t n_records, const uint8_t *d_qual, const uint64_t *d_qual_offsets,
-                     uint32_t uniform_len, void *after_stream) {
-        if (!flush_host()) return false;      // bytes written before this batch come first
+    // One more submission to the encoder, behind the bytes written before it; `call` hands it over (< 0: the encoder's error)
+    template <class F> bool submit(F call) {
+        if (!flush_host()) return false;
         if (!make_room()) return false;
-        if (kbbq_bgzf_submit_fastq(z_, blob, lens, n_records, d_qual, d_qual_offsets, uniform_len, after_stream) < 0) return fail_here();
+        if (call(z_) < 0) return fail_here();
         ++in_flight_;
         return true;
+    }
+    // One batch of FASTQ records (RecordStore layout) whose quality lines come from device memory: the device assembles the text.
+    bool fastq_batch(const char *blob, const uint32_t *lens, uint64_t n_records, const uint8_t *d_qual, const uint64_t *d_qual_offsets,
+                     uint32_t uniform_len, void *after_stream) {
+        return submit([&](kbbq_bgzf *z) { return kbbq_bgzf_submit_fastq(z, blob, lens, n_records, d_qual, d_qual_offsets, uniform_len, after_stream); });
     }
     // Bytes the caller has formatted itself in page-locked memory (a whole batch of BAM records): submitted as they are
     // (the caller's buffer is free again on return); what write() gathered before them goes first.
     bool submit_buffer(const char *pinned, size_t n) {
-        if (!flush_host()) return false;
-        if (!n) return true;
-        if (!make_room()) return false;
-        if (kbbq_bgzf_submit(z_, pinned, n, 0, nullptr) < 0) return fail_here();
-        ++in_flight_;
-        return true;
-    }
-    // The current chunk of a device reader with new qualities (kbbq_fastq_reader_write): text assembled from the device's
-    // own copy of the input.
-    bool reader_chunk(kbbq_fastq_reader *reader, const uint8_t *d_qual, void *after_stream) {
-        if (!flush_host()) return false;
-        if (!make_room()) return false;
-        if (kbbq_fastq_reader_write(reader, z_, d_qual, after_stream) < 0) return fail_here();
-        ++in_flight_;
-        return true;
-    }
-    // The current chunk of a device BAM reader with new qualities (kbbq_bam_reader_write): BamFile::recalibrate + write of
-    // every record on the device.
-    bool bam_chunk(kbbq_bam_reader *reader, const uint8_t *d_qual, bool set_oq, void *after_stream) {
-        if (!flush_host()) return false;
-        if (!make_room()) return false;
-        if (kbbq_bam_reader_write(reader, z_, d_qual, set_oq ? 1 : 0, after_stream) < 0) return fail_here();
-        ++in_flight_;
-        return true;
+        if (!n) return flush_host();
+        return submit([&](kbbq_bgzf *z) { return kbbq_bgzf_submit(z, pinned, n, 0, nullptr); });
     }
     // reads of the synthetic data set formatted on the device (kbbq_bgzf_submit_synth)
     bool synth_batch(kbbq_engine *e, const kbbq_synth_params *sp, uint64_t first, uint64_t n, int format) {
-        if (!flush_host()) return false;
-        if (!make_room()) return false;
-        if (kbbq_bgzf_submit_synth(z_, e, sp, first, n, format, nullptr) < 0) return fail_here();
-        ++in_flight_;
-        return true;
+        return submit([&](kbbq_bgzf *z) { return kbbq_bgzf_submit_synth(z, e, sp, first, n, format, nullptr); });
     }
     // every submission so far has left the device (a caller may then reuse device memory the submissions read)
     bool drain() { return drain_to(0); }
@@ -507,7 +580,7 @@ private:
             }
             if (left == 0 && produced == 0) break;
             if (consumed == 0 && left) {      // no whole block in what is left: a truncated file
-                if (file_end) { std::cerr << "BGZF input: the file ends inside a block." << std::endl; fail(); return; }
+                if (file_end) std::cerr << "BGZF input: the file ends inside a block." << std::endl;
                 fail();
                 return;
             }
@@ -550,6 +623,7 @@ private:
 // take is reported by the reader and the caller starts over with the host parsers.
 class DeviceFastqInput {
 public:
+    explicit DeviceFastqInput(const CliOptions &o) : kPiece(o.reader_piece), preload_(o.preload) {}
     ~DeviceFastqInput() { close(); }
     bool active = false;
     bool text_kept = false;                   // every chunk's text and index stayed in HBM: pass 4 reads nothing
@@ -565,8 +639,7 @@ public:
     const char *container = "BGZF";           // what the file is: BGZF, gzip (other gzip streams) or text
 
     bool open_bam(const std::string &path, bool use_oq, int32_t n_ref, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
-        bam_mode_ = true;
-        if (!open_file(path)) return false;
+        if (!open_file(path, true)) return false;
         std::vector<const char *> ids;
         for (auto &id : rg_ids) ids.push_back(id.c_str());
         if (kbbq_bam_reader_create(0, use_oq ? 1 : 0, n_ref, header_bytes, ids.data(), (uint32_t)ids.size(), &bam) < 0) return false;
@@ -574,12 +647,12 @@ public:
         return true;
     }
     bool open(const std::string &path) {
-        if (!open_file(path)) return false;
+        if (!open_file(path, false)) return false;
         if (kbbq_fastq_reader_create(0, &reader) < 0 || kbbq_fastq_reader_take_text(reader, 1) < 0) return false;
         start_pass();
         return true;
     }
-    bool open_file(const std::string &path) {
+    bool open_file(const std::string &path, bool bgzf_only) {
         fd_ = ::open(path.c_str(), O_RDONLY);
         if (fd_ < 0) return false;
         struct stat st;
@@ -594,9 +667,8 @@ public:
         const bool gz = magic[0] == 0x1f && magic[1] == 0x8b && magic[2] == 8;
         bgzf_ = bgzf_block_size(magic, (size_t)got) != 0;      // (fastq_io.h: the one rule for "this is BGZF")
         container = bgzf_ ? "BGZF" : gz ? "gzip" : "text";
-        const bool bgzf = bgzf_;
         if (!gz && magic[0] != '@') return false;
-        if (bam_mode_ && !bgzf) return false;
+        if (bgzf_only && !bgzf_) return false;
         for (int i = 0; i < 2; ++i) {
             void *p = nullptr;
             if (kbbq_host_alloc(kFront + kPiece, &p) < 0) return false;
@@ -604,12 +676,16 @@ public:
         }
         return true;
     }
-    void close() {
+    // the I/O thread joined, the reader -- its streams, the text it kept -- destroyed; the file and the page-locked buffers stay
+    void stop() {
         stop_io();
         if (reader) kbbq_fastq_reader_destroy(reader);
         reader = nullptr;
         if (bam) kbbq_bam_reader_destroy(bam);
         bam = nullptr;
+    }
+    void close() {
+        stop();
         for (int i = 0; i < 2; ++i) { if (buf_[i]) kbbq_host_free(buf_[i]); buf_[i] = nullptr; }
         if (fd_ >= 0) ::close(fd_);
         fd_ = -1;
@@ -619,7 +695,6 @@ public:
     // next one.  The same sequence of chunks comes out of every pass.
     void start_pass() {
         stop_io();
-        next_piece_ = 0;
         taken_piece_ = 0;
         left_ = 0;
         io_error_ = false;
@@ -645,7 +720,7 @@ public:
                 }
                 // the piece starts for the device at once: its copy overlaps the kernels of the piece before it
                 // (BGZF only: the reader decodes another gzip stream from the bytes it kept, and text is copied as it is)
-                if (ok && bgzf_ && !(getenv("KBBQ_PRELOAD") && atoi(getenv("KBBQ_PRELOAD")) == 0)) {
+                if (ok && bgzf_ && preload_) {
                     if (bam) (void)kbbq_bam_reader_preload(bam, buf_[b] + kFront, n, kFront);
                     else if (reader) (void)kbbq_fastq_reader_preload(reader, buf_[b] + kFront, n, kFront);
                 }
@@ -694,6 +769,24 @@ public:
         ++taken_piece_;
         return 1;
     }
+    // The calls both readers have, whichever this one holds (include/kbbq_bgzf.h)
+    const char *format() const { return bam ? "BAM" : "FASTQ"; }
+    int keep(bool on) { return bam ? kbbq_bam_reader_keep(bam, on ? 1 : 0) : kbbq_fastq_reader_keep(reader, on ? 1 : 0); }
+    int kept(uint64_t *n_chunks, uint64_t *n_bytes) { return bam ? kbbq_bam_reader_kept(bam, n_chunks, n_bytes) : kbbq_fastq_reader_kept(reader, n_chunks, n_bytes); }
+    int batch(kbbq_reads *dev) { return bam ? kbbq_bam_reader_batch(bam, dev) : kbbq_fastq_reader_batch(reader, dev); }
+    int rewind() { return bam ? kbbq_bam_reader_rewind(bam) : kbbq_fastq_reader_rewind(reader); }
+    // chunk i of the kept ones becomes the current chunk again (BAM: inflated and indexed again from the compressed bytes)
+    int select(uint64_t i, kbbq_fastq_chunk *info) { return bam ? kbbq_bam_reader_select(bam, i, info) : kbbq_fastq_reader_select(reader, i, info); }
+    // the kept text of the current chunk goes with this resident batch (FASTQ only: the BAM reader has no such call)
+    int attach(const kbbq_reads *batch) { return bam ? 0 : kbbq_fastq_reader_attach(reader, batch); }
+    void kernel_ms(double &inflate, double &index) { inflate = index = 0; if (bam) kbbq_bam_reader_kernel_ms(bam, &inflate, &index); else kbbq_fastq_reader_kernel_ms(reader, &inflate, &index); }
+    // The current chunk with new qualities to the writer, text assembled from the device's own copy of the input
+    // (kbbq_fastq_reader_write; kbbq_bam_reader_write: BamFile::recalibrate + write of every record on the device)
+    bool write_chunk(DeviceBgzfWriter &out, const uint8_t *d_qual, bool set_oq, void *after_stream) {
+        return out.submit([&](kbbq_bgzf *z) {
+            return bam ? kbbq_bam_reader_write(bam, z, d_qual, set_oq ? 1 : 0, after_stream) : kbbq_fastq_reader_write(reader, z, d_qual, after_stream);
+        });
+    }
 
 private:
     void stop_io() {
@@ -706,16 +799,17 @@ private:
     }
     static constexpr uint64_t kFront = 1ull << 16;
     // bytes of the file per chunk; KBBQ_READER_PIECE_KB shrinks it so that tests cross many chunk boundaries with small files
-    const uint64_t kPiece = getenv("KBBQ_READER_PIECE_KB") ? std::max<uint64_t>(64, strtoull(getenv("KBBQ_READER_PIECE_KB"), nullptr, 10)) << 10 : 256ull << 20;
+    const uint64_t kPiece;
+    const bool preload_;      // KBBQ_PRELOAD
     int fd_ = -1;
-    uint64_t size_ = 0, next_piece_ = 0, taken_piece_ = 0, left_ = 0, piece_bytes_[2] = {0, 0};
+    uint64_t size_ = 0, taken_piece_ = 0, left_ = 0, piece_bytes_[2] = {0, 0};
     uint8_t *buf_[2] = {nullptr, nullptr};
     uint8_t carry_[1 << 16];
     std::thread io_;
     std::mutex mu_;
     std::condition_variable cv_;
     bool filled_[2] = {false, false}, io_error_ = false, quit_ = false;
-    bool bam_mode_ = false, bgzf_ = false;
+    bool bgzf_ = false;
 };
 
 // What the output pass needs of one batch besides the new qualities, kept from the first scan when it fits in
@@ -787,7 +881,7 @@ struct Batch {
         std::vector<int> rg_map;
         bool complex = false;
         int lens_per_record = 3;                    // RecordStore's layout: FASTQ 3 lengths per record, BAM 1
-        double wait_s = 0;                          // time spent waiting for the parsers' next piece
+        int copy_threads = 1;                       // CliOptions::io_threads: up to 8 of them copy a batch's segments
     };
     // The pieces' arrays are copied into the batch's by a few threads at once (the segments and their places are known
     // first): one thread moved 580 bytes per BAM record -- sequence, qualities, the alignment block -- at 5 GB/s, which was
@@ -813,9 +907,7 @@ struct Batch {
                 return false;
             }
             if (!f.cur || f.at == f.cur->n()) {
-                const auto tw = std::chrono::steady_clock::now();
                 f.cur = f.parser->next();
-                f.wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
                 f.at = 0;
                 if (!f.cur) break;
                 if (f.cur->complex) { f.complex = true; return false; }
@@ -864,7 +956,7 @@ struct Batch {
                        (size_t)f.lens_per_record * (g.b - g.a) * sizeof(uint32_t));
             }
         };
-        const size_t n_threads = std::min<size_t>(segs.size(), (size_t)std::max(1, std::min(g_io_threads, 8)));
+        const size_t n_threads = std::min<size_t>(segs.size(), (size_t)std::max(1, std::min(f.copy_threads, 8)));
         if (n_threads <= 1) {
             for (size_t i = 0; i < segs.size(); ++i) copy_segment(i);
         } else {
@@ -916,13 +1008,6 @@ struct Batch {
     }
 };
 
-static uint64_t host_cache_budget() {
-    if (const char *s = getenv("KBBQ_HOST_CACHE_MB")) return strtoull(s, nullptr, 10) << 20;
-    const long pages = sysconf(_SC_PHYS_PAGES), psize = sysconf(_SC_PAGE_SIZE);
-    const uint64_t ram = pages > 0 && psize > 0 ? (uint64_t)pages * (uint64_t)psize : 0;
-    return std::min<uint64_t>(ram / 4, 64ULL << 30);
-}
-
 static int fail_engine(const char *what) {
     std::cerr << put_now << " Error: " << what << ": " << kbbq_last_error() << std::endl;
     return 1;
@@ -930,9 +1015,9 @@ static int fail_engine(const char *what) {
 
 // hidden helpers for the CPU test-suite: exercise the reader, the name rules and the BGZF writer
 // without touching the GPU
-static int io_test(int argc, char *argv[]) {
+static int io_test(int argc, char *argv[], const CliOptions &o) {
     const std::string what = argc > 2 ? argv[2] : "";
-    const int io_threads = getenv("KBBQ_IO_THREADS") ? atoi(getenv("KBBQ_IO_THREADS")) : 1;
+    const int io_threads = o.test_io_threads;
     if (what == "parse" && argc > 3) {
         FastqReader in(argv[3], io_threads);
         if (!in.ok()) return 2;
@@ -992,34 +1077,6 @@ static int io_test(int argc, char *argv[]) {
                    it.seq.c_str(), q.c_str());
         }
         printf("#end %d\n", rc);
-        return 0;
-    }
-    if (what == "bam-scan" && argc > 3) {     // the first scan's host side alone, timed: --io-test bam-scan FILE [parse threads] [keep records 0/1]
-        const int pt = argc > 4 ? atoi(argv[4]) : 4;
-        const bool keep = argc > 5 ? atoi(argv[5]) != 0 : true;
-        g_io_threads = io_threads;
-        const auto t0 = std::chrono::steady_clock::now();
-        Batch::Fast ff;
-        auto *bp = new BamChunkParser(argv[3], false, std::max(2, io_threads), pt, keep);
-        ff.parser.reset(bp);
-        ff.lens_per_record = 1;
-        if (!bp->ok()) return 2;
-        Batch batch;
-        batch.pack_on_host = false;
-        ReadGroups groups;
-        uint64_t reads = 0, bases = 0;
-        double fill_s = 0;
-        for (;;) {
-            RecordStore st;
-            const auto a = std::chrono::steady_clock::now();
-            if (!batch.fill_fast(ff, groups, (size_t)1 << 20, keep ? &st : nullptr)) break;
-            fill_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
-            reads += batch.c.n_reads;
-            bases += batch.c.n_bases;
-        }
-        const double all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        printf("reads %llu bases %llu wall %.3f s (in fill_fast %.3f s, of it waiting for pieces %.3f s) %.2f Gbases/s\n", (unsigned long long)reads,
-               (unsigned long long)bases, all, fill_s, ff.wait_s, bases / all / 1e9);
         return 0;
     }
     if (what == "bam-fast" && argc > 3) {     // the same lines from the block-parallel BAM parser: --io-test bam-fast FILE [use-oq] [threads]
@@ -1085,7 +1142,7 @@ static int io_test(int argc, char *argv[]) {
         kbbq_engine *e = nullptr;
         if (kbbq_engine_create(&prm, &e) < 0) { std::cerr << kbbq_last_error() << std::endl; return 1; }
         struct FreeEngine { kbbq_engine *e; ~FreeEngine() { kbbq_engine_destroy(e); } } free_engine{e};
-        DeviceBgzfWriter out(stdout, 0);
+        DeviceBgzfWriter out(stdout, 0, o.write_threads);
         if (!out.ok()) return 1;
         if (bam) {
             BamHeader h;
@@ -1110,327 +1167,237 @@ static int io_test(int argc, char *argv[]) {
     return 2;
 }
 
-int main(int argc, char *argv[]) {
-    if (argc > 1 && std::string(argv[1]) == "--io-test") return io_test(argc, argv);
-    int k = 32;
-    long double alpha = 0;
-    uint64_t genomelen = 0;
-    unsigned coverage = 0;
-    uint32_t seed = 0;
-    bool set_oq = false, use_oq = false;
-    int nthreads = 0;
-    std::string fixedinput;
-    int opt = 0, opt_idx = 0;
-    while ((opt = getopt_long(argc, argv, "k:usg:c:f:a:t:", long_options, &opt_idx)) != -1) {
-        switch (opt) {
-            case 'k':
-                k = std::stoi(std::string(optarg));
-                if (k <= 0 || k > KBBQ_MAX_KMER) {
-                    std::cerr << put_now << "  Error: k must be <= " << KBBQ_MAX_KMER << " and > 0." << std::endl;
-                    return 1;   // the reference only prints this and goes on (kbbq.cc:102-104)
-                }
-                break;
-            case 'u': use_oq = true; break;
-            case 's': set_oq = true; break;
-            case 'g': genomelen = std::stoull(std::string(optarg)); break;
-            case 'c': coverage = (unsigned)std::stoul(std::string(optarg)); break;
-            case 'f': fixedinput = std::string(optarg); break;
-            case 'a': alpha = std::stold(std::string(optarg)); break;
-            case 't':
-                nthreads = std::stoi(std::string(optarg));
-                if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
-                break;
-            case '?':
-            default:
-                std::cerr << put_now << "  Unknown argument " << (char)opt << std::endl;
-                return 1;
-        }
-    }
-    // --threads sizes the BGZF compression pool like the reference's htslib pool (kbbq.cc:159-168); unlike the
-    // reference, 0 does not mean "single-threaded" but "pick": the writer is the end-to-end bottleneck
-    const int out_threads = nthreads > 0 ? nthreads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    g_io_threads = out_threads;
-    std::string filename("-");
-    if (optind < argc) {
-        filename = std::string(argv[optind]);
-        while (++optind < argc) std::cerr << put_now << " Warning: Extra argument " << argv[optind] << " ignored." << std::endl;
-    }
-    const long double sampler_desiredfpr = 0.01, trusted_desiredfpr = 0.0005;   // kbbq.cc:155-156
+// Sets a switch for the length of one scope: the Batch switches that belong to one loop over the input.
+template <class T> struct ScopedSet {
+    T &ref;
+    const T old;
+    ScopedSet(T &r, T v) : ref(r), old(r) { ref = v; }
+    ~ScopedSet() { ref = old; }
+};
 
-    const Format fmt = sniff(filename);
-    if (fmt == Format::unknown) {
-        std::cerr << put_now << " Error opening file " << filename << std::endl;   // also: a pipe cannot be re-read by the passes
-        return 1;
+// The packed batches of the first scan in HBM (passes 1-4 run from there) and, when they fit in host memory, their records.
+struct Resident {
+    std::vector<kbbq_reads> dev;
+    std::vector<RecordStore> recs;      // the records of the same batches, when they fit in host memory
+    bool on = true, keep_recs = true;
+    uint64_t bytes = 0, budget = 0, rec_bytes = 0, rec_budget = 0;
+    Resident() = default;
+    Resident(const Resident &) = delete;
+    ~Resident() { drop(); }
+    void init(const CliOptions &o) {
+        on = true;
+        keep_recs = true;
+        bytes = rec_bytes = 0;
+        uint64_t free_b = 0, total_b = 0;
+        if (!o.resident || o.fixed_mode() || kbbq_device_memory(-1, &free_b, &total_b) < 0) on = false;
+        budget = (uint64_t)(0.6 * (double)free_b);
+        rec_budget = o.host_cache_budget();
+        if (!on || !rec_budget) keep_recs = false;
     }
-    if (fmt == Format::cram) {
-        std::cerr << put_now << " Error: CRAM input needs htslib, which this build does not have; use BAM or FASTQ." << std::endl;
-        return 1;
+    void drop_recs() {
+        std::vector<RecordStore>().swap(recs);
+        keep_recs = false;
     }
-    const bool is_bam = fmt == Format::bam;
-    // BGZF input that the host parsers read (BAM always) is inflated on the GPU as well
-    if (!(getenv("KBBQ_HOST_DEFLATE") && atoi(getenv("KBBQ_HOST_DEFLATE")) != 0) && !(getenv("KBBQ_DEVICE_INFLATE") && atoi(getenv("KBBQ_DEVICE_INFLATE")) == 0))
-        set_bgzf_source_factory(&DeviceBgzfSource::open);
+    void drop() {
+        for (auto &d : dev) { kbbq_reads_free_hints(&d); kbbq_reads_free(nullptr, &d); }
+        dev.clear();
+        drop_recs();
+        on = false;
+    }
+    // one more batch, made by make(&d), if it fits in the budget
+    template <class F> bool add(uint64_t need, F make) {
+        kbbq_reads d;
+        if (bytes + need > budget || make(&d) < 0) return false;
+        if (kbbq_reads_alloc_hints(&d) < 0) { kbbq_reads_free(nullptr, &d); return false; }
+        dev.push_back(d);
+        bytes += need;
+        return true;
+    }
+    // qualities 1 B + bases 1/4 + N mask 1/8 + two hint arrays 1/4 per base; offsets, flags, read groups (BAM: 18 B) per read
+    static uint64_t bytes_of(uint64_t n_bases, uint64_t n_reads, uint64_t per_read) { return n_bases * 13 / 8 + n_reads * per_read + (1 << 16); }
+};
 
-    // One scan before the engine exists: total length (the reference's coverage pass, kbbq.cc:229-250),
-    // read groups, longest read.  The packed batches of this scan are uploaded as they are made and stay
-    // resident in HBM, so passes 1-4 run from device memory instead of decoding the file four more times
-    // (288 GB of HBM hold a 30x human genome beside its filters); the records themselves are decoded once
-    // more, for the output pass.  Falls back to re-reading per pass if the batches do not fit (or with
-    // KBBQ_RESIDENT=0), and for the rare inputs where the passes would not see the same reads (an empty read
-    // ends the reference's sampling and coverage loops but not the others).
-    PhaseClock clock;
+// What the one scan before the engine exists finds out: total length (the reference's coverage pass, kbbq.cc:229-250),
+// read groups, longest read -- and the batches it left in HBM.
+struct ScanState {
     ReadGroups groups;
     uint64_t seqlen = 0, n_reads = 0;
     size_t longest = 0;
     BamHeader bam_header;
-    // reads per engine call; KBBQ_BATCH_READS shrinks it so that tests cross many batch boundaries with small files
-    const size_t batch_reads = getenv("KBBQ_BATCH_READS") ? std::max<size_t>(1, strtoull(getenv("KBBQ_BATCH_READS"), nullptr, 10)) : (size_t)1 << 20;
-    Batch batch;
-    struct Resident {
-        std::vector<kbbq_reads> dev;
-        std::vector<RecordStore> recs;      // the records of the same batches, when they fit in host memory
-        bool on = true, keep_recs = true;
-        uint64_t bytes = 0, budget = 0, rec_bytes = 0, rec_budget = 0;
-        void drop_recs() {
-            std::vector<RecordStore>().swap(recs);
-            keep_recs = false;
-        }
-        void drop() {
-            for (auto &d : dev) { kbbq_reads_free_hints(&d); kbbq_reads_free(nullptr, &d); }
-            dev.clear();
-            drop_recs();
-            on = false;
-        }
-    } resident;
-    const bool fixed_mode = !fixedinput.empty();
-    auto init_resident = [&]() {
-        resident.on = true;
-        resident.keep_recs = true;
-        resident.bytes = resident.rec_bytes = 0;
-        const char *env = getenv("KBBQ_RESIDENT");
-        uint64_t free_b = 0, total_b = 0;
-        if ((env && !strcmp(env, "0")) || fixed_mode || kbbq_device_memory(-1, &free_b, &total_b) < 0) resident.on = false;
-        resident.budget = (uint64_t)(0.6 * (double)free_b);
-        resident.rec_budget = host_cache_budget();
-        if (!resident.on || !resident.rec_budget) resident.keep_recs = false;
-    };
-    init_resident();
-    // The first scan parses its input with a pool: BAM always (bam_io.h: BamChunkParser), FASTQ when it is strictly
-    // four-line (fastq_io.h: FastqChunkParser) -- anything else, found out while parsing, starts the scan over with the
-    // serial reader.  KBBQ_SERIAL_PARSE=1: the serial readers at once.
-    // A FASTQ file -- BGZF, any other gzip stream or uncompressed -- is read on the GPU (DeviceFastqInput): the file's bytes
-    // go to the device, which inflates, finds the records and packs them; every chunk of the file is one resident batch.
-    // Anything that path does not take -- standard input, records that are not four lines, read groups in the names, reads that do not fit in HBM
-    // -- starts over with the host parsers below.  KBBQ_DEVICE_READER=0: the host parsers at once.
-    DeviceFastqInput dev_in;
-    // (KBBQ_HOST_DEFLATE=1, the zlib writer of rounds 1-2, goes with the host readers: the A/B of the whole host I/O path)
-    const bool host_io = getenv("KBBQ_HOST_DEFLATE") && atoi(getenv("KBBQ_HOST_DEFLATE")) != 0;
-    if (!is_bam && !fixed_mode && !host_io && resident.on && filename != "-" && !(getenv("KBBQ_DEVICE_READER") && atoi(getenv("KBBQ_DEVICE_READER")) == 0) &&
-        !(getenv("KBBQ_SERIAL_PARSE") && atoi(getenv("KBBQ_SERIAL_PARSE"))) && dev_in.open(filename)) {
-        bool ok = true;
-        // The inflated text stays in HBM beside the packed reads while both fit in three quarters of the free memory
-        // (resident.budget is 60 %): pass 4 then takes the record text from there and the file is read and inflated once.
-        // KBBQ_KEEP_TEXT=0: pass 4 reads the file again.
-        bool keeping = !(getenv("KBBQ_KEEP_TEXT") && atoi(getenv("KBBQ_KEEP_TEXT")) == 0) && kbbq_fastq_reader_keep(dev_in.reader, 1) == 0;
-        const uint64_t text_budget = resident.budget / 4 * 5;
-        for (;;) {
-            kbbq_fastq_chunk info;
-            const int rc = dev_in.next_chunk(info);
-            if (rc == 0) break;
-            if (rc < 0) { ok = false; break; }
-            dev_in.chunk_records.push_back(info.n_records);
-            if (!info.n_records) continue;
-            const uint64_t need = info.n_bases * 13 / 8 + info.n_records * 16 + (1 << 16);
-            if (keeping) {
-                uint64_t kept_chunks = 0, kept_bytes = 0;
-                if (kbbq_fastq_reader_kept(dev_in.reader, &kept_chunks, &kept_bytes) < 0 || resident.bytes + need + kept_bytes > text_budget) {
-                    kbbq_fastq_reader_keep(dev_in.reader, 0);
-                    keeping = false;
-                }
-            }
-            kbbq_reads d;
-            const auto tb = std::chrono::steady_clock::now();
-            if (info.longest > KBBQ_MAX_READ_LEN || resident.bytes + need > resident.budget || kbbq_fastq_reader_batch(dev_in.reader, &d) < 0) { ok = false; break; }
-            if (kbbq_reads_alloc_hints(&d) < 0) { kbbq_reads_free(nullptr, &d); ok = false; break; }
-            dev_in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
-            resident.dev.push_back(d);
-            resident.bytes += need;
-            seqlen += info.n_bases;
-            n_reads += info.n_records;
-            longest = std::max<size_t>(longest, info.longest);
-        }
-        if (ok && n_reads) {
-            dev_in.active = true;
-            uint64_t kept_chunks = 0;
-            if (kbbq_fastq_reader_rewind(dev_in.reader) == 0 && kbbq_fastq_reader_kept(dev_in.reader, &kept_chunks, &dev_in.kept_bytes) == 0)
-                dev_in.text_kept = kept_chunks == resident.dev.size();
-            if (!dev_in.text_kept) { kbbq_fastq_reader_keep(dev_in.reader, 0); dev_in.kept_bytes = 0; }
-            resident.keep_recs = false;      // the record text comes from the device's own copy of the input in pass 4
-            groups.index_of(std::string());  // FASTQ without read-group fields: the one read group "" (readutils.cc:98-103)
-        } else {
-            seqlen = n_reads = 0;
-            longest = 0;
-            resident.drop();
-            init_resident();
-            dev_in.close();
-        }
+    Resident resident;
+    bool scan_fast = false;      // the block-parallel parser read the whole stream
+    bool any_empty = false;      // some read was empty
+    // forget what a scan found: the next way of reading the input starts over
+    void reset(const CliOptions &o) {
+        groups = ReadGroups();
+        seqlen = n_reads = 0;
+        longest = 0;
+        scan_fast = any_empty = false;
+        resident.drop();
+        resident.init(o);
     }
-    // A BAM file takes the same road (DeviceFastqInput::open_bam; include/kbbq_bgzf.h: kbbq_bam_reader): the header is
-    // parsed here (its reference lengths are the genome length, kbbq.cc:196-216; its @RG ids are the table the record
-    // kernel looks read groups up in), everything behind it on the device.  The compressed bytes of every chunk stay in HBM
-    // for pass 4 while they fit; otherwise pass 4 reads the file again.  A shape that path does not take -- a read group
-    // without an @RG line, a record the host codec would report or end the stream on -- starts over with BamChunkParser.
-    if (is_bam && !fixed_mode && !host_io && resident.on && filename != "-" && !(getenv("KBBQ_DEVICE_READER") && atoi(getenv("KBBQ_DEVICE_READER")) == 0) &&
-        !(getenv("KBBQ_SERIAL_PARSE") && atoi(getenv("KBBQ_SERIAL_PARSE")))) {
-        BamReader head(filename, 1);
-        bool ok = head.ok();
+    // Passes 1-3 of the streaming mode (the reads did not stay in HBM) read the file through the block-parallel parser as
+    // well when the first scan found the stream of its shape and no empty read in it (an empty read ends the reference's
+    // sampling loop: the serial reader's case); the serial reader otherwise.  (scan_fast is a host scan's: never the device reader's.)
+    bool passes_fast() const { return scan_fast && !any_empty; }
+};
+
+struct EngineOwner {
+    kbbq_engine *e = nullptr;
+    ~EngineOwner() { release(); }
+    void release() { if (e) kbbq_engine_destroy(e); e = nullptr; }
+};
+
+// the ID fields of the @RG lines (SAMv1 1.3: tab-separated TAG:VALUE fields)
+static std::vector<std::string> read_group_ids(const std::string &header_text) {
+    std::vector<std::string> rg_ids;
+    std::istringstream lines(header_text);
+    for (std::string line; std::getline(lines, line);) {
+        if (line.compare(0, 3, "@RG") != 0) continue;
+        std::istringstream fields(line);
+        for (std::string field; std::getline(fields, field, '\t');)
+            if (field.size() >= 3 && field.compare(0, 3, "ID:") == 0) { rg_ids.push_back(field.substr(3)); break; }
+    }
+    return rg_ids;
+}
+
+// The first scan on the device.  A FASTQ file -- BGZF, any other gzip stream or uncompressed -- is read on the GPU
+// (DeviceFastqInput): the file's bytes go to the device, which inflates, finds the records and packs them; every chunk of the
+// file is one resident batch.  A BAM file takes the same road (DeviceFastqInput::open_bam; include/kbbq_bgzf.h:
+// kbbq_bam_reader): the header is parsed here (its reference lengths are the genome length, kbbq.cc:196-216; its @RG ids are
+// the table the record kernel looks read groups up in), everything behind it on the device.  The inflated text (BAM: the
+// compressed bytes) of every chunk stays in HBM for pass 4 while it fits; otherwise pass 4 reads the file again.
+// false: a shape this path does not take -- records that are not four lines, read groups in the names, a read group without
+// an @RG line, a record the host codec would report or end the stream on, reads that do not fit in HBM -- and the scan
+// state is as it was before: the caller starts over with the host parsers.
+static bool device_scan(const CliOptions &o, DeviceFastqInput &in, ScanState &s) {
+    Resident &resident = s.resident;
+    std::vector<std::string> rg_ids;
+    bool ok;
+    if (o.is_bam) {
+        BamReader head(o.filename, 1);
+        ok = head.ok();
         if (ok) {
-            bam_header = head.header();
-            uint64_t header_bytes = 12 + bam_header.text.size();
-            for (auto &r : bam_header.refs) header_bytes += 8 + r.first.size() + 1;
-            // the ID fields of the @RG lines (SAMv1 1.3: tab-separated TAG:VALUE fields)
-            std::vector<std::string> rg_ids;
-            {
-                const std::string &t = bam_header.text;
-                for (size_t at = 0; at < t.size();) {
-                    size_t eol = t.find('\n', at);
-                    if (eol == std::string::npos) eol = t.size();
-                    if (eol - at >= 3 && t.compare(at, 3, "@RG") == 0) {
-                        for (size_t f = at; f < eol;) {
-                            size_t tab = t.find('\t', f);
-                            if (tab == std::string::npos || tab > eol) tab = eol;
-                            if (tab - f >= 3 && t.compare(f, 3, "ID:") == 0) { rg_ids.push_back(t.substr(f + 3, tab - f - 3)); break; }
-                            f = tab + 1;
-                        }
-                    }
-                    at = eol + 1;
-                }
-            }
-            ok = !rg_ids.empty() && rg_ids.size() < 65535 && dev_in.open_bam(filename, use_oq, (int32_t)bam_header.refs.size(), header_bytes, rg_ids);
-            bool keeping = ok && !(getenv("KBBQ_KEEP_TEXT") && atoi(getenv("KBBQ_KEEP_TEXT")) == 0) && kbbq_bam_reader_keep(dev_in.bam, 1) == 0;
-            const uint64_t text_budget = resident.budget / 4 * 5;
-            while (ok) {
-                kbbq_bam_chunk info;
-                const int rc = dev_in.next_chunk(info);
-                if (rc == 0) break;
-                if (rc < 0) { ok = false; break; }
-                dev_in.chunk_records.push_back(info.n_records);
-                if (!info.n_records) continue;
-                const uint64_t need = info.n_bases * 13 / 8 + info.n_records * 18 + (1 << 16);
-                if (keeping) {
-                    uint64_t kept_chunks = 0, kept_bytes = 0;
-                    if (kbbq_bam_reader_kept(dev_in.bam, &kept_chunks, &kept_bytes) < 0 || resident.bytes + need + kept_bytes > text_budget) {
-                        kbbq_bam_reader_keep(dev_in.bam, 0);
-                        keeping = false;
-                    }
-                }
-                kbbq_reads d;
-                const auto tb = std::chrono::steady_clock::now();
-                if (info.longest > KBBQ_MAX_READ_LEN || resident.bytes + need > resident.budget || kbbq_bam_reader_batch(dev_in.bam, &d) < 0) { ok = false; break; }
-                if (kbbq_reads_alloc_hints(&d) < 0) { kbbq_reads_free(nullptr, &d); ok = false; break; }
-                dev_in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
-                resident.dev.push_back(d);
-                resident.bytes += need;
-                seqlen += info.n_bases;
-                n_reads += info.n_records;
-                longest = std::max<size_t>(longest, info.longest);
-                if (info.shortest == 0) ok = false;      // an empty read ends the reference's coverage and sampling loops: the host path's case
-            }
-            if (ok && set_oq && dev_in.oq_unwritable) ok = false;      // bam_aux_update_str would fail on some record: the host path reports it
-            if (ok && n_reads) {
-                // read groups in the order of their first records, as rg_to_int numbers them (readutils.cc:53-57)
-                std::vector<uint32_t> order(rg_ids.size());
-                uint32_t n_groups = 0;
-                if (kbbq_bam_reader_read_groups(dev_in.bam, order.data(), (uint32_t)order.size(), &n_groups) < 0) ok = false;
-                for (uint32_t g = 0; ok && g < n_groups; ++g) groups.index_of(rg_ids[order[g]]);
-            }
+            s.bam_header = head.header();
+            uint64_t header_bytes = 12 + s.bam_header.text.size();
+            for (auto &r : s.bam_header.refs) header_bytes += 8 + r.first.size() + 1;
+            rg_ids = read_group_ids(s.bam_header.text);
+            ok = !rg_ids.empty() && rg_ids.size() < 65535 && in.open_bam(o.filename, o.use_oq, (int32_t)s.bam_header.refs.size(), header_bytes, rg_ids);
         }
-        if (ok && n_reads) {
-            dev_in.active = true;
-            uint64_t kept_chunks = 0;
-            if (kbbq_bam_reader_rewind(dev_in.bam) == 0 && kbbq_bam_reader_kept(dev_in.bam, &kept_chunks, &dev_in.kept_bytes) == 0)
-                dev_in.text_kept = kept_chunks == resident.dev.size();
-            if (!dev_in.text_kept) { kbbq_bam_reader_keep(dev_in.bam, 0); dev_in.kept_bytes = 0; }
-            resident.keep_recs = false;      // the records come from the device's own copy of the input in pass 4
-        } else {
-            groups = ReadGroups();
-            seqlen = n_reads = 0;
-            longest = 0;
-            resident.drop();
-            init_resident();
-            dev_in.close();
-        }
+    } else {
+        ok = in.open(o.filename);
     }
-    batch.pack_on_host = false;      // (the scan's batches only ever go to the device: packed there)
-    bool scan_fast = false, any_empty = false;
-    for (int attempt = 0; attempt < 2 && !dev_in.active; ++attempt) {
-        const bool fast = attempt == 0 && g_io_threads > 1 && !(getenv("KBBQ_SERIAL_PARSE") && atoi(getenv("KBBQ_SERIAL_PARSE")));
-        if (attempt == 1) {
-            groups = ReadGroups();
-            seqlen = n_reads = 0;
-            longest = 0;
-            resident.drop();
-            init_resident();
+    // The text stays in HBM beside the packed reads while both fit in three quarters of the free memory
+    // (resident.budget is 60 %): pass 4 then takes the record text from there and the file is read and inflated once.
+    // KBBQ_KEEP_TEXT=0: pass 4 reads the file again.
+    bool keeping = ok && o.keep_text && in.keep(true) == 0;
+    const uint64_t text_budget = resident.budget / 4 * 5;
+    while (ok) {
+        kbbq_fastq_chunk info;
+        const int rc = in.next_chunk(info);
+        if (rc == 0) break;
+        if (rc < 0) { ok = false; break; }
+        in.chunk_records.push_back(info.n_records);
+        if (!info.n_records) continue;
+        const uint64_t need = Resident::bytes_of(info.n_bases, info.n_records, o.is_bam ? 18 : 16);
+        if (keeping) {
+            uint64_t kept_chunks = 0, kept_bytes = 0;
+            if (in.kept(&kept_chunks, &kept_bytes) < 0 || resident.bytes + need + kept_bytes > text_budget) {
+                in.keep(false);
+                keeping = false;
+            }
         }
+        const auto tb = std::chrono::steady_clock::now();
+        if (info.longest > KBBQ_MAX_READ_LEN || !resident.add(need, [&](kbbq_reads *d) { return in.batch(d); })) { ok = false; break; }
+        in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
+        s.seqlen += info.n_bases;
+        s.n_reads += info.n_records;
+        s.longest = std::max<size_t>(s.longest, info.longest);
+        if (o.is_bam && info.shortest == 0) ok = false;      // an empty read ends the reference's coverage and sampling loops: the host path's case
+    }
+    if (ok && o.set_oq && in.oq_unwritable) ok = false;      // bam_aux_update_str would fail on some record: the host path reports it
+    if (ok && s.n_reads && o.is_bam) {
+        // read groups in the order of their first records, as rg_to_int numbers them (readutils.cc:53-57)
+        std::vector<uint32_t> order(rg_ids.size());
+        uint32_t n_groups = 0;
+        if (kbbq_bam_reader_read_groups(in.bam, order.data(), (uint32_t)order.size(), &n_groups) < 0) ok = false;
+        for (uint32_t g = 0; ok && g < n_groups; ++g) s.groups.index_of(rg_ids[order[g]]);
+    }
+    if (ok && s.n_reads && !o.is_bam) s.groups.index_of(std::string());  // FASTQ without read-group fields: the one read group "" (readutils.cc:98-103)
+    if (!ok || !s.n_reads) {
+        s.reset(o);
+        in.close();
+        return false;
+    }
+    in.active = true;
+    uint64_t kept_chunks = 0;
+    if (in.rewind() == 0 && in.kept(&kept_chunks, &in.kept_bytes) == 0) in.text_kept = kept_chunks == resident.dev.size();
+    if (!in.text_kept) { in.keep(false); in.kept_bytes = 0; }
+    resident.keep_recs = false;      // the records come from the device's own copy of the input in pass 4
+    return true;
+}
+
+// The block-parallel parser of the input (bam_io.h: BamChunkParser; fastq_io.h: FastqChunkParser) into `f`; false: it cannot
+// read the file.  `header`, when given, receives a BAM file's header.
+static bool open_fast(const CliOptions &o, bool keep_records, Batch::Fast &f, BamHeader *header) {
+    f.copy_threads = o.io_threads;
+    if (o.is_bam) {
+        auto *bp = new BamChunkParser(o.filename, o.use_oq, o.io_threads, o.out_threads, keep_records);
+        f.parser.reset(bp);
+        f.lens_per_record = 1;
+        if (bp->ok() && header) *header = bp->header();
+        return bp->ok();
+    }
+    auto *fp = new FastqChunkParser(o.filename, o.io_threads, o.out_threads, keep_records);
+    f.parser.reset(fp);
+    return fp->ok();
+}
+
+// The first scan with the host parsers.  They parse the input with a pool: BAM always (bam_io.h: BamChunkParser), FASTQ when
+// it is strictly four-line (fastq_io.h: FastqChunkParser) -- anything else, found out while parsing, starts the scan over
+// with the serial reader.  KBBQ_SERIAL_PARSE=1: the serial readers at once.  The packed batches of this scan are uploaded
+// as they are made and stay resident in HBM, so passes 1-4 run from device memory instead of decoding the file four more
+// times (288 GB of HBM hold a 30x human genome beside its filters); the records themselves are decoded once more, for the
+// output pass.  Falls back to re-reading per pass if the batches do not fit (or with KBBQ_RESIDENT=0), and for the rare
+// inputs where the passes would not see the same reads (an empty read ends the reference's sampling and coverage loops
+// but not the others).  Returns the exit status: 0, or 1 with the message on stderr.
+static int host_scan(const CliOptions &o, ScanState &s, Batch &batch) {
+    ScopedSet<bool> packed_on_device(batch.pack_on_host, false);      // (the scan's batches only ever go to the device: packed there)
+    Resident &resident = s.resident;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const bool fast = attempt == 0 && o.io_threads > 1 && !o.serial_parse;
+        if (attempt == 1) s.reset(o);
         std::unique_ptr<Source> in;
         Batch::Fast ff;
-        if (fast && is_bam) {
-            auto *bp = new BamChunkParser(filename, use_oq, g_io_threads, out_threads, resident.on && resident.keep_recs);
-            ff.parser.reset(bp);
-            ff.lens_per_record = 1;
-            if (!bp->ok()) {
-                std::cerr << put_now << " Error opening file " << filename << std::endl;
-                return 1;
-            }
-            bam_header = bp->header();
-        } else if (fast) {
-            auto *fp = new FastqChunkParser(filename, g_io_threads, out_threads, resident.on && resident.keep_recs);
-            ff.parser.reset(fp);
-            if (!fp->ok()) {
-                std::cerr << put_now << " Error opening file " << filename << std::endl;
-                return 1;
-            }
+        if (fast) {
+            if (!open_fast(o, resident.on && resident.keep_recs, ff, &s.bam_header)) return give_up(" Error opening file " + o.filename);
         } else {
-            in = open_source(filename, is_bam, use_oq);
-            if (!in->ok()) {
-                std::cerr << put_now << " Error opening file " << filename << std::endl;
-                return 1;
-            }
-            if (is_bam) bam_header = static_cast<BamSource *>(in.get())->header();
+            in = open_source(o, o.filename);
+            if (!in->ok()) return give_up(" Error opening file " + o.filename);
         }
+        if (!fast && o.is_bam) s.bam_header = static_cast<BamSource *>(in.get())->header();
         bool counting = true;    // the coverage pass stops at the first empty read; the other passes do not
-        scan_fast = fast;
+        s.scan_fast = fast;
         for (;;) {
             const bool keep = resident.on && resident.keep_recs;
             RecordStore st;
-            if (!(fast ? batch.fill_fast(ff, groups, batch_reads, keep ? &st : nullptr) : batch.fill(*in, groups, batch_reads, keep, is_bam))) break;
+            if (!(fast ? batch.fill_fast(ff, s.groups, o.batch_reads, keep ? &st : nullptr) : batch.fill(*in, s.groups, o.batch_reads, keep, o.is_bam))) break;
             for (size_t r = 0; r < batch.c.n_reads && counting; ++r) {
                 const uint64_t l = batch.off[r + 1] - batch.off[r];
-                if (l == 0) counting = false; else seqlen += l;
+                if (l == 0) counting = false; else s.seqlen += l;
             }
-            longest = std::max(longest, batch.longest);
-            n_reads += batch.c.n_reads;
-            if (batch.saw_empty) any_empty = true;
+            s.longest = std::max(s.longest, batch.longest);
+            s.n_reads += batch.c.n_reads;
+            if (batch.saw_empty) s.any_empty = true;
             if (batch.saw_empty && resident.on) resident.drop();
             if (resident.on && batch.longest <= KBBQ_MAX_READ_LEN) {
-                // qualities 1 B + bases 1/4 + N mask 1/8 + two hint arrays 1/4 per base; offsets, flags, read groups per read
-                const uint64_t need = batch.c.n_bases * 13 / 8 + batch.c.n_reads * 16 + (1 << 16);
-                kbbq_reads d;
-                if (resident.bytes + need > resident.budget ||
-                    (batch.pack_on_host ? kbbq_reads_upload(nullptr, &batch.c, &d) : kbbq_reads_upload_text(nullptr, &batch.c, batch.seq.data(), &d)) < 0) {
-                    resident.drop();
-                } else if (kbbq_reads_alloc_hints(&d) < 0) {
-                    kbbq_reads_free(nullptr, &d);
-                    resident.drop();
-                } else {
-                    resident.dev.push_back(d);
-                    resident.bytes += need;
-                }
+                const uint64_t need = Resident::bytes_of(batch.c.n_bases, batch.c.n_reads, 16);
+                if (!resident.add(need, [&](kbbq_reads *d) { return kbbq_reads_upload_text(nullptr, &batch.c, batch.seq.data(), d); })) resident.drop();
             }
             if (resident.on && resident.keep_recs) {
                 if (!fast) {
-                    st.lens.reserve(batch.c.n_reads * (is_bam ? 1 : 3));
-                    if (is_bam) for (auto &b : batch.bam_recs) st.add(b);
+                    st.lens.reserve(batch.c.n_reads * (o.is_bam ? 1 : 3));
+                    if (o.is_bam) for (auto &b : batch.bam_recs) st.add(b);
                     else for (auto &f : batch.fq_recs) st.add(f);
                 }
                 resident.rec_bytes += st.bytes();
@@ -1439,693 +1406,704 @@ int main(int argc, char *argv[]) {
             }
         }
         if (batch.fatal) return 1;
-        if (fast && ff.complex) { scan_fast = false; continue; }
+        if (fast && ff.complex) { s.scan_fast = false; continue; }
         break;
     }
-    // Passes 1-3 of the streaming mode (the reads did not stay in HBM) read the file through the block-parallel parser as
-    // well when the first scan found the stream of its shape and no empty read in it (an empty read ends the reference's
-    // sampling loop: the serial reader's case); the serial reader otherwise.
-    struct PassInput {
+    return 0;
+}
+
+// The reads of one engine for passes 1-3, in file order: batches in device memory (every resident one, or the shard of one
+// rank, whose k-mer ordinals are known beforehand), or -- `host` set -- host batches that every pass parses from the file again.
+struct PassBatches {
+    const std::vector<kbbq_reads> *dev;
+    const uint64_t *ordinal;      // global k-mer ordinal of every device batch, or null: counted while pass 1 runs
+    Batch *host;
+    const CliOptions *opt;
+    ScanState *scan;
+    bool fatal() const { return host && host->fatal; }      // a parser gave up; its message is on stderr
+    // f(batch, index) for every batch; false when f said so.  stop_at_empty: pass 1 ends at the first empty read (kbbq.cc:234).
+    template <class F> bool each(bool stop_at_empty, F f) const {
+        if (!host) {
+            for (size_t i = 0; i < dev->size(); ++i) if (!f((*dev)[i], i)) return false;
+            return true;
+        }
+        // the block-parallel parser when the scan allows it, the serial reader otherwise
         std::unique_ptr<Source> serial;
         Batch::Fast fast;
-        bool use_fast = false;
-        bool next(Batch &b, ReadGroups &g, size_t max_reads) {
-            return use_fast ? b.fill_fast(fast, g, max_reads, nullptr) : b.fill(*serial, g, max_reads, false);
-        }
-    };
-    const bool passes_fast = scan_fast && !any_empty && !dev_in.active;
-    auto open_pass = [&]() -> std::unique_ptr<PassInput> {
-        std::unique_ptr<PassInput> in(new PassInput);
-        if (passes_fast) {
-            in->use_fast = true;
-            if (is_bam) { in->fast.parser.reset(new BamChunkParser(filename, use_oq, g_io_threads, out_threads, false)); in->fast.lens_per_record = 1; }
-            else in->fast.parser.reset(new FastqChunkParser(filename, g_io_threads, out_threads, false));
-        } else {
-            in->serial = open_source(filename, is_bam, use_oq);
-        }
-        return in;
-    };
-    batch.pack_on_host = true;       // (streaming passes hand host batches to the engine)
-    if (longest > KBBQ_MAX_READ_LEN) {
-        std::cerr << put_now << " Error: reads longer than " << KBBQ_MAX_READ_LEN << " bases are not supported by the GPU engine." << std::endl;
+        if (scan->passes_fast()) (void)open_fast(*opt, false, fast, nullptr);
+        else serial = open_source(*opt, opt->filename);
+        ScopedSet<bool> stop(host->stop_at_empty, stop_at_empty);
+        bool ok = true;
+        for (size_t i = 0; ok && (serial ? host->fill(*serial, scan->groups, opt->batch_reads, false) : host->fill_fast(fast, scan->groups, opt->batch_reads, nullptr)); ++i)
+            ok = f(host->c, i);
+        host->ended = false;
+        return ok;
+    }
+};
+
+// Passes 1-3 for one engine: sampling (kbbq.cc:277-283), the thresholds with their report and gate (kbbq.cc:304-331),
+// trusted k-mers (kbbq.cc:333-337), errors (kbbq.cc:363-366).  With an exchange group the engine is one rank of several
+// (include/kbbq_exchange.h): the filters and histograms are summed over the group after each pass and the printed counts
+// are the group's totals; `prints` says whether this rank writes the log lines and marks the clock.  die(what) reports an
+// engine error: it returns the exit status, or -- a rank of several -- ends the process.  Returns 0, or the exit status.
+template <class Die>
+static int run_passes(kbbq_engine *e, const CliOptions &o, long double alpha, const PassBatches &reads, kbbq_group *grp, bool prints, PhaseClock &clock, Die die) {
+    // (a single device counts a batch's k-mers behind its sampling call: the count overlaps the sampling kernels)
+    uint64_t ordinal = 0, nk = 0;
+    bool ok = reads.each(true, [&](const kbbq_reads &b, size_t i) {
+        if (reads.ordinal) return kbbq_sample_batch(e, &b, reads.ordinal[i]) >= 0;
+        if (kbbq_sample_batch(e, &b, ordinal) < 0 || kbbq_count_kmer_positions(e, &b, &nk) < 0) return false;
+        ordinal += nk;
+        return true;
+    });
+    if (!ok) return die("sampling");
+    if (reads.fatal()) return 1;
+    uint64_t inserted = 0, total = 0;
+    if (kbbq_sample_finish(e, &inserted) < 0 || (grp && kbbq_exchange_filter(e, 0, grp, 0, &total) < 0)) return die("sampling");
+    if (prints) std::cerr << put_now << " Sampled " << (grp ? total : inserted) << " valid kmers." << std::endl;
+    // every rank computes the same thresholds from the same (global) filter and count
+    char alpha_text[64], p_text[64];
+    snprintf(alpha_text, sizeof alpha_text, "%.25Le", alpha);
+    std::vector<int32_t> thresholds(o.k + 1);
+    double fprd = 0;
+    const int gate = kbbq_compute_thresholds(e, alpha_text, thresholds.data(), &fprd, p_text, sizeof p_text);
+    if (gate < 0) return die("thresholds");
+    const long double fpr = fprd;
+    if (prints) std::cerr << put_now << " Approximate false positive rate: " << fpr << std::endl;
+    if (gate == 1) {      // (every rank sees the same gate)
+        if (prints)
+            std::cerr << put_now << " Error: false positive rate is too high. "
+                      << "Increase genomelen parameter and try again." << std::endl;
         return 1;
     }
+    if (prints) {
+        const long double p_hit = strtold(p_text, nullptr);
+        std::cerr << put_now << " log CDF: [ ";
+        for (long double c : log_binom_cdf_values((unsigned long long)o.k, p_hit)) std::cerr << c << " ";
+        std::cerr << "]" << std::endl;
+        clock.mark("pass1");
+        std::cerr << put_now << " Finding trusted kmers" << std::endl;
+    }
+    ok = reads.each(false, [&](const kbbq_reads &b, size_t) { return kbbq_trusted_batch(e, &b, nullptr) >= 0; });
+    if (!ok) return die("finding trusted kmers");
+    if (reads.fatal()) return 1;
+    uint64_t trusted_inserted = 0;
+    if (kbbq_trusted_finish(e, grp ? nullptr : &trusted_inserted) < 0 || (grp && kbbq_exchange_filter(e, 1, grp, 0, &trusted_inserted) < 0))
+        return die("finding trusted kmers");
+    if (prints && o.qual_digest)      // (the reference prints no count here; bench.py's result.trusted_inserted)
+        std::cerr << "[digest] trusted_inserted " << trusted_inserted << std::endl;
+    if (prints) {
+        clock.mark("pass2");
+        std::cerr << put_now << " Finding errors" << std::endl;
+    }
+    ok = reads.each(false, [&](const kbbq_reads &b, size_t) { return kbbq_errors_batch(e, &b, nullptr) >= 0; });
+    if (!ok) return die("finding errors");
+    if (reads.fatal()) return 1;
+    if (grp && kbbq_exchange_histograms(e, grp) < 0) return die("summing the histograms");
+    return 0;
+}
 
+// kbbq.cc:405-407; in a group rank 0 trains and the tables are broadcast
+template <class Die>
+static int train_model(kbbq_engine *e, kbbq_group *grp, bool prints, PhaseClock &clock, Die die) {
+    if (prints) {
+        clock.mark("pass3");
+        std::cerr << put_now << " Training model" << std::endl;
+    }
+    if ((grp ? kbbq_exchange_dq(e, grp) : kbbq_train(e)) < 0) return die("training");
+    return 0;
+}
+
+// What the reference derives before it samples (kbbq.cc:196-270): genome length, coverage, the sampling rate `alpha`, and
+// with them the engine's alpha, approx_kmers and seed.  false: the message is on stderr.
+static bool derive_sampling(const CliOptions &o, const ScanState &s, kbbq_params &p, long double &alpha) {
+    uint64_t genomelen = o.genomelen;
+    unsigned coverage = o.coverage;
+    alpha = o.alpha;
+    if (genomelen == 0) {   // kbbq.cc:196-216
+        if (!o.is_bam) return !give_up(" Error: --genomelen must be specified if input is not a bam.");
+        std::cerr << put_now << " Estimating genome length" << std::endl;
+        genomelen = s.bam_header.genome_length();
+        if (genomelen == 0)
+            return !give_up(" Header does not contain genome information."
+                            " Unable to estimate genome length; please provide it on the command line"
+                            " using the --genomelen option.");
+        std::cerr << put_now << " Genome length is " << genomelen << " bp." << std::endl;
+    }
+    if (alpha == 0) {   // kbbq.cc:227-252
+        std::cerr << put_now << " Estimating alpha." << std::endl;
+        if (coverage == 0) {
+            std::cerr << put_now << " Estimating coverage." << std::endl;
+            if (s.seqlen == 0) return !give_up(" Error: total sequence length in file " + o.filename + " is 0. Check that the file isn't empty.");
+            std::cerr << put_now << " Total Sequence length: " << s.seqlen << std::endl;
+            std::cerr << put_now << " Genome length: " << genomelen << std::endl;
+            coverage = (unsigned)(s.seqlen / genomelen);
+            std::cerr << put_now << " Estimated coverage: " << coverage << std::endl;
+            if (coverage == 0) return !give_up(" Error: estimated coverage is 0.");
+        }
+        alpha = 7.0l / (long double)coverage;
+    }
+    if (coverage == 0) coverage = (unsigned)(7.0l / alpha);
+    std::cerr << put_now << " Sampling kmers at rate " << alpha << std::endl;
+    p.approx_kmers = (unsigned long long)(genomelen * coverage * alpha);   // kbbq.cc:264
+    p.seed = o.seed ? o.seed : time_pid_seed();
+    std::cerr << put_now << " Seed: " << p.seed << std::endl;
+    std::cerr << "p: " << (double)alpha << std::endl;   // KmerSubsampler ctor, htsiter.hh:143
+    p.alpha = (double)alpha;
+    return true;
+}
+
+// what both modes ask of the engine; what the filters hold (alpha, approx_kmers, seed) is the caller's
+static kbbq_params engine_params(const CliOptions &o, const ScanState &s) {
+    kbbq_params p;
+    memset(&p, 0, sizeof p);
+    p.k = o.k;
+    p.device = 0;
+    p.n_rg = (int32_t)std::max<size_t>(1, s.groups.size());
+    p.fpr_sampled = 0.01;      // sampler_desiredfpr, trusted_desiredfpr: kbbq.cc:155-156
+    p.fpr_trusted = 0.0005;
+    p.bloom_seed = KBBQ_DEFAULT_BLOOM_SEED;
+    p.max_read_len = (int32_t)std::max<size_t>(1, s.longest);
+    return p;
+}
+
+// KBBQ_DEVICES as a list; empty or one entry: one device
+static std::vector<int> device_list(const CliOptions &o, const ScanState &s) {
+    std::vector<int> devices;
+    for (const char *q = o.devices ? o.devices : ""; *q;) {
+        char *end = nullptr;
+        const long v = strtol(q, &end, 10);
+        if (end == q) break;
+        devices.push_back((int)v);
+        q = *end == ',' ? end + 1 : end;
+    }
+    if (devices.size() > 1 && (!s.resident.on || devices[0] != 0)) {
+        std::cerr << put_now << " KBBQ_DEVICES needs the reads resident on device 0 (the first entry): running on one device." << std::endl;
+        devices.clear();
+    }
+    return devices;
+}
+
+// KBBQ_DEVICES=0,1,...: the hot path -- passes 1-3 and the model -- sharded over several GPUs of the node inside this
+// process (contiguous shards of the reads in file order, full filter replicas, three exchange steps
+// and a broadcast: include/kbbq_exchange.h).  The reads were made resident on the first device by the scan; every
+// other device gets a copy of its shard; one host thread per device runs the passes on its engine and meets the
+// others in the exchanges -- over RCCL when the devices are distinct, through device-to-device copies when one device
+// is listed several times (RCCL refuses that; KBBQ_EXCHANGE=local forces it).  The first device then holds the
+// global model and writes the output exactly as a one-device run does: same bytes, whatever the list.
+static int run_on_devices(const std::vector<int> &devices, kbbq_engine *e, const kbbq_params &p, const CliOptions &o, long double alpha, ScanState &s, PhaseClock &clock) {
+    const Resident &resident = s.resident;
+    const int N = (int)devices.size();
+    const size_t nb = resident.dev.size();
+    // global k-mer ordinals of the batches (the sampler's draw stream is one, in file order), shards balanced by bases
+    std::vector<uint64_t> ordinal(nb + 1, 0), bases(nb + 1, 0);
+    for (size_t b = 0; b < nb; ++b) {
+        uint64_t nk = 0;
+        if (kbbq_count_kmer_positions(e, &resident.dev[b], &nk) < 0) return fail_engine("sampling");
+        ordinal[b + 1] = ordinal[b] + nk;
+        bases[b + 1] = bases[b] + resident.dev[b].n_bases;
+    }
+    std::vector<size_t> first(N + 1, nb);
+    first[0] = 0;
+    for (int d = 1; d < N; ++d) {
+        const uint64_t want = bases[nb] * (uint64_t)d / (uint64_t)N;
+        size_t b = first[d - 1];
+        while (b < nb && bases[b] < want) ++b;
+        first[d] = b;
+    }
+    std::vector<kbbq_engine *> eng(N, nullptr);
+    std::vector<std::vector<kbbq_reads>> shard(N);
+    std::vector<kbbq_group *> grp(N, nullptr);
+    eng[0] = e;
+    bool distinct = true;
+    for (int a = 0; a < N; ++a) for (int b = a + 1; b < N; ++b) if (devices[a] == devices[b]) distinct = false;
+    const bool use_rccl = distinct && !o.exchange_local;
+    uint8_t uid[KBBQ_RCCL_ID_BYTES];
+    if (use_rccl) { if (kbbq_group_rccl_unique_id(uid) < 0) return fail_engine("RCCL"); }
+    else if (kbbq_group_local_create(N, grp.data()) < 0) return fail_engine("exchange group");
+    for (int d = 1; d < N; ++d) {
+        kbbq_params pd = p;
+        pd.device = devices[d];
+        if (kbbq_engine_create(&pd, &eng[d]) < 0) return fail_engine("cannot create an engine");
+        for (size_t b = first[d]; b < first[d + 1]; ++b) {
+            kbbq_reads c;
+            if (kbbq_reads_clone(&resident.dev[b], devices[d], 1, &c) < 0) return fail_engine("copying a shard");
+            shard[d].push_back(c);
+        }
+    }
+    for (size_t b = first[0]; b < first[1]; ++b) shard[0].push_back(resident.dev[b]);      // (views: owned by `resident`)
+    std::cerr << put_now << " Passes 1-3 on " << N << " devices (" << (use_rccl ? "RCCL" : "in-process copies") << "): shards of";
+    for (int d = 0; d < N; ++d) std::cerr << " " << first[d + 1] - first[d];
+    std::cerr << " batches." << std::endl;
+    std::atomic<int> failed(0);
+    // one rank: exits the process on an error (a rank that fails must not leave the others in a collective)
+    auto die = [&](const char *what) -> int { std::cerr << put_now << " Error " << what << ": " << kbbq_last_error() << std::endl; _exit(1); };
+    auto rank_body = [&](int d) {
+        if (use_rccl && kbbq_group_rccl_create(uid, d, N, devices[d], &grp[d]) < 0) die("joining the RCCL group");
+        const PassBatches reads{&shard[d], ordinal.data() + first[d], nullptr, &o, &s};
+        if (run_passes(eng[d], o, alpha, reads, grp[d], d == 0, clock, die) || train_model(eng[d], grp[d], d == 0, clock, die)) failed = 1;
+    };
+    std::vector<std::thread> ranks;
+    for (int d = 1; d < N; ++d) ranks.emplace_back(rank_body, d);
+    rank_body(0);
+    for (auto &t : ranks) t.join();
+    for (int d = 0; d < N; ++d) if (grp[d]) kbbq_group_destroy(grp[d]);
+    for (int d = 1; d < N; ++d) {
+        for (auto &c : shard[d]) { kbbq_reads_free_hints(&c); kbbq_reads_free(eng[d], &c); }
+        kbbq_engine_destroy(eng[d]);
+    }
+    return failed ? 1 : 0;      // (the gate of the thresholds, which every rank sees alike: rank 0 has printed it)
+}
+
+// --fixed, kbbq.cc:367-378: errors = bases that differ from the corrected file
+static int tally_fixed(kbbq_engine *e, const CliOptions &o, ScanState &s, Batch &batch) {
+    // the second file is opened in the FIRST file's format (kbbq.cc:370 passes is_bam)
+    std::unique_ptr<Source> in = open_source(o, o.filename), fixed = open_source(o, o.fixedinput);
+    if (!fixed->ok()) return give_up(" Error opening file " + o.fixedinput);
+    Batch fb;
+    ReadGroups fixed_groups;
+    while (batch.fill(*in, s.groups, o.batch_reads, false) && fb.fill(*fixed, fixed_groups, batch.c.n_reads, false)) {
+        std::vector<uint64_t> err(batch.c.n_bases / 64 + 2, 0);
+        const size_t nr = std::min<size_t>(batch.c.n_reads, fb.c.n_reads);
+        for (size_t r = 0; r < nr; ++r) {
+            const uint64_t a = batch.off[r], len = batch.off[r + 1] - a, b = fb.off[r], flen = fb.off[r + 1] - b;
+            for (uint64_t i = 0; i < len && i < flen; ++i)
+                if (batch.seq[a + i] != fb.seq[b + i]) err[(a + i) >> 6] |= 1ULL << ((a + i) & 63);
+        }
+        if (fb.c.n_reads < batch.c.n_reads) {   // the fixed file ended first: the reference stops consuming there
+            batch.c.n_reads = nr;
+            batch.c.n_bases = batch.off[nr];
+        }
+        if (kbbq_tally_batch(e, &batch.c, err.data()) < 0) return fail_engine("tally");
+    }
+    return batch.fatal || fb.fatal ? 1 : 0;
+}
+
+// BamFile::recalibrate, htsiter.cc:11-33: the OQ tag takes the old qualities, the record the new ones (reversed for a
+// reverse-strand read).  false: the tag could not be updated (std::invalid_argument("Unable to update OQ tag.") in the reference).
+static bool rewrite_bam_record(BamRecord &b, const uint8_t *q, bool set_oq, std::string &scratch) {
+    const size_t len = b.l_seq();
+    if (set_oq) {
+        scratch.resize(len);
+        for (size_t i = 0; i < len; ++i) scratch[i] = (char)(b.qual()[i] + 33);
+        int status = 0;
+        if (!b.aux_update_string("OQ", scratch, status)) return false;
+    }
+    if (b.reverse()) std::reverse_copy(q, q + len, b.qual());
+    else std::copy(q, q + len, b.qual());
+    return true;
+}
+static int corrupt_tags() {
+    std::cerr << "Tag data is corrupt. Repair the tags and try again." << std::endl;
+    return 1;
+}
+static int input_changed() { return give_up(" Error: the input changed between the passes."); }
+// the resident batch that batch `bi` of pass 4's own reading of the file must be, or nullptr with the message on stderr
+static const kbbq_reads *same_batch(const Resident &resident, size_t bi, const kbbq_reads &host) {
+    if (bi >= resident.dev.size() || resident.dev[bi].n_bases != host.n_bases || resident.dev[bi].n_reads != host.n_reads) {
+        input_changed();
+        return nullptr;
+    }
+    return &resident.dev[bi];
+}
+
+// Pass 4's output.  The BGZF layer: the encoder on the GPU (DeviceBgzfWriter), or -- KBBQ_HOST_DEFLATE=1, the A/B switch --
+// zlib on a pool of host threads as in rounds 1-2.  Same decompressed stream.
+struct Sink {
+    std::unique_ptr<DeviceBgzfWriter> dev;
+    std::unique_ptr<BgzfWriter> host;
+    std::unique_ptr<BamWriter> bam;
+    std::string line, qtext;
+    uint64_t payload = 0, compressed = 0;      // what the device writer did, for the timing report (close())
+    double ms_format = 0, ms_deflate = 0, ms_gather = 0;
+    ByteSink &bytes() { return dev ? static_cast<ByteSink &>(*dev) : static_cast<ByteSink &>(*host); }
+    int open(const CliOptions &o, const ScanState &s) {
+        if (o.host_deflate) {
+            host.reset(new BgzfWriter(stdout, o.out_threads));
+        } else {
+            dev.reset(new DeviceBgzfWriter(stdout, 0, o.write_threads));
+            if (!dev->ok()) return fail_engine("cannot create the BGZF writer");
+        }
+        bam.reset(new BamWriter(bytes()));
+        return o.is_bam && !bam->write_header(s.bam_header) ? 1 : 0;      // BamFile::open_out, htsiter.cc:35-42
+    }
+    // FastqFile::write, htsiter.cc:75-86 (the comment goes on the '+' line); qualities as text, htsiter.cc:61-65
+    bool fastq(const char *name, size_t nl, const char *comment, size_t cl, const char *seq, size_t sl, const uint8_t *q) {
+        line.clear();
+        line += '@'; line.append(name, nl); line += '\n'; line.append(seq, sl); line += "\n+"; line.append(comment, cl); line += '\n';
+        const size_t at = line.size();
+        line.resize(at + sl);
+        for (size_t i = 0; i < sl; ++i) line[at + i] = (char)(q[i] + 33);
+        line += '\n';
+        return bytes().write(line.data(), line.size());
+    }
+    // the end of the stream; the writers and their threads are gone afterwards
+    bool close() {
+        const bool ok = bytes().close();
+        if (dev) {
+            payload = dev->payload_bytes; compressed = dev->compressed_bytes;
+            dev->kernel_ms(ms_format, ms_deflate, ms_gather);
+        }
+        bam.reset(); dev.reset(); host.reset();
+        return ok;
+    }
+    // BamFile::recalibrate + write, htsiter.cc:11-45
+    bool bam_record(BamRecord &b, const uint8_t *q, bool set_oq) {
+        if (!rewrite_bam_record(b, q, set_oq, qtext)) return !corrupt_tags();
+        return bam->write(b);
+    }
+};
+
+// Pass 4's pair of device quality arrays: batch n writes slot n & 1 while the writer still reads the other one.
+struct QualSlots {
+    kbbq_engine *e;
+    void *q[2] = {nullptr, nullptr};
+    size_t bytes[2] = {0, 0};
+    ~QualSlots() { for (int i = 0; i < 2; ++i) if (q[i]) kbbq_device_free(e, q[i]); }
+    // Pass 4 of batch d into slot t -- grown, with an eighth to spare, when the batch needs more room -- once the writer is
+    // through with what it read from there.  0 and the array in *to, or the exit status.
+    int recalibrate(DeviceBgzfWriter &out, int t, const kbbq_reads &d, const uint8_t **to) {
+        if (!out.drain_to(1)) return 1;      // (the array this batch writes was read by the submission two back)
+        if (bytes[t] < d.n_bases + 16) {
+            if (q[t] && kbbq_device_free(e, q[t]) < 0) return fail_engine("recalibrating");
+            q[t] = nullptr;
+            bytes[t] = d.n_bases + d.n_bases / 8 + 4096;
+            if (kbbq_device_alloc(e, bytes[t], &q[t]) < 0) return fail_engine("recalibrating");
+        }
+        if (kbbq_recalibrate_batch(e, &d, (uint8_t *)q[t]) < 0) return fail_engine("recalibrating");
+        *to = (const uint8_t *)q[t];
+        return 0;
+    }
+};
+
+// Pass 4, the device path: the file's chunks again (inflate + record index, as in the first scan) or the chunks kept in HBM,
+// pass 4 into a device array, the text assembled from the device's own copy of the input, deflated, written.  Nothing but
+// compressed bytes crosses the host link in either direction.
+static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceFastqInput &in) {
+    DeviceBgzfWriter &out = *sink.dev;
+    QualSlots slots{e};
+    size_t bi = 0;
+    if (!in.text_kept) {
+        in.start_pass();
+        if (in.rewind() < 0) return fail_engine("recalibrating");
+    }
+    for (size_t ci = 0; ci < in.chunk_records.size(); ++ci) {
+        kbbq_fastq_chunk info;
+        if (in.text_kept) {
+            // the chunk's text and index (BAM: its compressed bytes, inflated and indexed again) are still on the device
+            if (!in.chunk_records[ci]) continue;
+            if (in.select(bi, &info) < 0 || info.n_records != in.chunk_records[ci] || in.attach(&s.resident.dev[bi]) < 0) return fail_engine("recalibrating");
+        } else if (in.next_chunk(info) != 1 || info.n_records != in.chunk_records[ci]) {
+            return input_changed();
+        }
+        if (!info.n_records) continue;
+        const kbbq_reads &d = s.resident.dev[bi];
+        const int t = (int)(bi & 1);
+        ++bi;
+        const uint8_t *q = nullptr;
+        if (const int rc = slots.recalibrate(out, t, d, &q)) return rc;
+        // KBBQ_QUAL_DIGEST=1: the sum of every recalibrated quality, taken on the device from the array the writer reads
+        // (the number bench.py prints as recal_qual_sum for the same reads)
+        if (o.qual_digest && kbbq_digest_add(e, q, d.n_bases) < 0) return fail_engine("recalibrating");
+        if (!in.write_chunk(out, q, o.set_oq, kbbq_engine_stream(e))) return 1;
+    }
+    if (!out.drain()) return 1;
+    if (o.qual_digest) {
+        uint64_t sum = 0;
+        if (kbbq_digest_get(e, &sum, 1) < 0) return fail_engine("recalibrating");
+        std::cerr << "[digest] recal_qual_sum " << sum << " reads " << s.n_reads << " bases " << s.seqlen << std::endl;
+    }
+    return 0;
+}
+
+// FASTQ, every batch in HBM, its record text in host memory: the new qualities never leave the GPU.  Pass 4
+// writes them to a device array, the writer assembles "@name\nseq\n+comment\nqual\n" there (FastqFile::write,
+// htsiter.cc:75-86), deflates and hands back finished blocks; two batches are in flight, so the kernels of
+// one run while the blocks of the one before are written out.
+static int write_resident_fastq(kbbq_engine *e, ScanState &s, const CliOptions &, Sink &sink) {
+    DeviceBgzfWriter &out = *sink.dev;
+    QualSlots slots{e};
+    for (size_t bi = 0; bi < s.resident.dev.size(); ++bi) {
+        const kbbq_reads &d = s.resident.dev[bi];
+        const RecordStore &st = s.resident.recs[bi];
+        const uint8_t *q = nullptr;
+        if (const int rc = slots.recalibrate(out, (int)(bi & 1), d, &q)) return rc;
+        if (!out.fastq_batch(st.blob.data(), st.lens.data(), d.n_reads, q, d.offsets, d.read_len, kbbq_engine_stream(e))) return 1;
+    }
+    return out.drain() ? 0 : 1;
+}
+
+// BAM, every batch in HBM, its alignment blocks in host memory: BamFile::recalibrate + write (htsiter.cc:11-45) for a
+// whole batch by a pool -- every thread rewrites a run of records (OQ tag, qualities, reversed for reverse-strand
+// reads) into a buffer of its own, the runs are copied side by side into one page-locked buffer, and the
+// encoder on the GPU takes it from there.
+static int write_resident_bam(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink) {
+    const unsigned T = (unsigned)std::max(1, o.out_threads);
+    std::vector<std::string> part(T);
+    std::vector<int> part_rc(T, 0);
+    std::vector<uint8_t> newq;
+    char *pin = nullptr;
+    size_t pin_bytes = 0;
+    struct FreePin { char **p; ~FreePin() { if (*p) kbbq_host_free(*p); } } free_pin{&pin};
+    for (size_t bi = 0; bi < s.resident.dev.size(); ++bi) {
+        const kbbq_reads &d = s.resident.dev[bi];
+        const RecordStore &st = s.resident.recs[bi];
+        newq.assign(d.n_bases + 16, 0);
+        if (kbbq_recalibrate_batch_host(e, &d, newq.data()) < 0) return fail_engine("recalibrating");
+        // where every record's block and qualities start
+        std::vector<uint64_t> rec_at(d.n_reads + 1), q_at(d.n_reads + 1);
+        {
+            uint64_t at = 0, qa = 0;
+            for (size_t r = 0; r < d.n_reads; ++r) {
+                rec_at[r] = at; q_at[r] = qa;
+                at += st.lens[r];
+                const uint8_t *rec = (const uint8_t *)st.blob.data() + rec_at[r];
+                qa += (uint64_t)rec[16] | ((uint64_t)rec[17] << 8) | ((uint64_t)rec[18] << 16) | ((uint64_t)rec[19] << 24);      // l_seq
+            }
+            rec_at[d.n_reads] = at; q_at[d.n_reads] = qa;
+        }
+        std::vector<std::thread> pool;
+        for (unsigned t = 0; t < T; ++t) {
+            pool.emplace_back([&, t] {
+                const size_t r0 = d.n_reads * t / T, r1 = d.n_reads * (t + 1) / T;
+                std::string &out_s = part[t];
+                out_s.clear();
+                out_s.reserve((size_t)(rec_at[r1] - rec_at[r0]) + (r1 - r0) * (o.set_oq ? 8 : 4) + (o.set_oq ? (size_t)(q_at[r1] - q_at[r0]) : 0));
+                BamRecord b;
+                std::string qtext_t;
+                for (size_t r = r0; r < r1; ++r) {
+                    b.data.assign((const uint8_t *)st.blob.data() + rec_at[r], (const uint8_t *)st.blob.data() + rec_at[r + 1]);
+                    if (!rewrite_bam_record(b, newq.data() + q_at[r], o.set_oq, qtext_t)) { part_rc[t] = -1; return; }
+                    const uint32_t n = (uint32_t)b.data.size();
+                    const char len4[4] = {(char)(n & 0xFF), (char)((n >> 8) & 0xFF), (char)((n >> 16) & 0xFF), (char)((n >> 24) & 0xFF)};
+                    out_s.append(len4, 4);
+                    out_s.append((const char *)b.data.data(), b.data.size());
+                }
+            });
+        }
+        for (auto &th : pool) th.join();
+        size_t total = 0;
+        for (unsigned t = 0; t < T; ++t) {
+            if (part_rc[t] < 0) return corrupt_tags();
+            total += part[t].size();
+        }
+        if (pin_bytes < total) {
+            if (pin) kbbq_host_free(pin);
+            pin = nullptr;
+            pin_bytes = total + total / 8 + 4096;
+            void *p = nullptr;
+            if (kbbq_host_alloc(pin_bytes, &p) < 0) return fail_engine("recalibrating");
+            pin = (char *)p;
+        }
+        {
+            std::vector<std::thread> copiers;
+            size_t at = 0;
+            for (unsigned t = 0; t < T; ++t) {
+                copiers.emplace_back([&, t, at] { memcpy(pin + at, part[t].data(), part[t].size()); });
+                at += part[t].size();
+            }
+            for (auto &th : copiers) th.join();
+        }
+        if (!sink.dev->submit_buffer(pin, total)) return 1;
+    }
+    return sink.dev->drain() ? 0 : 1;
+}
+
+// The host writer (or FASTQ records in BamWriter's place): every batch is in HBM and its records are in host memory,
+// nothing is decoded again
+static int write_resident_records(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink) {
+    std::vector<uint8_t> newq;
+    BamRecord b;
+    for (size_t bi = 0; bi < s.resident.dev.size(); ++bi) {
+        const kbbq_reads &d = s.resident.dev[bi];
+        const RecordStore &st = s.resident.recs[bi];
+        newq.assign(d.n_bases + 16, 0);
+        if (kbbq_recalibrate_batch_host(e, &d, newq.data()) < 0) return fail_engine("recalibrating");
+        size_t at = 0, qa = 0;
+        for (size_t r = 0; r < d.n_reads; ++r) {
+            if (o.is_bam) {
+                const uint32_t n = st.lens[r];
+                b.data.assign((const uint8_t *)st.blob.data() + at, (const uint8_t *)st.blob.data() + at + n);
+                at += n;
+                const size_t len = b.l_seq();
+                if (!sink.bam_record(b, newq.data() + qa, o.set_oq)) return 1;
+                qa += len;
+            } else {
+                const uint32_t nl = st.lens[3 * r], cl = st.lens[3 * r + 1], sl = st.lens[3 * r + 2];
+                const char *p = st.blob.data() + at;
+                if (!sink.fastq(p, nl, p + nl, cl, p + nl + cl, sl, newq.data() + qa)) return 1;
+                at += (size_t)nl + cl + sl;
+                qa += sl;
+            }
+        }
+    }
+    return 0;
+}
+
+// FASTQ whose records were not kept (streaming mode, or the host cache was too small): the parsers decode the
+// file once more, and every batch goes the way of a resident one -- on the device (the resident copy, or
+// uploaded now with its bases packed there), pass 4 into a device array, the text assembled and deflated there.
+static int write_reparsed_fastq(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, Batch &batch) {
+    DeviceBgzfWriter &out = *sink.dev;
+    Batch::Fast fast;
+    (void)open_fast(o, true, fast, nullptr);
+    QualSlots slots{e};
+    kbbq_reads up[2];
+    bool up_live[2] = {false, false};
+    struct FreeUp {
+        kbbq_engine *e; kbbq_reads *up; bool *live;
+        ~FreeUp() { for (int i = 0; i < 2; ++i) if (live[i]) kbbq_reads_free(e, &up[i]); }
+    } free_up{e, up, up_live};
+    ScopedSet<bool> packed_on_device(batch.pack_on_host, false);
+    size_t bi = 0;
+    for (size_t n = 0;; ++n) {
+        RecordStore st;
+        if (!batch.fill_fast(fast, s.groups, o.batch_reads, &st)) break;
+        const int t = (int)(n & 1);
+        // the arrays of slot t were read by the submission two batches ago: that one must be through
+        if (!out.drain_to(1)) return 1;
+        if (up_live[t]) { kbbq_reads_free(e, &up[t]); up_live[t] = false; }
+        const kbbq_reads *d = nullptr;
+        if (s.resident.on) {
+            if (!(d = same_batch(s.resident, bi++, batch.c))) return 1;
+        } else {
+            if (kbbq_reads_upload_text(e, &batch.c, batch.seq.data(), &up[t]) < 0) return fail_engine("recalibrating");
+            up_live[t] = true;
+            d = &up[t];
+        }
+        const uint8_t *q = nullptr;
+        if (const int rc = slots.recalibrate(out, t, *d, &q)) return rc;
+        if (!out.fastq_batch(st.blob.data(), st.lens.data(), d->n_reads, q, d->offsets, d->read_len, kbbq_engine_stream(e))) return 1;
+    }
+    if (batch.fatal) return 1;
+    return out.drain() ? 0 : 1;
+}
+
+// Everything else: the serial reader decodes the file once more, record by record to the writer
+static int write_serial(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, Batch &batch) {
+    std::unique_ptr<Source> in = open_source(o, o.filename);
+    std::vector<uint8_t> newq;
+    size_t bi = 0;
+    while (batch.fill(*in, s.groups, o.batch_reads, true, o.is_bam)) {
+        newq.assign(batch.c.n_bases + 16, 0);
+        if (s.resident.on) {
+            const kbbq_reads *d = same_batch(s.resident, bi++, batch.c);
+            if (!d) return 1;
+            if (kbbq_recalibrate_batch_host(e, d, newq.data()) < 0) return fail_engine("recalibrating");
+        } else if (kbbq_recalibrate_batch(e, &batch.c, newq.data()) < 0) {
+            return fail_engine("recalibrating");
+        }
+        for (size_t r = 0; r < batch.c.n_reads; ++r) {
+            const uint8_t *q = newq.data() + batch.off[r];
+            if (o.is_bam) {
+                if (!sink.bam_record(batch.bam_recs[r], q, o.set_oq)) return 1;
+            } else {
+                const FastqRecord &f = batch.fq_recs[r];
+                if (!sink.fastq(f.name.data(), f.name.size(), f.comment.data(), f.comment.size(), f.seq.data(), f.seq.size(), q)) return 1;
+            }
+        }
+    }
+    return batch.fatal ? 1 : 0;
+}
+
+// KBBQ_TIMING=1: what the device reader and the device writer did
+static void report_io_timing(DeviceFastqInput &in, const Sink &w) {
+    if (in.active) {
+        double inf = 0, idx = 0;
+        in.kernel_ms(inf, idx);
+        std::cerr << "[timing] " << in.format() << " reader on the GPU (" << in.container << "; " << (in.text_kept ? "one scan, the text kept in HBM: " : "both scans: ")
+                  << (in.text_kept ? std::to_string(in.kept_bytes) + " bytes; " : std::string()) << "waiting for file reads " << in.wait_s
+                  << " s, device calls " << in.device_s << " s, packing + batch arrays " << in.batch_s << " s; kernels: inflate " << inf << " ms, index + pack " << idx << " ms" << std::endl;
+    }
+    if (w.payload)
+        std::cerr << "[timing] BGZF writer on the GPU: " << w.payload << " bytes -> " << w.compressed << " (ratio "
+                  << (double)w.payload / (double)std::max<uint64_t>(1, w.compressed) << "); kernels: format " << w.ms_format
+                  << " ms, deflate " << w.ms_deflate << " ms, gather " << w.ms_gather << " ms" << std::endl;
+}
+
+int main(int argc, char *argv[]) {
+    CliOptions opt;
+    if (argc > 1 && std::string(argv[1]) == "--io-test") return io_test(argc, argv, opt);
+    if (!opt.parse(argc, argv)) return 1;
+
+    const Format fmt = sniff(opt.filename);
+    if (fmt == Format::unknown) return give_up(" Error opening file " + opt.filename);   // also: a pipe cannot be re-read by the passes
+    if (fmt == Format::cram) return give_up(" Error: CRAM input needs htslib, which this build does not have; use BAM or FASTQ.");
+    opt.is_bam = fmt == Format::bam;
+    if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
+
+    // The one scan before the engine exists: on the device when that may be tried and takes the file, with the host parsers
+    // otherwise.  An early return unwinds these in the reverse order: resident batches, engine, the device reader and its thread.
+    PhaseClock clock(opt.timing);
+    DeviceFastqInput dev_in(opt);
+    EngineOwner engine;
+    ScanState scan;
+    Batch batch;
+    scan.resident.init(opt);
+    const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, dev_in, scan);
+    if (!read_on_device && host_scan(opt, scan, batch)) return 1;
+    if (scan.longest > KBBQ_MAX_READ_LEN)
+        return give_up(" Error: reads longer than " + std::to_string(KBBQ_MAX_READ_LEN) + " bases are not supported by the GPU engine.");
     clock.mark("scan+pack+upload");
-    kbbq_engine *e = nullptr;
-    bool multi_device_done = false;      // KBBQ_DEVICES: passes 1-3 and the model ran sharded over several devices
+    const Resident &resident = scan.resident;
     if (resident.on)
         std::cerr << put_now << " Reads are resident on the GPU: " << resident.dev.size() << " batches"
                   << (resident.keep_recs ? ", their records in host memory." : ".") << std::endl;
 
-    if (!fixed_mode) {
-        if (genomelen == 0) {
-            if (is_bam) {   // kbbq.cc:196-216
-                std::cerr << put_now << " Estimating genome length" << std::endl;
-                genomelen = bam_header.genome_length();
-                if (genomelen == 0) {
-                    std::cerr << put_now << " Header does not contain genome information."
-                              << " Unable to estimate genome length; please provide it on the command line"
-                              << " using the --genomelen option." << std::endl;
-                    return 1;
-                }
-                std::cerr << put_now << " Genome length is " << genomelen << " bp." << std::endl;
-            } else {
-                std::cerr << put_now << " Error: --genomelen must be specified if input is not a bam." << std::endl;
-                return 1;
-            }
-        }
-        if (alpha == 0) {   // kbbq.cc:227-252
-            std::cerr << put_now << " Estimating alpha." << std::endl;
-            if (coverage == 0) {
-                std::cerr << put_now << " Estimating coverage." << std::endl;
-                if (seqlen == 0) {
-                    std::cerr << put_now << " Error: total sequence length in file " << filename << " is 0. Check that the file isn't empty." << std::endl;
-                    return 1;
-                }
-                std::cerr << put_now << " Total Sequence length: " << seqlen << std::endl;
-                std::cerr << put_now << " Genome length: " << genomelen << std::endl;
-                coverage = (unsigned)(seqlen / genomelen);
-                std::cerr << put_now << " Estimated coverage: " << coverage << std::endl;
-                if (coverage == 0) {
-                    std::cerr << put_now << " Error: estimated coverage is 0." << std::endl;
-                    return 1;
-                }
-            }
-            alpha = 7.0l / (long double)coverage;
-        }
-        if (coverage == 0) coverage = (unsigned)(7.0l / alpha);
-        std::cerr << put_now << " Sampling kmers at rate " << alpha << std::endl;
-        const unsigned long long approx_kmers = (unsigned long long)(genomelen * coverage * alpha);   // kbbq.cc:264
-        if (const char *s = getenv("KBBQ_SEED")) seed = (uint32_t)strtoul(s, nullptr, 10);
-        if (seed == 0) seed = time_pid_seed();
-        std::cerr << put_now << " Seed: " << seed << std::endl;
-        std::cerr << "p: " << (double)alpha << std::endl;   // KmerSubsampler ctor, htsiter.hh:143
-
-        kbbq_params p;
-        memset(&p, 0, sizeof p);
-        p.k = k;
-        p.device = 0;
-        p.alpha = (double)alpha;
-        p.seed = seed;
-        p.n_rg = (int32_t)std::max<size_t>(1, groups.size());
-        p.approx_kmers = approx_kmers;
-        p.fpr_sampled = (double)sampler_desiredfpr;
-        p.fpr_trusted = (double)trusted_desiredfpr;
-        p.bloom_seed = KBBQ_DEFAULT_BLOOM_SEED;
-        p.max_read_len = (int32_t)std::max<size_t>(1, longest);
+    // parameters and engine, then passes 1-3 (on one device or on several) or --fixed, then the model
+    kbbq_engine *&e = engine.e;
+    kbbq_params p = engine_params(opt, scan);
+    bool trained = false;      // KBBQ_DEVICES: the model was trained and broadcast among the ranks
+    if (!opt.fixed_mode()) {
+        long double alpha = 0;
+        if (!derive_sampling(opt, scan, p, alpha)) return 1;
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
-
-        // KBBQ_DEVICES=0,1,...: the hot path -- passes 1-3 and the model -- sharded over several GPUs of the node inside this
-        // process (contiguous shards of the reads in file order, full filter replicas, three exchange steps
-        // and a broadcast: include/kbbq_exchange.h).  The reads were made resident on the first device by the scan; every
-        // other device gets a copy of its shard; one host thread per device runs the passes on its engine and meets the
-        // others in the exchanges -- over RCCL when the devices are distinct, through device-to-device copies when one device
-        // is listed several times (RCCL refuses that; KBBQ_EXCHANGE=local forces it).  The first device then holds the
-        // global model and writes the output exactly as a one-device run does: same bytes, whatever the list.
-        std::vector<int> devices;
-        if (const char *dl = getenv("KBBQ_DEVICES")) {
-            for (const char *q = dl; *q;) {
-                char *end = nullptr;
-                const long v = strtol(q, &end, 10);
-                if (end == q) break;
-                devices.push_back((int)v);
-                q = *end == ',' ? end + 1 : end;
-            }
-        }
-        if (devices.size() > 1 && (!resident.on || devices[0] != 0)) {
-            std::cerr << put_now << " KBBQ_DEVICES needs the reads resident on device 0 (the first entry): running on one device." << std::endl;
-            devices.clear();
-        }
+        const std::vector<int> devices = device_list(opt, scan);
+        const PassBatches reads{&resident.dev, nullptr, resident.on ? nullptr : &batch, &opt, &scan};
         if (devices.size() > 1) {
-            const int N = (int)devices.size();
-            const size_t nb = resident.dev.size();
-            // global k-mer ordinals of the batches (the sampler's draw stream is one, in file order), shards balanced by bases
-            std::vector<uint64_t> ordinal(nb + 1, 0), bases(nb + 1, 0);
-            for (size_t b = 0; b < nb; ++b) {
-                uint64_t nk = 0;
-                if (kbbq_count_kmer_positions(e, &resident.dev[b], &nk) < 0) return fail_engine("sampling");
-                ordinal[b + 1] = ordinal[b] + nk;
-                bases[b + 1] = bases[b] + resident.dev[b].n_bases;
-            }
-            std::vector<size_t> first(N + 1, nb);
-            first[0] = 0;
-            for (int d = 1; d < N; ++d) {
-                const uint64_t want = bases[nb] * (uint64_t)d / (uint64_t)N;
-                size_t b = first[d - 1];
-                while (b < nb && bases[b] < want) ++b;
-                first[d] = b;
-            }
-            std::vector<kbbq_engine *> eng(N, nullptr);
-            std::vector<std::vector<kbbq_reads>> shard(N);
-            std::vector<kbbq_group *> grp(N, nullptr);
-            eng[0] = e;
-            bool distinct = true;
-            for (int a = 0; a < N; ++a) for (int b = a + 1; b < N; ++b) if (devices[a] == devices[b]) distinct = false;
-            const bool use_rccl = distinct && !(getenv("KBBQ_EXCHANGE") && !strcmp(getenv("KBBQ_EXCHANGE"), "local"));
-            uint8_t uid[KBBQ_RCCL_ID_BYTES];
-            if (use_rccl) { if (kbbq_group_rccl_unique_id(uid) < 0) return fail_engine("RCCL"); }
-            else if (kbbq_group_local_create(N, grp.data()) < 0) return fail_engine("exchange group");
-            for (int d = 1; d < N; ++d) {
-                kbbq_params pd = p;
-                pd.device = devices[d];
-                if (kbbq_engine_create(&pd, &eng[d]) < 0) return fail_engine("cannot create an engine");
-                for (size_t b = first[d]; b < first[d + 1]; ++b) {
-                    kbbq_reads c;
-                    if (kbbq_reads_clone(&resident.dev[b], devices[d], 1, &c) < 0) return fail_engine("copying a shard");
-                    shard[d].push_back(c);
-                }
-            }
-            for (size_t b = first[0]; b < first[1]; ++b) shard[0].push_back(resident.dev[b]);      // (views: owned by `resident`)
-            std::cerr << put_now << " Passes 1-3 on " << N << " devices (" << (use_rccl ? "RCCL" : "in-process copies") << "): shards of";
-            for (int d = 0; d < N; ++d) std::cerr << " " << first[d + 1] - first[d];
-            std::cerr << " batches." << std::endl;
-            char alpha_text[64];
-            snprintf(alpha_text, sizeof alpha_text, "%.25Le", alpha);
-            std::atomic<int> gate_seen(0);
-            // one rank: returns 0, or exits the process on an error (a rank that fails must not leave the others in a collective)
-            auto die = [&](const char *what) { std::cerr << put_now << " Error " << what << ": " << kbbq_last_error() << std::endl; _exit(1); };
-            auto rank_body = [&](int d) {
-                kbbq_engine *ed = eng[d];
-                if (use_rccl && kbbq_group_rccl_create(uid, d, N, devices[d], &grp[d]) < 0) die("joining the RCCL group");
-                for (size_t i = 0; i < shard[d].size(); ++i)
-                    if (kbbq_sample_batch(ed, &shard[d][i], ordinal[first[d] + i]) < 0) die("sampling");
-                uint64_t inserted = 0, total = 0;
-                if (kbbq_sample_finish(ed, &inserted) < 0 || kbbq_exchange_filter(ed, 0, grp[d], 0, &total) < 0) die("sampling");
-                if (d == 0) std::cerr << put_now << " Sampled " << total << " valid kmers." << std::endl;
-                // every rank computes the same thresholds from the same (global) filter and count (kbbq.cc:304-331)
-                char p_text[64];
-                std::vector<int32_t> thresholds(k + 1);
-                double fprd = 0;
-                const int gate = kbbq_compute_thresholds(ed, alpha_text, thresholds.data(), &fprd, p_text, sizeof p_text);
-                if (gate < 0) die("thresholds");
-                if (d == 0) {
-                    const long double fpr = fprd;
-                    std::cerr << put_now << " Approximate false positive rate: " << fpr << std::endl;
-                    if (gate != 1) {
-                        const long double p_hit = strtold(p_text, nullptr);
-                        std::cerr << put_now << " log CDF: [ ";
-                        for (long double c : log_binom_cdf_values((unsigned long long)k, p_hit)) std::cerr << c << " ";
-                        std::cerr << "]" << std::endl;
-                    }
-                }
-                if (gate == 1) { gate_seen = 1; return; }      // (every rank sees the same gate)
-                if (d == 0) { clock.mark("pass1"); std::cerr << put_now << " Finding trusted kmers" << std::endl; }
-                for (auto &b : shard[d])
-                    if (kbbq_trusted_batch(ed, &b, nullptr) < 0) die("finding trusted kmers");
-                uint64_t trusted_inserted = 0;
-                if (kbbq_trusted_finish(ed, nullptr) < 0 || kbbq_exchange_filter(ed, 1, grp[d], 0, &trusted_inserted) < 0) die("finding trusted kmers");
-                if (d == 0 && getenv("KBBQ_QUAL_DIGEST") && atoi(getenv("KBBQ_QUAL_DIGEST"))) std::cerr << "[digest] trusted_inserted " << trusted_inserted << std::endl;
-                if (d == 0) { clock.mark("pass2"); std::cerr << put_now << " Finding errors" << std::endl; }
-                for (auto &b : shard[d])
-                    if (kbbq_errors_batch(ed, &b, nullptr) < 0) die("finding errors");
-                if (kbbq_exchange_histograms(ed, grp[d]) < 0) die("summing the histograms");
-                if (d == 0) { clock.mark("pass3"); std::cerr << put_now << " Training model" << std::endl; }
-                if (kbbq_exchange_dq(ed, grp[d]) < 0) die("training");      // rank 0 trains, the tables are broadcast
-            };
-            std::vector<std::thread> ranks;
-            for (int d = 1; d < N; ++d) ranks.emplace_back(rank_body, d);
-            rank_body(0);
-            for (auto &t : ranks) t.join();
-            for (int d = 0; d < N; ++d) if (grp[d]) kbbq_group_destroy(grp[d]);
-            for (int d = 1; d < N; ++d) {
-                for (auto &c : shard[d]) { kbbq_reads_free_hints(&c); kbbq_reads_free(eng[d], &c); }
-                kbbq_engine_destroy(eng[d]);
-            }
-            if (gate_seen) {
-                std::cerr << put_now << " Error: false positive rate is too high. "
-                          << "Increase genomelen parameter and try again." << std::endl;
-                return 1;
-            }
-            multi_device_done = true;
+            if (run_on_devices(devices, e, p, opt, alpha, scan, clock)) return 1;
+            trained = true;
+        } else if (const int rc = run_passes(e, opt, alpha, reads, nullptr, true, clock, fail_engine)) {
+            return rc;
         }
-
-        // pass 1, kbbq.cc:277-283
-        if (!multi_device_done) {
-            uint64_t ordinal = 0, nk = 0;
-            if (resident.on) {
-                for (auto &d : resident.dev) {
-                    if (kbbq_sample_batch(e, &d, ordinal) < 0) return fail_engine("sampling");
-                    if (kbbq_count_kmer_positions(e, &d, &nk) < 0) return fail_engine("sampling");
-                    ordinal += nk;
-                }
-            } else {
-                std::unique_ptr<PassInput> in = open_pass();
-                batch.stop_at_empty = true;
-                while (in->next(batch, groups, batch_reads)) {
-                    if (kbbq_sample_batch(e, &batch.c, ordinal) < 0) return fail_engine("sampling");
-                    if (kbbq_count_kmer_positions(e, &batch.c, &nk) < 0) return fail_engine("sampling");
-                    ordinal += nk;
-                }
-                if (batch.fatal) return 1;
-                batch.stop_at_empty = false;
-                batch.ended = false;
-            }
-            uint64_t inserted = 0;
-            if (kbbq_sample_finish(e, &inserted) < 0) return fail_engine("sampling");
-            std::cerr << put_now << " Sampled " << inserted << " valid kmers." << std::endl;
-        }
-        if (!multi_device_done) {
-        // kbbq.cc:304-331
-        char alpha_text[64], p_text[64];
-        snprintf(alpha_text, sizeof alpha_text, "%.25Le", alpha);
-        std::vector<int32_t> thresholds(k + 1);
-        double fprd = 0;
-        const int gate = kbbq_compute_thresholds(e, alpha_text, thresholds.data(), &fprd, p_text, sizeof p_text);
-        if (gate < 0) return fail_engine("thresholds");
-        const long double fpr = fprd;
-        std::cerr << put_now << " Approximate false positive rate: " << fpr << std::endl;
-        if (gate == 1) {
-            std::cerr << put_now << " Error: false positive rate is too high. "
-                      << "Increase genomelen parameter and try again." << std::endl;
-            return 1;
-        }
-        {
-            const long double p_hit = strtold(p_text, nullptr);
-            std::cerr << put_now << " log CDF: [ ";
-            for (long double c : log_binom_cdf_values((unsigned long long)k, p_hit)) std::cerr << c << " ";
-            std::cerr << "]" << std::endl;
-        }
-        // pass 2, kbbq.cc:333-337
-        clock.mark("pass1");
-        std::cerr << put_now << " Finding trusted kmers" << std::endl;
-        {
-            if (resident.on) {
-                for (auto &d : resident.dev)
-                    if (kbbq_trusted_batch(e, &d, nullptr) < 0) return fail_engine("finding trusted kmers");
-            } else {
-                std::unique_ptr<PassInput> in = open_pass();
-                while (in->next(batch, groups, batch_reads))
-                    if (kbbq_trusted_batch(e, &batch.c, nullptr) < 0) return fail_engine("finding trusted kmers");
-                if (batch.fatal) return 1;
-            }
-            uint64_t trusted_inserted = 0;
-            if (kbbq_trusted_finish(e, &trusted_inserted) < 0) return fail_engine("finding trusted kmers");
-            if (getenv("KBBQ_QUAL_DIGEST") && atoi(getenv("KBBQ_QUAL_DIGEST")))      // (the reference prints no count here; bench.py's result.trusted_inserted)
-                std::cerr << "[digest] trusted_inserted " << trusted_inserted << std::endl;
-        }
-        // pass 3, kbbq.cc:363-366
-        clock.mark("pass2");
-        std::cerr << put_now << " Finding errors" << std::endl;
-        {
-            if (resident.on) {
-                for (auto &d : resident.dev)
-                    if (kbbq_errors_batch(e, &d, nullptr) < 0) return fail_engine("finding errors");
-            } else {
-                std::unique_ptr<PassInput> in = open_pass();
-                while (in->next(batch, groups, batch_reads))
-                    if (kbbq_errors_batch(e, &batch.c, nullptr) < 0) return fail_engine("finding errors");
-                if (batch.fatal) return 1;
-            }
-        }
-        }      // (!multi_device_done)
     } else {
-        // --fixed, kbbq.cc:367-378: errors = bases that differ from the corrected file
         std::cerr << put_now << " Using fixed file to find errors." << std::endl;
-        kbbq_params p;
-        memset(&p, 0, sizeof p);
-        p.k = k; p.alpha = 0.5; p.seed = 1; p.approx_kmers = 1000;   // the filters are not used in this mode
-        p.n_rg = (int32_t)std::max<size_t>(1, groups.size());
-        p.fpr_sampled = 0.01; p.fpr_trusted = 0.0005; p.bloom_seed = KBBQ_DEFAULT_BLOOM_SEED;
-        p.max_read_len = (int32_t)std::max<size_t>(1, longest);
+        p.alpha = 0.5; p.seed = 1; p.approx_kmers = 1000;   // the filters are not used in this mode
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
-        // the second file is opened in the FIRST file's format (kbbq.cc:370 passes is_bam)
-        std::unique_ptr<Source> in = open_source(filename, is_bam, use_oq), fixed = open_source(fixedinput, is_bam, use_oq);
-        if (!fixed->ok()) {
-            std::cerr << put_now << " Error opening file " << fixedinput << std::endl;
-            return 1;
-        }
-        Batch fb;
-        ReadGroups fixed_groups;
-        while (batch.fill(*in, groups, batch_reads, false) && fb.fill(*fixed, fixed_groups, batch.c.n_reads, false)) {
-            std::vector<uint64_t> err(batch.c.n_bases / 64 + 2, 0);
-            const size_t nr = std::min<size_t>(batch.c.n_reads, fb.c.n_reads);
-            for (size_t r = 0; r < nr; ++r) {
-                const uint64_t a = batch.off[r], len = batch.off[r + 1] - a, b = fb.off[r], flen = fb.off[r + 1] - b;
-                for (uint64_t i = 0; i < len && i < flen; ++i)
-                    if (batch.seq[a + i] != fb.seq[b + i]) err[(a + i) >> 6] |= 1ULL << ((a + i) & 63);
-            }
-            if (fb.c.n_reads < batch.c.n_reads) {   // the fixed file ended first: the reference stops consuming there
-                batch.c.n_reads = nr;
-                batch.c.n_bases = batch.off[nr];
-            }
-            if (kbbq_tally_batch(e, &batch.c, err.data()) < 0) return fail_engine("tally");
-        }
-        if (batch.fatal || fb.fatal) return 1;
+        if (tally_fixed(e, opt, scan, batch)) return 1;
     }
-
-    // kbbq.cc:405-407
-    if (!multi_device_done) {
-        clock.mark("pass3");
-        std::cerr << put_now << " Training model" << std::endl;
-        if (kbbq_train(e) < 0) return fail_engine("training");
-    }
+    if (!trained && train_model(e, nullptr, true, clock, fail_engine)) return 1;
 
     // pass 4, kbbq.cc:455-457: recalibrate_and_write(file, dqs, "-")
     clock.mark("model");
     std::cerr << put_now << " Recalibrating file" << std::endl;
-    uint64_t out_payload = 0, out_compressed = 0;
-    double ms_format = 0, ms_deflate = 0, ms_gather = 0;
-    {
-        // The BGZF layer: the encoder on the GPU (DeviceBgzfWriter), or -- KBBQ_HOST_DEFLATE=1, the A/B switch -- zlib on
-        // a pool of host threads as in rounds 1-2.  Same decompressed stream.
-        const bool host_deflate = getenv("KBBQ_HOST_DEFLATE") && atoi(getenv("KBBQ_HOST_DEFLATE")) != 0;
-        std::unique_ptr<DeviceBgzfWriter> dev_out;
-        std::unique_ptr<BgzfWriter> host_out;
-        if (host_deflate) {
-            host_out.reset(new BgzfWriter(stdout, out_threads));
-        } else {
-            dev_out.reset(new DeviceBgzfWriter(stdout, 0));
-            if (!dev_out->ok()) return fail_engine("cannot create the BGZF writer");
-        }
-        ByteSink &out = host_deflate ? static_cast<ByteSink &>(*host_out) : static_cast<ByteSink &>(*dev_out);
-        BamWriter bam_out(out);
-        if (is_bam && !bam_out.write_header(bam_header)) return 1;      // BamFile::open_out, htsiter.cc:35-42
-        std::vector<uint8_t> newq;
-        std::string qtext, line;
-        // FastqFile::write, htsiter.cc:75-86 (the comment goes on the '+' line); qualities as text, htsiter.cc:61-65
-        auto emit_fastq = [&](const char *name, size_t nl, const char *comment, size_t cl, const char *seq, size_t sl, const uint8_t *q) {
-            line.clear();
-            line += '@'; line.append(name, nl); line += '\n'; line.append(seq, sl); line += "\n+"; line.append(comment, cl); line += '\n';
-            const size_t at = line.size();
-            line.resize(at + sl);
-            for (size_t i = 0; i < sl; ++i) line[at + i] = (char)(q[i] + 33);
-            line += '\n';
-            return out.write(line.data(), line.size());
-        };
-        // BamFile::recalibrate + write, htsiter.cc:11-45
-        auto emit_bam = [&](BamRecord &b, const uint8_t *q) -> int {
-            const size_t len = b.l_seq();
-            if (set_oq) {
-                qtext.resize(len);
-                for (size_t i = 0; i < len; ++i) qtext[i] = (char)(b.qual()[i] + 33);
-                int status = 0;
-                if (!b.aux_update_string("OQ", qtext, status)) {
-                    std::cerr << "Tag data is corrupt. Repair the tags and try again." << std::endl;
-                    return -1;   // std::invalid_argument("Unable to update OQ tag.") in the reference
-                }
-            }
-            if (b.reverse()) std::reverse_copy(q, q + len, b.qual());
-            else std::copy(q, q + len, b.qual());
-            return bam_out.write(b) ? 0 : -1;
-        };
-        if (dev_in.active && dev_out) {
-            // The device path: the file's chunks again (inflate + record index, as in the first scan), pass 4 into a device
-            // array, the text assembled from the device's own copy of the input, deflated, written.  Nothing but compressed
-            // bytes crosses the host link in either direction.
-            void *d_q[2] = {nullptr, nullptr};
-            size_t d_q_bytes[2] = {0, 0};
-            struct FreeQ { kbbq_engine *e; void **p; ~FreeQ() { for (int i = 0; i < 2; ++i) if (p[i]) kbbq_device_free(e, p[i]); } } free_q{e, d_q};
-            size_t bi = 0;
-            // KBBQ_QUAL_DIGEST=1: the sum of every recalibrated quality, taken on the device from the array the writer reads
-            // (the number bench.py prints as recal_qual_sum for the same reads)
-            const bool want_digest = getenv("KBBQ_QUAL_DIGEST") && atoi(getenv("KBBQ_QUAL_DIGEST"));
-            if (!dev_in.text_kept) {
-                dev_in.start_pass();
-                if ((dev_in.bam ? kbbq_bam_reader_rewind(dev_in.bam) : kbbq_fastq_reader_rewind(dev_in.reader)) < 0) return fail_engine("recalibrating");
-            }
-            for (size_t ci = 0; ci < dev_in.chunk_records.size(); ++ci) {
-                kbbq_fastq_chunk info;
-                if (dev_in.text_kept && dev_in.bam) {
-                    // the chunk's compressed bytes are still on the device: inflated and indexed again there
-                    if (!dev_in.chunk_records[ci]) continue;
-                    if (kbbq_bam_reader_select(dev_in.bam, bi, &info) < 0 || info.n_records != dev_in.chunk_records[ci]) return fail_engine("recalibrating");
-                } else if (dev_in.text_kept) {
-                    // the chunk's text and index are still on the device
-                    if (!dev_in.chunk_records[ci]) continue;
-                    if (kbbq_fastq_reader_select(dev_in.reader, bi, &info) < 0 || info.n_records != dev_in.chunk_records[ci] ||
-                        kbbq_fastq_reader_attach(dev_in.reader, &resident.dev[bi]) < 0)
-                        return fail_engine("recalibrating");
-                } else if (dev_in.next_chunk(info) != 1 || info.n_records != dev_in.chunk_records[ci]) {
-                    std::cerr << put_now << " Error: the input changed between the passes." << std::endl;
-                    return 1;
-                }
-                if (!info.n_records) continue;
-                const kbbq_reads &d = resident.dev[bi];
-                const int t = (int)(bi & 1);
-                ++bi;
-                if (!dev_out->drain_to(1)) return 1;      // (the array this batch writes was read by the submission two back)
-                if (d_q_bytes[t] < d.n_bases + 16) {
-                    if (d_q[t] && kbbq_device_free(e, d_q[t]) < 0) return fail_engine("recalibrating");
-                    d_q[t] = nullptr;
-                    d_q_bytes[t] = d.n_bases + d.n_bases / 8 + 4096;
-                    if (kbbq_device_alloc(e, d_q_bytes[t], &d_q[t]) < 0) return fail_engine("recalibrating");
-                }
-                if (kbbq_recalibrate_batch(e, &d, (uint8_t *)d_q[t]) < 0) return fail_engine("recalibrating");
-                if (want_digest && kbbq_digest_add(e, (const uint8_t *)d_q[t], d.n_bases) < 0) return fail_engine("recalibrating");
-                if (dev_in.bam ? !dev_out->bam_chunk(dev_in.bam, (const uint8_t *)d_q[t], set_oq, kbbq_engine_stream(e))
-                               : !dev_out->reader_chunk(dev_in.reader, (const uint8_t *)d_q[t], kbbq_engine_stream(e)))
-                    return 1;
-            }
-            if (!dev_out->drain()) return 1;
-            if (want_digest) {
-                uint64_t sum = 0;
-                if (kbbq_digest_get(e, &sum, 1) < 0) return fail_engine("recalibrating");
-                std::cerr << "[digest] recal_qual_sum " << sum << " reads " << n_reads << " bases " << seqlen << std::endl;
-            }
-        } else if (resident.on && resident.keep_recs && !is_bam && dev_out) {
-            // FASTQ, every batch in HBM, its record text in host memory: the new qualities never leave the GPU.  Pass 4
-            // writes them to a device array, the writer assembles "@name\nseq\n+comment\nqual\n" there (FastqFile::write,
-            // htsiter.cc:75-86), deflates and hands back finished blocks; two batches are in flight, so the kernels of
-            // one run while the blocks of the one before are written out.
-            void *d_q[2] = {nullptr, nullptr};
-            size_t d_q_bytes[2] = {0, 0};
-            struct FreeQ { kbbq_engine *e; void **p; ~FreeQ() { for (int i = 0; i < 2; ++i) if (p[i]) kbbq_device_free(e, p[i]); } } free_q{e, d_q};
-            for (size_t bi = 0; bi < resident.dev.size(); ++bi) {
-                const kbbq_reads &d = resident.dev[bi];
-                const RecordStore &st = resident.recs[bi];
-                const int t = (int)(bi & 1);
-                // the array this batch writes was read by the submission two batches ago: that one must be through
-                if (!dev_out->drain_to(1)) return 1;      // (the array this batch writes was read by the submission two back)
-                if (d_q_bytes[t] < d.n_bases + 16) {
-                    if (d_q[t] && kbbq_device_free(e, d_q[t]) < 0) return fail_engine("recalibrating");
-                    d_q[t] = nullptr;
-                    d_q_bytes[t] = d.n_bases + d.n_bases / 8 + 4096;
-                    if (kbbq_device_alloc(e, d_q_bytes[t], &d_q[t]) < 0) return fail_engine("recalibrating");
-                }
-                if (kbbq_recalibrate_batch(e, &d, (uint8_t *)d_q[t]) < 0) return fail_engine("recalibrating");
-                if (!dev_out->fastq_batch(st.blob.data(), st.lens.data(), d.n_reads, (const uint8_t *)d_q[t], d.offsets, d.read_len,
-                                          kbbq_engine_stream(e)))
-                    return 1;
-            }
-            if (!dev_out->drain()) return 1;
-        } else if (resident.on && resident.keep_recs && is_bam && dev_out) {
-            // BAM, every batch in HBM, its alignment blocks in host memory: BamFile::recalibrate + write (htsiter.cc:11-45) for a
-            // whole batch by a pool -- every thread rewrites a run of records (OQ tag, qualities, reversed for reverse-strand
-            // reads) into a buffer of its own, the runs are copied side by side into one page-locked buffer, and the
-            // encoder on the GPU takes it from there.
-            const unsigned T = (unsigned)std::max(1, out_threads);
-            std::vector<std::string> part(T);
-            std::vector<int> part_rc(T, 0);
-            char *pin = nullptr;
-            size_t pin_bytes = 0;
-            struct FreePin { char **p; ~FreePin() { if (*p) kbbq_host_free(*p); } } free_pin{&pin};
-            for (size_t bi = 0; bi < resident.dev.size(); ++bi) {
-                const kbbq_reads &d = resident.dev[bi];
-                const RecordStore &st = resident.recs[bi];
-                newq.assign(d.n_bases + 16, 0);
-                if (kbbq_recalibrate_batch_host(e, &d, newq.data()) < 0) return fail_engine("recalibrating");
-                // where every record's block and qualities start
-                std::vector<uint64_t> rec_at(d.n_reads + 1), q_at(d.n_reads + 1);
-                {
-                    uint64_t at = 0, qa = 0;
-                    for (size_t r = 0; r < d.n_reads; ++r) {
-                        rec_at[r] = at; q_at[r] = qa;
-                        at += st.lens[r];
-                        const uint8_t *rec = (const uint8_t *)st.blob.data() + rec_at[r];
-                        qa += (uint64_t)rec[16] | ((uint64_t)rec[17] << 8) | ((uint64_t)rec[18] << 16) | ((uint64_t)rec[19] << 24);      // l_seq
-                    }
-                    rec_at[d.n_reads] = at; q_at[d.n_reads] = qa;
-                }
-                std::vector<std::thread> pool;
-                for (unsigned t = 0; t < T; ++t) {
-                    pool.emplace_back([&, t] {
-                        const size_t r0 = d.n_reads * t / T, r1 = d.n_reads * (t + 1) / T;
-                        std::string &out_s = part[t];
-                        out_s.clear();
-                        out_s.reserve((size_t)(rec_at[r1] - rec_at[r0]) + (r1 - r0) * (set_oq ? 8 : 4) + (set_oq ? (size_t)(q_at[r1] - q_at[r0]) : 0));
-                        BamRecord b;
-                        std::string qtext_t;
-                        for (size_t r = r0; r < r1; ++r) {
-                            b.data.assign((const uint8_t *)st.blob.data() + rec_at[r], (const uint8_t *)st.blob.data() + rec_at[r + 1]);
-                            const size_t len = b.l_seq();
-                            const uint8_t *q = newq.data() + q_at[r];
-                            if (set_oq) {
-                                qtext_t.resize(len);
-                                for (size_t i = 0; i < len; ++i) qtext_t[i] = (char)(b.qual()[i] + 33);
-                                int status = 0;
-                                if (!b.aux_update_string("OQ", qtext_t, status)) { part_rc[t] = -1; return; }
-                            }
-                            if (b.reverse()) std::reverse_copy(q, q + len, b.qual());
-                            else std::copy(q, q + len, b.qual());
-                            const uint32_t n = (uint32_t)b.data.size();
-                            const char len4[4] = {(char)(n & 0xFF), (char)((n >> 8) & 0xFF), (char)((n >> 16) & 0xFF), (char)((n >> 24) & 0xFF)};
-                            out_s.append(len4, 4);
-                            out_s.append((const char *)b.data.data(), b.data.size());
-                        }
-                    });
-                }
-                for (auto &th : pool) th.join();
-                size_t total = 0;
-                for (unsigned t = 0; t < T; ++t) {
-                    if (part_rc[t] < 0) {
-                        std::cerr << "Tag data is corrupt. Repair the tags and try again." << std::endl;
-                        return 1;      // std::invalid_argument("Unable to update OQ tag.") in the reference
-                    }
-                    total += part[t].size();
-                }
-                if (pin_bytes < total) {
-                    if (pin) kbbq_host_free(pin);
-                    pin = nullptr;
-                    pin_bytes = total + total / 8 + 4096;
-                    void *p = nullptr;
-                    if (kbbq_host_alloc(pin_bytes, &p) < 0) return fail_engine("recalibrating");
-                    pin = (char *)p;
-                }
-                {
-                    std::vector<std::thread> copiers;
-                    size_t at = 0;
-                    for (unsigned t = 0; t < T; ++t) {
-                        copiers.emplace_back([&, t, at] { memcpy(pin + at, part[t].data(), part[t].size()); });
-                        at += part[t].size();
-                    }
-                    for (auto &th : copiers) th.join();
-                }
-                if (!dev_out->submit_buffer(pin, total)) return 1;
-            }
-            if (!dev_out->drain()) return 1;
-        } else if (resident.on && resident.keep_recs) {
-            // every batch is in HBM and its records are in host memory: nothing is decoded again
-            BamRecord b;
-            for (size_t bi = 0; bi < resident.dev.size(); ++bi) {
-                const kbbq_reads &d = resident.dev[bi];
-                const RecordStore &st = resident.recs[bi];
-                newq.assign(d.n_bases + 16, 0);
-                if (kbbq_recalibrate_batch_host(e, &d, newq.data()) < 0) return fail_engine("recalibrating");
-                size_t at = 0, qa = 0;
-                for (size_t r = 0; r < d.n_reads; ++r) {
-                    if (is_bam) {
-                        const uint32_t n = st.lens[r];
-                        b.data.assign((const uint8_t *)st.blob.data() + at, (const uint8_t *)st.blob.data() + at + n);
-                        at += n;
-                        const size_t len = b.l_seq();
-                        if (emit_bam(b, newq.data() + qa) < 0) return 1;
-                        qa += len;
-                    } else {
-                        const uint32_t nl = st.lens[3 * r], cl = st.lens[3 * r + 1], sl = st.lens[3 * r + 2];
-                        const char *p = st.blob.data() + at;
-                        if (!emit_fastq(p, nl, p + nl, cl, p + nl + cl, sl, newq.data() + qa)) return 1;
-                        at += (size_t)nl + cl + sl;
-                        qa += sl;
-                    }
-                }
-            }
-        } else if (passes_fast && !is_bam && dev_out) {
-            // FASTQ whose records were not kept (streaming mode, or the host cache was too small): the parsers decode the
-            // file once more, and every batch goes the way of a resident one -- on the device (the resident copy, or
-            // uploaded now with its bases packed there), pass 4 into a device array, the text assembled and deflated there.
-            PassInput in;
-            in.use_fast = true;
-            in.fast.parser.reset(new FastqChunkParser(filename, g_io_threads, out_threads, true));
-            void *d_q[2] = {nullptr, nullptr};
-            size_t d_q_bytes[2] = {0, 0};
-            kbbq_reads up[2];
-            bool up_live[2] = {false, false};
-            struct FreeAll {
-                kbbq_engine *e; void **q; kbbq_reads *up; bool *live;
-                ~FreeAll() { for (int i = 0; i < 2; ++i) { if (q[i]) kbbq_device_free(e, q[i]); if (live[i]) kbbq_reads_free(e, &up[i]); } }
-            } free_all{e, d_q, up, up_live};
-            batch.pack_on_host = false;
-            size_t bi = 0;
-            for (size_t n = 0;; ++n) {
-                RecordStore st;
-                if (!batch.fill_fast(in.fast, groups, batch_reads, &st)) break;
-                const int t = (int)(n & 1);
-                // the arrays of slot t were read by the submission two batches ago: that one must be through
-                if (!dev_out->drain_to(1)) return 1;      // (the array this batch writes was read by the submission two back)
-                if (up_live[t]) { kbbq_reads_free(e, &up[t]); up_live[t] = false; }
-                const kbbq_reads *d = nullptr;
-                if (resident.on) {
-                    if (bi >= resident.dev.size() || resident.dev[bi].n_bases != batch.c.n_bases || resident.dev[bi].n_reads != batch.c.n_reads) {
-                        std::cerr << put_now << " Error: the input changed between the passes." << std::endl;
-                        return 1;
-                    }
-                    d = &resident.dev[bi++];
-                } else {
-                    if (kbbq_reads_upload_text(e, &batch.c, batch.seq.data(), &up[t]) < 0) return fail_engine("recalibrating");
-                    up_live[t] = true;
-                    d = &up[t];
-                }
-                if (d_q_bytes[t] < d->n_bases + 16) {
-                    if (d_q[t] && kbbq_device_free(e, d_q[t]) < 0) return fail_engine("recalibrating");
-                    d_q[t] = nullptr;
-                    d_q_bytes[t] = d->n_bases + d->n_bases / 8 + 4096;
-                    if (kbbq_device_alloc(e, d_q_bytes[t], &d_q[t]) < 0) return fail_engine("recalibrating");
-                }
-                if (kbbq_recalibrate_batch(e, d, (uint8_t *)d_q[t]) < 0) return fail_engine("recalibrating");
-                if (!dev_out->fastq_batch(st.blob.data(), st.lens.data(), d->n_reads, (const uint8_t *)d_q[t], d->offsets, d->read_len, kbbq_engine_stream(e)))
-                    return 1;
-            }
-            batch.pack_on_host = true;
-            if (batch.fatal) return 1;
-            if (!dev_out->drain()) return 1;
-        } else {
-            std::unique_ptr<Source> in = open_source(filename, is_bam, use_oq);
-            size_t bi = 0;
-            while (batch.fill(*in, groups, batch_reads, true, is_bam)) {
-                newq.assign(batch.c.n_bases + 16, 0);
-                if (resident.on) {
-                    if (bi >= resident.dev.size() || resident.dev[bi].n_bases != batch.c.n_bases || resident.dev[bi].n_reads != batch.c.n_reads) {
-                        std::cerr << put_now << " Error: the input changed between the passes." << std::endl;
-                        return 1;
-                    }
-                    if (kbbq_recalibrate_batch_host(e, &resident.dev[bi], newq.data()) < 0) return fail_engine("recalibrating");
-                    ++bi;
-                } else if (kbbq_recalibrate_batch(e, &batch.c, newq.data()) < 0) {
-                    return fail_engine("recalibrating");
-                }
-                for (size_t r = 0; r < batch.c.n_reads; ++r) {
-                    const uint8_t *q = newq.data() + batch.off[r];
-                    if (is_bam) {
-                        if (emit_bam(batch.bam_recs[r], q) < 0) return 1;
-                    } else {
-                        const FastqRecord &f = batch.fq_recs[r];
-                        if (!emit_fastq(f.name.data(), f.name.size(), f.comment.data(), f.comment.size(), f.seq.data(), f.seq.size(), q)) return 1;
-                    }
-                }
-            }
-            if (batch.fatal) return 1;
-        }
-        if (!out.close()) return 1;
-        if (dev_out) {
-            out_payload = dev_out->payload_bytes; out_compressed = dev_out->compressed_bytes;
-            dev_out->kernel_ms(ms_format, ms_deflate, ms_gather);
-        }
-    }
+    Sink sink;
+    int rc = sink.open(opt, scan);
+    if (rc) return rc;
+    if (dev_in.active && sink.dev) rc = write_from_device_reader(e, scan, opt, sink, dev_in);
+    else if (resident.on && resident.keep_recs && !opt.is_bam && sink.dev) rc = write_resident_fastq(e, scan, opt, sink);
+    else if (resident.on && resident.keep_recs && opt.is_bam && sink.dev) rc = write_resident_bam(e, scan, opt, sink);
+    else if (resident.on && resident.keep_recs) rc = write_resident_records(e, scan, opt, sink);
+    else if (scan.passes_fast() && !opt.is_bam && sink.dev) rc = write_reparsed_fastq(e, scan, opt, sink, batch);
+    else rc = write_serial(e, scan, opt, sink, batch);
+    if (rc || !sink.close()) return 1;
     clock.mark("pass4+format+deflate+write");
-    if (clock.on && dev_in.active) {
-        double inf = 0, idx = 0;
-        if (dev_in.bam) kbbq_bam_reader_kernel_ms(dev_in.bam, &inf, &idx); else kbbq_fastq_reader_kernel_ms(dev_in.reader, &inf, &idx);
-        std::cerr << "[timing] " << (dev_in.bam ? "BAM" : "FASTQ") << " reader on the GPU (" << dev_in.container << "; " << (dev_in.text_kept ? "one scan, the text kept in HBM: " : "both scans: ")
-                  << (dev_in.text_kept ? std::to_string(dev_in.kept_bytes) + " bytes; " : std::string()) << "waiting for file reads " << dev_in.wait_s
-                  << " s, device calls " << dev_in.device_s << " s, packing + batch arrays " << dev_in.batch_s << " s; kernels: inflate " << inf << " ms, index + pack " << idx << " ms" << std::endl;
-    }
-    if (clock.on && out_payload)
-        std::cerr << "[timing] BGZF writer on the GPU: " << out_payload << " bytes -> " << out_compressed << " (ratio "
-                  << (double)out_payload / (double)std::max<uint64_t>(1, out_compressed) << "); kernels: format " << ms_format
-                  << " ms, deflate " << ms_deflate << " ms, gather " << ms_gather << " ms" << std::endl;
+    if (clock.on) report_io_timing(dev_in, sink);
     // Everything is written and flushed.  Handing 200 GB of device memory back allocation by allocation takes 2.2 s at
-    // BASELINE size (every hipFree waits for the device); the process ends here and the driver takes it all back at once.
-    // KBBQ_RELEASE=1: the orderly way (leak checkers).
-    if (!(getenv("KBBQ_RELEASE") && atoi(getenv("KBBQ_RELEASE")))) {
+    // BASELINE size (every hipFree waits for the device); the process ends here and the driver takes it all back at once
+    // -- behind the device reader, whose I/O thread and streams must not be alive beside the runtime's own teardown (its
+    // two page-locked buffers of 256 MB, 60 ms to unpin, go with the rest).
+    // KBBQ_RELEASE=1: the orderly way (leak checkers), which is also what every early return above takes.
+    if (!opt.release) {
+        dev_in.stop();
         clock.mark("end");
         clock.report();
         fflush(stdout);
         fflush(stderr);
         exit(0);      // (handlers registered with atexit still run: a profiler's, the runtime's)
     }
-    resident.drop();
-    kbbq_engine_destroy(e);
+    scan.resident.drop();
+    engine.release();
     clock.mark("release");
     return 0;
 }

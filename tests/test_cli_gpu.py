@@ -375,7 +375,8 @@ def test_cli_output_does_not_depend_on_the_batch_size(tmp_path):
     assert rc == 0, err
     one = gzip.decompress(one)
     for env in ({"KBBQ_BATCH_READS": "257"}, {"KBBQ_BATCH_READS": "1000", "KBBQ_RESIDENT": "0"},
-                {"KBBQ_BATCH_READS": "64", "KBBQ_HOST_CACHE_MB": "0"}):
+                {"KBBQ_BATCH_READS": "64", "KBBQ_HOST_CACHE_MB": "0"},
+                {"KBBQ_BATCH_READS": "257", "KBBQ_RELEASE": "1"}):      # (the orderly end: everything freed, no exit(0))
         rc, out, err = run_cli(["-g", d["genome_len"], fq], dict(env, KBBQ_SEED="99"))
         assert rc == 0, err
         assert gzip.decompress(out) == one, env
@@ -383,7 +384,7 @@ def test_cli_output_does_not_depend_on_the_batch_size(tmp_path):
     rc, one_b, err = run_cli(["--set-oq", path], {"KBBQ_SEED": "7"})
     assert rc == 0, err
     one_b = bamutil.bgzf_decompress(one_b)
-    for env in ({"KBBQ_BATCH_READS": "300"}, {"KBBQ_BATCH_READS": "777", "KBBQ_RESIDENT": "0"}):
+    for env in ({"KBBQ_BATCH_READS": "300"}, {"KBBQ_BATCH_READS": "777", "KBBQ_RESIDENT": "0"}, {"KBBQ_BATCH_READS": "300", "KBBQ_RELEASE": "1"}):
         rc, out, err = run_cli(["--set-oq", path], dict(env, KBBQ_SEED="7"))
         assert rc == 0, err
         assert bamutil.bgzf_decompress(out) == one_b, env
