@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -76,9 +77,10 @@ struct PendingEvent {
     hipEvent_t a, b;
 };
 
-// Behavioural switches, fixed when the engine is created: a KBBQ_F_* flag of kbbq_params.flags, or -- where no flag
-// says otherwise -- the environment variable of the same meaning (README.md) as it stands at kbbq_engine_create.
-// None changes a result.
+// Behavioural switches: a KBBQ_F_* flag of kbbq_params.flags, or -- where no flag says otherwise -- the environment
+// variable of the same meaning (README.md) as it stands at kbbq_engine_create; kbbq_engine_tune changes some between two
+// runs.  The environment is read nowhere else.  None changes a result.
+constexpr int kNoOverride = INT_MIN;
 struct Options {
     bool no_overlap = false;          // KBBQ_F_NO_OVERLAP / KBBQ_NO_OVERLAP: every kernel in order on one stream
     bool no_fastpath = false;         // KBBQ_F_NO_FASTPATH / KBBQ_NO_FASTPATH: every read with untrusted k-mers takes the walk
@@ -106,6 +108,67 @@ struct Options {
     int scan_blocks = -1;             // KBBQ_SCAN_BLOCKS / kbbq_engine_tune("scan_blocks", n)
     int walk_blocks = -1;             // KBBQ_WALK_BLOCKS / "walk_blocks"
     int infer_blocks = 0;             // KBBQ_INFER_BLOCKS / "infer_blocks"
+    // undocumented diagnostics: k_infer's subset plan (infer_subset_plan) overridden when it has one; results never depend on either
+    int subset_edge = kNoOverride;    // KBBQ_SUBSET_EDGE
+    int subset_pmask = kNoOverride;   // KBBQ_SUBSET_PMASK
+};
+
+// ---- scratch buffers, device counters, pass-3 context: which kernel may touch which buffer on which stream ----------
+
+// The engine's growing device buffers by name (scratch_buf).
+enum Scratch {
+    S_KMER_PREFIX,                  // exclusive k-mer-position prefix of a ragged batch (kmer_prefix)
+    S_HOST_OUT,                     // what a host batch's caller gets back: pass 2's returned flags and pass 4's qualities (never both at a
+                                    // time: either call waits for its copy back before it returns)
+    S_HOST_FLAGS,                   // kbbq_tally_batch: a host batch's error flags
+    S_DRAW0, S_DRAW1,               // pass 1: the two draw masks (draw_turn)
+    S_TAKE1,                        // pass 2: the second take-bit array (take_turn); the first is S_TAKE0 below
+    S_READ_INDEX0, S_READ_INDEX1,   // the tally's base -> read index (build_read_index) per STREAM: an overlapped batch of either side tallies
+                                    // on the side stream, in order (1); pass 4 builds its own where the in-order tallies do, on the engine's (0)
+    // once per side of pass 3: per_side(name, side); side 1's copies follow from S_SIDE1 on
+    S_TMASK, S_DIRTY, S_LIST, S_ERR, S_PATCH,
+    S_OFFCASE_LIST,                 // work list of the reads with off-case bases
+    S_WALK_WORDS,                   // long reads: the lane-form walk's working words
+    S_SIDE1,
+    S_COUNT = S_SIDE1 + (S_SIDE1 - S_TMASK),
+    // One buffer is pass 2's first take-bit array and the error bits of pass 3's side 1 (neither pass holds a bases/8-byte
+    // array the other could have had).  An emit of pass 2 may still read it on the side stream when pass 3 writes it on the
+    // engine's: safe because kbbq_errors_batch begins with bucket_flush_all, whose barrier flush of the trusted filter
+    // makes the engine's stream wait for everything queued on the side stream.
+    S_TAKE0 = S_ERR + (S_SIDE1 - S_TMASK),
+};
+constexpr int per_side(Scratch name, int side) { return name + side * (S_SIDE1 - S_TMASK); }
+
+// The three small device allocations.  Kernels on two streams update these words atomically, so the byte layouts stay as
+// they were (a word moved to another cache line changes the speed): the structs only name the words.
+struct SideCounters { unsigned long long list_len, queries; };      // a side's work-list length (k_compact) and its walk's Bloom queries: the kernels' cnt[0], cnt[1]
+struct Counters {                   // kbbq_engine::d_counters
+    SideCounters side0;
+    unsigned long long kmer_total;      // kmer_prefix: k-mer positions of a ragged batch
+    unsigned long long infer_fetched;   // Bloom blocks fetched by k_infer (stats[3])
+    SideCounters side1;
+    unsigned long long offcase_len[2];  // length of the off-case work list per side
+    SideCounters *side(int s) { return s ? &side1 : &side0; }      // (on the device pointer: address arithmetic only)
+};
+struct Tickets {                    // kbbq_engine::d_tickets: chunk counters of the kernels that hand their reads out dynamically (ReadChunks)
+    unsigned int infer, scan[2], walk[2], unused[11];      // k_infer; k_scan_trusted and k_correct_wave per side of pass 3
+};
+struct Totals {                     // kbbq_engine::d_totals
+    unsigned long long walk_reads, walk_queries;   // pass 3: reads sent to the correction kernels, Bloom queries there (k_add_counters)
+    unsigned long long digest, unused;             // running byte sum of kbbq_digest_add; kbbq_engine_reset leaves it alone
+};
+static_assert(sizeof(Counters) == 64 && offsetof(Counters, kmer_total) == 16 && offsetof(Counters, side1) == 32 && offsetof(Counters, offcase_len) == 48, "d_counters");
+static_assert(sizeof(Tickets) == 64 && offsetof(Tickets, scan) == 4 && offsetof(Tickets, walk) == 12, "d_tickets");
+static_assert(sizeof(Totals) == 32 && offsetof(Totals, digest) == 16, "d_totals");
+
+// What the launch helpers of pass 3 need to know about the batch in hand (kbbq_errors_batch builds it).
+struct Pass3 {
+    int side;                       // whose per-side scratch and counters
+    hipStream_t stream;             // where the next kernel goes: the engine's stream, then -- walk and tally of an overlapped batch -- the side stream
+    int stream_no;                  // ... 0 or 1: the tally's buffers exist once per stream (S_READ_INDEX0/1, d_rg_present)
+    unsigned long long *cnt;        // the side's SideCounters, as the kernels take them
+    unsigned int *scan_ticket, *wave_ticket;
+    bool shared;                    // the batch shares the chip with its neighbours' kernels (grid caps)
 };
 
 struct kbbq_engine {
@@ -123,8 +186,7 @@ struct kbbq_engine {
     bool ins_pending[2] = {false, false};
     int draw_turn = 0;
     bool side_busy[2] = {false, false};     // a batch of pass 3 used that side since the totals were last read
-    bool pass3_shared = false;              // the batch being submitted shares the chip with its neighbours' kernels (grid caps)
-    unsigned long long *d_totals = nullptr; // pass 3: [0] reads sent to the correction kernels, [1] Bloom queries there (k_add_counters)
+    Totals *d_totals = nullptr;
     int side_turn = 0;
     uint32_t *d_qpresent = nullptr;     // quality values seen by pass 2 (256 bits), read at kbbq_trusted_finish
     uint32_t qpresent[8] = {};          // ... as read then; pass 3 on its own (--fixed mode) adds each batch's values (k_qpresence)
@@ -132,8 +194,6 @@ struct kbbq_engine {
     uint8_t *d_dq_qslot = nullptr;      // apply kernel: quality -> LDS table slot (upload_dq)
     int dq_slots = 0;
     uint32_t *d_rg_present[2] = {nullptr, nullptr};     // which read groups a batch contains (run_tally), per stream
-    hipStream_t cur = nullptr;              // stream and counter pair the pass-3 launch helpers use
-    unsigned long long *cur_cnt = nullptr;
     FilterHost filt[2];
     Xoshiro256 seed_state;
     uint64_t draw_threshold = 0;
@@ -148,11 +208,11 @@ struct kbbq_engine {
     int16_t *d_dq_base = nullptr;
     int8_t *d_dq_cycle = nullptr;
     int8_t *d_dq_dinuc = nullptr;
-    // scratch
-    void *scratch[24] = {};
-    size_t scratch_bytes[24] = {};
-    unsigned long long *d_counters = nullptr;   // [0] work-list length, [1] correction queries, [2] scan total
-    unsigned int *d_tickets = nullptr;          // chunk counters of the kernels that hand their reads out dynamically (ReadChunks): [0] k_infer, [1 + side] k_scan_trusted, [3 + side] k_correct_wave
+    // scratch (enum Scratch) and the small counters
+    void *scratch[S_COUNT] = {};
+    size_t scratch_bytes[S_COUNT] = {};
+    Counters *d_counters = nullptr;
+    Tickets *d_tickets = nullptr;
     // Host batches: a ring of device staging slots owned by the engine and a copy stream.  A host batch is copied
     // into the next slot with hipMemcpyAsync on the copy stream (DMA straight from the caller's memory when that is
     // page-locked), the pass's kernels wait for the copy by event, and the entry point returns as soon as the COPY
@@ -217,19 +277,37 @@ struct kbbq_engine {
 
 namespace {
 
-int ensure_scratch(kbbq_engine *e, int idx, size_t bytes) {
-    if (e->scratch_bytes[idx] >= bytes) return KBBQ_OK;
-    if (e->scratch[idx]) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream2));
-        HIP_TRY(hipFree(e->scratch[idx]));
-        e->scratch[idx] = nullptr;
-        e->scratch_bytes[idx] = 0;
+// scratch buffer `name` with room for `bytes`, grown if need be (both streams are drained before the old one is freed)
+template <typename T> int scratch_buf(kbbq_engine *e, int name, size_t bytes, T **out) {
+    if (e->scratch_bytes[name] < bytes) {
+        if (e->scratch[name]) {
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream2));
+            HIP_TRY(hipFree(e->scratch[name]));
+            e->scratch[name] = nullptr;
+            e->scratch_bytes[name] = 0;
+        }
+        const size_t want = bytes + bytes / 8 + 256;
+        HIP_TRY(hipMalloc(&e->scratch[name], want));
+        e->scratch_bytes[name] = want;
     }
-    const size_t want = bytes + bytes / 8 + 256;
-    HIP_TRY(hipMalloc(&e->scratch[idx], want));
-    e->scratch_bytes[idx] = want;
+    *out = static_cast<T *>(e->scratch[name]);
     return KBBQ_OK;
+}
+
+// `waiter` runs after everything queued on `signaller` so far
+int run_after(hipStream_t waiter, hipStream_t signaller, hipEvent_t ev) {
+    HIP_TRY(hipEventRecord(ev, signaller));
+    HIP_TRY(hipStreamWaitEvent(waiter, ev, 0));
+    return KBBQ_OK;
+}
+
+// every event of the engine and of its staging slots (created and destroyed by walking this list)
+std::vector<hipEvent_t *> engine_events(kbbq_engine *e) {
+    std::vector<hipEvent_t *> v = {&e->ev_main, &e->ev_draw, &e->ev_ins[0], &e->ev_ins[1], &e->ev_side[0], &e->ev_side[1],
+                                   &e->bk.ev_flush, &e->bk.ev_est, &e->ev_infer, &e->ev_take[0], &e->ev_take[1]};
+    for (kbbq_engine::StageSlot &s : e->slot) v.insert(v.end(), {&s.h2d, &s.d2h, &s.done[0], &s.done[1]});
+    return v;
 }
 
 // quality -> slot map of the tally from the presence bits (256: a quality is any uint8_t).  At most `max_slots`
@@ -311,7 +389,7 @@ __global__ void k_add_counters(const unsigned long long *side, const unsigned lo
 
 int collect_totals(kbbq_engine *e) {      // (both streams are idle)
     unsigned long long t[2] = {0, 0};
-    HIP_TRY(hipMemcpy(t, e->d_totals, 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t, &e->d_totals->walk_reads, 16, hipMemcpyDeviceToHost));      // walk_reads, walk_queries
     e->stats[0] = t[0];
     e->stats[1] = t[1];
     e->side_busy[0] = e->side_busy[1] = false;
@@ -508,7 +586,7 @@ inline int shared_cap(const kbbq_engine *e, int per_cu, int auto_value = 0, int 
     return per_cu >= 0 ? per_cu : max_len <= 192 && uniform ? auto_value : 0;
 }
 
-// exclusive k-mer-position prefix for ragged batches (scratch slot 1); null for uniform ones
+// exclusive k-mer-position prefix for ragged batches (S_KMER_PREFIX); null for uniform ones
 int kmer_prefix(kbbq_engine *e, const ReadsDev &R, const uint64_t **kofs, uint64_t *total) {
     if (!R.offsets) {
         *kofs = nullptr;
@@ -517,17 +595,29 @@ int kmer_prefix(kbbq_engine *e, const ReadsDev &R, const uint64_t **kofs, uint64
         return KBBQ_OK;
     }
     const uint64_t n_tiles = (R.n_reads + SCAN_TILE - 1) / SCAN_TILE;
-    int rc = ensure_scratch(e, 1, (R.n_reads + 1 + n_tiles) * 8);
+    uint64_t *d;
+    int rc = scratch_buf(e, S_KMER_PREFIX, (R.n_reads + 1 + n_tiles) * 8, &d);
     if (rc) return rc;
-    uint64_t *d = (uint64_t *)e->scratch[1], *tiles = d + R.n_reads + 1;
+    uint64_t *tiles = d + R.n_reads + 1;
     hipLaunchKernelGGL(k_kmer_counts, dim3((unsigned)((R.n_reads + 255) / 256)), dim3(256), 0, e->stream, R, e->p.k, d);
     hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)n_tiles), dim3(256), 0, e->stream, d, R.n_reads, tiles);
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, tiles, n_tiles, (uint64_t *)&e->d_counters[2]);
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, e->stream, tiles, n_tiles, (uint64_t *)&e->d_counters->kmer_total);
     hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((R.n_reads + 255) / 256)), dim3(256), 0, e->stream, d, R.n_reads, (const uint64_t *)tiles);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(total, &e->d_counters[2], 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(total, &e->d_counters->kmer_total, 8, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     *kofs = d;
+    return KBBQ_OK;
+}
+
+// the tables into the caller's arrays (those it gave)
+int dq_out(const DqTables &d, kbbq_dq *out) {
+    out->n_rg = d.n_rg; out->n_cycle = d.n_cycle;
+    if (out->meanq) memcpy(out->meanq, d.meanq.data(), d.meanq.size() * 4);
+    if (out->rgdq) memcpy(out->rgdq, d.rgdq.data(), d.rgdq.size() * 4);
+    if (out->qdq) memcpy(out->qdq, d.qdq.data(), d.qdq.size() * 4);
+    if (out->cycledq) memcpy(out->cycledq, d.cycledq.data(), d.cycledq.size() * 4);
+    if (out->dinucdq) memcpy(out->dinucdq, d.dinucdq.data(), d.dinucdq.size() * 4);
     return KBBQ_OK;
 }
 
@@ -676,11 +766,11 @@ int bucket_flush(kbbq_engine *e, int w, bool barrier = true) {
     const FiltDev F = e->filt[w].dev();
     const hipStream_t emit_st = bucket_stream(e, w);
     hipStream_t st = emit_st;
+    int rc;
     if (w == 1 && e->opt.pass2_side == 2 && emit_st != e->stream) {
         // the flush alone on the engine's stream, behind the emits that filled the buffers; the emits after it wait for it
-        HIP_TRY(hipEventRecord(b.ev_flush, emit_st));
-        HIP_TRY(hipStreamWaitEvent(e->stream, b.ev_flush, 0));
         st = e->stream;
+        if ((rc = run_after(st, emit_st, b.ev_flush))) return rc;
     }
     HIP_TRY(hipMemsetAsync(b.tickets, 0, kTicketBytes, st));
     {
@@ -696,14 +786,8 @@ int bucket_flush(kbbq_engine *e, int w, bool barrier = true) {
     }
     HIP_TRY(hipMemsetAsync(b.l1_cnt, 0, kL1CntBytes, st));
     HIP_TRY(hipMemsetAsync(b.l2_cnt, 0, (size_t)B.nb1 * NB2 * 4, st));
-    if (st != emit_st) {
-        HIP_TRY(hipEventRecord(b.ev_flush, st));
-        HIP_TRY(hipStreamWaitEvent(emit_st, b.ev_flush, 0));
-    }
-    if (st != e->stream && barrier) {
-        HIP_TRY(hipEventRecord(b.ev_flush, st));
-        HIP_TRY(hipStreamWaitEvent(e->stream, b.ev_flush, 0));
-    }
+    if (st != emit_st && (rc = run_after(emit_st, st, b.ev_flush))) return rc;
+    if (st != e->stream && barrier && (rc = run_after(e->stream, st, b.ev_flush))) return rc;
     // how many records that was (k_infer counts every insert it decides, on the main stream): the estimate that times
     // the next flush, fetched without stopping a stream
     if (w == 1 && !barrier) {
@@ -725,10 +809,8 @@ int bucket_flush(kbbq_engine *e, int w, bool barrier = true) {
             }
         }
     }
-    {
-        if (e->opt.debug_bucket) fprintf(stderr, "[bucket] flush %d of filter %d: estimate %.3g records over %llu bases (%.4f per base), barrier %d\n",
-                           (int)b.flushes[w], w, b.pending_est[w], (unsigned long long)b.bases_since[w], w ? b.frac_trusted : 0.0, (int)barrier);
-    }
+    if (e->opt.debug_bucket) fprintf(stderr, "[bucket] flush %d of filter %d: estimate %.3g records over %llu bases (%.4f per base), barrier %d\n",
+                       (int)b.flushes[w], w, b.pending_est[w], (unsigned long long)b.bases_since[w], w ? b.frac_trusted : 0.0, (int)barrier);
     b.bases_since[w] = 0;
     b.pending[w] = false;
     b.pending_est[w] = 0;
@@ -743,6 +825,12 @@ int bucket_flush_all(kbbq_engine *e) {
         if (rc) return rc;
     }
     return KBBQ_OK;
+}
+
+// deferred inserts reach the filters (bucket.h), then both streams are idle and pass 3's totals collected
+int settle(kbbq_engine *e) {
+    int rc = bucket_flush_all(e);
+    return rc ? rc : sync_engine(e);
 }
 
 // room for `est` more records of filter w?  (the other filter's records share the buffers: they go first)
@@ -802,6 +890,8 @@ int kbbq_engine_create(const kbbq_params *params, kbbq_engine **out) {
         o.scan_blocks = env_int("KBBQ_SCAN_BLOCKS", o.scan_blocks);
         o.walk_blocks = env_int("KBBQ_WALK_BLOCKS", o.walk_blocks);
         o.infer_blocks = env_int("KBBQ_INFER_BLOCKS", o.infer_blocks);
+        o.subset_edge = env_int("KBBQ_SUBSET_EDGE", o.subset_edge);
+        o.subset_pmask = env_int("KBBQ_SUBSET_PMASK", o.subset_pmask);
     }
     e->K.k = params->k;
     e->K.shift = 2u * (unsigned)(params->k - 1);
@@ -817,23 +907,10 @@ int kbbq_engine_create(const kbbq_params *params, kbbq_engine **out) {
     }
     hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_draw, hipEventDisableTiming);
-    for (int t = 0; t < 2 && he == hipSuccess; ++t) he = hipEventCreateWithFlags(&e->ev_ins[t], hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_side[0], hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_side[1], hipEventDisableTiming);
     if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->copy, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->bk.ev_flush, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->bk.ev_est, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_infer, hipEventDisableTiming);
-    for (int t = 0; t < 2 && he == hipSuccess; ++t) he = hipEventCreateWithFlags(&e->ev_take[t], hipEventDisableTiming);
+    for (hipEvent_t *ev : engine_events(e))
+        if (he == hipSuccess) he = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     if (he == hipSuccess) he = hipHostMalloc((void **)&e->bk.h_inserted, 64, hipHostMallocDefault);
-    for (int i = 0; i < 3 && he == hipSuccess; ++i) {
-        he = hipEventCreateWithFlags(&e->slot[i].h2d, hipEventDisableTiming);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&e->slot[i].d2h, hipEventDisableTiming);
-        for (int t = 0; t < 2 && he == hipSuccess; ++t) he = hipEventCreateWithFlags(&e->slot[i].done[t], hipEventDisableTiming);
-    }
-    e->cur = e->stream;
     if (he != hipSuccess) { kbbq_engine_destroy(e); return fail(KBBQ_EIO, "hipStreamCreate: %s", hipGetErrorString(he)); }
 #define CREATE_TRY(expr)                                                                           \
     do {                                                                                           \
@@ -845,13 +922,12 @@ int kbbq_engine_create(const kbbq_params *params, kbbq_engine **out) {
             return code;                                                                           \
         }                                                                                          \
     } while (0)
-    CREATE_TRY(hipMalloc(&e->d_counters, 64));
-    CREATE_TRY(hipMemset(e->d_counters, 0, 64));
-    CREATE_TRY(hipMalloc(&e->d_tickets, 64));
-    CREATE_TRY(hipMemset(e->d_tickets, 0, 64));
-    CREATE_TRY(hipMalloc(&e->d_totals, 32));
-    CREATE_TRY(hipMemset(e->d_totals, 0, 32));      // ([2]: the running byte sum of kbbq_digest_add)
-    e->cur_cnt = e->d_counters;
+    CREATE_TRY(hipMalloc(&e->d_counters, sizeof(Counters)));
+    CREATE_TRY(hipMemset(e->d_counters, 0, sizeof(Counters)));
+    CREATE_TRY(hipMalloc(&e->d_tickets, sizeof(Tickets)));
+    CREATE_TRY(hipMemset(e->d_tickets, 0, sizeof(Tickets)));
+    CREATE_TRY(hipMalloc(&e->d_totals, sizeof(Totals)));
+    CREATE_TRY(hipMemset(e->d_totals, 0, sizeof(Totals)));
     CREATE_TRY(hipMalloc(&e->d_dq_qslot, KBBQ_NQ));
     CREATE_TRY(hipMalloc(&e->d_qpresent, 32));
     for (int i = 0; i < 2; ++i) CREATE_TRY(hipMalloc(&e->d_rg_present[i], (((size_t)params->n_rg + 31) / 32) * 4 + 4));
@@ -892,17 +968,10 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     if (e->stream2) hipStreamSynchronize(e->stream2);
     if (e->copy) hipStreamSynchronize(e->copy);
     drain_profile(e);
-    for (int i = 0; i < 3; ++i) {
-        hipFree(e->slot[i].dev);
-        if (e->slot[i].h2d) hipEventDestroy(e->slot[i].h2d);
-        if (e->slot[i].d2h) hipEventDestroy(e->slot[i].d2h);
-        for (int t = 0; t < 2; ++t) if (e->slot[i].done[t]) hipEventDestroy(e->slot[i].done[t]);
-    }
+    for (hipEvent_t *ev : engine_events(e))
+        if (*ev) hipEventDestroy(*ev);
+    for (int i = 0; i < 3; ++i) hipFree(e->slot[i].dev);
     if (e->copy) hipStreamDestroy(e->copy);
-    if (e->bk.ev_flush) hipEventDestroy(e->bk.ev_flush);
-    if (e->bk.ev_est) hipEventDestroy(e->bk.ev_est);
-    if (e->ev_infer) hipEventDestroy(e->ev_infer);
-    for (int t = 0; t < 2; ++t) if (e->ev_take[t]) hipEventDestroy(e->ev_take[t]);
     if (e->bk.h_inserted) hipHostFree(e->bk.h_inserted);
     for (int w = 0; w < 2; ++w) {
         hipFree(e->filt[w].d_table);
@@ -923,19 +992,14 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->d_qcum);
     hipFree(e->d_errthr);
     hipFree(e->bk.l1); hipFree(e->bk.l2); hipFree(e->bk.l1_cnt); hipFree(e->bk.l2_cnt); hipFree(e->bk.tickets); hipFree(e->bk.direct);
-    for (int i = 0; i < 24; ++i) hipFree(e->scratch[i]);
+    for (int i = 0; i < S_COUNT; ++i) hipFree(e->scratch[i]);
     if (e->stream2) { hipStreamSynchronize(e->stream2); hipStreamDestroy(e->stream2); }
-    if (e->ev_main) hipEventDestroy(e->ev_main);
-    if (e->ev_draw) hipEventDestroy(e->ev_draw);
-    for (int t = 0; t < 2; ++t) if (e->ev_ins[t]) hipEventDestroy(e->ev_ins[t]);
-    for (int i = 0; i < 2; ++i) if (e->ev_side[i]) hipEventDestroy(e->ev_side[i]);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
 }
 
 int kbbq_engine_reset(kbbq_engine *e) {
     ENGINE_DEVICE(e);
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
     int rc0 = sync_engine(e);     // a tally may still be adding to the histograms on the side stream
     if (rc0) return rc0;
     for (int w = 0; w < 2; ++w) {
@@ -943,8 +1007,8 @@ int kbbq_engine_reset(kbbq_engine *e) {
         HIP_TRY(hipMemsetAsync(e->filt[w].d_inserted, 0, 8, e->stream));
     }
     HIP_TRY(hipMemsetAsync(e->d_hist, 0, (e->hist_cycle_words + e->hist_dinuc_words) * 8, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_counters, 0, 64, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_totals, 0, 16, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_counters, 0, sizeof(Counters), e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_totals, 0, offsetof(Totals, digest), e->stream));      // (the digest has its own reset: kbbq_digest_get)
     HIP_TRY(hipMemsetAsync(e->d_qpresent, 0, 32, e->stream));
     memset(e->qpresent, 0, sizeof e->qpresent);
     e->qpresent_known = false;
@@ -966,9 +1030,7 @@ int kbbq_engine_reset(kbbq_engine *e) {
 
 int kbbq_engine_sync(kbbq_engine *e) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
-    return sync_engine(e);
+    return settle(e);
 }
 
 void *kbbq_engine_stream(kbbq_engine *e) { return e ? (void *)e->stream : nullptr; }
@@ -993,21 +1055,13 @@ int kbbq_engine_tune(kbbq_engine *e, const char *name, uint64_t value) {
         (name[0] == 's' ? e->opt.scan_blocks : name[0] == 'w' ? e->opt.walk_blocks : e->opt.infer_blocks) = value == 17 ? (name[0] == 'i' ? 0 : -1) : (int)value;
     } else if (!strcmp(name, "infer_subset")) {
         e->opt.infer_subset = value != 0;      // (same results either way: an A/B switch between two runs)
-    } else if (!strcmp(name, "pass2_side")) {
+    } else if (!strcmp(name, "pass2_side") || !strcmp(name, "no_overlap")) {
+        // between two runs.  no_overlap: every kernel in order on one stream (exclusive kernel durations for a profile) or back
         ENGINE_DEVICE(e);
-        { int frc = bucket_flush_all(e); if (frc) return frc; }
-        int rc = sync_engine(e);
+        int rc = settle(e);
         if (rc) return rc;
-        if (value > 2) return fail(KBBQ_EINVAL, "pass2_side: 0, 1 or 2");
-        e->opt.pass2_side = (int)value;
-        e->bk.stream[0] = e->bk.stream[1] = nullptr;
-    } else if (!strcmp(name, "no_overlap")) {
-        // between two runs: every kernel in order on one stream (exclusive kernel durations for a profile) or back
-        ENGINE_DEVICE(e);
-        { int frc = bucket_flush_all(e); if (frc) return frc; }
-        int rc = sync_engine(e);
-        if (rc) return rc;
-        e->opt.no_overlap = value != 0;
+        if (name[0] == 'p' && value > 2) return fail(KBBQ_EINVAL, "pass2_side: 0, 1 or 2");
+        if (name[0] == 'p') e->opt.pass2_side = (int)value; else e->opt.no_overlap = value != 0;
         e->bk.stream[0] = e->bk.stream[1] = nullptr;
     } else {
         return fail(KBBQ_EINVAL, "unknown knob '%s'", name);
@@ -1017,8 +1071,9 @@ int kbbq_engine_tune(kbbq_engine *e, const char *name, uint64_t value) {
 
 int kbbq_filter_info_get(kbbq_engine *e, int which, kbbq_filter_info *out) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || !out || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
+    if (!out || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
+    int rc = settle(e);
+    if (rc) return rc;
     const FilterSpec &s = e->filt[which].spec;
     memset(out, 0, sizeof *out);
     out->bits = s.bits;
@@ -1029,8 +1084,6 @@ int kbbq_filter_info_get(kbbq_engine *e, int which, kbbq_filter_info *out) {
     out->n_hash = s.n_hash;
     out->n_salt = s.n_salt;
     for (uint32_t i = 0; i < s.n_salt; ++i) out->salt[i] = s.salt[i];
-    int rc = sync_engine(e);
-    if (rc) return rc;
     HIP_TRY(hipMemcpy(&out->inserted, e->filt[which].d_inserted, 8, hipMemcpyDeviceToHost));
     return KBBQ_OK;
 }
@@ -1045,11 +1098,10 @@ void *kbbq_filter_device_counter(kbbq_engine *e, int which) { return e && which 
 
 int kbbq_filter_download(kbbq_engine *e, int which, uint64_t *host_words, uint64_t n_words) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || !host_words || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
+    if (!host_words || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
     const uint64_t n_blocks = e->filt[which].spec.n_blocks;
     if (n_words != n_blocks * 8) return fail(KBBQ_EINVAL, "filter has %llu words", (unsigned long long)n_blocks * 8);
-    int rc = sync_engine(e);
+    int rc = settle(e);
     if (rc) return rc;
     // the device holds 128-bit blocks; the caller gets the reference's 512-bit ones
     const uint64_t chunk = 1 << 20;
@@ -1064,7 +1116,7 @@ int kbbq_filter_download(kbbq_engine *e, int which, uint64_t *host_words, uint64
 
 int kbbq_filter_patterns_download(kbbq_engine *e, int which, uint64_t *host_words) {
     ENGINE_DEVICE(e);
-    if (!e || !host_words || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
+    if (!host_words || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
     std::vector<uint64_t> packed(kNumPatterns * 2);
     HIP_TRY(hipMemcpy(packed.data(), e->filt[which].d_patterns, kNumPatterns * kEngineBlockBytes, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < kNumPatterns; ++i) expand_block(&packed[i * 2], host_words + i * 8);
@@ -1074,7 +1126,7 @@ int kbbq_filter_patterns_download(kbbq_engine *e, int which, uint64_t *host_word
 int kbbq_filter_or_from(kbbq_engine *e, int which, const void *src_device, uint64_t word_offset, uint64_t n_words) {
     ENGINE_DEVICE(e);
     { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || !src_device || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
+    if (!src_device || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
     const uint64_t total = e->filt[which].spec.n_blocks * 2;   // words of the engine's 128-bit blocks
     if (word_offset > total || n_words > total - word_offset || (word_offset & 1)) return fail(KBBQ_EINVAL, "range outside the filter");
     if (!n_words) return KBBQ_OK;
@@ -1087,7 +1139,7 @@ int kbbq_filter_or_from(kbbq_engine *e, int which, const void *src_device, uint6
 
 int kbbq_device_or(kbbq_engine *e, void *dst_device, const void *src_device, uint64_t n_words) {
     ENGINE_DEVICE(e);
-    if (!e || !dst_device || !src_device) return fail(KBBQ_EINVAL, "bad argument");
+    if (!dst_device || !src_device) return fail(KBBQ_EINVAL, "bad argument");
     if (((uintptr_t)dst_device | (uintptr_t)src_device) & 15) return fail(KBBQ_EINVAL, "buffers must be 16-byte aligned");
     if (!n_words) return KBBQ_OK;
     Timed t(e, "k_or_words");
@@ -1115,28 +1167,28 @@ __global__ void __launch_bounds__(256) k_sum_bytes(const uint8_t *d, uint64_t n,
 
 int kbbq_digest_add(kbbq_engine *e, const uint8_t *device_bytes, uint64_t n) {
     ENGINE_DEVICE(e);
-    if (!e || (!device_bytes && n)) return fail(KBBQ_EINVAL, "bad argument");
+    if (!device_bytes && n) return fail(KBBQ_EINVAL, "bad argument");
     if (!n) return KBBQ_OK;
-    hipLaunchKernelGGL(k_sum_bytes, dim3((unsigned)std::min<uint64_t>((n / 16 + 256) / 256, 4096)), dim3(256), 0, e->stream, device_bytes, n, e->d_totals + 2);
+    hipLaunchKernelGGL(k_sum_bytes, dim3((unsigned)std::min<uint64_t>((n / 16 + 256) / 256, 4096)), dim3(256), 0, e->stream, device_bytes, n, &e->d_totals->digest);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
 
 int kbbq_digest_get(kbbq_engine *e, uint64_t *sum, int32_t reset) {
     ENGINE_DEVICE(e);
-    if (!e || !sum) return fail(KBBQ_EINVAL, "bad argument");
+    if (!sum) return fail(KBBQ_EINVAL, "bad argument");
     HIP_TRY(hipStreamSynchronize(e->stream));
     unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, e->d_totals + 2, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&v, &e->d_totals->digest, 8, hipMemcpyDeviceToHost));
     *sum = v;
-    if (reset) HIP_TRY(hipMemset(e->d_totals + 2, 0, 8));
+    if (reset) HIP_TRY(hipMemset(&e->d_totals->digest, 0, 8));
     return KBBQ_OK;
 }
 
 int kbbq_device_or_pieces(kbbq_engine *e, void *dst_device, const void *src_device, uint64_t piece_words,
                           int32_t n_pieces, int32_t skip) {
     ENGINE_DEVICE(e);
-    if (!e || !dst_device || !src_device || n_pieces < 1) return fail(KBBQ_EINVAL, "bad argument");
+    if (!dst_device || !src_device || n_pieces < 1) return fail(KBBQ_EINVAL, "bad argument");
     if ((((uintptr_t)dst_device | (uintptr_t)src_device) & 15) || (piece_words & 1))
         return fail(KBBQ_EINVAL, "buffers must be 16-byte aligned and pieces an even number of words");
     if (!piece_words) return KBBQ_OK;
@@ -1150,7 +1202,7 @@ int kbbq_device_or_pieces(kbbq_engine *e, void *dst_device, const void *src_devi
 int kbbq_filter_set_inserted(kbbq_engine *e, int which, uint64_t inserted) {
     ENGINE_DEVICE(e);
     { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
+    if (which < 0 || which > 1) return fail(KBBQ_EINVAL, "bad argument");
     HIP_TRY(hipMemcpyAsync(e->filt[which].d_inserted, &inserted, 8, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return KBBQ_OK;
@@ -1226,6 +1278,32 @@ int kbbq_pack_bases_case(const uint8_t *seq, uint64_t n_bases, uint64_t *bases_o
     return pack_impl(seq, n_bases, bases_out, nmask_out, offcase_out, n_offcase);
 }
 
+// Every array of batch `from` into a fresh device allocation of batch `to` (+ `pad` zeroed elements behind it), queued on the
+// copy stream `cs` of the calling function; on a failure what was allocated so far is freed and the function returns.
+#define COPY_ARRAY(from, to, kind, what, field, type, count, pad)                                 \
+    if ((from)->field) {                                                                          \
+        void *d = nullptr;                                                                        \
+        hipError_t he = hipMalloc(&d, ((count) + (pad)) * sizeof(type));                          \
+        if (he == hipSuccess) {                                                                   \
+            (to)->field = (const type *)d;                                                        \
+            if (pad) he = hipMemsetAsync((char *)d + (count) * sizeof(type), 0, (pad) * sizeof(type), cs); \
+        }                                                                                         \
+        if (he == hipSuccess) he = hipMemcpyAsync(d, (from)->field, (count) * sizeof(type), kind, cs); \
+        if (he != hipSuccess) {                                                                   \
+            hipStreamSynchronize(cs);                                                             \
+            kbbq_reads_free(nullptr, to);                                                         \
+            return fail(he == hipErrorOutOfMemory ? KBBQ_ENOMEM : KBBQ_EIO, what " of %s: %s", #field, hipGetErrorString(he)); \
+        }                                                                                         \
+    }
+#define COPY_BATCH_ARRAYS(from, to, kind, what)                                  \
+    COPY_ARRAY(from, to, kind, what, bases, uint64_t, (from)->n_bases / 32 + 1, 1)   \
+    COPY_ARRAY(from, to, kind, what, nmask, uint64_t, (from)->n_bases / 64 + 1, 1)   \
+    COPY_ARRAY(from, to, kind, what, qual, uint8_t, (from)->n_bases, 16)             \
+    COPY_ARRAY(from, to, kind, what, offsets, uint64_t, (from)->n_reads + 1, 0)      \
+    COPY_ARRAY(from, to, kind, what, flags, uint8_t, (from)->n_reads, 0)             \
+    COPY_ARRAY(from, to, kind, what, rg, uint16_t, (from)->n_reads, 0)               \
+    COPY_ARRAY(from, to, kind, what, offcase, uint64_t, (from)->n_bases / 64 + 1, 1)
+
 int kbbq_reads_upload(kbbq_engine *e, const kbbq_reads *host, kbbq_reads *dev) {
     // e may be NULL: batches can be made resident before the engine (whose size depends on them) exists
     if (!host || !dev) return fail(KBBQ_EINVAL, "null argument");
@@ -1249,29 +1327,7 @@ int kbbq_reads_upload(kbbq_engine *e, const kbbq_reads *host, kbbq_reads *dev) {
         HIP_TRY(hipGetDevice(&cur));
         if (!(cs = shared_copy_stream(cur))) return fail(KBBQ_EIO, "no copy stream for device %d", cur);
     }
-#define UP(field, type, count, pad)                                                               \
-    if (host->field) {                                                                            \
-        void *d = nullptr;                                                                        \
-        hipError_t he = hipMalloc(&d, ((count) + (pad)) * sizeof(type));                          \
-        if (he == hipSuccess) {                                                                   \
-            dev->field = (const type *)d;                                                         \
-            if (pad) he = hipMemsetAsync((char *)d + (count) * sizeof(type), 0, (pad) * sizeof(type), cs); \
-        }                                                                                         \
-        if (he == hipSuccess) he = hipMemcpyAsync(d, host->field, (count) * sizeof(type), hipMemcpyHostToDevice, cs); \
-        if (he != hipSuccess) {                                                                   \
-            hipStreamSynchronize(cs);                                                             \
-            kbbq_reads_free(nullptr, dev);   /* what was allocated so far */                      \
-            return fail(he == hipErrorOutOfMemory ? KBBQ_ENOMEM : KBBQ_EIO, "upload of %s: %s", #field, hipGetErrorString(he)); \
-        }                                                                                         \
-    }
-    UP(bases, uint64_t, host->n_bases / 32 + 1, 1)
-    UP(nmask, uint64_t, host->n_bases / 64 + 1, 1)
-    UP(qual, uint8_t, host->n_bases, 16)
-    UP(offsets, uint64_t, host->n_reads + 1, 0)
-    UP(flags, uint8_t, host->n_reads, 0)
-    UP(rg, uint16_t, host->n_reads, 0)
-    UP(offcase, uint64_t, host->n_bases / 64 + 1, 1)
-#undef UP
+    COPY_BATCH_ARRAYS(host, dev, hipMemcpyHostToDevice, "upload")
     HIP_TRY(hipStreamSynchronize(cs));
     return KBBQ_OK;
 }
@@ -1287,29 +1343,7 @@ int kbbq_reads_clone(const kbbq_reads *src, int32_t device, int32_t with_hints, 
     *out = *src;
     out->hint_sampled = nullptr; out->hint_trusted = nullptr;
     out->bases = nullptr; out->nmask = nullptr; out->qual = nullptr; out->offsets = nullptr; out->flags = nullptr; out->rg = nullptr; out->offcase = nullptr;
-#define CL(field, type, count, pad)                                                               \
-    if (src->field) {                                                                             \
-        void *d = nullptr;                                                                        \
-        hipError_t he = hipMalloc(&d, ((count) + (pad)) * sizeof(type));                          \
-        if (he == hipSuccess) {                                                                   \
-            out->field = (const type *)d;                                                         \
-            if (pad) he = hipMemsetAsync((char *)d + (count) * sizeof(type), 0, (pad) * sizeof(type), cs); \
-        }                                                                                         \
-        if (he == hipSuccess) he = hipMemcpyAsync(d, src->field, (count) * sizeof(type), hipMemcpyDefault, cs); \
-        if (he != hipSuccess) {                                                                   \
-            hipStreamSynchronize(cs);                                                             \
-            kbbq_reads_free(nullptr, out);                                                        \
-            return fail(he == hipErrorOutOfMemory ? KBBQ_ENOMEM : KBBQ_EIO, "copy of %s: %s", #field, hipGetErrorString(he)); \
-        }                                                                                         \
-    }
-    CL(bases, uint64_t, src->n_bases / 32 + 1, 1)
-    CL(nmask, uint64_t, src->n_bases / 64 + 1, 1)
-    CL(qual, uint8_t, src->n_bases, 16)
-    CL(offsets, uint64_t, src->n_reads + 1, 0)
-    CL(flags, uint8_t, src->n_reads, 0)
-    CL(rg, uint16_t, src->n_reads, 0)
-    CL(offcase, uint64_t, src->n_bases / 64 + 1, 1)
-#undef CL
+    COPY_BATCH_ARRAYS(src, out, hipMemcpyDefault, "copy")
     HIP_TRY(hipStreamSynchronize(cs));
     if (with_hints) {
         const int rc = kbbq_reads_alloc_hints(out);      // (on the current device: the guard's)
@@ -1507,7 +1541,7 @@ int kbbq_device_memory(int32_t device, uint64_t *free_bytes, uint64_t *total_byt
 // ---- pass 1
 int kbbq_count_kmer_positions(kbbq_engine *e, const kbbq_reads *reads, uint64_t *out) {
     ENGINE_DEVICE(e);
-    if (!e || !reads || !out) return fail(KBBQ_EINVAL, "null argument");
+    if (!reads || !out) return fail(KBBQ_EINVAL, "null argument");
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
     int rc = device_view(e, reads, &R, &max_len, false);
@@ -1582,7 +1616,6 @@ extern "C" {
 
 int kbbq_sample_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_kmer_ordinal) {
     ENGINE_DEVICE(e);
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
     int rc = device_view(e, reads, &R, &max_len, false);      // pass 1 reads bases only
@@ -1592,9 +1625,8 @@ int kbbq_sample_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_km
     if (n_draws == 0) return KBBQ_OK;
     const bool overlap = reads->on_device && !e->opt.no_overlap;
     const int turn = overlap ? e->draw_turn : 0;
-    const int slot = turn ? 13 : 0;
-    if ((rc = ensure_scratch(e, slot, (n_draws / 64 + 2) * 8))) return rc;
-    uint64_t *mask = (uint64_t *)e->scratch[slot];
+    uint64_t *mask;
+    if ((rc = scratch_buf(e, turn ? S_DRAW1 : S_DRAW0, (n_draws / 64 + 2) * 8, &mask))) return rc;
     hipStream_t ds = overlap ? e->stream2 : e->stream;
     if (overlap) {
         e->draw_turn ^= 1;
@@ -1612,10 +1644,7 @@ int kbbq_sample_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_km
                            (uint64_t)0, n_draws, e->draw_threshold, e->draw_always ? 1 : 0, mask);
         HIP_TRY(hipGetLastError());
     }
-    if (overlap) {
-        HIP_TRY(hipEventRecord(e->ev_draw, ds));
-        HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_draw, 0));
-    }
+    if (overlap && (rc = run_after(e->stream, ds, e->ev_draw))) return rc;
     if (max_len > kStagedMax) {
         Timed t(e, "k_insert_sampled_long");
         hipLaunchKernelGGL(k_insert_marked_long<false>, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, e->K, e->filt[0].dev(),
@@ -1639,9 +1668,7 @@ int kbbq_sample_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_km
 
 int kbbq_sample_finish(kbbq_engine *e, uint64_t *inserted) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
-    int rc = sync_engine(e);
+    int rc = settle(e);
     if (rc) return rc;
     if (inserted) HIP_TRY(hipMemcpy(inserted, e->filt[0].d_inserted, 8, hipMemcpyDeviceToHost));
     return KBBQ_OK;
@@ -1651,9 +1678,8 @@ int kbbq_sample_finish(kbbq_engine *e, uint64_t *inserted) {
 int kbbq_compute_thresholds(kbbq_engine *e, const char *alpha_text, int32_t *thresholds_out, double *fpr_out,
                             char *p_text_out, size_t p_text_len) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || !alpha_text) return fail(KBBQ_EINVAL, "null argument");
-    int rc = sync_engine(e);
+    if (!alpha_text) return fail(KBBQ_EINVAL, "null argument");
+    int rc = settle(e);
     if (rc) return rc;
     uint64_t inserted = 0;
     HIP_TRY(hipMemcpy(&inserted, e->filt[0].d_inserted, 8, hipMemcpyDeviceToHost));
@@ -1671,7 +1697,7 @@ int kbbq_compute_thresholds(kbbq_engine *e, const char *alpha_text, int32_t *thr
 
 int kbbq_set_thresholds(kbbq_engine *e, const int32_t *thresholds, int32_t n) {
     ENGINE_DEVICE(e);
-    if (!e || !thresholds) return fail(KBBQ_EINVAL, "null argument");
+    if (!thresholds) return fail(KBBQ_EINVAL, "null argument");
     if (n != e->p.k + 1) return fail(KBBQ_EINVAL, "expected k+1 = %d thresholds", e->p.k + 1);
     if (thresholds != e->thresholds.data()) e->thresholds.assign(thresholds, thresholds + n);
     e->thresholds_set = true;
@@ -1702,23 +1728,28 @@ static bool infer_subset_plan(const std::vector<int> &thr, int k, int *edge_out,
     return false;
 }
 
+static Thresholds fill_thresholds(const kbbq_engine *e) {
+    Thresholds thr;
+    memset(&thr, 0, sizeof thr);
+    for (size_t i = 0; i < e->thresholds.size() && i <= KBBQ_MAX_KMER; ++i) thr.v[i] = e->thresholds[i];
+    return thr;
+}
+
 template <int NW> struct LaunchTrusted {
     static int go(kbbq_engine *e, ReadsDev R, uint32_t *take_bits, uint32_t *err_out, int max_len) {
-        Thresholds thr;
-        memset(&thr, 0, sizeof thr);
-        for (size_t i = 0; i < e->thresholds.size() && i <= KBBQ_MAX_KMER; ++i) thr.v[i] = e->thresholds[i];
-        HIP_TRY(hipMemsetAsync(e->d_tickets, 0, 4, e->stream));      // the kernel's chunk counter (ReadChunks)
+        const Thresholds thr = fill_thresholds(e);
+        HIP_TRY(hipMemsetAsync(&e->d_tickets->infer, 0, 4, e->stream));      // the kernel's chunk counter (ReadChunks)
         {
             Timed t(e, "k_infer");
             int edge = -1, pmask = 3;
             if (e->opt.infer_subset && !infer_subset_plan(e->thresholds, e->p.k, &edge, &pmask)) edge = -1;
-            if (edge >= 0 && getenv("KBBQ_SUBSET_EDGE")) edge = atoi(getenv("KBBQ_SUBSET_EDGE"));        // (diagnostic overrides: results
-            if (edge >= 0 && getenv("KBBQ_SUBSET_PMASK")) pmask = atoi(getenv("KBBQ_SUBSET_PMASK"));     //  never depend on either)
+            if (edge >= 0 && e->opt.subset_edge != kNoOverride) edge = e->opt.subset_edge;
+            if (edge >= 0 && e->opt.subset_pmask != kNoOverride) pmask = e->opt.subset_pmask;
             // NK: chunks of 64 lanes that can hold a k-mer start (150-base reads, k = 32: 119 starts, two of the three chunks)
             const bool short_nk = std::max(1, max_len - e->p.k + 1) <= (NW - 1) * 64;
 #define KBBQ_LAUNCH_INFER(NK_, SUB_)                                                                                              \
     hipLaunchKernelGGL((k_infer<NW, NK_, 1, SUB_>), dim3(wave_grid(R.n_reads, shared_cap(e, e->opt.infer_blocks))), dim3(256), 0, e->stream, R, e->K, e->filt[0].dev(), thr, \
-                       take_bits, e->filt[1].d_inserted, err_out, e->d_qpresent, e->d_counters + 3, e->d_tickets, edge, pmask)
+                       take_bits, e->filt[1].d_inserted, err_out, e->d_qpresent, &e->d_counters->infer_fetched, &e->d_tickets->infer, edge, pmask)
             if (edge >= 0) { if (short_nk) KBBQ_LAUNCH_INFER(NW - 1, true); else KBBQ_LAUNCH_INFER(NW, true); }
             else { if (short_nk) KBBQ_LAUNCH_INFER(NW - 1, false); else KBBQ_LAUNCH_INFER(NW, false); }
 #undef KBBQ_LAUNCH_INFER
@@ -1736,14 +1767,14 @@ template <int NW> struct LaunchTrusted {
             // (KBBQ_F_NO_OVERLAP).
             const bool side = e->opt.pass2_side != 0 && !e->opt.no_overlap;
             e->bk.stream[1] = side ? e->stream2 : e->stream;
+            int rc;
             if (side) {
-                HIP_TRY(hipEventRecord(e->ev_infer, e->stream));
-                HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_infer, 0));
+                if ((rc = run_after(e->stream2, e->stream, e->ev_infer))) return rc;
                 e->cur_slot_side = true;      // (a host batch: its staging slot is read on the side stream as well)
             }
             bucket_poll_estimate(e);
             e->bk.frac_used = e->bk.frac_trusted;
-            int rc = bucket_reserve(e, 1, (double)R.n_bases * e->bk.frac_trusted + 4096.0, R.n_bases);
+            rc = bucket_reserve(e, 1, (double)R.n_bases * e->bk.frac_trusted + 4096.0, R.n_bases);
             if (rc) return rc;
             return dispatch_emit(e, 1, max_len, R, (const uint64_t *)take_bits, R.n_bases / 64 + 2, (const uint64_t *)nullptr,
                                  (unsigned long long *)nullptr);
@@ -1760,16 +1791,15 @@ template <int NW> struct LaunchTrusted {
 };
 extern "C" {
 
-static int bit_out_begin(kbbq_engine *e, const kbbq_reads *reads, uint64_t *user, int slot, uint32_t **dev) {
+static int bit_out_begin(kbbq_engine *e, const kbbq_reads *reads, uint64_t *user, Scratch name, uint32_t **dev) {
     *dev = nullptr;
     if (!user) return KBBQ_OK;
     const size_t bytes = (reads->n_bases / 64 + 2) * 8;
     if (reads->on_device) {
         *dev = (uint32_t *)user;
     } else {
-        int rc = ensure_scratch(e, slot, bytes);
+        int rc = scratch_buf(e, name, bytes, dev);
         if (rc) return rc;
-        *dev = (uint32_t *)e->scratch[slot];
     }
     HIP_TRY(hipMemsetAsync(*dev, 0, (reads->n_bases / 64 + 1) * 8, e->stream));
     return KBBQ_OK;
@@ -1784,14 +1814,13 @@ static int bit_out_end(kbbq_engine *e, const kbbq_reads *reads, uint64_t *user, 
 int kbbq_trusted_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *infer_errors_out) {
     ENGINE_DEVICE(e);
     { int frc = bucket_flush(e, 0); if (frc) return frc; }      // pass 2 reads the sampled filter: its deferred inserts go in first
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
     if (!e->thresholds_set) return fail(KBBQ_ESTATE, "thresholds are not set");
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
     int rc = device_view(e, reads, &R, &max_len);
     if (rc) return rc;
     uint32_t *d_err;
-    if ((rc = bit_out_begin(e, reads, infer_errors_out, 2, &d_err))) return rc;
+    if ((rc = bit_out_begin(e, reads, infer_errors_out, S_HOST_OUT, &d_err))) return rc;
     // the insert decisions of k_infer: the caller's hint array when there is one (pass 3 then reuses
     // them), a scratch bit array otherwise
     uint32_t *take_bits = R.hint_trusted;
@@ -1800,43 +1829,33 @@ int kbbq_trusted_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *infer_
         // two scratch arrays in turn: the side stream may still be reading the one before last (ev_take)
         take_slot = e->take_turn;
         e->take_turn ^= 1;
-        const int sl = take_slot ? 22 : 8;
         if (e->take_pending[take_slot]) {
             HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_take[take_slot], 0));
             e->take_pending[take_slot] = false;
         }
-        if ((rc = ensure_scratch(e, sl, (R.n_bases / 64 + 2) * 8))) return rc;
-        take_bits = (uint32_t *)e->scratch[sl];
+        if ((rc = scratch_buf(e, take_slot ? S_TAKE1 : S_TAKE0, (R.n_bases / 64 + 2) * 8, &take_bits))) return rc;
         HIP_TRY(hipMemsetAsync(take_bits, 0, (R.n_bases / 64 + 2) * 8, e->stream));
     }
     if (max_len > kStagedMax) {
-        Thresholds thr;
-        memset(&thr, 0, sizeof thr);
-        for (size_t i = 0; i < e->thresholds.size() && i <= KBBQ_MAX_KMER; ++i) thr.v[i] = e->thresholds[i];
+        const Thresholds thr = fill_thresholds(e);
         {
             Timed t(e, "k_infer_long");
             hipLaunchKernelGGL(k_infer_long, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, e->K, e->filt[0].dev(), thr, take_bits,
-                               e->filt[1].d_inserted, d_err, e->d_qpresent, e->d_counters + 3);
+                               e->filt[1].d_inserted, d_err, e->d_qpresent, &e->d_counters->infer_fetched);
             HIP_TRY(hipGetLastError());
         }
         // These inserts are atomic ORs straight into the trusted filter.  Batches of short reads of the same pass may have
         // records pending, or a flush (k_apply: load a slice, OR, store it back -- no atomics) running, on the side
         // stream: the direct inserts wait for what is queued there, and what is queued there later waits for them.
         const bool side_busy = e->bk.stream[1] && e->bk.stream[1] != e->stream;
-        if (side_busy) {
-            HIP_TRY(hipEventRecord(e->bk.ev_flush, e->bk.stream[1]));
-            HIP_TRY(hipStreamWaitEvent(e->stream, e->bk.ev_flush, 0));
-        }
+        if (side_busy && (rc = run_after(e->stream, e->bk.stream[1], e->bk.ev_flush))) return rc;
         {
             Timed t(e, "k_insert_trusted_long");
             hipLaunchKernelGGL(k_insert_marked_long<true>, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, e->K, e->filt[1].dev(),
                                (const uint64_t *)take_bits, R.n_bases / 64 + 2, (const uint64_t *)nullptr, (unsigned long long *)nullptr);
             HIP_TRY(hipGetLastError());
         }
-        if (side_busy) {
-            HIP_TRY(hipEventRecord(e->ev_infer, e->stream));
-            HIP_TRY(hipStreamWaitEvent(e->bk.stream[1], e->ev_infer, 0));
-        }
+        if (side_busy && (rc = run_after(e->bk.stream[1], e->stream, e->ev_infer))) return rc;
     } else if ((rc = dispatch_nw<LaunchTrusted>(max_len, e, R, take_bits, d_err, max_len))) return rc;
     if (take_slot >= 0 && bucket_stream(e, 1) != e->stream && e->bk.mode[1] == 1 && max_len <= kStagedMax) {
         HIP_TRY(hipEventRecord(e->ev_take[take_slot], bucket_stream(e, 1)));      // the emit has read this scratch array
@@ -1848,9 +1867,7 @@ int kbbq_trusted_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *infer_
 
 int kbbq_trusted_finish(kbbq_engine *e, uint64_t *inserted) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
-    int rc = sync_engine(e);
+    int rc = settle(e);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(e->qpresent, e->d_qpresent, 32, hipMemcpyDeviceToHost));      // the tally sizes its LDS tables by these (run_tally)
     e->qpresent_known = true;
@@ -1861,25 +1878,30 @@ int kbbq_trusted_finish(kbbq_engine *e, uint64_t *inserted) {
 // ---- pass 3
 }  // extern "C"
 
+// grid of a persistent kernel of pass 3: capped (Options::scan_blocks, walk_blocks) while the batch shares the chip
+static int pass3_grid(const kbbq_engine *e, const Pass3 &c, const ReadsDev &R, int per_cu, int auto_value, int max_len) {
+    return wave_grid(R.n_reads, c.shared ? shared_cap(e, per_cu, auto_value, max_len, !R.offsets) : 0);
+}
+
 template <int NW> struct LaunchScan {
-    static int go(kbbq_engine *e, ReadsDev R, uint64_t *tmask, uint8_t *dirty, uint32_t *err_bits, int fast, int max_len) {
-        unsigned int *ticket = e->d_tickets + 1 + (e->cur_cnt != e->d_counters ? 1 : 0);      // per side of pass 3
-        HIP_TRY(hipMemsetAsync(ticket, 0, 4, e->cur));
-        Timed t(e, "k_scan_trusted", e->cur);
+    static int go(kbbq_engine *e, const Pass3 &c, ReadsDev R, uint64_t *tmask, uint8_t *dirty, uint32_t *err_bits, int fast, int max_len) {
+        HIP_TRY(hipMemsetAsync(c.scan_ticket, 0, 4, c.stream));
+        Timed t(e, "k_scan_trusted", c.stream);
+        const int grid = pass3_grid(e, c, R, e->opt.scan_blocks, 4, max_len);
         if (std::max(1, max_len - e->p.k + 1) <= (NW - 1) * 64)      // (NK: see k_infer)
-            hipLaunchKernelGGL((k_scan_trusted<NW, NW - 1>), dim3(wave_grid(R.n_reads, e->pass3_shared ? shared_cap(e, e->opt.scan_blocks, 4, max_len, !R.offsets) : 0)), dim3(256), 0, e->cur, R, e->K,
-                               e->filt[1].dev(), tmask, dirty, err_bits, e->cur_cnt, fast, ticket);
+            hipLaunchKernelGGL((k_scan_trusted<NW, NW - 1>), dim3(grid), dim3(256), 0, c.stream, R, e->K,
+                               e->filt[1].dev(), tmask, dirty, err_bits, c.cnt, fast, c.scan_ticket);
         else
-            hipLaunchKernelGGL((k_scan_trusted<NW, NW>), dim3(wave_grid(R.n_reads, e->pass3_shared ? shared_cap(e, e->opt.scan_blocks, 4, max_len, !R.offsets) : 0)), dim3(256), 0, e->cur, R, e->K,
-                               e->filt[1].dev(), tmask, dirty, err_bits, e->cur_cnt, fast, ticket);
+            hipLaunchKernelGGL((k_scan_trusted<NW, NW>), dim3(grid), dim3(256), 0, c.stream, R, e->K,
+                               e->filt[1].dev(), tmask, dirty, err_bits, c.cnt, fast, c.scan_ticket);
         HIP_TRY(hipGetLastError());
         return KBBQ_OK;
     }
 };
 
 template <int MAXL, int BLOCK>
-static int launch_correct(kbbq_engine *e, ReadsDev R, const uint32_t *list, const unsigned long long *n_list, const uint64_t *tmask, int tw,
-                          uint32_t *err_bits, uint32_t *patch, int max_len = 0, int side = 0) {
+static int launch_correct(kbbq_engine *e, const Pass3 &c, ReadsDev R, const uint32_t *list, const unsigned long long *n_list, const uint64_t *tmask, int tw,
+                          uint32_t *err_bits, uint32_t *patch, int max_len = 0) {
     typedef Corrector<MAXL> C;
     if (MAXL == 0) {
         // reads longer than 512 bases: the lane's working words (C::words_for(len) of them) live in a global scratch
@@ -1888,12 +1910,12 @@ static int launch_correct(kbbq_engine *e, ReadsDev R, const uint32_t *list, cons
         const size_t words = (size_t)C::words_for(dyn_len);
         const uint64_t fit = std::max<uint64_t>(1, ((uint64_t)1 << 30) / (words * 4 * BLOCK));
         const int blocks = (int)std::min<uint64_t>(std::min<uint64_t>((R.n_reads + BLOCK - 1) / BLOCK, 256 * 4), fit);
-        const int slot = side ? 21 : 20;
-        int rc = ensure_scratch(e, slot, (size_t)blocks * BLOCK * words * 4);
+        uint32_t *walk_words;
+        int rc = scratch_buf(e, per_side(S_WALK_WORDS, c.side), (size_t)blocks * BLOCK * words * 4, &walk_words);
         if (rc) return rc;
-        Timed t(e, "k_correct_long", e->cur);
-        hipLaunchKernelGGL((k_correct<MAXL, BLOCK>), dim3(blocks), dim3(BLOCK), 0, e->cur, R, e->K, e->filt[1].dev(), list,
-                           n_list, tmask, tw, err_bits, patch, e->cur_cnt, dyn_len, (uint32_t *)e->scratch[slot]);
+        Timed t(e, "k_correct_long", c.stream);
+        hipLaunchKernelGGL((k_correct<MAXL, BLOCK>), dim3(blocks), dim3(BLOCK), 0, c.stream, R, e->K, e->filt[1].dev(), list,
+                           n_list, tmask, tw, err_bits, patch, c.cnt, dyn_len, walk_words);
         HIP_TRY(hipGetLastError());
         return KBBQ_OK;
     }
@@ -1903,45 +1925,45 @@ static int launch_correct(kbbq_engine *e, ReadsDev R, const uint32_t *list, cons
         HIP_TRY(hipFuncSetAttribute((const void *)k_correct<MAXL, BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         raised = lds;
     }
-    Timed t(e, "k_correct", e->cur);
+    Timed t(e, "k_correct", c.stream);
     // the work-list length is only known on the device: size the grid for the batch and let lanes stride
     const int blocks = (int)std::min<uint64_t>((R.n_reads + BLOCK - 1) / BLOCK, 256 * 8);
-    hipLaunchKernelGGL((k_correct<MAXL, BLOCK>), dim3(blocks), dim3(BLOCK), lds, e->cur, R, e->K, e->filt[1].dev(), list,
-                       n_list, tmask, tw, err_bits, patch, e->cur_cnt, 0, (uint32_t *)nullptr);
+    hipLaunchKernelGGL((k_correct<MAXL, BLOCK>), dim3(blocks), dim3(BLOCK), lds, c.stream, R, e->K, e->filt[1].dev(), list,
+                       n_list, tmask, tw, err_bits, patch, c.cnt, 0, (uint32_t *)nullptr);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
 
 template <int NB, int NN>
-static int launch_correct_wave(kbbq_engine *e, ReadsDev R, const uint32_t *list, const uint64_t *tmask, int tw,
+static int launch_correct_wave(kbbq_engine *e, const Pass3 &c, ReadsDev R, const uint32_t *list, const uint64_t *tmask, int tw,
                                uint32_t *err_bits, uint32_t *patch) {
-    unsigned int *ticket = e->d_tickets + 3 + (e->cur_cnt != e->d_counters ? 1 : 0);      // per side of pass 3
-    HIP_TRY(hipMemsetAsync(ticket, 0, 4, e->cur));
-    Timed t(e, "k_correct_wave", e->cur);
-    const int blocks = wave_grid(R.n_reads, e->pass3_shared ? shared_cap(e, e->opt.walk_blocks, 2, NB <= 5 ? 160 : 512, !R.offsets) : 0);
-    hipLaunchKernelGGL((k_correct_wave<NB, NN>), dim3(blocks), dim3(256), 0, e->cur, R, e->K, e->filt[1].dev(), list,
-                       (const unsigned long long *)e->cur_cnt, tmask, tw, err_bits, patch, e->cur_cnt, ticket);
+    HIP_TRY(hipMemsetAsync(c.wave_ticket, 0, 4, c.stream));
+    Timed t(e, "k_correct_wave", c.stream);
+    const int blocks = pass3_grid(e, c, R, e->opt.walk_blocks, 2, NB <= 5 ? 160 : 512);
+    hipLaunchKernelGGL((k_correct_wave<NB, NN>), dim3(blocks), dim3(256), 0, c.stream, R, e->K, e->filt[1].dev(), list,
+                       (const unsigned long long *)c.cnt, tmask, tw, err_bits, patch, c.cnt, c.wave_ticket);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
 extern "C" {
 
-// coarse base -> read index of a ragged batch (kernels.h: k_read_index), in scratch slot `slot`; null for uniform batches
-static int build_read_index(kbbq_engine *e, const ReadsDev &R, int slot, hipStream_t stream, const uint32_t **index) {
+// coarse base -> read index of a ragged batch (kernels.h: k_read_index), in the stream's buffer (0: the engine's stream,
+// 1: the side stream); null for uniform batches
+static int build_read_index(kbbq_engine *e, const ReadsDev &R, int stream_no, hipStream_t stream, const uint32_t **index) {
     *index = nullptr;
     if (!R.offsets || !R.n_reads) return KBBQ_OK;
     const size_t entries = R.n_bases / READ_INDEX_STEP + 2;
-    int rc = ensure_scratch(e, slot, entries * 4);
+    uint32_t *d;
+    int rc = scratch_buf(e, stream_no ? S_READ_INDEX1 : S_READ_INDEX0, entries * 4, &d);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_read_index, dim3((unsigned)((R.n_reads + 255) / 256)), dim3(256), 0, stream, R.offsets, R.n_reads, (uint32_t *)e->scratch[slot]);
+    hipLaunchKernelGGL(k_read_index, dim3((unsigned)((R.n_reads + 255) / 256)), dim3(256), 0, stream, R.offsets, R.n_reads, d);
     HIP_TRY(hipGetLastError());
-    *index = (const uint32_t *)e->scratch[slot];
+    *index = d;
     return KBBQ_OK;
 }
 
-static int run_tally(kbbq_engine *e, const ReadsDev &R, const uint32_t *err_bits, const uint32_t *patch, int max_len,
-                     hipStream_t stream = nullptr) {
-    if (!stream) stream = e->cur;
+static int run_tally(kbbq_engine *e, const Pass3 &c, const ReadsDev &R, const uint32_t *err_bits, const uint32_t *patch, int max_len) {
+    const hipStream_t stream = c.stream;
     HistDev H;
     H.cycle = e->d_hist;
     H.dinuc = e->d_hist + e->hist_cycle_words;
@@ -1985,11 +2007,11 @@ static int run_tally(kbbq_engine *e, const ReadsDev &R, const uint32_t *err_bits
     const int blocks = (int)std::min<uint64_t>((groups + 1023) / 1024, lds <= 76 * 1024 ? 512 : 256);
     const int vec_ok = ((uintptr_t)R.qual & 15) == 0;
     const uint32_t *read_index;
-    int rc = build_read_index(e, R, stream == e->stream2 ? 15 : 14, stream, &read_index);
+    int rc = build_read_index(e, R, c.stream_no, stream, &read_index);
     if (rc) return rc;
     const uint32_t *present = nullptr;
     if (n_rg > per_launch) {     // several launches: mark the read groups that occur, so that the others cost nothing
-        uint32_t *pr = e->d_rg_present[stream == e->stream2 ? 1 : 0];
+        uint32_t *pr = e->d_rg_present[c.stream_no];
         HIP_TRY(hipMemsetAsync(pr, 0, (((size_t)e->p.n_rg + 31) / 32) * 4, stream));
         hipLaunchKernelGGL(k_rg_presence, dim3((unsigned)((R.n_reads + 255) / 256)), dim3(256), 0, stream, R.rg, R.n_reads, (uint32_t)e->p.n_rg, pr);
         present = pr;
@@ -2018,8 +2040,10 @@ static int run_tally(kbbq_engine *e, const ReadsDev &R, const uint32_t *err_bits
 
 int kbbq_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *errors_out) {
     ENGINE_DEVICE(e);
-    { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || !reads) return fail(KBBQ_EINVAL, "null argument");
+    // deferred inserts reach the filters first (bucket.h).  The barrier flush also makes the engine's stream wait for what pass 2
+    // queued on the side stream: S_TAKE0, which an emit there may still be reading, is side 1's S_ERR below (enum Scratch)
+    { int frc = bucket_flush_all(e); if (frc) return frc; }
+    if (!reads) return fail(KBBQ_EINVAL, "null argument");
     const bool own_err = !(errors_out && reads->on_device);
     // A batch whose flags stay inside the engine may still be in flight while the next one is submitted: such
     // batches alternate between the two sides (a device-resident batch stays put by contract, a host batch sits in
@@ -2036,93 +2060,77 @@ int kbbq_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *errors_
     } else {
         if ((rc = sync_engine(e))) return rc;              // both sides' scratch is free
     }
-    e->pass3_shared = overlap;
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
     if ((rc = device_view(e, reads, &R, &max_len))) return rc;
     const bool long_reads = max_len > kStagedMax;
     // words of trusted mask per read: the staged kernels' NW; long reads: 8 per window of 512 k-mer starts
     const int NW = max_len <= 192 ? 3 : max_len <= 320 ? 5 : !long_reads ? 8 : 8 * ((std::max(1, max_len - e->p.k + 1) + 511) / 512);
-    // scratch per side: trusted masks, dirty flags, work list, error bits, seq patches
-    const int s_tmask = side ? 10 : 3, s_dirty = side ? 11 : 4, s_list = side ? 12 : 5, s_err = side ? 8 : 6, s_patch = side ? 9 : 7;
-    if ((rc = ensure_scratch(e, s_tmask, R.n_reads * NW * 8))) return rc;
-    if ((rc = ensure_scratch(e, s_dirty, R.n_reads))) return rc;
-    if ((rc = ensure_scratch(e, s_list, R.n_reads * 4))) return rc;
-    if ((rc = ensure_scratch(e, s_patch, R.n_reads * 4))) return rc;
-    uint32_t *d_err;
-    if (own_err) {
-        if ((rc = ensure_scratch(e, s_err, (R.n_bases / 64 + 2) * 8))) return rc;
-        d_err = (uint32_t *)e->scratch[s_err];
-    } else {
-        d_err = (uint32_t *)errors_out;
-    }
-    e->cur = e->stream;
-    e->cur_cnt = e->d_counters + 4 * side;
-    struct Restore { kbbq_engine *e; ~Restore() { e->cur = e->stream; e->cur_cnt = e->d_counters; } } restore = {e};
-    HIP_TRY(hipMemsetAsync(d_err, 0, (R.n_bases / 64 + 1) * 8, e->cur));
-    HIP_TRY(hipMemsetAsync(e->scratch[s_patch], 0, R.n_reads * 4, e->cur));
-    HIP_TRY(hipMemsetAsync(e->cur_cnt, 0, 16, e->cur));
-    uint64_t *tmask = (uint64_t *)e->scratch[s_tmask];
-    uint8_t *dirty = (uint8_t *)e->scratch[s_dirty];
-    uint32_t *list = (uint32_t *)e->scratch[s_list];
-    uint32_t *patch = (uint32_t *)e->scratch[s_patch];
+    // scratch per side: trusted masks, dirty flags, work list, seq patches, error bits
+    uint64_t *tmask; uint8_t *dirty; uint32_t *list, *patch, *d_err;
+    if ((rc = scratch_buf(e, per_side(S_TMASK, side), R.n_reads * NW * 8, &tmask))) return rc;
+    if ((rc = scratch_buf(e, per_side(S_DIRTY, side), R.n_reads, &dirty))) return rc;
+    if ((rc = scratch_buf(e, per_side(S_LIST, side), R.n_reads * 4, &list))) return rc;
+    if ((rc = scratch_buf(e, per_side(S_PATCH, side), R.n_reads * 4, &patch))) return rc;
+    if (!own_err) d_err = (uint32_t *)errors_out;
+    else if ((rc = scratch_buf(e, per_side(S_ERR, side), (R.n_bases / 64 + 2) * 8, &d_err))) return rc;
+    SideCounters *const cnt = e->d_counters->side(side);
+    unsigned long long *const offcase_len = &e->d_counters->offcase_len[side];
+    Pass3 c = {side, e->stream, 0, &cnt->list_len, &e->d_tickets->scan[side], &e->d_tickets->walk[side], overlap};
+    HIP_TRY(hipMemsetAsync(d_err, 0, (R.n_bases / 64 + 1) * 8, c.stream));
+    HIP_TRY(hipMemsetAsync(patch, 0, R.n_reads * 4, c.stream));
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof *cnt, c.stream));
     // isolated single errors are settled inside the scan (fast_path); the walk gets what is left (dirty == 1)
-    const bool no_fast = e->opt.no_fastpath;
     if (long_reads) {
-        Timed t(e, "k_scan_trusted_long", e->cur);
-        hipLaunchKernelGGL(k_scan_trusted_long, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->cur, R, e->K, e->filt[1].dev(), tmask, NW, dirty);
+        Timed t(e, "k_scan_trusted_long", c.stream);
+        hipLaunchKernelGGL(k_scan_trusted_long, dim3(wave_grid(R.n_reads)), dim3(256), 0, c.stream, R, e->K, e->filt[1].dev(), tmask, NW, dirty);
         HIP_TRY(hipGetLastError());
-    } else if ((rc = dispatch_nw<LaunchScan>(max_len, e, R, tmask, dirty, d_err, (!no_fast && e->p.k >= 3) ? 1 : 0, max_len))) return rc;
+    } else if ((rc = dispatch_nw<LaunchScan>(max_len, e, c, R, tmask, dirty, d_err, (!e->opt.no_fastpath && e->p.k >= 3) ? 1 : 0, max_len))) return rc;
     {
-        Timed t(e, "k_compact", e->cur);
+        Timed t(e, "k_compact", c.stream);
         // (long reads: every read that is not clean takes the run-time-sized lane-form walk, off-case or not)
-        hipLaunchKernelGGL(k_compact, dim3((unsigned)((R.n_reads + 1023) / 1024)), dim3(1024), 0, e->cur, dirty, R.n_reads, list, e->cur_cnt,
+        hipLaunchKernelGGL(k_compact, dim3((unsigned)((R.n_reads + 1023) / 1024)), dim3(1024), 0, c.stream, dirty, R.n_reads, list, c.cnt,
                            long_reads ? 0 : 1);
         HIP_TRY(hipGetLastError());
     }
     // The scan and the fast path of every batch run on the engine's stream; the walk and the tally of a
     // device-resident batch move to the side stream, where they overlap the next batch's scan.
     if (overlap) {
-        HIP_TRY(hipEventRecord(e->ev_main, e->stream));
-        HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_main, 0));
-        e->cur = e->stream2;
+        if ((rc = run_after(e->stream2, e->stream, e->ev_main))) return rc;
+        c.stream = e->stream2;
+        c.stream_no = 1;
         e->cur_slot_side = true;      // (a host batch: its staging slot is read on the side stream as well)
     }
-    // one read per wavefront (correct_wave.h); the one-read-per-lane form (correct.h) serves k < 3
-    // and KBBQ_CORRECT=lane (A/B checks)
-    const bool lane_form = e->opt.lane_walk;
-    if (long_reads) {
-        rc = launch_correct<0, 64>(e, R, list, e->cur_cnt, tmask, NW, d_err, patch, max_len, side);
-    } else if (lane_form || e->p.k < 3) {
-        if (max_len <= 160) rc = launch_correct<160, 256>(e, R, list, e->cur_cnt, tmask, NW, d_err, patch);
-        else if (max_len <= 320) rc = launch_correct<320, 128>(e, R, list, e->cur_cnt, tmask, NW, d_err, patch);
-        else rc = launch_correct<512, 64>(e, R, list, e->cur_cnt, tmask, NW, d_err, patch);
-    } else {
-        if (max_len <= 160) rc = launch_correct_wave<5, 3>(e, R, list, tmask, NW, d_err, patch);
-        else if (max_len <= 320) rc = launch_correct_wave<10, 5>(e, R, list, tmask, NW, d_err, patch);
-        else rc = launch_correct_wave<16, 8>(e, R, list, tmask, NW, d_err, patch);
-    }
+    // the one-read-per-lane walk (correct.h) over a work list, its form by the longest read (here, behind the scan, because the
+    // compiler emits the kernels in the order of their first use)
+    auto lane_walk = [&](const uint32_t *work, const unsigned long long *n_work) {
+        if (long_reads) return launch_correct<0, 64>(e, c, R, work, n_work, tmask, NW, d_err, patch, max_len);
+        if (max_len <= 160) return launch_correct<160, 256>(e, c, R, work, n_work, tmask, NW, d_err, patch);
+        if (max_len <= 320) return launch_correct<320, 128>(e, c, R, work, n_work, tmask, NW, d_err, patch);
+        return launch_correct<512, 64>(e, c, R, work, n_work, tmask, NW, d_err, patch);
+    };
+    // one read per wavefront (correct_wave.h); the lane form serves long reads, k < 3 and KBBQ_CORRECT=lane (A/B checks)
+    if (long_reads || e->opt.lane_walk || e->p.k < 3) rc = lane_walk(list, c.cnt);
+    else if (max_len <= 160) rc = launch_correct_wave<5, 3>(e, c, R, list, tmask, NW, d_err, patch);
+    else if (max_len <= 320) rc = launch_correct_wave<10, 5>(e, c, R, list, tmask, NW, d_err, patch);
+    else rc = launch_correct_wave<16, 8>(e, c, R, list, tmask, NW, d_err, patch);
     if (rc) return rc;
     if (R.offcase && !long_reads) {
         // reads with off-case bases (scan state 3) follow the reference's raw-character comparisons: the one-read-per-lane
         // walk carries the case bits (correct.h); a second, usually empty, work list
-        if ((rc = ensure_scratch(e, side ? 18 : 17, R.n_reads * 4))) return rc;
-        uint32_t *list3 = (uint32_t *)e->scratch[side ? 18 : 17];
-        unsigned long long *cnt3 = e->d_counters + 6 + side;
-        HIP_TRY(hipMemsetAsync(cnt3, 0, 8, e->cur));
-        hipLaunchKernelGGL(k_compact, dim3((unsigned)((R.n_reads + 1023) / 1024)), dim3(1024), 0, e->cur, dirty, R.n_reads, list3, cnt3, 3);
+        uint32_t *list3;
+        if ((rc = scratch_buf(e, per_side(S_OFFCASE_LIST, side), R.n_reads * 4, &list3))) return rc;
+        HIP_TRY(hipMemsetAsync(offcase_len, 0, 8, c.stream));
+        hipLaunchKernelGGL(k_compact, dim3((unsigned)((R.n_reads + 1023) / 1024)), dim3(1024), 0, c.stream, dirty, R.n_reads, list3, offcase_len, 3);
         HIP_TRY(hipGetLastError());
-        if (max_len <= 160) rc = launch_correct<160, 256>(e, R, list3, cnt3, tmask, NW, d_err, patch);
-        else if (max_len <= 320) rc = launch_correct<320, 128>(e, R, list3, cnt3, tmask, NW, d_err, patch);
-        else rc = launch_correct<512, 64>(e, R, list3, cnt3, tmask, NW, d_err, patch);
-        if (rc) return rc;
+        if ((rc = lane_walk(list3, offcase_len))) return rc;
     }
-    if ((rc = run_tally(e, R, d_err, patch, max_len, e->cur))) return rc;
-    if (!(R.offcase && !long_reads)) HIP_TRY(hipMemsetAsync(e->d_counters + 6 + side, 0, 8, e->cur));
-    hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(1), 0, e->cur, (const unsigned long long *)(e->d_counters + 4 * side),
-                       (const unsigned long long *)(e->d_counters + 6 + side), e->d_totals);
+    if ((rc = run_tally(e, c, R, d_err, patch, max_len))) return rc;
+    if (!(R.offcase && !long_reads)) HIP_TRY(hipMemsetAsync(offcase_len, 0, 8, c.stream));
+    hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(1), 0, c.stream, (const unsigned long long *)c.cnt, (const unsigned long long *)offcase_len,
+                       &e->d_totals->walk_reads);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->ev_side[side], e->cur));
+    HIP_TRY(hipEventRecord(e->ev_side[side], c.stream));
     e->side_busy[side] = true;
     e->stats[2] += R.n_reads;
     if (!overlap) {
@@ -2136,7 +2144,7 @@ int kbbq_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *errors_
 int kbbq_tally_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *errors) {
     ENGINE_DEVICE(e);
     { int frc = bucket_flush_all(e); if (frc) return frc; }      // deferred inserts reach the filters first (bucket.h)
-    if (!e || !errors) return fail(KBBQ_EINVAL, "null argument");
+    if (!errors) return fail(KBBQ_EINVAL, "null argument");
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
     int rc = device_view(e, reads, &R, &max_len);
@@ -2144,12 +2152,14 @@ int kbbq_tally_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *er
     const uint32_t *d_err = (const uint32_t *)errors;
     if (!reads->on_device) {      // --fixed mode with host batches: the caller's flags go through a scratch array
         const size_t bytes = (reads->n_bases / 64 + 1) * 8;
-        if ((rc = ensure_scratch(e, 16, bytes + 8))) return rc;
-        HIP_TRY(hipMemsetAsync((char *)e->scratch[16] + bytes, 0, 8, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->scratch[16], errors, bytes, hipMemcpyHostToDevice, e->stream));
-        d_err = (const uint32_t *)e->scratch[16];
+        char *flags;
+        if ((rc = scratch_buf(e, S_HOST_FLAGS, bytes + 8, &flags))) return rc;
+        HIP_TRY(hipMemsetAsync(flags + bytes, 0, 8, e->stream));
+        HIP_TRY(hipMemcpyAsync(flags, errors, bytes, hipMemcpyHostToDevice, e->stream));
+        d_err = (const uint32_t *)flags;
     }
-    if ((rc = run_tally(e, R, d_err, nullptr, max_len))) return rc;
+    const Pass3 c = {0, e->stream, 0, nullptr, nullptr, nullptr, false};      // side 0 on the engine's stream; the tally takes no counters
+    if ((rc = run_tally(e, c, R, d_err, nullptr, max_len))) return rc;
     return reads->on_device ? KBBQ_OK : sync_engine(e);      // the caller's flag array is free again on return
 }
 
@@ -2171,7 +2181,7 @@ static int fetch_hist(kbbq_engine *e, std::vector<uint64_t> &cyc, std::vector<ui
 
 int kbbq_covariates_get(kbbq_engine *e, kbbq_covariates *out) {
     ENGINE_DEVICE(e);
-    if (!e || !out) return fail(KBBQ_EINVAL, "null argument");
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
     std::vector<uint64_t> cyc, di, q, rg;
     int rc = fetch_hist(e, cyc, di);
     if (rc) return rc;
@@ -2187,7 +2197,6 @@ int kbbq_covariates_get(kbbq_engine *e, kbbq_covariates *out) {
 
 int kbbq_train(kbbq_engine *e) {
     ENGINE_DEVICE(e);
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
     std::vector<uint64_t> cyc, di, q, rg;
     int rc = fetch_hist(e, cyc, di);
     if (rc) return rc;
@@ -2198,22 +2207,14 @@ int kbbq_train(kbbq_engine *e) {
 
 int kbbq_dq_get(kbbq_engine *e, kbbq_dq *out) {
     ENGINE_DEVICE(e);
-    if (!e || !out) return fail(KBBQ_EINVAL, "null argument");
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
     if (!e->dq_set) return fail(KBBQ_ESTATE, "no delta-Q tables yet");
-    const DqTables &d = e->dq;
-    out->n_rg = d.n_rg;
-    out->n_cycle = d.n_cycle;
-    if (out->meanq) memcpy(out->meanq, d.meanq.data(), d.meanq.size() * 4);
-    if (out->rgdq) memcpy(out->rgdq, d.rgdq.data(), d.rgdq.size() * 4);
-    if (out->qdq) memcpy(out->qdq, d.qdq.data(), d.qdq.size() * 4);
-    if (out->cycledq) memcpy(out->cycledq, d.cycledq.data(), d.cycledq.size() * 4);
-    if (out->dinucdq) memcpy(out->dinucdq, d.dinucdq.data(), d.dinucdq.size() * 4);
-    return KBBQ_OK;
+    return dq_out(e->dq, out);
 }
 
 int kbbq_set_dq(kbbq_engine *e, const kbbq_dq *in) {
     ENGINE_DEVICE(e);
-    if (!e || !in || !in->meanq || !in->rgdq || !in->qdq || !in->cycledq || !in->dinucdq) return fail(KBBQ_EINVAL, "null argument");
+    if (!in || !in->meanq || !in->rgdq || !in->qdq || !in->cycledq || !in->dinucdq) return fail(KBBQ_EINVAL, "null argument");
     if (in->n_rg != (uint64_t)e->p.n_rg || in->n_cycle != (uint64_t)e->p.max_read_len)
         return fail(KBBQ_EINVAL, "delta-Q tables must be [%d rg][%d cycles]", e->p.n_rg, e->p.max_read_len);
     // The device holds the cycle and dinucleotide deltas as int8 and meanq + rgdq + qdq as int16, and the apply
@@ -2259,7 +2260,7 @@ int kbbq_recalibrate_batch_host(kbbq_engine *e, const kbbq_reads *reads, uint8_t
 
 static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qual_out, bool out_on_host) {
     ENGINE_DEVICE(e);
-    if (!e || !qual_out || !reads) return fail(KBBQ_EINVAL, "null argument");
+    if (!qual_out || !reads) return fail(KBBQ_EINVAL, "null argument");
     if (!e->dq_set) return fail(KBBQ_ESTATE, "no delta-Q tables yet");
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
@@ -2281,15 +2282,14 @@ static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qu
     if (deferred_out) {
         d_out = (uint8_t *)so.dev;
     } else if (out_on_host) {
-        if ((rc = ensure_scratch(e, 2, R.n_bases + 16))) return rc;
-        d_out = (uint8_t *)e->scratch[2];
+        if ((rc = scratch_buf(e, S_HOST_OUT, R.n_bases + 16, &d_out))) return rc;
     }
     DqDev D;
     D.base = e->d_dq_base; D.cycle = e->d_dq_cycle; D.dinuc = e->d_dq_dinuc;
     D.qslot = e->d_dq_qslot;
     D.n_rg = e->p.n_rg; D.n_cycle = e->p.max_read_len; D.n_slots = e->dq_slots;
     const uint32_t *read_index;
-    if ((rc = build_read_index(e, R, 14, e->stream, &read_index))) return rc;
+    if ((rc = build_read_index(e, R, 0, e->stream, &read_index))) return rc;      // (the engine's stream's index: pass 3's in-order tallies use the same one)
     const int per_rg = (D.n_slots * (4 * D.n_cycle + 16) + KBBQ_NQ * 2 + 3) & ~3;
     // tables of as many read groups as fit (kernels.h: compacted over the quality axis): two 1024-lane blocks
     // per CU share the 160 KB of LDS when one group takes at most 64 KB; otherwise one block per CU and up to 152 KB.
@@ -2327,11 +2327,9 @@ static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qu
             HIP_TRY(hipMemcpyAsync(dc.d_bases + w0 * 8, reads->bases + w0, (w1 - w0) * 8, hipMemcpyHostToDevice, e->copy));
             HIP_TRY(hipMemcpyAsync(dc.d_nmask + m0 * 8, reads->nmask + m0, (m1 - m0) * 8, hipMemcpyHostToDevice, e->copy));
             HIP_TRY(hipMemcpyAsync(dc.d_qual + b0, reads->qual + b0, b1 - b0, hipMemcpyHostToDevice, e->copy));
-            HIP_TRY(hipEventRecord(dc.slot->h2d, e->copy));      // (the guard waits for the last of them: the whole batch has left the caller's memory)
-            HIP_TRY(hipStreamWaitEvent(e->stream, dc.slot->h2d, 0));
+            if ((rc = run_after(e->stream, e->copy, dc.slot->h2d))) return rc;      // (the guard waits for the last of them: the whole batch has left the caller's memory)
             if ((rc = launch(b0, b1))) return rc;
-            HIP_TRY(hipEventRecord(e->ev_main, e->stream));
-            HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_main, 0));
+            if ((rc = run_after(e->stream2, e->stream, e->ev_main))) return rc;
             HIP_TRY(hipMemcpyAsync(qual_out + b0, d_out + b0, b1 - b0, hipMemcpyDeviceToHost, e->stream2));
         }
         if (deferred_out) {
@@ -2382,36 +2380,29 @@ struct AsyncCall {
 };
 }  // namespace
 
+}  // extern "C"
+
+template <typename Call> static int submit(kbbq_engine *e, kbbq_ticket *ticket, Call call) {
+    if (!e || !ticket) return fail(KBBQ_EINVAL, "null argument");
+    AsyncCall a(e);
+    const int rc = call();
+    *ticket = a.finish(rc);
+    return rc;
+}
+
+extern "C" {
+
 int kbbq_sample_batch_submit(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_kmer_ordinal, kbbq_ticket *ticket) {
-    if (!e || !ticket) return fail(KBBQ_EINVAL, "null argument");
-    AsyncCall a(e);
-    const int rc = kbbq_sample_batch(e, reads, first_kmer_ordinal);
-    *ticket = a.finish(rc);
-    return rc;
+    return submit(e, ticket, [&] { return kbbq_sample_batch(e, reads, first_kmer_ordinal); });
 }
-
 int kbbq_trusted_batch_submit(kbbq_engine *e, const kbbq_reads *reads, kbbq_ticket *ticket) {
-    if (!e || !ticket) return fail(KBBQ_EINVAL, "null argument");
-    AsyncCall a(e);
-    const int rc = kbbq_trusted_batch(e, reads, nullptr);
-    *ticket = a.finish(rc);
-    return rc;
+    return submit(e, ticket, [&] { return kbbq_trusted_batch(e, reads, nullptr); });
 }
-
 int kbbq_errors_batch_submit(kbbq_engine *e, const kbbq_reads *reads, kbbq_ticket *ticket) {
-    if (!e || !ticket) return fail(KBBQ_EINVAL, "null argument");
-    AsyncCall a(e);
-    const int rc = kbbq_errors_batch(e, reads, nullptr);
-    *ticket = a.finish(rc);
-    return rc;
+    return submit(e, ticket, [&] { return kbbq_errors_batch(e, reads, nullptr); });
 }
-
 int kbbq_recalibrate_batch_submit(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qual_out, kbbq_ticket *ticket) {
-    if (!e || !ticket) return fail(KBBQ_EINVAL, "null argument");
-    AsyncCall a(e);
-    const int rc = kbbq_recalibrate_batch(e, reads, qual_out);
-    *ticket = a.finish(rc);
-    return rc;
+    return submit(e, ticket, [&] { return kbbq_recalibrate_batch(e, reads, qual_out); });
 }
 
 int kbbq_batch_wait(kbbq_engine *e, kbbq_ticket ticket) {
@@ -2448,7 +2439,7 @@ int kbbq_synth_tables(const kbbq_synth_params *sp, uint32_t *qcum /* [read_len][
 
 int kbbq_synth_reads(kbbq_engine *e, const kbbq_synth_params *sp, uint64_t first_read, uint64_t n, kbbq_reads *dev) {
     ENGINE_DEVICE(e);
-    if (!e || !sp || !dev || n == 0) return fail(KBBQ_EINVAL, "bad argument");
+    if (!sp || !dev || n == 0) return fail(KBBQ_EINVAL, "bad argument");
     if (sp->read_len == 0 || sp->genome_len < sp->read_len || sp->n_rg == 0) return fail(KBBQ_EINVAL, "bad synthetic parameters");
     if (e->qcum_len != sp->read_len) {
         std::vector<uint32_t> qc(4 * (size_t)sp->read_len), et(94);
@@ -2491,7 +2482,7 @@ int kbbq_synth_reads(kbbq_engine *e, const kbbq_synth_params *sp, uint64_t first
 // ---- measurement
 int kbbq_profile_get(kbbq_engine *e, kbbq_profile_entry *out, int32_t max_entries, int32_t *n_out) {
     ENGINE_DEVICE(e);
-    if (!e || !n_out) return fail(KBBQ_EINVAL, "null argument");
+    if (!n_out) return fail(KBBQ_EINVAL, "null argument");
     int rc = sync_engine(e);
     if (rc) return rc;
     int n = 0;
@@ -2507,7 +2498,6 @@ int kbbq_profile_get(kbbq_engine *e, kbbq_profile_entry *out, int32_t max_entrie
 
 int kbbq_profile_reset(kbbq_engine *e) {
     ENGINE_DEVICE(e);
-    if (!e) return fail(KBBQ_EINVAL, "null engine");
     int rc = sync_engine(e);
     if (rc) return rc;
     for (size_t i = 0; i < e->prof.size(); ++i) { e->prof[i].launches = 0; e->prof[i].ms = 0; }
@@ -2516,10 +2506,10 @@ int kbbq_profile_reset(kbbq_engine *e) {
 
 int kbbq_stats_get(kbbq_engine *e, uint64_t *out, int32_t n) {
     ENGINE_DEVICE(e);
-    if (!e || !out) return fail(KBBQ_EINVAL, "null argument");
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
     int rc = sync_engine(e);      // batches of pass 3 may still be in flight; their counters are collected here
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(&e->stats[3], e->d_counters + 3, 8, hipMemcpyDeviceToHost));      // [3] Bloom blocks fetched by k_infer
+    HIP_TRY(hipMemcpy(&e->stats[3], &e->d_counters->infer_fetched, 8, hipMemcpyDeviceToHost));      // [3] Bloom blocks fetched by k_infer
     for (int i = 0; i < n && i < 4; ++i) out[i] = e->stats[i];
     // [4],[5] flushes of the bucketed inserts per filter, [6] records inserted directly because a region was full,
     // [7] records gathered per flush (0: the filters take direct inserts)
@@ -2586,13 +2576,7 @@ int kbbq_host_train(const kbbq_covariates *cov, kbbq_dq *out) {
     std::vector<uint64_t> q, rg;
     derive_q_rg(cov->n_rg, cov->n_cycle, cov->cycle, q, rg);
     DqTables d = train_model(cov->n_rg, cov->n_cycle, rg.data(), q.data(), cov->cycle, cov->dinuc);
-    out->n_rg = d.n_rg; out->n_cycle = d.n_cycle;
-    if (out->meanq) memcpy(out->meanq, d.meanq.data(), d.meanq.size() * 4);
-    if (out->rgdq) memcpy(out->rgdq, d.rgdq.data(), d.rgdq.size() * 4);
-    if (out->qdq) memcpy(out->qdq, d.qdq.data(), d.qdq.size() * 4);
-    if (out->cycledq) memcpy(out->cycledq, d.cycledq.data(), d.cycledq.size() * 4);
-    if (out->dinucdq) memcpy(out->dinucdq, d.dinucdq.data(), d.dinucdq.size() * 4);
-    return KBBQ_OK;
+    return dq_out(d, out);
 }
 
 uint64_t kbbq_host_bernoulli_threshold(double p, int32_t *always) {

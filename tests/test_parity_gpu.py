@@ -725,7 +725,10 @@ def test_overlapped_and_in_order_pass3_agree_on_device_batches():
     outs = []
     # (the default caps the scan at four and the walk at two workgroups per CU while both streams are in use; 0 = as many as
     # fit, round 3's launches; 1 / 1: as little room as there is)
-    for extra in ({}, {"KBBQ_NO_OVERLAP": "1"}, {"KBBQ_SCAN_BLOCKS": "0", "KBBQ_WALK_BLOCKS": "0"}, {"KBBQ_SCAN_BLOCKS": "1", "KBBQ_WALK_BLOCKS": "1"}):
+    # (... and bucketed inserts with small record buffers: without hint arrays pass 2's emits read its take-bit scratch on the
+    # side stream, and the first of those two arrays is the buffer that holds the error bits of pass 3's second side)
+    for extra in ({}, {"KBBQ_NO_OVERLAP": "1"}, {"KBBQ_SCAN_BLOCKS": "0", "KBBQ_WALK_BLOCKS": "0"}, {"KBBQ_SCAN_BLOCKS": "1", "KBBQ_WALK_BLOCKS": "1"},
+                  {"KBBQ_BUCKET": "1", "KBBQ_BUCKET_RECORDS": "3000"}, {"KBBQ_BUCKET": "1", "KBBQ_BUCKET_RECORDS": "3000", "KBBQ_PASS2_SIDE": "1"}):
         out = subprocess.run([sys.executable, "-c", code], cwd=common.ROOT, env=dict(os.environ, **extra), capture_output=True, text=True, timeout=600)
         assert out.returncode == 0 and "pass3 ok" in out.stdout, out.stdout + out.stderr
         outs.append(out.stdout.strip().splitlines()[-1])
