@@ -1,7 +1,12 @@
-// bam_reader.h -- host side of kbbq_bam_reader (include/kbbq_bgzf.h): buffers, the chunk loop and the launches of
-// bam_device.h's kernels.  Included once, at the end of bgzf_device.hip (it uses that file's Buf, Submission, device_scan,
-// begin_submission and launch_deflate).
-#pragma once
+// bam_reader.hip -- host side of kbbq_bam_reader (include/kbbq_bgzf.h): buffers, the chunk loop and the launches of
+// bam_device.h's kernels (MI355X, gfx950).  The BGZF walk, the inflate launch, the scan, the text packing and the hand-over
+// to the writer are io_common.h's.
+#include "io_common.h"
+
+#include "bam_device.h"
+
+using namespace kbbq::dfl;
+using namespace kbbq::io;
 
 struct kbbq_bam_reader {
     Preload pre;                            // pieces of the file copied ahead of their chunk call (kbbq_bam_reader_preload)
@@ -12,7 +17,8 @@ struct kbbq_bam_reader {
     int32_t n_ref = 0;
     uint64_t header_left = 0;               // bytes of the BAM header still to skip at the front of the stream
     uint64_t header_bytes = 0;
-    Buf comp, text, status, blk_meta, h_meta, h_small, carry, tile_sums;
+    Buf comp, text, h_small, carry, tile_sums;
+    Inflater inf;
     Buf seg_u32, seg_slots, seg_counts;     // BamSegs
     Buf idx_u32, idx_u16, idx_u64;          // BamIndex
     Buf d_out;                              // small device words: [0..1] chain flags, [4..6] record flags / longest / shortest
@@ -23,7 +29,6 @@ struct kbbq_bam_reader {
     std::vector<uint32_t> h_id_off;
     std::vector<int32_t> dense_of;          // table index -> dense read-group index (first appearance, readutils.cc:53-57), -1: not met
     std::vector<uint32_t> order;            // dense index -> table index
-    unsigned inflate_grid = 0;
     uint64_t carry_bytes = 0;
     // the current chunk
     uint64_t text_bytes = 0, n_records = 0, n_bases = 0, idx_cap = 0;
@@ -34,9 +39,8 @@ struct kbbq_bam_reader {
     // bytes the chunk before them left over; pass 4 inflates and indexes them again (kbbq_bam_reader_select)
     struct Kept {
         Buf comp, carry;
-        std::vector<uint64_t> c_off, o_off;
-        std::vector<uint32_t> c_len, o_len;
-        uint64_t carry_bytes = 0, skip = 0, text = 0, n_records = 0;
+        BlockTable blocks;
+        uint64_t carry_bytes = 0, skip = 0, n_records = 0;
     };
     std::vector<Kept> kept;
     bool keeping = false;
@@ -73,88 +77,15 @@ BamIndex bam_index(kbbq_bam_reader *r) {
     return X;
 }
 
-// the BGZF blocks at the front of file_bytes: where their DEFLATE streams lie and where their bytes go; false: not BGZF
-bool bam_parse_blocks(const uint8_t *file_bytes, uint64_t n_bytes, uint64_t text0, std::vector<uint64_t> &c_off, std::vector<uint64_t> &o_off,
-                      std::vector<uint32_t> &c_len, std::vector<uint32_t> &o_len, uint64_t *consumed, uint64_t *text_out) {
-    uint64_t at = 0, text = text0;
-    const uint64_t text_cap = 3500000000ull;      // record offsets travel in 32 bits
-    while (at + 18 <= n_bytes) {
-        const uint8_t *h = file_bytes + at;
-        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return false;
-        const uint32_t xlen = h[10] | (h[11] << 8);
-        if (at + 12 + xlen > n_bytes) break;
-        uint32_t bsize = 0;
-        for (uint32_t x = 0; x + 4 <= xlen;) {
-            const uint8_t *sf = h + 12 + x;
-            const uint32_t slen = sf[2] | (sf[3] << 8);
-            if (sf[0] == 66 && sf[1] == 67 && slen == 2 && x + 6 <= xlen) bsize = (sf[4] | (sf[5] << 8)) + 1u;
-            x += 4 + slen;
-        }
-        if (!bsize || bsize < 12 + xlen + 8) return false;
-        if (at + bsize > n_bytes) break;      // the chunk ends inside this block
-        const uint8_t *tail = h + bsize - 8;
-        const uint32_t isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
-        if (isize > 65536) return false;
-        if (text + isize > text_cap) break;
-        if (isize) {
-            c_off.push_back(at + 12 + xlen);
-            c_len.push_back(bsize - (12 + xlen) - 8);
-            o_off.push_back(text);
-            o_len.push_back(isize);
-            text += isize;
-        }
-        at += bsize;
-    }
-    *consumed = at;
-    *text_out = text;
-    return true;
-}
-
-// inflate + checksum of the blocks described by the vectors, from the device copy `d_comp` of the compressed bytes into
-// r->text (whose first carry bytes are in place); returns when every block's status has been read
-int bam_inflate(kbbq_bam_reader *r, const void *d_comp, const std::vector<uint64_t> &c_off, const std::vector<uint64_t> &o_off,
-                const std::vector<uint32_t> &c_len, const std::vector<uint32_t> &o_len, uint64_t text) {
-    const uint32_t nb = (uint32_t)c_off.size();
+// inflate + checksum of the table's blocks, from the device copy `d_comp` of the compressed bytes into r->text (whose first
+// carry bytes are in place); returns when every block's status has been read
+int bam_inflate(kbbq_bam_reader *r, const void *d_comp, const BlockTable &T) {
     int rc;
-    if ((rc = r->status.reserve((size_t)nb * 4 + 64))) return rc;
-    const size_t meta_bytes = (size_t)nb * 24 + 64;
-    if ((rc = r->blk_meta.reserve(meta_bytes))) return rc;
-    if ((rc = r->h_meta.reserve(meta_bytes))) return rc;
     HIP_TRY(hipEventRecord(r->t0, r->st));
-    if (nb) {
-        uint64_t *hm = (uint64_t *)r->h_meta.p;
-        memcpy(hm, c_off.data(), (size_t)nb * 8);
-        memcpy(hm + nb, o_off.data(), (size_t)nb * 8);
-        memcpy((uint32_t *)(hm + 2 * (size_t)nb), c_len.data(), (size_t)nb * 4);
-        memcpy((uint32_t *)(hm + 2 * (size_t)nb) + nb, o_len.data(), (size_t)nb * 4);
-        HIP_TRY(hipMemcpyAsync(r->blk_meta.p, hm, (size_t)nb * 24, hipMemcpyHostToDevice, r->st));
-        InflateArgs A;
-        A.comp = (const uint8_t *)d_comp;
-        A.c_off = (const uint64_t *)r->blk_meta.p;
-        A.o_off = A.c_off + nb;
-        A.c_len = (const uint32_t *)(A.c_off + 2 * (size_t)nb);
-        A.o_len = A.c_len + nb;
-        A.out = (uint8_t *)r->text.p;
-        A.n_blocks = nb;
-        A.status = (uint32_t *)r->status.p;
-        if (!r->inflate_grid && (rc = inflate_resident_waves(r->device, &r->inflate_grid))) return rc;
-        hipLaunchKernelGGL(k_inflate, dim3(std::min<unsigned>(nb, r->inflate_grid)), dim3(64 * INF_WAVES), 0, r->st, A);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_block_crc, dim3(std::min<unsigned>((nb + 3) / 4, 256 * 16)), dim3(256), 0, r->st, A);      // as bgzf_read verifies them
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemsetAsync((char *)r->text.p + text, 0, 64, r->st));
+    if ((rc = inflate_queue(r->inf, r->device, r->st, T, d_comp, r->text.p, nullptr))) return rc;
+    HIP_TRY(hipMemsetAsync((char *)r->text.p + T.text, 0, 64, r->st));
     HIP_TRY(hipEventRecord(r->t1, r->st));
-    if (nb) {
-        std::vector<uint32_t> stt(nb);
-        HIP_TRY(hipMemcpyAsync(stt.data(), r->status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, r->st));
-        HIP_TRY(hipStreamSynchronize(r->st));
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (stt[b] == INF_BAD_CRC) return fail(KBBQ_EIO, "BGZF block %u of the chunk: CRC32 checksum mismatch", b);
-            if (stt[b] != INF_OK) return fail(KBBQ_EIO, "BGZF block %u of the chunk does not inflate (code %u)", b, stt[b]);
-        }
-    }
-    return KBBQ_OK;
+    return inflate_check(r->inf, r->st, T.n_blocks(), "chunk");
 }
 
 // The records of the stream r->text[0, text): chain, index, fields.  skip: bytes in front of the first record (the BAM
@@ -281,10 +212,11 @@ void kbbq_bam_reader_destroy(kbbq_bam_reader *r) {
     if (!r) return;
     KbbqDeviceGuard guard(r->device);
     if (r->st) (void)hipStreamSynchronize(r->st);
-    Buf *all[] = {&r->comp, &r->text, &r->status, &r->blk_meta, &r->h_meta, &r->h_small, &r->carry, &r->tile_sums, &r->seg_u32, &r->seg_slots,
+    Buf *all[] = {&r->comp, &r->text, &r->h_small, &r->carry, &r->tile_sums, &r->seg_u32, &r->seg_slots,
                   &r->seg_counts, &r->idx_u32, &r->idx_u16, &r->idx_u64, &r->d_out, &r->rg_ids, &r->rg_off, &r->rg_hash, &r->first_seen, &r->dense, &r->seq_text,
                   &r->counter};
     for (Buf *b : all) b->release();
+    r->inf.release();
     r->pre.release();
     bam_release_kept(r);
     hipEvent_t evs[] = {r->t0, r->t1, r->t2};
@@ -297,9 +229,8 @@ int kbbq_bam_reader_create(int32_t device, int32_t use_oq, int32_t n_ref, uint64
                            kbbq_bam_reader **out) {
     if (!out || (n_rg_ids && !rg_ids)) return fail(KBBQ_EINVAL, "null argument");
     if (n_rg_ids > 65535) return fail(KBBQ_ERANGE, "%u @RG lines: read-group indices travel in 16 bits", n_rg_ids);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KBBQ_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(KBBQ_ENODEV, "device %d of %d", device, ndev);
+    int rc = device_exists(device);
+    if (rc) return rc;
     KbbqDeviceGuard guard(device);
     HIP_TRY(guard.err);
     kbbq_bam_reader *r = new kbbq_bam_reader;
@@ -307,7 +238,7 @@ int kbbq_bam_reader_create(int32_t device, int32_t use_oq, int32_t n_ref, uint64
     r->use_oq = use_oq ? 1 : 0;
     r->n_ref = n_ref;
     r->header_bytes = r->header_left = header_bytes;
-    r->h_meta.host = r->h_small.host = true;
+    r->h_small.host = true;
     r->h_id_off.push_back(0);
     for (uint32_t i = 0; i < n_rg_ids; ++i) {
         const char *s = rg_ids[i] ? rg_ids[i] : "";
@@ -319,7 +250,6 @@ int kbbq_bam_reader_create(int32_t device, int32_t use_oq, int32_t n_ref, uint64
     if (he == hipSuccess) he = hipEventCreate(&r->t0);
     if (he == hipSuccess) he = hipEventCreate(&r->t1);
     if (he == hipSuccess) he = hipEventCreate(&r->t2);
-    int rc = KBBQ_OK;
     if (he == hipSuccess) {
         if (!(rc = r->rg_ids.reserve(r->h_ids.size() + 64)) && !(rc = r->rg_off.reserve(r->h_id_off.size() * 4 + 64)) &&
             !(rc = r->first_seen.reserve((size_t)n_rg_ids * 8 + 64)) && !(rc = r->dense.reserve((size_t)n_rg_ids * 2 + 64))) {
@@ -405,36 +335,24 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
     HIP_TRY(guard.err);
     memset(info, 0, sizeof *info);
     r->have_chunk = false;
-    std::vector<uint64_t> c_off, o_off;
-    std::vector<uint32_t> c_len, o_len;
-    uint64_t at = 0, text = r->carry_bytes;
-    if (!bam_parse_blocks(file_bytes, n_bytes, r->carry_bytes, c_off, o_off, c_len, o_len, &at, &text)) { info->flags |= BAMF_FALLBACK; return KBBQ_OK; }
+    BlockTable T;
+    if (walk_blocks(file_bytes, n_bytes, r->carry_bytes, TEXT_CAP, T).why != WALK_END) { info->flags |= BAMF_FALLBACK; return KBBQ_OK; }      // (consumed 0)
+    const uint64_t at = T.consumed, text = T.text;
     info->consumed = at;
-    info->n_blocks = (uint32_t)c_off.size();
-    if (at == 0 && n_bytes && !last && c_off.empty()) return fail(KBBQ_EINVAL, "the chunk holds no complete BGZF block");
+    info->n_blocks = T.n_blocks();
+    if (at == 0 && n_bytes && !last && !T.n_blocks()) return fail(KBBQ_EINVAL, "the chunk holds no complete BGZF block");
     int rc;
-    auto reserve_or_drop = [&](Buf &b, size_t need) -> int {
-        int rc2 = b.reserve(need);
-        if (rc2 == KBBQ_ENOMEM && (r->keeping || !r->kept.empty())) {
-            (void)hipGetLastError();
-            bam_release_kept(r);
-            r->keeping = false;
-            rc2 = b.reserve(need);
-        }
-        return rc2;
+    auto drop_kept = [r] {
+        if (!r->keeping && r->kept.empty()) return false;
+        bam_release_kept(r);
+        r->keeping = false;
+        return true;
     };
-    void *d_comp = r->pre.take(file_bytes, n_bytes, r->st);      // copied ahead by the caller's I/O thread?
-    if (!d_comp && (rc = reserve_or_drop(r->comp, at + 4096))) return rc;
-    if ((rc = reserve_or_drop(r->text, text + 4096))) return rc;
+    void *d_comp = nullptr;
+    if ((rc = stage_compressed(r->pre, r->comp, file_bytes, n_bytes, at, r->st, [&](Buf &b, size_t need) { return reserve_or_drop(b, need, drop_kept); }, &d_comp))) return rc;
+    if ((rc = reserve_or_drop(r->text, text + 4096, drop_kept))) return rc;
     const uint64_t carry_in = r->carry_bytes;
     if (carry_in) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, carry_in, hipMemcpyDeviceToDevice, r->st));
-    if (!d_comp) {
-        d_comp = r->comp.p;
-        if (at) {
-            HIP_TRY(hipMemcpyAsync(d_comp, file_bytes, at, hipMemcpyHostToDevice, r->st));
-            HIP_TRY(hipMemsetAsync((char *)d_comp + at, 0, 4096, r->st));
-        }
-    }
     // the header's bytes come first in the stream; a header longer than this chunk's stream is not this path's case
     uint64_t skip = 0;
     if (r->header_left) {
@@ -458,15 +376,15 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
             if (carry_in) HIP_TRY(hipMemcpyAsync(k.carry.p, r->carry.p, carry_in, hipMemcpyDeviceToDevice, r->st));
         }
     }
-    if ((rc = bam_inflate(r, d_comp, c_off, o_off, c_len, o_len, text))) { k.comp.release(); k.carry.release(); return rc; }
+    if ((rc = bam_inflate(r, d_comp, T))) { k.comp.release(); k.carry.release(); return rc; }
     info->text_bytes = text - carry_in;
     rc = bam_index_stream(r, text, skip, last, true, info);
     if (rc) { k.comp.release(); k.carry.release(); return rc; }
     r->header_left = 0;
     if (keep_this) {
         if (r->n_records && !(info->flags & (BAMF_FALLBACK | BAMF_TRUNCATED))) {
-            k.c_off.swap(c_off); k.o_off.swap(o_off); k.c_len.swap(c_len); k.o_len.swap(o_len);
-            k.carry_bytes = carry_in; k.skip = skip; k.text = text; k.n_records = r->n_records;
+            k.blocks = std::move(T);
+            k.carry_bytes = carry_in; k.skip = skip; k.n_records = r->n_records;
             r->kept_bytes += k.comp.bytes + k.carry.bytes;
             r->kept.push_back(std::move(k));
         } else {
@@ -487,12 +405,12 @@ int kbbq_bam_reader_select(kbbq_bam_reader *r, uint64_t i, kbbq_bam_chunk *info)
     memset(info, 0, sizeof *info);
     r->have_chunk = false;
     int rc;
-    if ((rc = r->text.reserve(k.text + 4096))) return rc;
+    if ((rc = r->text.reserve(k.blocks.text + 4096))) return rc;
     if (k.carry_bytes) HIP_TRY(hipMemcpyAsync(r->text.p, k.carry.p, k.carry_bytes, hipMemcpyDeviceToDevice, r->st));
-    if ((rc = bam_inflate(r, k.comp.p, k.c_off, k.o_off, k.c_len, k.o_len, k.text))) return rc;
-    info->n_blocks = (uint32_t)k.c_off.size();
-    info->text_bytes = k.text - k.carry_bytes;
-    if ((rc = bam_index_stream(r, k.text, k.skip, 0, false, info))) return rc;
+    if ((rc = bam_inflate(r, k.comp.p, k.blocks))) return rc;
+    info->n_blocks = k.blocks.n_blocks();
+    info->text_bytes = k.blocks.text - k.carry_bytes;
+    if ((rc = bam_index_stream(r, k.blocks.text, k.skip, 0, false, info))) return rc;
     if (r->n_records != k.n_records) return fail(KBBQ_EIO, "kept chunk %llu: %llu records where the scan found %llu", (unsigned long long)i,
                                                  (unsigned long long)r->n_records, (unsigned long long)k.n_records);
     return KBBQ_OK;
@@ -511,36 +429,28 @@ int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev) {
     dev->n_bases = nbases;
     dev->on_device = 1;
     void *b = nullptr, *m = nullptr, *q = nullptr, *off = nullptr, *fl = nullptr, *rg = nullptr;
-    auto release = [&]() { void *all[] = {b, m, q, off, fl, rg}; for (void *x : all) (void)hipFree(x); };
-    int rc0;
+    BatchArrays arrays;
+    int rc;
     const uint64_t words = nbases / 64 + 1;
-    if ((rc0 = r->seq_text.reserve(nbases + 64))) return rc0;
-    if ((rc0 = r->counter.reserve((words + 2) * 8 + 64))) return rc0;      // [0..1] counts, then the (always empty) off-case words
-    void *seq_text = r->seq_text.p;
-    unsigned long long *cnt = (unsigned long long *)r->counter.p;
-#define RB_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { release(); return fail(_e == hipErrorOutOfMemory ? KBBQ_ENOMEM : KBBQ_EIO, "%s: %s", #expr, hipGetErrorString(_e)); } } while (0)
-    RB_TRY(hipMalloc(&b, (2 * words + 2) * 8));
-    RB_TRY(hipMalloc(&m, (words + 2) * 8));
-    RB_TRY(hipMalloc(&q, nbases + 16));
-    RB_TRY(hipMalloc(&fl, n));
-    RB_TRY(hipMalloc(&rg, n * 2 + 16));
+    if ((rc = r->seq_text.reserve(nbases + 64))) return rc;
+    if ((rc = r->counter.reserve((words + 2) * 8 + 64))) return rc;      // [0..1] counts, then the (always empty) off-case words
+    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
+    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
+    if ((rc = arrays.alloc(&q, nbases + 16))) return rc;
+    if ((rc = arrays.alloc(&fl, n))) return rc;
+    if ((rc = arrays.alloc(&rg, n * 2 + 16))) return rc;
     const bool uniform = r->longest == r->shortest;
-    if (!uniform) RB_TRY(hipMalloc(&off, (n + 1) * 8));
-    RB_TRY(hipMemsetAsync(cnt, 0, 16, r->st));
-    RB_TRY(hipMemsetAsync((char *)b + 2 * words * 8, 0, 16, r->st));
-    RB_TRY(hipMemsetAsync((char *)m + words * 8, 0, 16, r->st));
-    RB_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
+    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
+    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));      // (in front of the kernels, not between them)
+    HIP_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
     hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
-                       (const uint64_t *)X.base_sz, n, r->use_oq, (uint8_t *)seq_text, (uint8_t *)q);
-    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch)
-    hipLaunchKernelGGL(k_pack_text, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)seq_text, nbases, (uint64_t *)b,
-                       (uint64_t *)m, (uint64_t *)(cnt + 2), cnt);
+                       (const uint64_t *)X.base_sz, n, r->use_oq, (uint8_t *)r->seq_text.p, (uint8_t *)q);
     hipLaunchKernelGGL(k_bam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->dense.p, (uint8_t *)fl,
                        (uint16_t *)rg);
-    RB_TRY(hipGetLastError());
-    if (!uniform) RB_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
-    RB_TRY(hipStreamSynchronize(r->st));
-#undef RB_TRY
+    HIP_TRY(hipGetLastError());
+    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch and the counts are not read)
+    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, nullptr))) return rc;
+    arrays.release();
     dev->bases = (const uint64_t *)b;
     dev->nmask = (const uint64_t *)m;
     dev->qual = (const uint8_t *)q;
@@ -588,42 +498,11 @@ int kbbq_bam_reader_write(kbbq_bam_reader *r, kbbq_bgzf *z, const uint8_t *d_qua
     return KBBQ_OK;
 }
 
-int kbbq_bgzf_submit_synth(kbbq_bgzf *z, kbbq_engine *e, const kbbq_synth_params *sp, uint64_t first_read, uint64_t n, int32_t format,
-                           uint64_t *payload_bytes) {
-    if (!z || !e || !sp || !n || format < 0 || format > 2) return fail(KBBQ_EINVAL, "bad argument");
-    KbbqDeviceGuard guard(z->device);
-    HIP_TRY(guard.err);
-    kbbq_reads dev;
-    int rc = kbbq_synth_reads(e, sp, first_read, n, &dev);
-    if (rc) return rc;
-    struct FreeBatch { kbbq_engine *e; kbbq_reads *d; ~FreeBatch() { kbbq_reads_free(e, d); } } free_batch{e, &dev};
-    const uint32_t W = format == 0 ? synth_fastq_record(sp->read_len) : synth_bam_record(sp->read_len, format == 2);
-    const uint64_t t = n * (uint64_t)W;
-    Submission *sp2;
-    if ((rc = begin_submission(z, kbbq_engine_stream(e), &sp2))) return rc;
-    Submission &s = *sp2;
-    s.n = t;
-    s.formatted = true;
-    if ((rc = s.payload.reserve(t + 16))) return rc;
-    HIP_TRY(hipMemsetAsync((char *)s.payload.p + t, 0, 16, z->st));
-    HIP_TRY(hipEventRecord(s.t0, z->st));
-    SynthBatch B;
-    B.bases = dev.bases; B.nmask = dev.nmask; B.qual = dev.qual; B.first = first_read; B.n = n; B.read_len = sp->read_len;
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32);
-    if (format == 0) hipLaunchKernelGGL(k_synth_fastq, dim3(grid), dim3(256), 0, z->st, B, (uint8_t *)s.payload.p);
-    else hipLaunchKernelGGL(k_synth_bam, dim3(grid), dim3(256), 0, z->st, B, format == 2 ? 1 : 0, (uint8_t *)s.payload.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = launch_deflate(z, s))) return rc;
-    HIP_TRY(hipEventSynchronize(s.t1));      // the batch is freed on return: the formatting kernel must be through with it
-    if (payload_bytes) *payload_bytes = t;
-    return KBBQ_OK;
-}
-
 int kbbq_bam_reader_preload(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint64_t front_room) {
     if (!r || !file_bytes || !n_bytes) return fail(KBBQ_EINVAL, "bad argument");
     KbbqDeviceGuard guard(r->device);
     HIP_TRY(guard.err);
-    return r->pre.start(r->device, file_bytes, n_bytes, front_room);
+    return r->pre.start(file_bytes, n_bytes, front_room);
 }
 
 int kbbq_bam_reader_kernel_ms(kbbq_bam_reader *r, double *inflate_ms, double *index_ms) {

@@ -1,4 +1,4 @@
-// bgzf_host.cc -- host-only twin of the device BGZF encoder (bgzf_device.hip): the same scalar pieces
+// bgzf_host.cc -- host-only twin of the device BGZF encoder (bgzf_writer.hip): the same scalar pieces
 // (deflate_common.h: Huffman lengths, canonical codes, code-length header, token bits, CRC chaining, framing) around a
 // plain serial match finder.  It exists so that those shared pieces are exercised without a GPU (tests/test_bgzf_cpu.py
 // inflates its output with zlib); the command line never calls it -- its output path is the device encoder.

@@ -1,6 +1,6 @@
 // bgzf_inflate.h -- the input side of the BGZF codec on the device (gfx950): every BGZF block of a file inflated by one
-// wavefront, then the four-line FASTQ records of the inflated text indexed and packed into the engine's read layout.
-// Included once by bgzf_device.hip.
+// wavefront and its CRC-32 checked.  Included once, by io_common.hip (what the blocks hold is fastq_device.h's and
+// bam_device.h's business).
 //
 // What it replaces: the reference reads its input through htslib -- bgzf_read under kseq_read (htsiter.hh:101-126,
 // htsiter.cc:49-60) -- on the host, once per pass.  Here the compressed file goes to HBM as it is and stays there;
@@ -17,17 +17,12 @@
 //                        match that reaches further back (DEFLATE allows 32 KB) is read back from HBM.  What the serial
 //                        chain computes is split between the scalar unit (counters, branches) and the vector ALU (the
 //                        stream's bits, table indices, lengths and distances): in_vgpr below.
-//   k_count_newlines / k_newline_positions   where the lines of the inflated text start
-//   k_fastq_records      per record (four lines): name / comment / sequence / quality fields, kseq's rules
-//                        (htsiter.cc:52-59, kseq.h) and the read-name rules of readutils.cc:74-97 that need no dictionary
-//   k_fastq_gather       sequence text and qualities (- 33) of the records into the batch's contiguous arrays
-//   k_pack_text          2 bit per base, N mask, off-case bits from the sequence text (kbbq_pack_bases_case on the device)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bgzf_device.h"
 #include "deflate_common.h"
+#include "wave_helpers.h"
 
 namespace kbbq {
 namespace dfl {
@@ -639,252 +634,6 @@ __global__ void __launch_bounds__(256) k_block_crc(InflateArgs A) {
         const uint32_t want = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
         const uint32_t got = wave_crc32(A.out + A.o_off[blk], (int)A.o_len[blk], tab, lane, xq_for, xq, xq4);
         if (lane == 0 && got != want && !KBBQ_INF_EXPERIMENT_NOFAR) A.status[blk] = INF_BAD_CRC;
-    }
-}
-
-// ---- exclusive scan of u64 values in place, three launches (tiles of 2048, their sums by one workgroup, the offsets back)
-constexpr int DSCAN_TILE = 2048;
-__global__ void __launch_bounds__(256) k_dscan_tiles(uint64_t *data, uint64_t n, uint64_t *tile_sums) {
-    __shared__ uint64_t wave_tot[4];
-    const uint64_t base = (uint64_t)blockIdx.x * DSCAN_TILE + (uint64_t)threadIdx.x * 8;
-    uint64_t v[8], run = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { v[j] = base + j < n ? data[base + j] : 0; const uint64_t x = v[j]; v[j] = run; run += x; }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t inc = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint64_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-    if (lane == 63) wave_tot[w] = inc;
-    __syncthreads();
-    uint64_t before = inc - run;
-    for (int i = 0; i < w; ++i) before += wave_tot[i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) if (base + j < n) data[base + j] = v[j] + before;
-    if (threadIdx.x == 255) tile_sums[blockIdx.x] = before + run;
-}
-__global__ void __launch_bounds__(1024) k_dscan_sums(uint64_t *tile_sums, uint64_t n_tiles, uint64_t *total) {
-    __shared__ uint64_t part[1024];
-    const int tid = threadIdx.x;
-    const uint64_t per = (n_tiles + 1023) / 1024;
-    const uint64_t b = min(n_tiles, per * tid), e = min(n_tiles, b + per);
-    uint64_t s = 0;
-    for (uint64_t i = b; i < e; ++i) s += tile_sums[i];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t run = 0;
-        for (int i = 0; i < 1024; ++i) { const uint64_t v = part[i]; part[i] = run; run += v; }
-        *total = run;
-    }
-    __syncthreads();
-    uint64_t run = part[tid];
-    for (uint64_t i = b; i < e; ++i) { const uint64_t v = tile_sums[i]; tile_sums[i] = run; run += v; }
-}
-__global__ void __launch_bounds__(256) k_dscan_add(uint64_t *data, uint64_t n, const uint64_t *tile_sums) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) data[i] += tile_sums[i / DSCAN_TILE];
-}
-
-// ---- where the lines start ------------------------------------------------------------------------------------------------
-// newlines per tile of 16 KB (256 lanes x 64 bytes), then -- behind the scan of the tile counts -- their positions
-constexpr int NL_TILE = 16384;
-__device__ __forceinline__ uint64_t newline_bits(const uint8_t *p, uint64_t avail) {      // bit i: p[i] == '\n', i < min(64, avail)
-    uint64_t m = 0;
-    if (avail >= 64) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(p + 16 * w);
-            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    if (((d[k] >> (8 * b)) & 0xFF) == 10u) m |= 1ull << (16 * w + 4 * k + b);
-        }
-    } else {
-        for (uint64_t i = 0; i < avail; ++i) if (p[i] == 10) m |= 1ull << i;
-    }
-    return m;
-}
-__global__ void __launch_bounds__(256) k_count_newlines(const uint8_t *text, uint64_t n, uint64_t *tile_counts) {
-    __shared__ uint32_t wave_cnt[4];
-    const uint64_t at = (uint64_t)blockIdx.x * NL_TILE + (uint64_t)threadIdx.x * 64;
-    const uint32_t c = at < n ? (uint32_t)__popcll(newline_bits(text + at, n - at)) : 0u;
-    uint32_t s = c;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = (uint64_t)wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-}
-__global__ void __launch_bounds__(256) k_newline_positions(const uint8_t *text, uint64_t n, const uint64_t *tile_first, uint32_t *nl_pos,
-                                                            uint64_t nl_capacity) {
-    __shared__ uint32_t wave_cnt[4];
-    const uint64_t at = (uint64_t)blockIdx.x * NL_TILE + (uint64_t)threadIdx.x * 64;
-    uint64_t m = at < n ? newline_bits(text + at, n - at) : 0ull;
-    const uint32_t c = (uint32_t)__popcll(m);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = c;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-    if (lane == 63) wave_cnt[w] = inc;
-    __syncthreads();
-    uint64_t idx = tile_first[blockIdx.x] + (inc - c);
-    for (int i = 0; i < w; ++i) idx += wave_cnt[i];
-    while (m) {
-        const int b = __builtin_ctzll(m);
-        m &= m - 1;
-        if (idx < nl_capacity) nl_pos[idx] = (uint32_t)(at + (uint64_t)b);
-        ++idx;
-    }
-}
-
-// ---- records ------------------------------------------------------------------------------------------------------------------
-// Record r is lines 4r .. 4r+3 of the text.  kseq's reading of a four-line record (htsiter.cc:52-59): the name is the
-// header line behind '@' up to the first white-space character, the comment what follows that character; the third line
-// only has to start with '+'; sequence and quality lines are equally long.  The read-name rules of the FASTQ constructor
-// (readutils.cc:74-97): the part before the first '_' names the read, "/2" at its end makes it second-in-pair; a later
-// field "RG:..." would name a read group -- that needs the dictionary of the host path, as do all shapes other than
-// this one (flagged, and the caller falls back to the serial reader, which stays the definition).
-struct FastqIndex {
-    uint32_t *name_off, *name_len, *com_off, *com_len, *seq_off, *seq_len, *qual_off;      // per record, offsets into the text
-    uint8_t *second;
-    uint64_t *base_sz;        // per record: seq_len (u64, scanned into base offsets)
-    uint64_t *text_sz;        // per record: bytes of its output text (scanned into text offsets)
-    uint32_t *flags;          // [0] bit 0: a shape the device path does not take; bit 1: a read name shorter than 2 characters
-                              // [1] longest read  [2] shortest read
-};
-__device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); }
-
-__global__ void __launch_bounds__(256) k_fastq_records(const uint8_t *text, const uint32_t *nl_pos, uint64_t n_records, FastqIndex X) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_records) return;
-    const uint32_t l0 = r ? nl_pos[4 * r - 1] + 1 : 0u;
-    const uint32_t e0 = nl_pos[4 * r], e1 = nl_pos[4 * r + 1], e2 = nl_pos[4 * r + 2], e3 = nl_pos[4 * r + 3];
-    const uint32_t l1 = e0 + 1, l2 = e1 + 1, l3 = e2 + 1;
-    uint32_t bad = 0;
-    if (e0 == l0 || text[l0] != '@') bad |= 1;
-    if (e2 == l2 || text[l2] != '+') bad |= 1;
-    const uint32_t sl = e1 - l1, ql = e3 - l3;
-    if (sl != ql || sl == 0) bad |= 1;
-    // a carriage return before any of the four newlines: kseq would strip it; not this path
-    if ((e0 > l0 && text[e0 - 1] == 13) || (e1 > l1 && text[e1 - 1] == 13) || (e2 > l2 && text[e2 - 1] == 13) || (e3 > l3 && text[e3 - 1] == 13)) bad |= 1;
-    // name and comment
-    uint32_t p = l0 + 1;
-    while (p < e0 && !is_space(text[p])) ++p;
-    const uint32_t nl = p > l0 ? p - (l0 + 1) : 0u;
-    const uint32_t c0 = p < e0 ? p + 1 : e0, cl = e0 - c0;
-    if (nl == 0) bad |= 1;
-    // the read-name rules
-    uint32_t first_len = nl;
-    for (uint32_t i = 0; i < nl; ++i)
-        if (text[l0 + 1 + i] == '_') {
-            if (first_len == nl) first_len = i;
-            if (i + 3 < nl && text[l0 + 2 + i] == 'R' && text[l0 + 3 + i] == 'G' && text[l0 + 4 + i] == ':') bad |= 1;      // a read-group field
-        }
-    if (first_len < 2) bad |= 2;
-    const bool second = first_len >= 2 && text[l0 + 1 + first_len - 2] == '/' && text[l0 + 1 + first_len - 1] == '2';
-    X.name_off[r] = l0 + 1; X.name_len[r] = nl; X.com_off[r] = c0; X.com_len[r] = cl;
-    X.seq_off[r] = l1; X.seq_len[r] = sl; X.qual_off[r] = l3;
-    X.second[r] = second ? 1 : 0;
-    X.base_sz[r] = sl;
-    X.text_sz[r] = (uint64_t)nl + cl + 2 * (uint64_t)sl + 6;
-    if (bad) atomicOr(&X.flags[0], bad);
-    atomicMax(&X.flags[1], sl);
-    atomicMin(&X.flags[2], sl);
-}
-
-// sequence text and qualities of every record into the batch's contiguous arrays (one wavefront per record)
-__global__ void __launch_bounds__(256) k_fastq_gather(const uint8_t *text, FastqIndex X, const uint64_t *base_off, uint64_t n_records,
-                                                       uint8_t *seq_text, uint8_t *qual) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t r = wave; r < n_records; r += n_waves) {
-        const uint32_t sl = X.seq_len[r];
-        const uint8_t *s = text + X.seq_off[r], *q = text + X.qual_off[r];
-        const uint64_t at = base_off[r];
-        for (uint32_t i = lane; i < sl; i += 64) {
-            seq_text[at + i] = s[i];
-            qual[at + i] = (uint8_t)(q[i] - 33);      // readutils.cc:70-71
-        }
-    }
-}
-
-// 64 bases per lane: the 2-bit words, the non-ACGT mask and the off-case bits (kbbq_pack_bases_case, engine.hip: same table)
-// n_offcase[0] counts the off-case bases, n_offcase[1] the characters that the packed form cannot give back (anything but
-// ACGTN and acgt: digits, IUPAC codes, a lower-case n)
-__global__ void __launch_bounds__(256) k_pack_text(const uint8_t *seq_text, uint64_t n_bases, uint64_t *bases, uint64_t *nmask, uint64_t *offcase,
-                                                    unsigned long long *n_offcase) {
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t words = n_bases / 64 + 1;
-    if (w >= words) return;
-    const uint64_t first = w * 64;
-    const int n = (int)min((uint64_t)64, n_bases > first ? n_bases - first : 0);
-    uint64_t b0 = 0, b1 = 0, nm = 0, oc = 0;
-    uint32_t exotic = 0;
-    for (int j = 0; j < n; ++j) {
-        const uint8_t ch = seq_text[first + j];
-        exotic += !(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' || ch == 'N' || ch == 'a' || ch == 'c' || ch == 'g' || ch == 't');
-        // seq_nt16_int[seq_nt16_table[ch]] (bloom.hh:351): A/a/0 = 0, C/c/1 = 1, G/g/2 = 2, T/t/3 = 3, everything else non-ACGT
-        uint32_t code = 4, odd = 0;
-        switch (ch) {
-            case 'A': code = 0; break; case 'C': code = 1; break; case 'G': code = 2; break; case 'T': code = 3; break;
-            case 'a': case '0': code = 0; odd = 1; break; case 'c': case '1': code = 1; odd = 1; break;
-            case 'g': case '2': code = 2; odd = 1; break; case 't': case '3': code = 3; odd = 1; break;
-            default: break;
-        }
-        const uint64_t c2 = code & 3 & (code < 4 ? 3u : 0u);
-        if (j < 32) b0 |= c2 << (2 * j); else b1 |= c2 << (2 * (j - 32));
-        nm |= (uint64_t)(code >> 2) << j;
-        oc |= (uint64_t)odd << j;
-    }
-    bases[2 * w] = b0;
-    bases[2 * w + 1] = b1;
-    nmask[w] = nm;
-    offcase[w] = oc;
-    if (oc) atomicAdd(n_offcase, (unsigned long long)__popcll(oc));
-    if (exotic) atomicAdd(n_offcase + 1, (unsigned long long)exotic);
-}
-
-// the output text of a batch assembled from the DEVICE copy of the input text (pass 4 of the device path): the same
-// "@name\nseq\n+comment\nqual\n" as k_fastq_text, the pieces found by the record index
-__global__ void __launch_bounds__(256) k_fastq_text_indexed(const uint8_t *text, FastqIndex X, const uint64_t *text_off, const uint64_t *base_off,
-                                                             const uint8_t *new_qual, uint64_t n_records, uint8_t *out) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t r = wave; r < n_records; r += n_waves) {
-        const uint32_t nl = X.name_len[r], cl = X.com_len[r], sl = X.seq_len[r];
-        const uint8_t *name = text + X.name_off[r], *comment = text + X.com_off[r], *seq = text + X.seq_off[r];
-        const SeqSource from = {seq, nullptr, nullptr, nullptr, 0};
-        emit_fastq_record(lane, name, nl, comment, cl, from, sl, new_qual + base_off[r], out + text_off[r]);
-    }
-}
-
-// A chunk kept without its text (kbbq_fastq_reader_keep): the names and comments of its records back to back -- record r's at
-// text_off[r] - 2 base_off[r] - 6 r, the sum of the name and comment lengths before it (a record's output text is name +
-// comment + 2 x sequence + 6 bytes) -- and the two lengths; the sequence line comes back from the packed batch.
-__global__ void __launch_bounds__(256) k_fastq_keep_names(const uint8_t *text, FastqIndex X, const uint64_t *text_off, const uint64_t *base_off,
-                                                           uint64_t n_records, uint8_t *names, uint32_t *lens) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t r = wave; r < n_records; r += n_waves) {
-        const uint32_t nl = X.name_len[r], cl = X.com_len[r];
-        uint8_t *to = names + (text_off[r] - 2 * base_off[r] - 6 * r);
-        const uint8_t *name = text + X.name_off[r], *comment = text + X.com_off[r];
-        for (uint32_t i = lane; i < nl + cl; i += 64) to[i] = i < nl ? name[i] : comment[i - nl];
-        if (lane == 0) { lens[2 * r] = nl; lens[2 * r + 1] = cl; }
-    }
-}
-__global__ void __launch_bounds__(256) k_fastq_text_packed(const uint8_t *names, const uint32_t *lens, const uint64_t *text_off, const uint64_t *base_off,
-                                                            const uint64_t *bases, const uint64_t *nmask, const uint64_t *offcase,
-                                                            const uint8_t *new_qual, uint64_t n_records, uint8_t *out) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t r = wave; r < n_records; r += n_waves) {
-        const uint32_t nl = lens[2 * r], cl = lens[2 * r + 1];
-        const uint64_t b0 = base_off[r];
-        const uint32_t sl = (uint32_t)(base_off[r + 1] - b0);
-        const uint8_t *name = names + (text_off[r] - 2 * b0 - 6 * r);
-        const SeqSource from = {nullptr, bases, nmask, offcase, b0};
-        emit_fastq_record(lane, name, nl, name + nl, cl, from, sl, new_qual + b0, out + text_off[r]);
     }
 }
 

@@ -1,0 +1,619 @@
+// fastq_reader.hip -- the host side of kbbq_fastq_reader (include/kbbq_bgzf.h): a FASTQ file -- BGZF, plain gzip or text --
+// read on the device (MI355X, gfx950).  A chunk call reads top to bottom as: detect the container, obtain the text (BGZF
+// blocks through io_common.h's walk and inflate, a gzip stream through gzip_stream.h, or the bytes themselves), index the
+// lines, index the records (fastq_device.h), carry over what the chunk's end cut.
+#include "gzip_stream.h"
+#include "io_common.h"
+
+#include "fastq_device.h"
+
+using namespace kbbq::dfl;
+using namespace kbbq::io;
+
+// the counts of a chunk: of the current one in the reader itself, of a kept one beside its buffers
+struct FastqCounts {
+    uint64_t text_bytes = 0, n_records = 0, n_bases = 0;
+    uint64_t out_text_bytes = 0;            // bytes of the chunk's records written out as FASTQ text
+    uint32_t longest = 0, shortest = 0;
+};
+
+struct kbbq_fastq_reader : FastqCounts {
+    Preload pre;
+    int device = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+    Buf comp, text;                         // compressed chunk, inflated text (carry first)
+    Inflater inf;
+    Buf tile_counts, tile_sums, nl_pos;     // newline index
+    Buf idx_u32, idx_second, base_sz, text_sz, flags;      // record index (FastqIndex)
+    Buf carry;                              // text of the record the previous chunk's end cut (device)
+    Buf h_small;                            // page-locked scratch for small read-backs
+    Buf seq_text, counter;                  // scratch of kbbq_fastq_reader_batch (the chunk's sequence lines back to back)
+    uint64_t carry_bytes = 0;
+    bool have_chunk = false;
+    double ms_inflate = 0, ms_index = 0;
+    // chunks of the first scan that stay in device memory (kbbq_fastq_reader_keep): their text and record index
+    // Two forms: the whole text with its record index, or -- when the chunk's batch was built and its sequence lines hold
+    // nothing but ACGTN / acgt, so that the packed batch gives them back exactly -- only names and comments (a seventh of the
+    // memory: what is not allocated need not be cleared by the driver either, 20-36 ms per GB of re-used memory).
+    struct Kept : FastqCounts {
+        Buf text, idx_u32, base_sz, text_sz;
+        Buf names, lens;            // the short form: names + comments back to back, (name, comment) lengths
+        bool short_form = false;
+    };
+    bool packed_is_exact = false;              // the current chunk's batch gives its sequence text back (set by batch())
+    const uint64_t *att_bases = nullptr, *att_nmask = nullptr, *att_offcase = nullptr;      // kbbq_fastq_reader_attach
+    std::vector<Kept> kept;
+    // the short form's arrays are carved from slabs of 2 GB (four hipMalloc per chunk were four trips to the driver)
+    std::vector<Buf> slabs;
+    size_t slab_used = 0;
+    bool keeping = false;
+    int64_t selected = -1;      // the kept chunk that is the current one (pass 4), or -1: the live buffers
+    uint64_t kept_bytes = 0;
+    // The container, decided by the first bytes after create / rewind: BGZF blocks, another gzip stream, or the text itself
+    enum { C_UNKNOWN, C_BGZF, C_GZIP, C_TEXT } container = C_UNKNOWN;
+    bool take_text = false;                 // kbbq_fastq_reader_take_text
+    GzStream gz;                            // the state of a gzip stream between chunk calls
+};
+
+namespace {
+
+int device_scan(kbbq_fastq_reader *r, uint64_t *d, uint64_t n, uint64_t *d_total /* device */) {
+    return device_scan_on(r->tile_sums, r->st, d, n, d_total);
+}
+
+FastqIndex index_from(void *idx_u32, void *second, void *base_sz, void *text_sz, void *flags, uint64_t cap) {
+    FastqIndex X;
+    uint32_t *u = (uint32_t *)idx_u32;
+    X.name_off = u; X.name_len = u + cap; X.com_off = u + 2 * cap; X.com_len = u + 3 * cap;
+    X.seq_off = u + 4 * cap; X.seq_len = u + 5 * cap; X.qual_off = u + 6 * cap;
+    X.second = (uint8_t *)second;
+    X.base_sz = (uint64_t *)base_sz;
+    X.text_sz = (uint64_t *)text_sz;
+    X.flags = (uint32_t *)flags;
+    return X;
+}
+FastqIndex index_of(kbbq_fastq_reader *r, uint64_t cap) {
+    return index_from(r->idx_u32.p, r->idx_second.p, r->base_sz.p, r->text_sz.p, r->flags.p, cap);
+}
+
+void release_kept(kbbq_fastq_reader *r) {
+    for (auto &k : r->kept) {
+        if (k.short_form) continue;      // (its arrays are pieces of the slabs)
+        k.text.release(); k.idx_u32.release(); k.base_sz.release(); k.text_sz.release();
+    }
+    for (auto &b : r->slabs) b.release();
+    r->slabs.clear();
+    r->slab_used = 0;
+    r->kept.clear();
+    r->kept_bytes = 0;
+    r->selected = -1;
+}
+
+// a piece of a slab (256-byte aligned); null when the device is full
+void *slab_piece(kbbq_fastq_reader *r, size_t bytes) {
+    bytes = (bytes + 255) & ~(size_t)255;
+    if (r->slabs.empty() || r->slab_used + bytes > r->slabs.back().bytes) {
+        // slabs grow from 64 MB to 2 GB (a small file keeps little)
+        const size_t next = r->slabs.empty() ? ((size_t)64 << 20) : std::min<size_t>(r->slabs.back().bytes * 2, (size_t)2 << 30);
+        Buf b;
+        b.exact = true;
+        if (b.reserve(std::max(next, bytes))) { (void)hipGetLastError(); return nullptr; }
+        r->slabs.push_back(b);
+        r->slab_used = 0;
+    }
+    void *p = (char *)r->slabs.back().p + r->slab_used;
+    r->slab_used += bytes;
+    r->kept_bytes += bytes;
+    return p;
+}
+
+// The live chunk moves into the kept list (its buffers with it: the next chunk allocates its own).
+void stash_current(kbbq_fastq_reader *r) {
+    if (!r->keeping || r->selected >= 0 || !r->have_chunk || !r->n_records) return;
+    kbbq_fastq_reader::Kept k;
+    static_cast<FastqCounts &>(k) = *r;
+    const uint64_t n = r->n_records;
+    const uint64_t names_bytes = r->out_text_bytes - 2 * r->n_bases - 6 * n;      // sum of name + comment lengths
+    bool short_form = r->packed_is_exact;
+    if (short_form) {
+        // names, lengths and the two scans into pieces of exactly their size; the working buffers stay the reader's
+        k.names.p = slab_piece(r, names_bytes + 64);
+        k.lens.p = k.names.p ? slab_piece(r, n * 8) : nullptr;
+        k.base_sz.p = k.lens.p ? slab_piece(r, (n + 1) * 8) : nullptr;
+        k.text_sz.p = k.base_sz.p ? slab_piece(r, (n + 1) * 8) : nullptr;
+        if (!k.text_sz.p) {
+            k.names.p = k.lens.p = k.base_sz.p = k.text_sz.p = nullptr;
+            short_form = false;      // (the long form below takes the buffers that exist already)
+        } else {
+            const FastqIndex X = index_of(r, n);
+            hipLaunchKernelGGL(k_fastq_keep_names, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
+                               (const uint64_t *)X.text_sz, (const uint64_t *)X.base_sz, n, (uint8_t *)k.names.p, (uint32_t *)k.lens.p);
+            (void)hipMemcpyAsync(k.base_sz.p, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st);
+            (void)hipMemcpyAsync(k.text_sz.p, X.text_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st);
+            // (the reader's next chunk is queued on the same stream: it overwrites the working buffers behind these)
+            k.short_form = true;
+        }
+    }
+    if (!short_form) {
+        k.text = r->text; k.idx_u32 = r->idx_u32; k.base_sz = r->base_sz; k.text_sz = r->text_sz;
+        r->text = Buf(); r->idx_u32 = Buf(); r->base_sz = Buf(); r->text_sz = Buf();
+        r->kept_bytes += k.text.bytes + k.idx_u32.bytes + k.base_sz.bytes + k.text_sz.bytes;
+    }
+    r->kept.push_back(k);
+    r->have_chunk = false;
+    r->packed_is_exact = false;
+}
+
+// a new stream begins (create / rewind)
+void new_stream(kbbq_fastq_reader *r) {
+    r->container = kbbq_fastq_reader::C_UNKNOWN;
+    r->gz.reset();
+}
+
+// while chunks are kept, a buffer that no longer fits gives up the kept ones: pass 4 then inflates the file again
+int reserve_or_drop_kept(kbbq_fastq_reader *r, Buf &b, size_t need) {
+    return reserve_or_drop(b, need, [r] {
+        if (!r->keeping && r->kept.empty()) return false;
+        release_kept(r);
+        r->keeping = false;
+        return true;
+    });
+}
+
+// The container from the first bytes of a stream: 1 decided, 0 more bytes are needed
+int detect_container(kbbq_fastq_reader *r, const uint8_t *p, uint64_t n, bool last) {
+    using R = kbbq_fastq_reader;
+    if (n >= 1 && p[0] == '@') { r->container = r->take_text ? R::C_TEXT : R::C_BGZF; return 1; }
+    if (n >= 1 && p[0] != 0x1f) { r->container = R::C_BGZF; return 1; }      // (the BGZF path flags it)
+    if (n < 12) { if (!last) return 0; r->container = R::C_BGZF; return 1; }
+    if (p[1] != 0x8b || p[2] != 8) { r->container = R::C_BGZF; return 1; }
+    if (!(p[3] & 4)) { r->container = R::C_GZIP; return 1; }
+    const uint32_t xlen = p[10] | (p[11] << 8);
+    if (12 + (uint64_t)xlen > n) { if (!last) return 0; r->container = R::C_GZIP; return 1; }
+    r->container = bc_block_size(p + 12, xlen) ? R::C_BGZF : R::C_GZIP;
+    return 1;
+}
+
+// The text of a chunk call, two ways.  Both put it behind the carried bytes in r->text (queued on r->st, t0 recorded), set
+// *text to the total and fill info->consumed / n_blocks; info->flags bit 0: not this path's input, nothing was queued.
+
+// plain gzip (gzip_stream.h) or the text itself: every byte is taken, the reader keeps what it cannot decode yet
+int text_from_stream(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, bool last, kbbq_fastq_chunk *info, uint64_t *text) {
+    int rc;
+    HIP_TRY(hipEventRecord(r->t0, r->st));
+    (void)r->pre.take(file_bytes, n_bytes, r->st);      // (a piece copied ahead is not used: the stream's state comes first)
+    uint64_t produced = n_bytes;
+    const void *from = nullptr;      // (null: the caller's bytes)
+    if (r->container == kbbq_fastq_reader::C_GZIP) {
+        if ((rc = gz_decode(r->gz, r->st, r->device, file_bytes, n_bytes, last, false, &produced, &info->flags, &info->n_blocks))) return rc;
+        info->n_redecoded = (uint32_t)r->gz.redecoded;
+        from = r->gz.output();
+    }
+    info->consumed = n_bytes;
+    const uint64_t carried = r->carry_bytes;
+    if (carried + produced > TEXT_CAP) info->flags |= 1;
+    if (info->flags & 1) return KBBQ_OK;
+    if ((rc = reserve_or_drop_kept(r, r->text, carried + produced + 4096))) return rc;
+    if ((rc = r->h_small.reserve(4096))) return rc;
+    if (carried) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, carried, hipMemcpyDeviceToDevice, r->st));
+    if (produced) HIP_TRY(hipMemcpyAsync((char *)r->text.p + carried, from ? from : file_bytes, produced, from ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, r->st));
+    *text = carried + produced;
+    return KBBQ_OK;
+}
+
+// BGZF: the whole blocks at the front of the bytes, inflated; *nb blocks wait for inflate_check
+int text_from_bgzf(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, bool last, kbbq_fastq_chunk *info, uint64_t *text, uint32_t *nb) {
+    BlockTable T;
+    const WalkEnd end = walk_blocks(file_bytes, n_bytes, r->carry_bytes, TEXT_CAP, T);
+    info->consumed = T.consumed;
+    info->n_blocks = T.n_blocks();
+    if (end.why != WALK_END) { info->flags |= 1; return KBBQ_OK; }      // not BGZF: the blocks in front of it are left to the caller too
+    if (T.consumed == 0 && n_bytes && !last && !T.n_blocks()) return fail(KBBQ_EINVAL, "the chunk holds no complete BGZF block");
+    int rc;
+    void *d_comp = nullptr;
+    if ((rc = stage_compressed(r->pre, r->comp, file_bytes, n_bytes, T.consumed, r->st, [](Buf &b, size_t need) { return b.reserve(need); }, &d_comp))) return rc;
+    if ((rc = reserve_or_drop_kept(r, r->text, T.text + 4096))) return rc;
+    if ((rc = r->h_small.reserve(4096))) return rc;
+    if (r->carry_bytes) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, r->carry_bytes, hipMemcpyDeviceToDevice, r->st));
+    // (t0 behind the uploads: ms_inflate is the kernel alone, the compressed bytes' way to the device is not in its time)
+    if ((rc = inflate_queue(r->inf, r->device, r->st, T, d_comp, r->text.p, r->t0))) return rc;
+    *text = T.text;
+    *nb = T.n_blocks();
+    return KBBQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbbq_fastq_reader_create(int32_t device, kbbq_fastq_reader **out) {
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
+    int rc = device_exists(device);
+    if (rc) return rc;
+    KbbqDeviceGuard guard(device);
+    HIP_TRY(guard.err);
+    kbbq_fastq_reader *r = new kbbq_fastq_reader;
+    r->device = device;
+    r->h_small.host = true;
+    hipError_t he = hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking);
+    if (he == hipSuccess) he = hipEventCreate(&r->t0);
+    if (he == hipSuccess) he = hipEventCreate(&r->t1);
+    if (he == hipSuccess) he = hipEventCreate(&r->t2);
+    if (he != hipSuccess) {
+        kbbq_fastq_reader_destroy(r);
+        return fail(KBBQ_EIO, "creating the reader's stream: %s", hipGetErrorString(he));
+    }
+    *out = r;
+    return KBBQ_OK;
+}
+
+void kbbq_fastq_reader_destroy(kbbq_fastq_reader *r) {
+    if (!r) return;
+    KbbqDeviceGuard guard(r->device);
+    if (r->st) (void)hipStreamSynchronize(r->st);
+    Buf *all[] = {&r->comp, &r->text, &r->tile_counts, &r->tile_sums, &r->nl_pos, &r->idx_u32, &r->idx_second, &r->base_sz, &r->text_sz,
+                  &r->flags, &r->carry, &r->h_small, &r->seq_text, &r->counter};
+    for (Buf *b : all) b->release();
+    r->inf.release();
+    r->gz.release();
+    r->pre.release();
+    release_kept(r);
+    hipEvent_t evs[] = {r->t0, r->t1, r->t2};
+    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+    if (r->st) (void)hipStreamDestroy(r->st);
+    delete r;
+}
+
+int kbbq_fastq_reader_rewind(kbbq_fastq_reader *r) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    KbbqDeviceGuard guard(r->device);      // stash_current launches kernels and may allocate
+    HIP_TRY(guard.err);
+    stash_current(r);
+    r->keeping = false;      // what was kept stays; a second scan keeps nothing more
+    r->selected = -1;
+    r->carry_bytes = 0;
+    r->have_chunk = false;
+    new_stream(r);
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_keep(kbbq_fastq_reader *r, int32_t on) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    if (on) {
+        if (r->have_chunk || !r->kept.empty()) return fail(KBBQ_ESTATE, "keeping starts before the first chunk of a scan");
+        r->keeping = true;
+    } else {
+        HIP_TRY(hipStreamSynchronize(r->st));
+        release_kept(r);
+        r->keeping = false;
+    }
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_kept(kbbq_fastq_reader *r, uint64_t *n_chunks, uint64_t *n_bytes) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (n_chunks) *n_chunks = r->kept.size() + ((r->keeping && r->selected < 0 && r->have_chunk && r->n_records) ? 1 : 0);
+    if (n_bytes) *n_bytes = r->kept_bytes + ((r->keeping && r->selected < 0 && r->have_chunk && r->n_records)
+                                                 ? r->text.bytes + r->idx_u32.bytes + r->base_sz.bytes + r->text_sz.bytes : 0);
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_select(kbbq_fastq_reader *r, uint64_t i, kbbq_fastq_chunk *info) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    stash_current(r);
+    if (i >= r->kept.size()) return fail(KBBQ_EINVAL, "kept chunk %llu of %llu", (unsigned long long)i, (unsigned long long)r->kept.size());
+    const kbbq_fastq_reader::Kept &k = r->kept[i];
+    r->selected = (int64_t)i;
+    r->have_chunk = true;
+    r->att_bases = r->att_nmask = r->att_offcase = nullptr;
+    static_cast<FastqCounts &>(*r) = k;
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->n_records = k.n_records; info->n_bases = k.n_bases; info->longest = k.longest; info->shortest = k.shortest;
+        info->text_bytes = k.text_bytes;
+    }
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, int32_t last, kbbq_fastq_chunk *info) {
+    if (!r || !info || (!file_bytes && n_bytes)) return fail(KBBQ_EINVAL, "bad argument");
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    memset(info, 0, sizeof *info);
+    stash_current(r);
+    r->selected = -1;
+    r->have_chunk = false;
+    r->packed_is_exact = false;
+    int rc;
+    if (r->container == kbbq_fastq_reader::C_UNKNOWN && !detect_container(r, file_bytes, n_bytes, last != 0)) return KBBQ_OK;      // (consumed 0)
+    // ---- the text: the carried bytes, then what this call's bytes hold
+    uint64_t text = 0;
+    uint32_t nb = 0;      // BGZF blocks whose status is still to be looked at
+    if (r->container == kbbq_fastq_reader::C_BGZF) rc = text_from_bgzf(r, file_bytes, n_bytes, last != 0, info, &text, &nb);
+    else rc = text_from_stream(r, file_bytes, n_bytes, last != 0, info, &text);
+    if (rc || (info->flags & 1)) return rc;
+    HIP_TRY(hipMemsetAsync((char *)r->text.p + text, 0, 64, r->st));
+    HIP_TRY(hipEventRecord(r->t1, r->st));
+    // ---- lines
+    const uint64_t n_tiles = (text + NL_TILE - 1) / NL_TILE;
+    uint64_t n_lines = 0;
+    if (text) {
+        if ((rc = r->tile_counts.reserve((n_tiles + 2) * 8))) return rc;
+        uint64_t *tc = (uint64_t *)r->tile_counts.p;
+        hipLaunchKernelGGL(k_count_newlines, dim3((unsigned)n_tiles), dim3(256), 0, r->st, (const uint8_t *)r->text.p, text, tc);
+        HIP_TRY(hipGetLastError());
+        if ((rc = device_scan(r, tc, n_tiles, tc + n_tiles))) return rc;
+        HIP_TRY(hipMemcpyAsync(r->h_small.p, tc + n_tiles, 8, hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipStreamSynchronize(r->st));
+        n_lines = *(const uint64_t *)r->h_small.p;
+        // (and whether every block inflated, read only now: the line count needed the wait anyway)
+        if ((rc = inflate_check(r->inf, r->st, nb, "chunk"))) return rc;
+    }
+    const uint64_t n_rec = n_lines / 4;
+    info->text_bytes = text - r->carry_bytes;
+    uint64_t rec_end = 0;      // first byte behind the last complete record
+    if (n_rec) {
+        if ((rc = r->nl_pos.reserve((n_lines + 4) * 4))) return rc;
+        hipLaunchKernelGGL(k_newline_positions, dim3((unsigned)n_tiles), dim3(256), 0, r->st, (const uint8_t *)r->text.p, text,
+                           (const uint64_t *)r->tile_counts.p, (uint32_t *)r->nl_pos.p, n_lines);
+        HIP_TRY(hipGetLastError());
+        // ---- records
+        if ((rc = reserve_or_drop_kept(r, r->idx_u32, n_rec * 7 * 4))) return rc;
+        if ((rc = r->idx_second.reserve(n_rec))) return rc;
+        if ((rc = reserve_or_drop_kept(r, r->base_sz, (n_rec + 2) * 8))) return rc;
+        if ((rc = reserve_or_drop_kept(r, r->text_sz, (n_rec + 2) * 8))) return rc;
+        if ((rc = r->flags.reserve(64))) return rc;
+        const uint32_t init_flags[4] = {0, 0, 0xFFFFFFFFu, 0};
+        HIP_TRY(hipMemcpyAsync(r->flags.p, init_flags, 16, hipMemcpyHostToDevice, r->st));
+        const FastqIndex X = index_of(r, n_rec);
+        hipLaunchKernelGGL(k_fastq_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p,
+                           (const uint32_t *)r->nl_pos.p, n_rec, X);
+        HIP_TRY(hipGetLastError());
+        if ((rc = device_scan(r, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
+        if ((rc = device_scan(r, X.text_sz, n_rec, X.text_sz + n_rec))) return rc;
+        uint64_t *hs = (uint64_t *)r->h_small.p;
+        HIP_TRY(hipMemcpyAsync(hs, X.base_sz + n_rec, 8, hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipMemcpyAsync(hs + 1, X.flags, 16, hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipMemcpyAsync(hs + 4, (const uint32_t *)r->nl_pos.p + (4 * n_rec - 1), 4, hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipMemcpyAsync(hs + 5, X.text_sz + n_rec, 8, hipMemcpyDeviceToHost, r->st));
+        HIP_TRY(hipStreamSynchronize(r->st));
+        r->n_bases = hs[0];
+        r->out_text_bytes = hs[5];
+        const uint32_t *fl = (const uint32_t *)(hs + 1);
+        info->flags |= fl[0];
+        r->longest = fl[1];
+        r->shortest = fl[2];
+        rec_end = (uint64_t)(*(const uint32_t *)(hs + 4)) + 1;
+    }
+    HIP_TRY(hipEventRecord(r->t2, r->st));
+    // ---- what the chunk's end cut: kept for the next chunk
+    const uint64_t left = text - rec_end;
+    if (left) {
+        if (last) info->flags |= 4;      // the file ends inside a record (or without a final newline): the serial reader's case
+        if ((rc = r->carry.reserve(left + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(r->carry.p, (const char *)r->text.p + rec_end, left, hipMemcpyDeviceToDevice, r->st));
+    }
+    HIP_TRY(hipStreamSynchronize(r->st));
+    r->carry_bytes = left;
+    r->text_bytes = text;
+    r->n_records = n_rec;
+    r->have_chunk = true;
+    info->n_records = n_rec;
+    info->n_bases = n_rec ? r->n_bases : 0;
+    info->longest = n_rec ? r->longest : 0;
+    info->shortest = n_rec ? r->shortest : 0;
+    float a = 0, b = 0;
+    if (hipEventElapsedTime(&a, r->t0, r->t1) == hipSuccess) r->ms_inflate += a;
+    if (hipEventElapsedTime(&b, r->t1, r->t2) == hipSuccess) r->ms_index += b;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_inflate(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint8_t *host_out, uint64_t capacity,
+                              uint64_t *consumed, uint64_t *produced) {
+    if (!r || !host_out || !consumed || !produced || (!file_bytes && n_bytes)) return fail(KBBQ_EINVAL, "bad argument");
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    stash_current(r);
+    r->selected = -1;
+    r->have_chunk = false;
+    *consumed = *produced = 0;
+    if (r->container == kbbq_fastq_reader::C_UNKNOWN && n_bytes && !detect_container(r, file_bytes, n_bytes, false)) return KBBQ_OK;
+    if (r->container == kbbq_fastq_reader::C_TEXT) {      // the bytes are the text
+        const uint64_t n = std::min(n_bytes, capacity);
+        memcpy(host_out, file_bytes, n);
+        *consumed = *produced = n;
+        return KBBQ_OK;
+    }
+    if (r->container == kbbq_fastq_reader::C_GZIP) {
+        // Every byte is taken (the reader keeps what it cannot decode yet); what does not fit in `capacity` is held back on the
+        // device and comes first in the next call.  n_bytes == 0: the end of the input.
+        GzStream &g = r->gz;
+        *consumed = n_bytes;
+        int rc;
+        if (!g.hold_bytes) {
+            HIP_TRY(hipEventRecord(r->t0, r->st));
+            uint64_t got = 0;
+            uint32_t flags = 0, n_acc = 0;
+            if (g.failed) return fail(KBBQ_EIO, "the gzip stream ends inside a member, or a member is too large for the device decoder");
+            if ((rc = gz_decode(g, r->st, r->device, file_bytes, n_bytes, n_bytes == 0, true, &got, &flags, &n_acc))) return rc;
+            HIP_TRY(hipEventRecord(r->t1, r->st));
+            // (what was decoded in front of the trouble comes out first, as gzread gives it; the error with the next call)
+            if (flags & 1) g.failed = true;
+            if ((rc = grow_keep(g.hold, got + 64, 0, r->st))) return rc;
+            if (got) HIP_TRY(hipMemcpyAsync(g.hold.p, g.output(), got, hipMemcpyDeviceToDevice, r->st));
+            g.hold_bytes = got;
+            g.hold_off = 0;
+            HIP_TRY(hipStreamSynchronize(r->st));
+            float a = 0;
+            if (hipEventElapsedTime(&a, r->t0, r->t1) == hipSuccess) r->ms_inflate += a;
+        } else if (n_bytes) {
+            g.pending.insert(g.pending.end(), file_bytes, file_bytes + n_bytes);
+        }
+        const uint64_t n = std::min(g.hold_bytes, capacity);
+        if (!n && g.failed) return fail(KBBQ_EIO, "the gzip stream ends inside a member, or a member is too large for the device decoder");
+        if (n) HIP_TRY(hipMemcpy(host_out, (const char *)g.hold.p + g.hold_off, n, hipMemcpyDeviceToHost));
+        g.hold_off += n;
+        g.hold_bytes -= n;
+        *produced = n;
+        return KBBQ_OK;
+    }
+    // whole blocks while their inflated bytes fit
+    BlockTable T;
+    const WalkEnd end = walk_blocks(file_bytes, n_bytes, 0, capacity, T);
+    if (end.why == WALK_NOT_GZIP) return fail(KBBQ_EIO, "not a BGZF block at byte %llu of the piece", (unsigned long long)end.at);
+    if (end.why == WALK_NO_BSIZE) return fail(KBBQ_EIO, "a BGZF header without its BC field at byte %llu of the piece", (unsigned long long)end.at);
+    if (end.why == WALK_BIG_ISIZE) return fail(KBBQ_EIO, "a BGZF block of %u bytes", end.isize);
+    *consumed = T.consumed;
+    *produced = T.text;
+    if (!T.n_blocks()) return KBBQ_OK;
+    int rc;
+    if ((rc = r->comp.reserve(T.consumed + 4096))) return rc;
+    if ((rc = r->text.reserve(T.text + 4096))) return rc;
+    HIP_TRY(hipMemcpyAsync(r->comp.p, file_bytes, T.consumed, hipMemcpyHostToDevice, r->st));
+    HIP_TRY(hipMemsetAsync((char *)r->comp.p + T.consumed, 0, 4096, r->st));
+    if ((rc = inflate_queue(r->inf, r->device, r->st, T, r->comp.p, r->text.p, r->t0))) return rc;
+    HIP_TRY(hipEventRecord(r->t1, r->st));
+    HIP_TRY(hipMemcpyAsync(host_out, r->text.p, T.text, hipMemcpyDeviceToHost, r->st));
+    if ((rc = inflate_check(r->inf, r->st, T.n_blocks(), "piece"))) return rc;      // (its wait is the text copy's too)
+    float a = 0;
+    if (hipEventElapsedTime(&a, r->t0, r->t1) == hipSuccess) r->ms_inflate += a;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_batch(kbbq_fastq_reader *r, kbbq_reads *dev) {
+    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records || r->selected >= 0) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    const uint64_t n = r->n_records, nbases = r->n_bases;
+    const FastqIndex X = index_of(r, n);
+    memset(dev, 0, sizeof *dev);
+    dev->n_reads = n;
+    dev->n_bases = nbases;
+    dev->on_device = 1;
+    void *b = nullptr, *m = nullptr, *q = nullptr, *oc = nullptr, *off = nullptr, *fl = nullptr;
+    BatchArrays arrays;
+    int rc;
+    const uint64_t words = nbases / 64 + 1;
+    if ((rc = r->seq_text.reserve(nbases + 64))) return rc;
+    // [0..1] the two counts of k_pack_text, behind them the off-case words: nearly every chunk has none, and an array
+    // allocated and freed again per chunk was a hipMalloc (which clears) and a hipFree (which waits for the device) for nothing
+    if ((rc = r->counter.reserve((words + 4) * 8 + 64))) return rc;
+    void *oc_scratch = (char *)r->counter.p + 16;
+    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
+    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
+    if ((rc = arrays.alloc(&q, nbases + 16))) return rc;
+    if ((rc = arrays.alloc(&fl, n))) return rc;
+    const bool uniform = r->longest == r->shortest;
+    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
+    // (the copies in front of the kernels, not between them)
+    HIP_TRY(hipMemcpyAsync(fl, X.second, n, hipMemcpyDeviceToDevice, r->st));
+    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
+    HIP_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
+    hipLaunchKernelGGL(k_fastq_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
+                       (const uint64_t *)X.base_sz, n, (uint8_t *)r->seq_text.p, (uint8_t *)q);
+    HIP_TRY(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};      // off-case bases; characters the packed form cannot give back
+    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, oc_scratch, r->counter.p, counts))) return rc;
+    if (counts[0]) {      // soft-masked text: the batch gets its off-case bits
+        if ((rc = arrays.alloc(&oc, (words + 2) * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(oc, oc_scratch, (words + 2) * 8, hipMemcpyDeviceToDevice, r->st));
+        HIP_TRY(hipStreamSynchronize(r->st));
+    }
+    arrays.release();
+    r->packed_is_exact = counts[1] == 0;
+    dev->bases = (const uint64_t *)b;
+    dev->nmask = (const uint64_t *)m;
+    dev->qual = (const uint8_t *)q;
+    dev->offsets = (const uint64_t *)off;
+    dev->flags = (const uint8_t *)fl;
+    dev->rg = nullptr;
+    dev->read_len = uniform ? r->longest : 0;
+    dev->offcase = (const uint64_t *)oc;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, void *after_stream) {
+    if (!r || !z || !d_qual) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->device != z->device) return fail(KBBQ_EINVAL, "reader and writer are on different devices");
+    KbbqDeviceGuard guard(z->device);
+    HIP_TRY(guard.err);
+    if (r->selected >= 0 && r->kept[(size_t)r->selected].short_form && !r->att_bases)
+        return fail(KBBQ_ESTATE, "the chunk was kept without its sequence text: attach its batch first (kbbq_fastq_reader_attach)");
+    Submission *sp;
+    int rc = begin_submission(z, after_stream, &sp);
+    if (rc) return rc;
+    Submission &s = *sp;
+    const uint64_t n = r->n_records;
+    const bool from_kept = r->selected >= 0;
+    const kbbq_fastq_reader::Kept *k = from_kept ? &r->kept[(size_t)r->selected] : nullptr;
+    const FastqIndex X = from_kept ? index_from(k->idx_u32.p, nullptr, k->base_sz.p, k->text_sz.p, nullptr, n) : index_of(r, n);
+    const uint8_t *text = (const uint8_t *)(from_kept ? k->text.p : r->text.p);
+    const uint64_t t = r->out_text_bytes;      // (the scanned sizes' total, read back with the chunk's other counts)
+    s.n = t;
+    s.formatted = true;
+    if ((rc = s.payload.reserve(t + 16))) return rc;
+    HIP_TRY(hipMemsetAsync((char *)s.payload.p + t, 0, 16, z->st));
+    HIP_TRY(hipEventRecord(s.t0, z->st));
+    if (from_kept && k->short_form)
+        hipLaunchKernelGGL(k_fastq_text_packed, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, (const uint8_t *)k->names.p,
+                           (const uint32_t *)k->lens.p, (const uint64_t *)k->text_sz.p, (const uint64_t *)k->base_sz.p, r->att_bases, r->att_nmask,
+                           r->att_offcase, d_qual, n, (uint8_t *)s.payload.p);
+    else
+        hipLaunchKernelGGL(k_fastq_text_indexed, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, text, X,
+                           (const uint64_t *)X.text_sz, (const uint64_t *)X.base_sz, d_qual, n, (uint8_t *)s.payload.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = launch_deflate(z, s))) return rc;
+    // the reader's live text and index are read by the kernel just queued: the next kbbq_fastq_reader_chunk must not
+    // overwrite them before it has run (a kept chunk's buffers stay as they are)
+    if (!from_kept) HIP_TRY(hipEventSynchronize(s.t1));
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_attach(kbbq_fastq_reader *r, const kbbq_reads *batch) {
+    if (!r || !batch) return fail(KBBQ_EINVAL, "null argument");
+    if (!batch->on_device || !batch->bases || !batch->nmask) return fail(KBBQ_EINVAL, "not a device batch");
+    if (r->selected < 0) return fail(KBBQ_ESTATE, "no kept chunk is selected");
+    const kbbq_fastq_reader::Kept &k = r->kept[(size_t)r->selected];
+    if (batch->n_reads != k.n_records || batch->n_bases != k.n_bases) return fail(KBBQ_EINVAL, "the batch is not this chunk's");
+    r->att_bases = batch->bases;
+    r->att_nmask = batch->nmask;
+    r->att_offcase = batch->offcase;
+    return KBBQ_OK;
+}
+int kbbq_fastq_reader_preload(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint64_t front_room) {
+    if (!r || !file_bytes || !n_bytes) return fail(KBBQ_EINVAL, "bad argument");
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    return r->pre.start(file_bytes, n_bytes, front_room);
+}
+
+int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (inflate_ms) *inflate_ms = r->ms_inflate;      // (a gzip stream's stages included: kbbq_fastq_reader_gzip_ms splits them)
+    if (index_ms) *index_ms = r->ms_index;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_take_text(kbbq_fastq_reader *r, int32_t on) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    r->take_text = on != 0;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_gzip_ms(kbbq_fastq_reader *r, double *find_ms, double *decode_ms, double *chain_ms, double *resolve_ms) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (find_ms) *find_ms = r->gz.ms_find;
+    if (decode_ms) *decode_ms = r->gz.ms_decode;
+    if (chain_ms) *chain_ms = r->gz.ms_chain;
+    if (resolve_ms) *resolve_ms = r->gz.ms_resolve;
+    return KBBQ_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // gzip_inflate.h -- a plain gzip stream (RFC 1952: one or more members, no block index) inflated on the device (gfx950).
-// Included once by bgzf_device.hip, which drives it from kbbq_fastq_reader_chunk / _inflate.
+// Included once, by gzip_stream.hip, which kbbq_fastq_reader_chunk / _inflate drive.
 //
 // A BGZF file tells where every DEFLATE stream starts; a plain gzip member is one DEFLATE stream whose blocks can only be
 // found by decoding the blocks in front of them.  The two-stage speculative decode of pugz and rapidgzip makes it parallel:
@@ -34,7 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bgzf_device.h"
+#include "wave_helpers.h"
 #include "deflate_common.h"
 
 namespace kbbq {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/deflate_probe.py [MB] -- where k_deflate's time goes: run with KBBQ_LIB=tools/build/libkbbq_prof.so (bgzf_device.hip
+"""tools/deflate_probe.py [MB] -- where k_deflate's time goes: run with KBBQ_LIB=tools/build/libkbbq_prof.so (bgzf_writer.hip
 compiled with -DKBBQ_DFL_PROFILE: cycle counter read between the phases of every block, summed over the wavefronts)."""
 import ctypes
 import os
