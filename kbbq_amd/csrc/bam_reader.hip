@@ -350,15 +350,18 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
     };
     void *d_comp = nullptr;
     if ((rc = stage_compressed(r->pre, r->comp, file_bytes, n_bytes, at, r->st, [&](Buf &b, size_t need) { return reserve_or_drop(b, need, drop_kept); }, &d_comp))) return rc;
+    // A header longer than this chunk's stream (small pieces, thousands of references): the whole chunk is header, which the
+    // caller has parsed on the host -- nothing to inflate or index here, no record, the rest of the header comes with the
+    // next chunk.  (No record was met yet, so nothing is carried: `text` is this chunk's blocks alone.)
+    if (r->header_left > text) {
+        r->header_left -= text;
+        return KBBQ_OK;
+    }
     if ((rc = reserve_or_drop(r->text, text + 4096, drop_kept))) return rc;
     const uint64_t carry_in = r->carry_bytes;
     if (carry_in) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, carry_in, hipMemcpyDeviceToDevice, r->st));
-    // the header's bytes come first in the stream; a header longer than this chunk's stream is not this path's case
-    uint64_t skip = 0;
-    if (r->header_left) {
-        if (r->header_left > text) { info->flags |= BAMF_FALLBACK; return KBBQ_OK; }
-        skip = r->header_left;
-    }
+    // the header's bytes -- what is left of them -- come first in the stream
+    const uint64_t skip = r->header_left;
     // kept for pass 4 (before the carry buffer is overwritten below): compressed bytes, block table, the bytes carried in
     kbbq_bam_reader::Kept k;
     bool keep_this = r->keeping && at;

@@ -1,10 +1,11 @@
 // kbbq_cli.cc -- the `kbbq` command line over the MI355X engine.
 //
 // Mirrors main() of the reference (kbbq.cc:81-459): same flags, same defaults, same stderr lines with
-// the same "[%F %T %Z]" stamps, recalibrated FASTQ through BGZF on stdout.  Every pass re-opens the
-// input like the reference does (kbbq.cc:232,258,336,365,456) and hands batches of reads to the engine
-// through the C ABI (include/kbbq_engine.h); nothing is computed on the host except what the reference
-// also computes there (coverage, alpha, thresholds, the delta-Q model -- inside the library).
+// the same "[%F %T %Z]" stamps, recalibrated FASTQ through BGZF on stdout.  The reference re-opens its
+// input for every pass (kbbq.cc:232,258,336,365,456); here the first scan leaves the reads in HBM and the
+// passes run from there (a file that does not fit is re-opened per pass as in the reference).  Batches of
+// reads go to the engine through the C ABI (include/kbbq_engine.h); nothing is computed on the host except
+// what the reference also computes there (coverage, alpha, thresholds, the delta-Q model -- inside the library).
 //
 // Differences, all deliberate:
 //   * BAM goes through this tool's own codec (bam_io.*) because htslib is not in this image; CRAM and SAM
@@ -17,10 +18,16 @@
 //     0 = up to 16 threads instead of none.  The compressed stream does not depend on the thread count;
 //   * the packed reads stay resident in GPU memory between the passes when they fit (KBBQ_RESIDENT=0
 //     turns that off): same results, four decodes of the input fewer;
+//   * the input may be standard input ("-", the default, as in the reference's usage line), a pipe or a FIFO: the
+//     reference cannot read one, because it opens its input once per pass.  Such a stream is read once by the device
+//     reader, cut into the pieces of a file of the same bytes, and must fit in GPU memory with its text; whatever needs
+//     the input twice (KBBQ_RESIDENT=0, the host parsers, --fixed) is refused for it with one line.  "-" with a regular
+//     file on standard input is that file;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
 #include <getopt.h>
+#include <sys/mman.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -50,6 +57,7 @@
 #include "bam_io.h"
 #include "fastq_io.h"
 #include "host_model.h"
+#include "piece_reader.h"
 
 using namespace kbbq;
 
@@ -86,6 +94,12 @@ struct CliOptions {
     bool set_oq = false, use_oq = false;
     int nthreads = 0;
     std::string filename = "-", fixedinput;
+    // What is opened for `filename` and for --fixed.  "-" with a regular file on standard input (kbbq ... < reads.fq.gz) is
+    // that file under a name that can be opened once per pass; the log lines keep saying "-".
+    std::string input = "-", fixed_path;
+    // The input is not a regular file -- a pipe on standard input, a FIFO, /dev/stdin on a pipe: it is read once, front to
+    // back, by the device reader (main(): StreamInput), and whatever would read it a second time is refused.
+    bool stream = false, fixed_stream = false;
     int out_threads = 1;      // --threads, or "pick" (parse())
     int io_threads = 1;       // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
     bool is_bam = false;      // what sniff() found
@@ -102,7 +116,8 @@ struct CliOptions {
     bool resident = !env_is(getenv("KBBQ_RESIDENT"), "0");                   // =0: every pass reads the file again, nothing stays in HBM
     bool device_reader = env_num(getenv("KBBQ_DEVICE_READER"), 1) != 0;      // =0: the host parsers at once
     bool serial_parse = env_num(getenv("KBBQ_SERIAL_PARSE"), 0) != 0;        // =1: the serial readers at once
-    bool keep_text = env_num(getenv("KBBQ_KEEP_TEXT"), 1) != 0;              // =0: pass 4 of the device reader reads the file again
+    bool keep_text = env_num(getenv("KBBQ_KEEP_TEXT"), 1) != 0;              // =0: pass 4 of the device reader reads the file again (a stream: always 1)
+    long long text_budget_mb = env_num(getenv("KBBQ_TEXT_BUDGET_MB"), -1);   // HBM for resident reads + kept text; unset: 3/4 of the free memory
     uint32_t seed = (uint32_t)env_num(getenv("KBBQ_SEED"), 0);               // the sampler's seed; 0: from time and pid like the reference
     const char *devices = getenv("KBBQ_DEVICES");                            // 0,1,...: passes 1-3 sharded over these devices (run_on_devices)
     bool exchange_local = env_is(getenv("KBBQ_EXCHANGE"), "local");          // in-process copies even between distinct devices
@@ -113,9 +128,30 @@ struct CliOptions {
     bool host_io() const { return host_deflate; }
     // BGZF input that the host parsers read (BAM always) is inflated on the GPU as well
     bool inflate_on_device() const { return !host_deflate && device_inflate; }
-    // The device reader (DeviceFastqInput) may be tried: it makes resident batches of a regular file
+    // The device reader (DeviceFastqInput) may be tried: it makes resident batches of the input
     bool may_read_on_device(bool resident_on) const {
-        return !fixed_mode() && !host_io() && resident_on && filename != "-" && device_reader && !serial_parse;
+        return !fixed_mode() && !host_io() && resident_on && device_reader && !serial_parse;
+    }
+    // What was asked for that reads the input more than once, which a stream does not allow; null: nothing
+    const char *needs_a_file() const {
+        if (fixed_mode()) return "--fixed reads both of its files with the host parsers";
+        if (!resident) return "KBBQ_RESIDENT=0 reads it again in every pass";
+        if (!device_reader) return "KBBQ_DEVICE_READER=0 leaves it to the host parsers, which read it again for the output";
+        if (serial_parse) return "KBBQ_SERIAL_PARSE=1 leaves it to the host parsers, which read it again for the output";
+        if (host_deflate) return "KBBQ_HOST_DEFLATE=1 leaves it to the host parsers, which read it again for the output";
+        return nullptr;
+    }
+    // The name to open for a file argument, and whether it is a stream
+    static std::string resolve(const std::string &name, bool &is_stream) {
+        struct stat st;
+        is_stream = false;
+        if (name == "-") {
+            if (fstat(0, &st) == 0 && S_ISREG(st.st_mode)) return "/proc/self/fd/0";      // (a fresh description at offset 0 per open)
+            is_stream = true;
+        } else if (stat(name.c_str(), &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode)) {
+            is_stream = true;
+        }
+        return name;
     }
     uint64_t host_cache_budget() const {
         if (host_cache_mb != LLONG_MIN) return (uint64_t)host_cache_mb << 20;
@@ -156,6 +192,8 @@ struct CliOptions {
             filename = std::string(argv[optind]);
             while (++optind < argc) std::cerr << put_now << " Warning: Extra argument " << argv[optind] << " ignored." << std::endl;
         }
+        input = resolve(filename, stream);
+        if (fixed_mode()) fixed_path = resolve(fixedinput, fixed_stream);
         return true;
     }
 };
@@ -190,6 +228,56 @@ static Format sniff(const std::string &path) {   // hts_detect_format, as far as
     if (n >= 1 && b[0] == '@') return Format::fastq;
     return Format::unknown;
 }
+
+// An input that is not a regular file (CliOptions::stream).  Its first bytes are read into host memory -- the head -- and
+// stand in for the input wherever a name is opened before the pieces flow: an in-memory file holds a copy of them, which
+// sniff() and BamReader open as /proc/self/fd/N.  The device reader then gets the head back as the first bytes of the
+// stream (piece_reader.h: PieceSource), so the input is read exactly once.
+struct StreamInput {
+    PieceSource src;
+    std::string head_path;      // the in-memory copy of the head, by name
+    StreamInput() = default;
+    StreamInput(const StreamInput &) = delete;
+    ~StreamInput() { if (memfd_ >= 0) ::close(memfd_); }
+    // false: nothing can be read from it (a terminal on standard input included: nobody is asked to type a file)
+    bool open(const CliOptions &o) {
+        src.stream = true;
+        if (o.filename == "-") {
+            if (isatty(0)) return false;
+            src.fd = 0;
+            src.owns_fd = false;
+        } else {
+            src.fd = ::open(o.input.c_str(), O_RDONLY);
+        }
+        if (src.fd < 0) return false;
+#ifdef F_SETPIPE_SZ
+        struct stat st;      // a pipe: as much buffer as the system grants, as on the output side (DeviceBgzfWriter)
+        if (fstat(src.fd, &st) == 0 && S_ISFIFO(st.st_mode)) (void)fcntl(src.fd, F_SETPIPE_SZ, 1 << 20);
+#endif
+        memfd_ = memfd_create("kbbq-head", MFD_CLOEXEC);
+        if (memfd_ < 0) return false;
+        head_path = "/proc/self/fd/" + std::to_string(memfd_);
+        return grow(kHead) && !src.head.empty();
+    }
+    // the head, and its copy, grown to `want` bytes or to the end of the stream
+    bool grow(size_t want) {
+        if (!src.grow_head(want)) return false;
+        while (copied_ < src.head.size()) {
+            const ssize_t w = pwrite(memfd_, src.head.data() + copied_, src.head.size() - copied_, (off_t)copied_);
+            if (w <= 0) return false;
+            copied_ += (size_t)w;
+        }
+        return true;
+    }
+    // A BAM header may be longer than any head chosen beforehand: the head is doubled until the header is in it
+    bool grow_more() { return !src.head_is_all && src.head.size() < kMaxHead && grow(2 * src.head.size()); }
+
+private:
+    // (a gzip header's fixed part and its longest extra field, or a whole first BGZF block, with room to spare)
+    static constexpr size_t kHead = (size_t)1 << 17, kMaxHead = (size_t)1 << 31;
+    int memfd_ = -1;
+    size_t copied_ = 0;
+};
 
 // One read as the passes see it (what HTSFile::get() puts into CReadData), plus the record it came from.
 struct Item {
@@ -620,10 +708,11 @@ private:
 // device as it is, chunk by chunk -- inflate, line index, record rules and packing are kernels -- and every chunk becomes one
 // resident batch.  Pass 4 feeds the same chunks again and the records' text is re-assembled there around the new qualities.
 // What the reference does with kseq_read over bgzf_read once per pass (htsiter.cc:49-60).  Any shape this path does not
-// take is reported by the reader and the caller starts over with the host parsers.
+// take is reported by the reader and the caller starts over with the host parsers -- or, the input being a stream that
+// cannot be read again (StreamInput), ends the run with `refusal`.
 class DeviceFastqInput {
 public:
-    explicit DeviceFastqInput(const CliOptions &o) : kPiece(o.reader_piece), preload_(o.preload) {}
+    explicit DeviceFastqInput(const CliOptions &o) : kPiece(o.reader_piece), preload_(o.preload), pieces_(o.reader_piece) {}
     ~DeviceFastqInput() { close(); }
     bool active = false;
     bool text_kept = false;                   // every chunk's text and index stayed in HBM: pass 4 reads nothing
@@ -637,33 +726,43 @@ public:
     bool oq_unwritable = false;               // some record's OQ tag bam_aux_update_str could not update (--set-oq: host path)
     double wait_s = 0, device_s = 0, batch_s = 0;
     const char *container = "BGZF";           // what the file is: BGZF, gzip (other gzip streams) or text
+    // why the scan could not go on (device_scan): a file starts over with the host parsers, a stream's run ends with this line
+    std::string refusal;
 
-    bool open_bam(const std::string &path, bool use_oq, int32_t n_ref, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
-        if (!open_file(path, true)) return false;
+    // `stream`: the input when it is not a regular file (its head has been read), null for the file `path`
+    bool open_bam(const std::string &path, StreamInput *stream, bool use_oq, int32_t n_ref, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
+        if (!open_file(path, stream, true)) return false;
         std::vector<const char *> ids;
         for (auto &id : rg_ids) ids.push_back(id.c_str());
         if (kbbq_bam_reader_create(0, use_oq ? 1 : 0, n_ref, header_bytes, ids.data(), (uint32_t)ids.size(), &bam) < 0) return false;
         start_pass();
         return true;
     }
-    bool open(const std::string &path) {
-        if (!open_file(path, false)) return false;
+    bool open(const std::string &path, StreamInput *stream) {
+        if (!open_file(path, stream, false)) return false;
         if (kbbq_fastq_reader_create(0, &reader) < 0 || kbbq_fastq_reader_take_text(reader, 1) < 0) return false;
         start_pass();
         return true;
     }
-    bool open_file(const std::string &path, bool bgzf_only) {
-        fd_ = ::open(path.c_str(), O_RDONLY);
-        if (fd_ < 0) return false;
-        struct stat st;
-        if (fstat(fd_, &st) != 0 || !S_ISREG(st.st_mode)) return false;      // a pipe cannot be read twice
-        size_ = (uint64_t)st.st_size;
+    bool open_file(const std::string &path, StreamInput *stream, bool bgzf_only) {
+        std::vector<unsigned char> file_head(12 + 65535);      // (a gzip header's fixed part and the longest extra field)
+        const unsigned char *magic = file_head.data();
+        ssize_t got = 0;
+        if (stream) {
+            src_ = &stream->src;
+            magic = stream->src.head.data();
+            got = (ssize_t)stream->src.head.size();
+        } else {
+            file_.fd = ::open(path.c_str(), O_RDONLY);
+            if (file_.fd < 0) return false;
+            struct stat st;
+            if (fstat(file_.fd, &st) != 0 || !S_ISREG(st.st_mode)) return false;      // (what is not a regular file comes as a StreamInput)
+            src_ = &file_;
+            got = pread(file_.fd, file_head.data(), file_head.size(), 0);
+        }
+        if (got < 4) return false;
         // BGZF, another gzip stream (one member or several) or the text itself (include/kbbq_bgzf.h: the reader decides the
         // same way); BAM is BGZF
-        std::vector<unsigned char> head(12 + 65535);      // (a gzip header's fixed part and the longest extra field)
-        const ssize_t got = pread(fd_, head.data(), head.size(), 0);
-        if (got < 4) return false;
-        const unsigned char *magic = head.data();
         const bool gz = magic[0] == 0x1f && magic[1] == 0x8b && magic[2] == 8;
         bgzf_ = bgzf_block_size(magic, (size_t)got) != 0;      // (fastq_io.h: the one rule for "this is BGZF")
         container = bgzf_ ? "BGZF" : gz ? "gzip" : "text";
@@ -687,87 +786,61 @@ public:
     void close() {
         stop();
         for (int i = 0; i < 2; ++i) { if (buf_[i]) kbbq_host_free(buf_[i]); buf_[i] = nullptr; }
-        if (fd_ >= 0) ::close(fd_);
-        fd_ = -1;
+        if (file_.fd >= 0) ::close(file_.fd);
+        file_.fd = -1;
     }
-    // The file is read front to back in pieces of 256 MB by a thread of its own, into two page-locked buffers in turn; the
-    // bytes the device did not take from one piece (the last, incomplete BGZF block: less than 64 KB) go in front of the
-    // next one.  The same sequence of chunks comes out of every pass.
+    // The input is read front to back in pieces of 256 MB by a thread of its own (piece_reader.h), into two page-locked
+    // buffers in turn; the bytes the device did not take from one piece (the last, incomplete BGZF block: less than 64 KB)
+    // go in front of the next one.  The same sequence of chunks comes out of every pass over a file -- and out of the one
+    // pass over a stream of the same bytes.
     void start_pass() {
         stop_io();
-        taken_piece_ = 0;
         left_ = 0;
-        io_error_ = false;
-        quit_ = false;
-        filled_[0] = filled_[1] = false;
-        io_ = std::thread([this] {
-            for (uint64_t k = 0;; ++k) {
-                const uint64_t at = k * kPiece;
-                if (at >= size_) break;
-                const int b = (int)(k & 1);
-                {
-                    std::unique_lock<std::mutex> lk(mu_);
-                    cv_.wait(lk, [&] { return quit_ || !filled_[b]; });
-                    if (quit_) return;
-                }
-                const uint64_t n = std::min<uint64_t>(kPiece, size_ - at);
-                uint64_t got = 0;
-                bool ok = true;
-                while (got < n) {
-                    const ssize_t r = pread(fd_, buf_[b] + kFront + got, n - got, (off_t)(at + got));
-                    if (r <= 0) { ok = false; break; }
-                    got += (uint64_t)r;
-                }
-                // the piece starts for the device at once: its copy overlaps the kernels of the piece before it
-                // (BGZF only: the reader decodes another gzip stream from the bytes it kept, and text is copied as it is)
-                if (ok && bgzf_ && preload_) {
-                    if (bam) (void)kbbq_bam_reader_preload(bam, buf_[b] + kFront, n, kFront);
-                    else if (reader) (void)kbbq_fastq_reader_preload(reader, buf_[b] + kFront, n, kFront);
-                }
-                {
-                    std::lock_guard<std::mutex> lk(mu_);
-                    if (!ok) io_error_ = true;
-                    filled_[b] = true;
-                    piece_bytes_[b] = n;
-                }
-                cv_.notify_all();
-                if (!ok) return;
-            }
-        });
+        read_twice_ = !src_->rewind();      // (a stream is never read twice: the callers see to that)
+        if (read_twice_) return;
+        std::function<void(uint8_t *, uint64_t)> ahead;
+        // the piece starts for the device at once: its copy overlaps the kernels of the piece before it
+        // (BGZF only: the reader decodes another gzip stream from the bytes it kept, and text is copied as it is)
+        if (bgzf_ && preload_)
+            ahead = [this](uint8_t *piece, uint64_t n) {
+                if (bam) (void)kbbq_bam_reader_preload(bam, piece, n, kFront);
+                else if (reader) (void)kbbq_fastq_reader_preload(reader, piece, n, kFront);
+            };
+        pieces_.start(src_, buf_[0] + kFront, buf_[1] + kFront, ahead);
     }
     // 1 = the next chunk is in `info` (its records, if any, are the reader's current chunk), 0 = end of file, -1 = I/O or device
     // error, -2 = a shape for the host parsers
     int next_chunk(kbbq_fastq_chunk &info) {
-        const uint64_t at = taken_piece_ * kPiece;
-        if (at >= size_) return 0;
-        const int b = (int)(taken_piece_ & 1);
         const auto t0 = std::chrono::steady_clock::now();
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] { return filled_[b] || io_error_; });
-            if (io_error_) return -1;
-        }
+        PieceReader::Piece piece;
+        const int got = read_twice_ ? -1 : pieces_.next(piece);
+        if (got <= 0) return got;
         wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        const uint64_t n = piece_bytes_[b];
-        const int last = at + n >= size_;
-        uint8_t *data = buf_[b] + kFront - left_;
+        const uint64_t n = piece.bytes;
+        const int last = piece.last;
+        uint8_t *data = piece.data - left_;
         if (left_) memcpy(data, carry_, left_);
         const auto t1 = std::chrono::steady_clock::now();
         if ((bam ? kbbq_bam_reader_chunk(bam, data, left_ + n, last, &info) : kbbq_fastq_reader_chunk(reader, data, left_ + n, last, &info)) < 0) return -1;
         device_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
         if (bam && (info.flags & 8)) oq_unwritable = true;
-        if (info.flags & 7) return -2;      // (a read name that is too short included: the host path reports it)
         const uint64_t rest = left_ + n - info.consumed;
-        if (rest > kFront || (rest && last)) return -2;      // a block that does not end: not a file this path reads
+        // (a read name that is too short included: the host path reports it)
+        if (info.flags & 2) refusal = " Error: a read name is shorter than 2 characters before the first '_'.";
+        else if (info.flags & 4) refusal = needs_host_parsers("an input that ends inside a record");
+        else if (info.flags & 1)
+            refusal = needs_host_parsers(bam ? "a BAM record the device reader hands back (no usable RG tag, no @RG line for it, or malformed)"
+                                             : "FASTQ the device reader hands back (multi-line records, RG: fields in read names, carriage returns, empty reads)");
+        else if (rest > kFront || (rest && last)) refusal = needs_host_parsers("a compressed block that does not end");      // not a file this path reads
+        if (!refusal.empty()) return -2;
         if (rest) memcpy(carry_, data + info.consumed, rest);
         left_ = rest;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            filled_[b] = false;
-        }
-        cv_.notify_all();
-        ++taken_piece_;
+        pieces_.release();
         return 1;
+    }
+    // the one line a stream's run ends with when the host parsers would have to take over
+    static std::string needs_host_parsers(const std::string &what) {
+        return " Error: input from a pipe is read once, and " + what + " is left to the host parsers, which read it again: write the input to a file first.";
     }
     // The calls both readers have, whichever this one holds (include/kbbq_bgzf.h)
     const char *format() const { return bam ? "BAM" : "FASTQ"; }
@@ -789,27 +862,19 @@ public:
     }
 
 private:
-    void stop_io() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            quit_ = true;
-        }
-        cv_.notify_all();
-        if (io_.joinable()) io_.join();
-    }
+    void stop_io() { pieces_.stop(); }
     static constexpr uint64_t kFront = 1ull << 16;
     // bytes of the file per chunk; KBBQ_READER_PIECE_KB shrinks it so that tests cross many chunk boundaries with small files
     const uint64_t kPiece;
     const bool preload_;      // KBBQ_PRELOAD
-    int fd_ = -1;
-    uint64_t size_ = 0, taken_piece_ = 0, left_ = 0, piece_bytes_[2] = {0, 0};
+    PieceSource file_;        // a regular file; a stream's source is the StreamInput's
+    PieceSource *src_ = nullptr;
+    PieceReader pieces_;
+    uint64_t left_ = 0;
     uint8_t *buf_[2] = {nullptr, nullptr};
     uint8_t carry_[1 << 16];
-    std::thread io_;
-    std::mutex mu_;
-    std::condition_variable cv_;
-    bool filled_[2] = {false, false}, io_error_ = false, quit_ = false;
     bool bgzf_ = false;
+    bool read_twice_ = false;      // a second pass over a stream was asked for: every chunk call fails
 };
 
 // What the output pass needs of one batch besides the new qualities, kept from the first scan when it fits in
@@ -1164,6 +1229,28 @@ static int io_test(int argc, char *argv[], const CliOptions &o) {
             if (!out.write(buf.data(), n)) return 1;
         return out.close() ? 0 : 1;
     }
+    if (what == "pieces" && argc > 3) {
+        // Standard input through the device reader's byte source and I/O thread (piece_reader.h), no GPU call:
+        // --io-test pieces PIECE_KB [HEAD_BYTES].  One line per piece: index, bytes, last (0 or 1), CRC-32 of its bytes.
+        // HEAD_BYTES of a stream are read beforehand and replayed, as main() does with the bytes it sniffs (StreamInput).
+        const uint64_t piece = (uint64_t)std::max(1ll, atoll(argv[3])) << 10;
+        PieceSource src;
+        struct stat st;
+        src.fd = 0;
+        src.owns_fd = false;
+        src.stream = !(fstat(0, &st) == 0 && S_ISREG(st.st_mode));
+        if (src.stream && argc > 4 && !src.grow_head((size_t)atoll(argv[4]))) return 1;
+        std::vector<uint8_t> buf[2] = {std::vector<uint8_t>(piece), std::vector<uint8_t>(piece)};
+        PieceReader pieces(piece);
+        pieces.start(&src, buf[0].data(), buf[1].data());
+        PieceReader::Piece p;
+        int rc;
+        for (uint64_t k = 0; (rc = pieces.next(p)) == 1; ++k) {
+            printf("%llu %llu %d %08lx\n", (unsigned long long)k, (unsigned long long)p.bytes, p.last ? 1 : 0, crc32(crc32(0L, Z_NULL, 0), p.data, (uInt)p.bytes));
+            pieces.release();
+        }
+        return rc < 0 ? 1 : 0;
+    }
     return 2;
 }
 
@@ -1269,34 +1356,55 @@ static std::vector<std::string> read_group_ids(const std::string &header_text) {
 // compressed bytes) of every chunk stays in HBM for pass 4 while it fits; otherwise pass 4 reads the file again.
 // false: a shape this path does not take -- records that are not four lines, read groups in the names, a read group without
 // an @RG line, a record the host codec would report or end the stream on, reads that do not fit in HBM -- and the scan
-// state is as it was before: the caller starts over with the host parsers.
-static bool device_scan(const CliOptions &o, DeviceFastqInput &in, ScanState &s) {
+// state is as it was before: the caller starts over with the host parsers.  `stream`: the input is not a regular file but
+// this stream, read once -- the BAM header comes from its head, its text must stay in HBM, and in.refusal is the line the
+// run ends with where a file would start over (empty: the stream held no read).
+static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceFastqInput &in, ScanState &s) {
     Resident &resident = s.resident;
     std::vector<std::string> rg_ids;
     bool ok;
     if (o.is_bam) {
-        BamReader head(o.filename, 1);
-        ok = head.ok();
+        // (a stream: from the head, which grows until the whole header -- any number of BGZF blocks -- is in it)
+        std::unique_ptr<BamReader> head;
+        do head.reset(new BamReader(stream ? stream->head_path : o.input, 1));
+        while (!head->ok() && stream && stream->grow_more());
+        ok = head->ok();
+        if (!ok) in.refusal = " Error opening file " + o.filename;
         if (ok) {
-            s.bam_header = head.header();
+            s.bam_header = head->header();
             uint64_t header_bytes = 12 + s.bam_header.text.size();
             for (auto &r : s.bam_header.refs) header_bytes += 8 + r.first.size() + 1;
             rg_ids = read_group_ids(s.bam_header.text);
-            ok = !rg_ids.empty() && rg_ids.size() < 65535 && in.open_bam(o.filename, o.use_oq, (int32_t)s.bam_header.refs.size(), header_bytes, rg_ids);
+            ok = !rg_ids.empty() && rg_ids.size() < 65535;
+            if (!ok) in.refusal = DeviceFastqInput::needs_host_parsers("a BAM header without @RG lines (or with 65535 of them)");
+            ok = ok && in.open_bam(o.input, stream, o.use_oq, (int32_t)s.bam_header.refs.size(), header_bytes, rg_ids);
         }
     } else {
-        ok = in.open(o.filename);
+        ok = in.open(o.input, stream);
     }
+    if (!ok && in.refusal.empty()) in.refusal = " Error opening file " + o.filename;
+    // the line of a stream whose reads and text do not both stay in HBM
+    auto does_not_fit = [&] {
+        uint64_t free_b = 0, total_b = 0;
+        (void)kbbq_device_memory(-1, &free_b, &total_b);
+        return " Error: input from a pipe must fit in GPU memory with its text: " + std::to_string(s.seqlen) + " bases had been read when it no longer did, and " +
+               std::to_string(free_b >> 20) + " MB of GPU memory are free.  Write the input to a file first.";
+    };
     // The text stays in HBM beside the packed reads while both fit in three quarters of the free memory
     // (resident.budget is 60 %): pass 4 then takes the record text from there and the file is read and inflated once.
-    // KBBQ_KEEP_TEXT=0: pass 4 reads the file again.
-    bool keeping = ok && o.keep_text && in.keep(true) == 0;
-    const uint64_t text_budget = resident.budget / 4 * 5;
+    // KBBQ_KEEP_TEXT=0: pass 4 reads the file again.  KBBQ_TEXT_BUDGET_MB: that share, set by hand.  A stream cannot be read again: its text is kept or the run ends.
+    bool keeping = ok && (o.keep_text || stream) && in.keep(true) == 0;
+    if (ok && stream && !keeping) { ok = false; in.refusal = std::string(" Error: ") + kbbq_last_error(); }
+    const uint64_t text_budget = o.text_budget_mb >= 0 ? (uint64_t)o.text_budget_mb << 20 : resident.budget / 4 * 5;
     while (ok) {
         kbbq_fastq_chunk info;
         const int rc = in.next_chunk(info);
         if (rc == 0) break;
-        if (rc < 0) { ok = false; break; }
+        if (rc < 0) {
+            if (rc == -1) in.refusal = std::string(" Error: reading the input: ") + kbbq_last_error();
+            ok = false;
+            break;
+        }
         in.chunk_records.push_back(info.n_records);
         if (!info.n_records) continue;
         const uint64_t need = Resident::bytes_of(info.n_bases, info.n_records, o.is_bam ? 18 : 16);
@@ -1305,17 +1413,29 @@ static bool device_scan(const CliOptions &o, DeviceFastqInput &in, ScanState &s)
             if (in.kept(&kept_chunks, &kept_bytes) < 0 || resident.bytes + need + kept_bytes > text_budget) {
                 in.keep(false);
                 keeping = false;
+                if (stream) { in.refusal = does_not_fit(); ok = false; break; }
             }
         }
         const auto tb = std::chrono::steady_clock::now();
-        if (info.longest > KBBQ_MAX_READ_LEN || !resident.add(need, [&](kbbq_reads *d) { return in.batch(d); })) { ok = false; break; }
+        if (info.longest > KBBQ_MAX_READ_LEN) {
+            in.refusal = " Error: reads longer than " + std::to_string(KBBQ_MAX_READ_LEN) + " bases are not supported by the GPU engine.";
+            ok = false;
+            break;
+        }
+        if (!resident.add(need, [&](kbbq_reads *d) { return in.batch(d); })) { in.refusal = does_not_fit(); ok = false; break; }
         in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
         s.seqlen += info.n_bases;
         s.n_reads += info.n_records;
         s.longest = std::max<size_t>(s.longest, info.longest);
-        if (o.is_bam && info.shortest == 0) ok = false;      // an empty read ends the reference's coverage and sampling loops: the host path's case
+        if (o.is_bam && info.shortest == 0) {      // an empty read ends the reference's coverage and sampling loops: the host path's case
+            in.refusal = DeviceFastqInput::needs_host_parsers("a BAM record without bases");
+            ok = false;
+        }
     }
-    if (ok && o.set_oq && in.oq_unwritable) ok = false;      // bam_aux_update_str would fail on some record: the host path reports it
+    if (ok && o.set_oq && in.oq_unwritable) {      // bam_aux_update_str would fail on some record: the host path reports it
+        in.refusal = DeviceFastqInput::needs_host_parsers("--set-oq on a record whose OQ tag cannot be updated");
+        ok = false;
+    }
     if (ok && s.n_reads && o.is_bam) {
         // read groups in the order of their first records, as rg_to_int numbers them (readutils.cc:53-57)
         std::vector<uint32_t> order(rg_ids.size());
@@ -1324,14 +1444,15 @@ static bool device_scan(const CliOptions &o, DeviceFastqInput &in, ScanState &s)
         for (uint32_t g = 0; ok && g < n_groups; ++g) s.groups.index_of(rg_ids[order[g]]);
     }
     if (ok && s.n_reads && !o.is_bam) s.groups.index_of(std::string());  // FASTQ without read-group fields: the one read group "" (readutils.cc:98-103)
+    uint64_t kept_chunks = 0;
+    if (ok && s.n_reads && in.rewind() == 0 && in.kept(&kept_chunks, &in.kept_bytes) == 0) in.text_kept = kept_chunks == resident.dev.size();
+    if (ok && s.n_reads && stream && !in.text_kept) { in.refusal = does_not_fit(); ok = false; }      // (the reader gave its chunks up)
     if (!ok || !s.n_reads) {
         s.reset(o);
         in.close();
         return false;
     }
     in.active = true;
-    uint64_t kept_chunks = 0;
-    if (in.rewind() == 0 && in.kept(&kept_chunks, &in.kept_bytes) == 0) in.text_kept = kept_chunks == resident.dev.size();
     if (!in.text_kept) { in.keep(false); in.kept_bytes = 0; }
     resident.keep_recs = false;      // the records come from the device's own copy of the input in pass 4
     return true;
@@ -1342,13 +1463,13 @@ static bool device_scan(const CliOptions &o, DeviceFastqInput &in, ScanState &s)
 static bool open_fast(const CliOptions &o, bool keep_records, Batch::Fast &f, BamHeader *header) {
     f.copy_threads = o.io_threads;
     if (o.is_bam) {
-        auto *bp = new BamChunkParser(o.filename, o.use_oq, o.io_threads, o.out_threads, keep_records);
+        auto *bp = new BamChunkParser(o.input, o.use_oq, o.io_threads, o.out_threads, keep_records);
         f.parser.reset(bp);
         f.lens_per_record = 1;
         if (bp->ok() && header) *header = bp->header();
         return bp->ok();
     }
-    auto *fp = new FastqChunkParser(o.filename, o.io_threads, o.out_threads, keep_records);
+    auto *fp = new FastqChunkParser(o.input, o.io_threads, o.out_threads, keep_records);
     f.parser.reset(fp);
     return fp->ok();
 }
@@ -1372,7 +1493,7 @@ static int host_scan(const CliOptions &o, ScanState &s, Batch &batch) {
         if (fast) {
             if (!open_fast(o, resident.on && resident.keep_recs, ff, &s.bam_header)) return give_up(" Error opening file " + o.filename);
         } else {
-            in = open_source(o, o.filename);
+            in = open_source(o, o.input);
             if (!in->ok()) return give_up(" Error opening file " + o.filename);
         }
         if (!fast && o.is_bam) s.bam_header = static_cast<BamSource *>(in.get())->header();
@@ -1431,7 +1552,7 @@ struct PassBatches {
         std::unique_ptr<Source> serial;
         Batch::Fast fast;
         if (scan->passes_fast()) (void)open_fast(*opt, false, fast, nullptr);
-        else serial = open_source(*opt, opt->filename);
+        else serial = open_source(*opt, opt->input);
         ScopedSet<bool> stop(host->stop_at_empty, stop_at_empty);
         bool ok = true;
         for (size_t i = 0; ok && (serial ? host->fill(*serial, scan->groups, opt->batch_reads, false) : host->fill_fast(fast, scan->groups, opt->batch_reads, nullptr)); ++i)
@@ -1658,7 +1779,7 @@ static int run_on_devices(const std::vector<int> &devices, kbbq_engine *e, const
 // --fixed, kbbq.cc:367-378: errors = bases that differ from the corrected file
 static int tally_fixed(kbbq_engine *e, const CliOptions &o, ScanState &s, Batch &batch) {
     // the second file is opened in the FIRST file's format (kbbq.cc:370 passes is_bam)
-    std::unique_ptr<Source> in = open_source(o, o.filename), fixed = open_source(o, o.fixedinput);
+    std::unique_ptr<Source> in = open_source(o, o.input), fixed = open_source(o, o.fixed_path);
     if (!fixed->ok()) return give_up(" Error opening file " + o.fixedinput);
     Batch fb;
     ReadGroups fixed_groups;
@@ -1981,7 +2102,7 @@ static int write_reparsed_fastq(kbbq_engine *e, ScanState &s, const CliOptions &
 
 // Everything else: the serial reader decodes the file once more, record by record to the writer
 static int write_serial(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, Batch &batch) {
-    std::unique_ptr<Source> in = open_source(o, o.filename);
+    std::unique_ptr<Source> in = open_source(o, o.input);
     std::vector<uint8_t> newq;
     size_t bi = 0;
     while (batch.fill(*in, s.groups, o.batch_reads, true, o.is_bam)) {
@@ -2026,10 +2147,22 @@ int main(int argc, char *argv[]) {
     if (argc > 1 && std::string(argv[1]) == "--io-test") return io_test(argc, argv, opt);
     if (!opt.parse(argc, argv)) return 1;
 
-    const Format fmt = sniff(opt.filename);
-    if (fmt == Format::unknown) return give_up(" Error opening file " + opt.filename);   // also: a pipe cannot be re-read by the passes
+    // An input that is not a regular file is read once: what it holds is decided from its first bytes, which are kept and
+    // replayed (StreamInput), and it can only go the way that reads an input once -- the device reader with everything
+    // resident.  What was asked for beyond that is refused here, before the passes, with the reason.
+    std::unique_ptr<StreamInput> stream;
+    if (opt.stream) {
+        stream.reset(new StreamInput);
+        if (!stream->open(opt)) return give_up(" Error opening file " + opt.filename);
+    }
+    const Format fmt = sniff(stream ? stream->head_path : opt.input);
+    if (fmt == Format::unknown) return give_up(" Error opening file " + opt.filename);
     if (fmt == Format::cram) return give_up(" Error: CRAM input needs htslib, which this build does not have; use BAM or FASTQ.");
     opt.is_bam = fmt == Format::bam;
+    if (opt.stream || opt.fixed_stream) {
+        if (const char *why = opt.needs_a_file())
+            return give_up(std::string(" Error: input from a pipe is read once, and ") + why + ": write the input to a file first.");
+    }
     if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
 
     // The one scan before the engine exists: on the device when that may be tried and takes the file, with the host parsers
@@ -2040,8 +2173,14 @@ int main(int argc, char *argv[]) {
     ScanState scan;
     Batch batch;
     scan.resident.init(opt);
-    const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, dev_in, scan);
-    if (!read_on_device && host_scan(opt, scan, batch)) return 1;
+    const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, stream.get(), dev_in, scan);
+    if (!read_on_device && stream) {
+        // no host parsers behind a stream; without a reason the stream held no read at all, and nothing is left to read
+        if (!scan.resident.on) return give_up(" Error: input from a pipe is read once, and the reads cannot stay in GPU memory: write the input to a file first.");
+        if (!dev_in.refusal.empty()) return give_up(dev_in.refusal);
+    } else if (!read_on_device && host_scan(opt, scan, batch)) {
+        return 1;
+    }
     if (scan.longest > KBBQ_MAX_READ_LEN)
         return give_up(" Error: reads longer than " + std::to_string(KBBQ_MAX_READ_LEN) + " bases are not supported by the GPU engine.");
     clock.mark("scan+pack+upload");
