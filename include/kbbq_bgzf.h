@@ -143,6 +143,12 @@ int kbbq_fastq_reader_inflate(kbbq_fastq_reader *r, const uint8_t *file_bytes, u
 /* The current chunk's records as a device batch (arrays owned by the library: kbbq_reads_free): bases, N mask, qualities,
  * offsets (NULL and read_len for equally long reads), second-in-pair flags, off-case bits when a base is not upper-case. */
 int kbbq_fastq_reader_batch(kbbq_fastq_reader *r, kbbq_reads *dev);
+/* Whether the batch kbbq_fastq_reader_batch built for the current chunk is exact: *exact = 1 when the chunk's sequence lines
+ * hold nothing but ACGTN and acgt, so that the packed batch gives their text back character for character (and comparing two
+ * such batches is comparing their text: kbbq_fixed_errors_batch); 0 when some other character was met -- an IUPAC code,
+ * a digit, '.' -- which packs to code 0 with its nmask bit like any other.  Valid after kbbq_fastq_reader_batch, until the
+ * next chunk, select or rewind; KBBQ_ESTATE before it. */
+int kbbq_fastq_reader_batch_exact(kbbq_fastq_reader *r, int32_t *exact);
 /* Pass 4: the current chunk's records as "@name\nseq\n+comment\nqual\n" (FastqFile::write, htsiter.cc:75-86) with
  * d_qual (device: the batch's new qualities, in the batch's base order) on the quality lines, submitted to writer z
  * (kbbq_bgzf_collect returns the blocks).  after_stream as in kbbq_bgzf_submit. */

@@ -212,6 +212,10 @@ int kbbq_pack_bases_case(const uint8_t *seq, uint64_t n_bases, uint64_t *bases_o
  * device pointers (on_device=1).  Free with kbbq_reads_free. */
 int kbbq_reads_upload(kbbq_engine *e, const kbbq_reads *host, kbbq_reads *dev);
 int kbbq_reads_free(kbbq_engine *e, kbbq_reads *dev);
+/* Where read `read` (0..n_reads) of a batch starts, in bases: offsets[read] -- an 8-byte copy for a device batch, which waits
+ * for it -- or read * read_len for a uniform batch.  What a caller needs to submit the first reads of a resident batch on
+ * their own (n_reads = read, n_bases = *base). */
+int kbbq_reads_offset(kbbq_engine *e, const kbbq_reads *reads, uint64_t read, uint64_t *base);
 /* A device batch copied onto `device` (arrays owned by the library; free with that device current, or through an engine
  * of that device): a single-process multi-device caller gives every engine its shard this way.  with_hints != 0: with zeroed
  * hint arrays (kbbq_reads_alloc_hints). */
@@ -276,6 +280,21 @@ int kbbq_trusted_finish(kbbq_engine *e, uint64_t *inserted);
 int kbbq_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t *errors_out);
 /* --fixed mode (kbbq.cc:367-378): tally with caller-supplied error bits. */
 int kbbq_tally_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *errors);
+/* --fixed on the device (kbbq.cc:371-375): error bit of base i of read first_read+j of `reads` = its character differs from
+ * base i of read fixed_first_read+j of `fixed`, for i < min(len, fixed len); bases past the fixed read's end get no bit.
+ * Both batches are device batches (KBBQ_EINVAL for a host batch, or for a record range that leaves either batch), each with
+ * an offsets array or uniform; the work is queued on the engine's stream like every call with a device batch.
+ * The comparison is made on the packed form: "differs" = the 2-bit code, the nmask bit or the offcase bit differs (a NULL
+ * offcase is all zero).  That is the reference's comparison of raw characters exactly when both batches hold nothing but
+ * ACGTN and acgt -- every other character packs to code 0 with its nmask bit, so two different ones would compare equal --
+ * and the caller sees to that (kbbq_bgzf.h: kbbq_fastq_reader_batch_exact).
+ * errors: device memory in the layout of nmask for `reads` (n_bases/64+2 words), zeroed by the caller before the first call.
+ * Several calls may fill one array for consecutive record ranges of the same `reads`: a call ORs its bits into the words of
+ * its range and touches no other word, the calls are ordered on the engine's stream, and within a call every word is
+ * written by one lane -- the result does not depend on how the ranges were cut. */
+int kbbq_fixed_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_read,
+                            const kbbq_reads *fixed, uint64_t fixed_first_read, uint64_t n_reads,
+                            uint64_t *errors /* device, nmask's layout for `reads`: n_bases/64+2 words, zeroed by the caller before the first call */);
 
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]

@@ -99,6 +99,7 @@ SYMBOLS = {
     "kbbq_pack_bases_case": (ctypes.c_int, [c_u8p, c_u64, c_u64p, c_u64p, c_u64p, c_u64p]),
     "kbbq_reads_upload": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.POINTER(Reads)]),
     "kbbq_reads_free": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_reads_offset": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, c_u64p]),
     "kbbq_sample_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64]),
     "kbbq_count_kmer_positions": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64p]),
     "kbbq_sample_finish": (ctypes.c_int, [c_vp, c_u64p]),
@@ -109,6 +110,7 @@ SYMBOLS = {
     "kbbq_trusted_finish": (ctypes.c_int, [c_vp, c_u64p]),
     "kbbq_errors_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp]),
     "kbbq_tally_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp]),
+    "kbbq_fixed_errors_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_vp]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),
@@ -159,6 +161,7 @@ SYMBOLS = {
     "kbbq_fastq_reader_rewind": (ctypes.c_int, [c_vp]),
     "kbbq_fastq_reader_chunk": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int32, ctypes.POINTER(FastqChunk)]),
     "kbbq_fastq_reader_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_fastq_reader_batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
     "kbbq_fastq_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "kbbq_fastq_reader_keep": (ctypes.c_int, [c_vp, ctypes.c_int32]),
     "kbbq_fastq_reader_kept": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

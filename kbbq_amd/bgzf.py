@@ -97,6 +97,12 @@ class FastqReader:
         _lib.check(self.L.kbbq_fastq_reader_batch(self.h, ctypes.byref(d)))
         return d
 
+    def batch_exact(self):
+        """Whether the batch just built holds nothing but ACGTN / acgt (kbbq_fastq_reader_batch_exact)."""
+        x = ctypes.c_int32()
+        _lib.check(self.L.kbbq_fastq_reader_batch_exact(self.h, ctypes.byref(x)))
+        return bool(x.value)
+
     def write(self, writer, d_qual, after_stream=None):
         _lib.check(self.L.kbbq_fastq_reader_write(self.h, writer.h, d_qual, after_stream))
 

@@ -44,6 +44,7 @@ int kbbq_fail(int code, const char *fmt, ...) {      // (abi_internal.h: shared 
 #include "kernels.h"
 #include "bucket.h"
 #include "long_reads.h"
+#include "fixed_compare.h"
 
 // ============================================================ engine object
 
@@ -1499,6 +1500,15 @@ int kbbq_reads_free(kbbq_engine *e, kbbq_reads *dev) {
     return KBBQ_OK;
 }
 
+int kbbq_reads_offset(kbbq_engine *e, const kbbq_reads *reads, uint64_t read, uint64_t *base) {
+    ENGINE_DEVICE(e);
+    if (!reads || !base || read > reads->n_reads) return fail(KBBQ_EINVAL, "bad argument");
+    if (!reads->offsets) *base = read * (uint64_t)reads->read_len;
+    else if (!reads->on_device) *base = reads->offsets[read];
+    else HIP_TRY(hipMemcpy(base, reads->offsets + read, 8, hipMemcpyDeviceToHost));
+    return KBBQ_OK;
+}
+
 int kbbq_reads_alloc_hints(kbbq_reads *dev) {
     if (!dev || !dev->on_device) return fail(KBBQ_EINVAL, "not a device batch");
     if (dev->hint_sampled || dev->hint_trusted) return fail(KBBQ_ESTATE, "batch already has hint arrays");
@@ -2161,6 +2171,40 @@ int kbbq_tally_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *er
     const Pass3 c = {0, e->stream, 0, nullptr, nullptr, nullptr, false};      // side 0 on the engine's stream; the tally takes no counters
     if ((rc = run_tally(e, c, R, d_err, nullptr, max_len))) return rc;
     return reads->on_device ? KBBQ_OK : sync_engine(e);      // the caller's flag array is free again on return
+}
+
+// the side of a device batch the compare kernel reads, or an error: not a device batch, not a whole one, records out of range
+static int fixed_side(const kbbq_reads *b, uint64_t first, uint64_t n, const char *which, FixedSide *out) {
+    if (!b || !b->on_device) return fail(KBBQ_EINVAL, "%s: not a device batch", which);
+    if (!b->bases || !b->nmask) return fail(KBBQ_EINVAL, "%s: batch without bases or nmask", which);
+    if (!b->offsets && b->read_len == 0) return fail(KBBQ_EINVAL, "%s: batch has neither offsets nor read_len", which);
+    if (!b->offsets && b->n_bases != b->n_reads * (uint64_t)b->read_len) return fail(KBBQ_EINVAL, "%s: uniform batch: n_bases != n_reads * read_len", which);
+    if (first > b->n_reads || n > b->n_reads - first)
+        return fail(KBBQ_EINVAL, "%s: records %llu..+%llu leave a batch of %llu", which, (unsigned long long)first, (unsigned long long)n, (unsigned long long)b->n_reads);
+    out->bases = b->bases; out->nmask = b->nmask; out->offcase = b->offcase;
+    out->offsets = b->offsets;
+    out->read_len = b->read_len;
+    out->n_bases = b->n_bases;
+    return KBBQ_OK;
+}
+
+int kbbq_fixed_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_read, const kbbq_reads *fixed, uint64_t fixed_first_read,
+                            uint64_t n_reads, uint64_t *errors) {
+    ENGINE_DEVICE(e);
+    if (!errors) return fail(KBBQ_EINVAL, "null argument");
+    FixedSide a, f;
+    int rc;
+    if ((rc = fixed_side(reads, first_read, n_reads, "reads", &a)) || (rc = fixed_side(fixed, fixed_first_read, n_reads, "fixed", &f))) return rc;
+    if (!n_reads) return KBBQ_OK;
+    // One lane per word of the whole batch: where the range lies in a ragged batch is in its offsets, on the device, and the
+    // call only queues work; the lanes of words outside the range leave at once.
+    const uint64_t words = reads->n_bases / 64 + 1, blocks = (words + 255) / 256;
+    if (!reads->n_bases) return KBBQ_OK;
+    if (blocks > 0x7FFFFFFFULL) return fail(KBBQ_ERANGE, "a batch of %llu bases", (unsigned long long)reads->n_bases);
+    Timed t(e, "k_fixed_errors");
+    hipLaunchKernelGGL(k_fixed_errors, dim3((unsigned)blocks), dim3(256), 0, e->stream, a, first_read, f, fixed_first_read, n_reads, errors);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
 }
 
 void *kbbq_covariates_device(kbbq_engine *e, uint64_t *n_words) {

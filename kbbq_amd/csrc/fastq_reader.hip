@@ -42,6 +42,7 @@ struct kbbq_fastq_reader : FastqCounts {
         bool short_form = false;
     };
     bool packed_is_exact = false;              // the current chunk's batch gives its sequence text back (set by batch())
+    bool batch_built = false;                  // batch() ran for the current chunk: packed_is_exact is known
     const uint64_t *att_bases = nullptr, *att_nmask = nullptr, *att_offcase = nullptr;      // kbbq_fastq_reader_attach
     std::vector<Kept> kept;
     // the short form's arrays are carved from slabs of 2 GB (four hipMalloc per chunk were four trips to the driver)
@@ -143,6 +144,7 @@ void stash_current(kbbq_fastq_reader *r) {
     r->kept.push_back(k);
     r->have_chunk = false;
     r->packed_is_exact = false;
+    r->batch_built = false;
 }
 
 // a new stream begins (create / rewind)
@@ -329,6 +331,7 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     r->selected = -1;
     r->have_chunk = false;
     r->packed_is_exact = false;
+    r->batch_built = false;
     int rc;
     if (r->container == kbbq_fastq_reader::C_UNKNOWN && !detect_container(r, file_bytes, n_bytes, last != 0)) return KBBQ_OK;      // (consumed 0)
     // ---- the text: the carried bytes, then what this call's bytes hold
@@ -527,6 +530,7 @@ int kbbq_fastq_reader_batch(kbbq_fastq_reader *r, kbbq_reads *dev) {
     }
     arrays.release();
     r->packed_is_exact = counts[1] == 0;
+    r->batch_built = true;
     dev->bases = (const uint64_t *)b;
     dev->nmask = (const uint64_t *)m;
     dev->qual = (const uint8_t *)q;
@@ -535,6 +539,13 @@ int kbbq_fastq_reader_batch(kbbq_fastq_reader *r, kbbq_reads *dev) {
     dev->rg = nullptr;
     dev->read_len = uniform ? r->longest : 0;
     dev->offcase = (const uint64_t *)oc;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_batch_exact(kbbq_fastq_reader *r, int32_t *exact) {
+    if (!r || !exact) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || r->selected >= 0 || !r->batch_built) return fail(KBBQ_ESTATE, "no batch was built for the current chunk");
+    *exact = r->packed_is_exact ? 1 : 0;
     return KBBQ_OK;
 }
 

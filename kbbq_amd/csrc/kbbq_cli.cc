@@ -23,6 +23,12 @@
 //     reader, cut into the pieces of a file of the same bytes, and must fit in GPU memory with its text; whatever needs
 //     the input twice (KBBQ_RESIDENT=0, the host parsers, --fixed) is refused for it with one line.  "-" with a regular
 //     file on standard input is that file;
+//   * --fixed on FASTQ reads both files on the GPU (tally_fixed_on_device): the corrected file goes through a second device
+//     reader, its packed batches are compared with the resident ones by a kernel, record by record, and the tally runs from
+//     the error bits that leaves in HBM.  The reference compares the two files' characters on the host (kbbq.cc:371-375);
+//     the packed comparison is the same one while both files hold nothing but ACGTN / acgt, and anything else -- IUPAC
+//     codes, read groups in the names, records that are not four lines -- hands the run back to the host loop
+//     (tally_fixed), which stays the definition and is all a BAM input gets;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -100,6 +106,9 @@ struct CliOptions {
     // The input is not a regular file -- a pipe on standard input, a FIFO, /dev/stdin on a pipe: it is read once, front to
     // back, by the device reader (main(): StreamInput), and whatever would read it a second time is refused.
     bool stream = false, fixed_stream = false;
+    // --fixed may read both of its files on the GPU: FASTQ, and none of the switches below that ask for the host parsers
+    // (main() decides once the format is known, and clears it when the run is handed back to the host loop)
+    bool fixed_on_device = false;
     int out_threads = 1;      // --threads, or "pick" (parse())
     int io_threads = 1;       // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
     bool is_bam = false;      // what sniff() found
@@ -130,11 +139,12 @@ struct CliOptions {
     bool inflate_on_device() const { return !host_deflate && device_inflate; }
     // The device reader (DeviceFastqInput) may be tried: it makes resident batches of the input
     bool may_read_on_device(bool resident_on) const {
-        return !fixed_mode() && !host_io() && resident_on && device_reader && !serial_parse;
+        return (!fixed_mode() || fixed_on_device) && !host_io() && resident_on && device_reader && !serial_parse;
     }
+    bool fixed_may_read_on_device() const { return fixed_mode() && !is_bam && !host_io() && resident && device_reader && !serial_parse; }
     // What was asked for that reads the input more than once, which a stream does not allow; null: nothing
     const char *needs_a_file() const {
-        if (fixed_mode()) return "--fixed reads both of its files with the host parsers";
+        if (fixed_mode()) return "--fixed reads two files side by side and starts over with the host parsers, which read both again, when the GPU readers hand one back";
         if (!resident) return "KBBQ_RESIDENT=0 reads it again in every pass";
         if (!device_reader) return "KBBQ_DEVICE_READER=0 leaves it to the host parsers, which read it again for the output";
         if (serial_parse) return "KBBQ_SERIAL_PARSE=1 leaves it to the host parsers, which read it again for the output";
@@ -1276,7 +1286,7 @@ struct Resident {
         keep_recs = true;
         bytes = rec_bytes = 0;
         uint64_t free_b = 0, total_b = 0;
-        if (!o.resident || o.fixed_mode() || kbbq_device_memory(-1, &free_b, &total_b) < 0) on = false;
+        if (!o.resident || (o.fixed_mode() && !o.fixed_on_device) || kbbq_device_memory(-1, &free_b, &total_b) < 0) on = false;
         budget = (uint64_t)(0.6 * (double)free_b);
         rec_budget = o.host_cache_budget();
         if (!on || !rec_budget) keep_recs = false;
@@ -1424,6 +1434,16 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceFastqInp
         }
         if (!resident.add(need, [&](kbbq_reads *d) { return in.batch(d); })) { in.refusal = does_not_fit(); ok = false; break; }
         in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
+        if (o.fixed_mode() && in.reader) {
+            // --fixed compares the packed batches (kbbq_fixed_errors_batch), which is the comparison of the text only while the
+            // text holds nothing but ACGTN / acgt: any other character leaves the run to the host loop
+            int32_t exact = 0;
+            if (kbbq_fastq_reader_batch_exact(in.reader, &exact) < 0 || !exact) {
+                in.refusal = DeviceFastqInput::needs_host_parsers("--fixed on reads with characters other than ACGTN");
+                ok = false;
+                break;
+            }
+        }
         s.seqlen += info.n_bases;
         s.n_reads += info.n_records;
         s.longest = std::max<size_t>(s.longest, info.longest);
@@ -1800,6 +1820,83 @@ static int tally_fixed(kbbq_engine *e, const CliOptions &o, ScanState &s, Batch 
     return batch.fatal || fb.fatal ? 1 : 0;
 }
 
+// What the device form of --fixed did, for the timing report
+struct FixedOnDevice {
+    bool used = false;
+    const char *container = "";
+    uint64_t chunks = 0, records = 0, batches = 0, calls = 0, straddled = 0;
+    double ms_inflate = 0, ms_index = 0, ms_compare = 0;
+};
+
+// --fixed with both files on the GPU.  The first file's reads are resident (device_scan); the corrected file goes through a
+// device reader of its own, chunk by chunk, and nothing of it stays: every chunk's batch is compared with the resident
+// batch or batches whose records it faces -- the two files are cut where their own bytes say, so the pairing goes by the
+// running record ordinal and a chunk may end one resident batch and begin the next (one kbbq_fixed_errors_batch call per
+// overlap, into that batch's zeroed hint array, which no pass uses in this mode) -- and freed.  Only when the corrected file
+// has ended cleanly are the resident batches tallied, in order, with their error bits (consume_read, kbbq.cc:376): until
+// then the engine has counted nothing and the host loop can still take the whole run over.
+// The corrected file ends first: the batch with the last paired read is tallied up to that read, later ones not at all
+// (the reference stops consuming there).  The first file ends first: the rest of the corrected file is not read.
+// 0: tallied; 1: the message is on stderr; -1: handed back -- the corrected file cannot be opened here, a chunk of it has a
+// shape the device reader does not take or a character other than ACGTN / acgt -- and tally_fixed() does it all.
+static int tally_fixed_on_device(kbbq_engine *e, const CliOptions &o, ScanState &s, FixedOnDevice &rep) {
+    std::vector<kbbq_reads> &main = s.resident.dev;
+    // the second file is opened in the FIRST file's format (kbbq.cc:370 passes is_bam): as FASTQ, whatever it holds
+    DeviceFastqInput fin(o);
+    if (!fin.open(o.fixed_path, nullptr)) return -1;
+    size_t bi = 0;          // the resident batch the next record of the corrected file faces
+    uint64_t done = 0;      // records of it that have their partners
+    for (;;) {
+        kbbq_fastq_chunk info;
+        const int got = bi < main.size() ? fin.next_chunk(info) : 0;
+        if (got == 0) break;
+        if (got < 0 || info.flags) return -1;
+        ++rep.chunks;
+        if (!info.n_records) continue;
+        kbbq_reads fb;
+        int32_t exact = 0;
+        if (fin.batch(&fb) < 0) return -1;
+        const bool usable = kbbq_fastq_reader_batch_exact(fin.reader, &exact) == 0 && exact;
+        uint64_t at = 0, calls = 0;
+        int rc = 0;
+        while (usable && rc == 0 && at < fb.n_reads && bi < main.size()) {
+            const uint64_t take = std::min<uint64_t>(main[bi].n_reads - done, fb.n_reads - at);
+            rc = kbbq_fixed_errors_batch(e, &main[bi], done, &fb, at, take, main[bi].hint_sampled);
+            ++calls;
+            at += take;
+            done += take;
+            if (done == main[bi].n_reads) { ++bi; done = 0; }
+        }
+        rep.records += at;
+        rep.calls += calls;
+        if (calls > 1) ++rep.straddled;
+        if (kbbq_reads_free(e, &fb) < 0 || rc < 0) return fail_engine("comparing with the fixed file");      // (waits for the compare kernels)
+        if (!usable) return -1;
+    }
+    fin.kernel_ms(rep.ms_inflate, rep.ms_index);
+    rep.container = fin.container;
+    rep.batches = main.size();
+    fin.close();
+    for (size_t i = 0; i < main.size() && (i < bi || done); ++i) {
+        kbbq_reads b = main[i];
+        b.hint_sampled = b.hint_trusted = nullptr;
+        if (i == bi) {      // the corrected file ended inside this batch
+            b.n_reads = done;
+            if (kbbq_reads_offset(e, &main[i], done, &b.n_bases) < 0) return fail_engine("tally");
+            done = 0;
+        }
+        if (kbbq_tally_batch(e, &b, main[i].hint_sampled) < 0) return fail_engine("tally");
+    }
+    if (o.timing) {
+        kbbq_profile_entry prof[64];
+        int32_t n = 0;
+        if (kbbq_engine_sync(e) == 0 && kbbq_profile_get(e, prof, 64, &n) == 0)
+            for (int32_t i = 0; i < n && i < 64; ++i) if (!strcmp(prof[i].name, "k_fixed_errors")) rep.ms_compare = prof[i].total_ms;
+    }
+    rep.used = true;
+    return 0;
+}
+
 // BamFile::recalibrate, htsiter.cc:11-33: the OQ tag takes the old qualities, the record the new ones (reversed for a
 // reverse-strand read).  false: the tag could not be updated (std::invalid_argument("Unable to update OQ tag.") in the reference).
 static bool rewrite_bam_record(BamRecord &b, const uint8_t *q, bool set_oq, std::string &scratch) {
@@ -2128,7 +2225,12 @@ static int write_serial(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink 
 }
 
 // KBBQ_TIMING=1: what the device reader and the device writer did
-static void report_io_timing(DeviceFastqInput &in, const Sink &w) {
+static void report_io_timing(DeviceFastqInput &in, const Sink &w, const FixedOnDevice &fixed) {
+    if (fixed.used)
+        std::cerr << "[timing] --fixed: both files read on the GPU (the fixed file: " << fixed.container << ", " << fixed.chunks << " chunks, " << fixed.records
+                  << " records paired with " << fixed.batches << " resident batches in " << fixed.calls << " compare calls; " << fixed.straddled
+                  << " chunks straddled a batch boundary; kernels of the fixed file: inflate " << fixed.ms_inflate << " ms, index + pack " << fixed.ms_index
+                  << " ms; compare " << fixed.ms_compare << " ms)" << std::endl;
     if (in.active) {
         double inf = 0, idx = 0;
         in.kernel_ms(inf, idx);
@@ -2159,6 +2261,7 @@ int main(int argc, char *argv[]) {
     if (fmt == Format::unknown) return give_up(" Error opening file " + opt.filename);
     if (fmt == Format::cram) return give_up(" Error: CRAM input needs htslib, which this build does not have; use BAM or FASTQ.");
     opt.is_bam = fmt == Format::bam;
+    opt.fixed_on_device = opt.fixed_may_read_on_device();
     if (opt.stream || opt.fixed_stream) {
         if (const char *why = opt.needs_a_file())
             return give_up(std::string(" Error: input from a pipe is read once, and ") + why + ": write the input to a file first.");
@@ -2172,20 +2275,25 @@ int main(int argc, char *argv[]) {
     EngineOwner engine;
     ScanState scan;
     Batch batch;
+    FixedOnDevice fixed_report;
     scan.resident.init(opt);
     const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, stream.get(), dev_in, scan);
     if (!read_on_device && stream) {
         // no host parsers behind a stream; without a reason the stream held no read at all, and nothing is left to read
         if (!scan.resident.on) return give_up(" Error: input from a pipe is read once, and the reads cannot stay in GPU memory: write the input to a file first.");
         if (!dev_in.refusal.empty()) return give_up(dev_in.refusal);
-    } else if (!read_on_device && host_scan(opt, scan, batch)) {
-        return 1;
+    } else if (!read_on_device) {
+        if (opt.fixed_on_device) {      // --fixed with the host parsers: nothing resident (tally_fixed)
+            opt.fixed_on_device = false;
+            scan.resident.init(opt);
+        }
+        if (host_scan(opt, scan, batch)) return 1;
     }
     if (scan.longest > KBBQ_MAX_READ_LEN)
         return give_up(" Error: reads longer than " + std::to_string(KBBQ_MAX_READ_LEN) + " bases are not supported by the GPU engine.");
     clock.mark("scan+pack+upload");
     const Resident &resident = scan.resident;
-    if (resident.on)
+    if (resident.on && !opt.fixed_mode())      // (--fixed: its lines are the host loop's, which the run may yet be handed back to)
         std::cerr << put_now << " Reads are resident on the GPU: " << resident.dev.size() << " batches"
                   << (resident.keep_recs ? ", their records in host memory." : ".") << std::endl;
 
@@ -2208,8 +2316,27 @@ int main(int argc, char *argv[]) {
     } else {
         std::cerr << put_now << " Using fixed file to find errors." << std::endl;
         p.alpha = 0.5; p.seed = 1; p.approx_kmers = 1000;   // the filters are not used in this mode
+        if (read_on_device && opt.timing) p.flags |= KBBQ_F_PROFILE;      // (the compare kernel's time, for the report)
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
-        if (tally_fixed(e, opt, scan, batch)) return 1;
+        const int on_device = read_on_device ? tally_fixed_on_device(e, opt, scan, fixed_report) : -1;
+        if (on_device > 0) return 1;
+        if (on_device < 0 && read_on_device) {
+            // Handed back: the run starts over as it would have without the device readers -- nothing resident, the scan by the
+            // host parsers, a new engine for what that scan found (the first one has tallied nothing).
+            engine.release();
+            dev_in.close();
+            dev_in.active = false;
+            opt.fixed_on_device = false;
+            scan.reset(opt);
+            if (host_scan(opt, scan, batch)) return 1;
+            if (scan.longest > KBBQ_MAX_READ_LEN)
+                return give_up(" Error: reads longer than " + std::to_string(KBBQ_MAX_READ_LEN) + " bases are not supported by the GPU engine.");
+            p = engine_params(opt, scan);
+            p.alpha = 0.5; p.seed = 1; p.approx_kmers = 1000;
+            if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
+        }
+        if (on_device < 0 && tally_fixed(e, opt, scan, batch)) return 1;
+        if (on_device == 0) clock.mark("fixed: read + compare + tally");
     }
     if (!trained && train_model(e, nullptr, true, clock, fail_engine)) return 1;
 
@@ -2227,7 +2354,7 @@ int main(int argc, char *argv[]) {
     else rc = write_serial(e, scan, opt, sink, batch);
     if (rc || !sink.close()) return 1;
     clock.mark("pass4+format+deflate+write");
-    if (clock.on) report_io_timing(dev_in, sink);
+    if (clock.on) report_io_timing(dev_in, sink, fixed_report);
     // Everything is written and flushed.  Handing 200 GB of device memory back allocation by allocation takes 2.2 s at
     // BASELINE size (every hipFree waits for the device); the process ends here and the driver takes it all back at once
     // -- behind the device reader, whose I/O thread and streams must not be alive beside the runtime's own teardown (its

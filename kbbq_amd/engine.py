@@ -240,6 +240,13 @@ class Engine:
         error_words = np.ascontiguousarray(error_words, dtype=np.uint64)
         _lib.check(self.L.kbbq_tally_batch(self.h, self._c(batch), error_words.ctypes.data))
 
+    def fixed_errors(self, batch, first_read, fixed, fixed_first_read, n_reads, errors_device_ptr):
+        """--fixed on the device: OR the bits of the bases of reads first_read.. of `batch` that differ from reads
+        fixed_first_read.. of `fixed` (two DeviceReads) into a device bit array in the layout of nmask
+        (n_bases/64+2 words, zeroed by the caller).  Queued on the engine's stream."""
+        _lib.check(self.L.kbbq_fixed_errors_batch(self.h, self._c(batch), first_read, self._c(fixed), fixed_first_read, n_reads,
+                                                  errors_device_ptr))
+
     def covariates(self):
         R, C = self.n_rg, self.max_read_len
         out = dict(R=R, C=C, rg=np.zeros((R, 2), np.uint64), q=np.zeros((R, NQ, 2), np.uint64),
