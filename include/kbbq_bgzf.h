@@ -201,11 +201,52 @@ int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev);
 int kbbq_bam_reader_write(kbbq_bam_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, int32_t set_oq, void *after_stream);
 int kbbq_bam_reader_kernel_ms(kbbq_bam_reader *r, double *inflate_ms, double *index_ms);
 
+/* ---- the input side: SAM text read on the device ------------------------------------------------------------------------
+ * The reference's main() refuses SAM (kbbq.cc:181-190); this tool takes it, defined by its BAM twin: the passes see of a line
+ * what they see of the BAM record sam_parse1 makes of it, the output is the input's text with QUAL (and OQ:Z) changed
+ * (csrc/sam_io.h is the definition on the host).  The ABI has the shape of kbbq_bam_reader's; the containers, the carry of a
+ * line cut by a chunk's end and the newline index are kbbq_fastq_reader's: BGZF, any other gzip stream and uncompressed text,
+ * in pieces of any size.  The caller parses the header itself -- the leading lines that start with '@' -- and says how long
+ * it is; the device indexes every line behind it (eleven TAB-separated fields, FLAG as a decimal number, the first RG and OQ
+ * fields among the tags, RG looked up in the header's @RG ids), decodes SEQ through htslib's character -> 4-bit table and
+ * bam_seq_str's rule (case is lost, IUPAC codes stay on the forward strand and are N on the reverse strand, anything else
+ * is N; reverse-strand records reverse-complemented with their qualities reversed), takes the qualities from QUAL - 33 or,
+ * with use_oq, from the OQ value, and pass 4 writes every line again with the new qualities + 33 in QUAL and, with set_oq,
+ * the stored QUAL text as the value of the first OQ:Z field (or "\tOQ:Z:<qual>" appended).  The batch equals, array for
+ * array, what kbbq_bam_reader_batch returns for the twin BAM.  Shapes this path does not take are reported in flags and left
+ * to the host reader:
+ *   bit 0  SEQ or QUAL "*", QUAL and SEQ of different lengths, fewer than eleven fields, a FLAG that is no decimal number,
+ *          a carriage return, a tag field shorter than "XX:T:" or of no SAM type, no RG field of type Z or H or one the header
+ *          has no @RG line for; with use_oq a missing OQ field, one of another type, or one whose value is not as long as SEQ
+ *   bit 2  the text ended without a final newline
+ *   bit 3  some line's OQ field is not of type Z: the caller must not use kbbq_sam_reader_write with set_oq on this file
+ * What is kept for pass 4 (kbbq_sam_reader_keep) is the whole inflated text of every chunk with records, with its index. */
+typedef struct kbbq_sam_reader kbbq_sam_reader;
+typedef struct kbbq_fastq_chunk kbbq_sam_chunk;      /* same fields; flags as above */
+/* header_bytes: size of the header in the inflated text (it may span several chunks); rg_ids: the ID fields of its @RG lines. */
+int kbbq_sam_reader_create(int32_t device, int32_t use_oq, uint64_t header_bytes, const char *const *rg_ids, uint32_t n_rg_ids, kbbq_sam_reader **out);
+void kbbq_sam_reader_destroy(kbbq_sam_reader *r);
+int kbbq_sam_reader_rewind(kbbq_sam_reader *r);
+int kbbq_sam_reader_keep(kbbq_sam_reader *r, int32_t on);
+int kbbq_sam_reader_kept(kbbq_sam_reader *r, uint64_t *n_chunks, uint64_t *n_bytes);
+int kbbq_sam_reader_select(kbbq_sam_reader *r, uint64_t i, kbbq_sam_chunk *info);
+int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, int32_t last, kbbq_sam_chunk *info);
+int kbbq_sam_reader_preload(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint64_t front_room);   /* as kbbq_fastq_reader_preload */
+/* The read groups met so far in dense-index order: table_index[d] = index into rg_ids of the group with dense index d. */
+int kbbq_sam_reader_read_groups(kbbq_sam_reader *r, uint32_t *table_index, uint32_t capacity, uint32_t *n);
+/* The current chunk's records as a device batch (arrays owned by the library: kbbq_reads_free), rg = dense indices. */
+int kbbq_sam_reader_batch(kbbq_sam_reader *r, kbbq_reads *dev);
+/* Pass 4: the current (or selected) chunk's lines with d_qual (device: the batch's new qualities in the batch's base order)
+ * in their QUAL fields, submitted to writer z (kbbq_bgzf_collect returns the blocks).  after_stream as in kbbq_bgzf_submit. */
+int kbbq_sam_reader_write(kbbq_sam_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, int32_t set_oq, void *after_stream);
+int kbbq_sam_reader_kernel_ms(kbbq_sam_reader *r, double *inflate_ms, double *index_ms);
+
 /* ---- test and bench data as files: reads [first_read, first_read + n) of the synthetic data set (kbbq_synth_params: the
  * generator bench.py measures on) formatted on the device and submitted to z like any payload.  format 0: four-line FASTQ,
  * names "r%010llu"; 1: unaligned BAM records with RG:Z:grp0, about half of them reverse-flagged (stored reverse-complemented,
  * qualities reversed); 2: the same with the true qualities in OQ:Z and 11s in the quality field (BASELINE configs[3]:
- * --use-oq).  Every record has the same size.  The caller writes the BAM header itself.  `kbbq --io-test synth-fastq|synth-bam`. */
+ * --use-oq); 3 and 4: the records of 1 and 2 as SAM lines, whose BAM twins those are (FLAG "04" or "20").  Every record has the
+ * same size.  The caller writes the BAM or SAM header itself.  `kbbq --io-test synth-fastq|synth-bam|synth-sam`. */
 int kbbq_bgzf_submit_synth(kbbq_bgzf *z, kbbq_engine *e, const kbbq_synth_params *sp, uint64_t first_read, uint64_t n, int32_t format,
                            uint64_t *payload_bytes);
 

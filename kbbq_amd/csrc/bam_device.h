@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rg_table.h"
+
 namespace kbbq {
 namespace dfl {
 
@@ -76,16 +78,8 @@ struct BamIndex {
     uint64_t *out_sz;       // pass 4: bytes of the rewritten record with its block_size field, then scanned
 };
 
-struct BamRgTable {
-    const uint8_t *ids;         // the ids back to back
-    const uint32_t *id_off;     // n_ids + 1 offsets
-    uint32_t n_ids;
-    // more than a handful of @RG lines (merged cohorts carry hundreds): an open-addressing table over the ids' FNV-1a
-    // hashes, so that a record compares its RG value with one or two ids instead of all of them
-    const uint16_t *hash_slots; // hash_mask + 1 entries: id index, 0xFFFF = empty
-    uint32_t hash_mask;         // 0: no table (few ids: compared one by one)
-};
-__host__ __device__ __forceinline__ uint32_t bam_fnv1a(uint32_t h, uint8_t c) { return (h ^ c) * 16777619u; }
+// the header's @RG table and its hash step are rg_table.h's, shared with the SAM reader
+using BamRgTable = RgTable;
 
 // unaligned little-endian loads from the stream (the buffer is readable 4 KB behind its end)
 __device__ __forceinline__ uint32_t bam_ld32(const uint8_t *t, uint64_t p) {
@@ -330,29 +324,11 @@ __global__ void __launch_bounds__(256) k_bam_records(const uint8_t *text, uint64
         fl |= BAMF_FALLBACK;
     } else {
         const uint64_t v = rg_at + 1;
-        auto same_as = [&](uint32_t i) -> bool {
-            const uint32_t o = T.id_off[i], len = T.id_off[i + 1] - o;
-            bool same = v + len < end && text[v + len] == 0;      // (the value's NUL lies inside the record)
-            for (uint32_t j = 0; j < len && same; ++j) same = text[v + j] == T.ids[o + j];
-            return same;
-        };
-        if (T.hash_mask) {
-            uint32_t h = 2166136261u;
-            for (uint64_t j = v; j < end && text[j]; ++j) h = bam_fnv1a(h, text[j]);
-            for (uint32_t probe = 0; probe <= T.hash_mask && rg == 0xFFFF; ++probe) {
-                const uint32_t i = T.hash_slots[(h + probe) & T.hash_mask];
-                if (i == 0xFFFF) break;
-                if (same_as(i)) rg = i;
-            }
-        } else {
-            for (uint32_t i = 0; i < T.n_ids && rg == 0xFFFF; ++i)
-                if (same_as(i)) rg = i;
-        }
+        uint32_t len = 0;
+        while (v + len < end && text[v + len]) ++len;      // (the value's NUL lies inside the record: the walk got past it)
+        rg = rg_lookup(T, text + v, len);
         if (rg == 0xFFFF) fl |= BAMF_FALLBACK;      // a read group without an @RG line: the host path's dictionary handles it
-        // first appearance: a look first -- after the first wavefronts of a chunk nearly every record finds a smaller
-        // ordinal there already (with an atomic per record, 2.5e6 of them on one address were 25 of the kernel's 28 ms)
-        else if (__hip_atomic_load(&first_seen[rg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (unsigned long long)r)
-            atomicMin(&first_seen[rg], (unsigned long long)r);
+        else rg_note_first(first_seen, rg, r);
     }
     // OQ (readutils.cc:16-31; htsiter.cc:13-26)
     uint32_t oq_vlen = 0;

@@ -8,21 +8,8 @@ namespace kbbq {
 
 // ------------------------------------------------------------------ record ----
 void BamRecord::sequence(std::string &out) const {
-    static const char letters[] = "=ACMGRSVTWYHKDBN";                      // seq_nt16_str
-    static const int8_t two_bit[16] = {4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4};   // seq_nt16_int
-    const uint32_t n = l_seq();
     const uint8_t *s = data.data() + seq_at();
-    out.resize(n);
-    const bool rev = reverse();
-    for (uint32_t i = 0; i < n; ++i) {
-        const int code = (s[i >> 1] >> ((~i & 1) << 2)) & 15;              // bam_seqi
-        if (!rev) {
-            out[i] = letters[code];
-        } else {
-            const int b = two_bit[code];
-            out[n - 1 - i] = b < 4 ? "TGCA"[b] : 'N';                       // readutils.hh:35-36, then the reversal
-        }
-    }
+    sequence_from_codes(l_seq(), reverse(), [s](uint32_t i) { return (s[i >> 1] >> ((~i & 1) << 2)) & 15; /* bam_seqi */ }, out);
 }
 
 // length of the value that starts with the type byte at s (skip_aux of htslib), or 0 if it does not fit

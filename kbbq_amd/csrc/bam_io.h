@@ -31,6 +31,25 @@ struct BamHeader {
     }
 };
 
+// bam_seq_str (readutils.hh:30-42) over n 4-bit base codes, code_at(i) in stored order: bases in sequencing orientation; on
+// reverse-strand records every code that is not A/C/G/T comes out as 'N', on forward ones as its "=ACMGRSVTWYHKDBN" letter.
+// The one statement of that rule on the host: a BAM record's packed nibbles and a SAM line's characters (sam_io.h) both
+// come through here.
+template <class CodeAt> inline void sequence_from_codes(uint32_t n, bool rev, CodeAt code_at, std::string &out) {
+    static const char letters[] = "=ACMGRSVTWYHKDBN";                      // seq_nt16_str
+    static const int8_t two_bit[16] = {4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4};   // seq_nt16_int
+    out.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const int code = code_at(i) & 15;
+        if (!rev) {
+            out[i] = letters[code];
+        } else {
+            const int b = two_bit[code];
+            out[n - 1 - i] = b < 4 ? "TGCA"[b] : 'N';                       // readutils.hh:35-36, then the reversal
+        }
+    }
+}
+
 enum { BAM_AUX_OK = 0, BAM_AUX_MISSING = 1, BAM_AUX_CORRUPT = 2 };   // errno ENOENT / EINVAL of bam_aux_get
 
 struct BamRecord {

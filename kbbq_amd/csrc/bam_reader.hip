@@ -2,6 +2,7 @@
 // bam_device.h's kernels (MI355X, gfx950).  The BGZF walk, the inflate launch, the scan, the text packing and the hand-over
 // to the writer are io_common.h's.
 #include "io_common.h"
+#include "rg_table.h"
 
 #include "bam_device.h"
 
@@ -22,13 +23,8 @@ struct kbbq_bam_reader {
     Buf seg_u32, seg_slots, seg_counts;     // BamSegs
     Buf idx_u32, idx_u16, idx_u64;          // BamIndex
     Buf d_out;                              // small device words: [0..1] chain flags, [4..6] record flags / longest / shortest
-    Buf rg_ids, rg_off, rg_hash, first_seen, dense;  // the header's @RG table (+ hash slots), first appearance per chunk, table index -> dense index
-    uint32_t rg_hash_mask = 0;
+    RgGroups groups;                        // the header's @RG table and the dense numbering of the groups met (rg_table.h)
     Buf seq_text, counter;                  // scratch of kbbq_bam_reader_batch
-    std::vector<uint8_t> h_ids;
-    std::vector<uint32_t> h_id_off;
-    std::vector<int32_t> dense_of;          // table index -> dense read-group index (first appearance, readutils.cc:53-57), -1: not met
-    std::vector<uint32_t> order;            // dense index -> table index
     uint64_t carry_bytes = 0;
     // the current chunk
     uint64_t text_bytes = 0, n_records = 0, n_bases = 0, idx_cap = 0;
@@ -147,38 +143,21 @@ int bam_index_stream(kbbq_bam_reader *r, uint64_t text, uint64_t skip, int32_t l
             }
             const BamIndex X = bam_index(r);
             hipLaunchKernelGGL(k_bam_rec_offsets, dim3(n_segs), dim3(256), 0, r->st, G, (const uint64_t *)counts, (uint32_t)bias, X.rec_off);
-            BamRgTable T;
-            T.ids = (const uint8_t *)r->rg_ids.p; T.id_off = (const uint32_t *)r->rg_off.p; T.n_ids = (uint32_t)r->dense_of.size();
-            T.hash_slots = (const uint16_t *)r->rg_hash.p; T.hash_mask = r->rg_hash_mask;
-            hipLaunchKernelGGL(k_bam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, t, n_rec, r->use_oq, T, X, out + 4,
-                               (unsigned long long *)r->first_seen.p);
+            hipLaunchKernelGGL(k_bam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, t, n_rec, r->use_oq, r->groups.table(), X, out + 4,
+                               (unsigned long long *)r->groups.first_seen.p);
             HIP_TRY(hipGetLastError());
             if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
             HIP_TRY(hipMemcpyAsync(hs + 32, X.base_sz + n_rec, 8, hipMemcpyDeviceToHost, r->st));
             HIP_TRY(hipMemcpyAsync(hs + 36, out + 4, 12, hipMemcpyDeviceToHost, r->st));
-            const size_t n_ids = r->dense_of.size();
-            std::vector<unsigned long long> seen(n_ids);
-            if (assign_groups && n_ids) HIP_TRY(hipMemcpyAsync(seen.data(), r->first_seen.p, n_ids * 8, hipMemcpyDeviceToHost, r->st));
+            std::vector<unsigned long long> seen;
+            if (assign_groups && (rc = r->groups.read_seen(r->st, seen))) return rc;
             HIP_TRY(hipStreamSynchronize(r->st));
             r->n_records = n_rec;
             r->n_bases = *(const uint64_t *)(hs + 32);
             info->flags |= hs[36];
             r->longest = hs[37];
             r->shortest = hs[38];
-            if (assign_groups && n_ids) {
-                // read groups in the order their first records appear (rg_to_int[rg] = rg_to_int.size(), readutils.cc:53-57)
-                std::vector<std::pair<unsigned long long, uint32_t>> fresh;
-                for (size_t i = 0; i < n_ids; ++i)
-                    if (seen[i] != ~0ull && r->dense_of[i] < 0) fresh.emplace_back(seen[i], (uint32_t)i);
-                std::sort(fresh.begin(), fresh.end());
-                for (auto &f : fresh) { r->dense_of[f.second] = (int32_t)r->order.size(); r->order.push_back(f.second); }
-                if (!fresh.empty()) {
-                    std::vector<uint16_t> dn(n_ids);
-                    for (size_t i = 0; i < n_ids; ++i) dn[i] = (uint16_t)(r->dense_of[i] < 0 ? 0 : r->dense_of[i]);
-                    HIP_TRY(hipMemcpy(r->dense.p, dn.data(), n_ids * 2, hipMemcpyHostToDevice));
-                }
-                HIP_TRY(hipMemsetAsync(r->first_seen.p, 0xFF, n_ids * 8, r->st));
-            }
+            if (assign_groups && (rc = r->groups.assign(r->st, seen))) return rc;
         }
     }
     HIP_TRY(hipEventRecord(r->t2, r->st));
@@ -213,9 +192,9 @@ void kbbq_bam_reader_destroy(kbbq_bam_reader *r) {
     KbbqDeviceGuard guard(r->device);
     if (r->st) (void)hipStreamSynchronize(r->st);
     Buf *all[] = {&r->comp, &r->text, &r->h_small, &r->carry, &r->tile_sums, &r->seg_u32, &r->seg_slots,
-                  &r->seg_counts, &r->idx_u32, &r->idx_u16, &r->idx_u64, &r->d_out, &r->rg_ids, &r->rg_off, &r->rg_hash, &r->first_seen, &r->dense, &r->seq_text,
-                  &r->counter};
+                  &r->seg_counts, &r->idx_u32, &r->idx_u16, &r->idx_u64, &r->d_out, &r->seq_text, &r->counter};
     for (Buf *b : all) b->release();
+    r->groups.release();
     r->inf.release();
     r->pre.release();
     bam_release_kept(r);
@@ -239,50 +218,11 @@ int kbbq_bam_reader_create(int32_t device, int32_t use_oq, int32_t n_ref, uint64
     r->n_ref = n_ref;
     r->header_bytes = r->header_left = header_bytes;
     r->h_small.host = true;
-    r->h_id_off.push_back(0);
-    for (uint32_t i = 0; i < n_rg_ids; ++i) {
-        const char *s = rg_ids[i] ? rg_ids[i] : "";
-        r->h_ids.insert(r->h_ids.end(), s, s + strlen(s));
-        r->h_id_off.push_back((uint32_t)r->h_ids.size());
-    }
-    r->dense_of.assign(n_rg_ids, -1);
     hipError_t he = hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipEventCreate(&r->t0);
     if (he == hipSuccess) he = hipEventCreate(&r->t1);
     if (he == hipSuccess) he = hipEventCreate(&r->t2);
-    if (he == hipSuccess) {
-        if (!(rc = r->rg_ids.reserve(r->h_ids.size() + 64)) && !(rc = r->rg_off.reserve(r->h_id_off.size() * 4 + 64)) &&
-            !(rc = r->first_seen.reserve((size_t)n_rg_ids * 8 + 64)) && !(rc = r->dense.reserve((size_t)n_rg_ids * 2 + 64))) {
-            if (!r->h_ids.empty()) he = hipMemcpy(r->rg_ids.p, r->h_ids.data(), r->h_ids.size(), hipMemcpyHostToDevice);
-            if (he == hipSuccess) he = hipMemcpy(r->rg_off.p, r->h_id_off.data(), r->h_id_off.size() * 4, hipMemcpyHostToDevice);
-            if (he == hipSuccess) he = hipMemset(r->first_seen.p, 0xFF, (size_t)n_rg_ids * 8 + 64);
-            if (he == hipSuccess) he = hipMemset(r->dense.p, 0, (size_t)n_rg_ids * 2 + 64);
-        }
-        if (he == hipSuccess && !rc && n_rg_ids > 8) {
-            // open addressing over the ids' hashes, at most half full (an id listed twice keeps its first index: the first wins
-            // a linear comparison as well)
-            uint32_t size = 16;
-            while (size < 2 * n_rg_ids) size *= 2;
-            std::vector<uint16_t> slots(size, 0xFFFF);
-            for (uint32_t i = 0; i < n_rg_ids; ++i) {
-                uint32_t h = 2166136261u;
-                for (uint32_t j = r->h_id_off[i]; j < r->h_id_off[i + 1]; ++j) h = bam_fnv1a(h, r->h_ids[j]);
-                uint32_t at = h & (size - 1);
-                bool dup = false;
-                while (slots[at] != 0xFFFF) {
-                    const uint32_t o = slots[at];
-                    const uint32_t la = r->h_id_off[o + 1] - r->h_id_off[o], lb = r->h_id_off[i + 1] - r->h_id_off[i];
-                    if (la == lb && !memcmp(&r->h_ids[r->h_id_off[o]], &r->h_ids[r->h_id_off[i]], la)) { dup = true; break; }
-                    at = (at + 1) & (size - 1);
-                }
-                if (!dup) slots[at] = (uint16_t)i;
-            }
-            if (!(rc = r->rg_hash.reserve((size_t)size * 2 + 64))) {
-                he = hipMemcpy(r->rg_hash.p, slots.data(), (size_t)size * 2, hipMemcpyHostToDevice);
-                r->rg_hash_mask = size - 1;
-            }
-        }
-    }
+    if (he == hipSuccess) rc = r->groups.create(rg_ids, n_rg_ids);
     if (he != hipSuccess || rc) {
         kbbq_bam_reader_destroy(r);
         return rc ? rc : fail(KBBQ_EIO, "creating the BAM reader: %s", hipGetErrorString(he));
@@ -324,8 +264,8 @@ int kbbq_bam_reader_kept(kbbq_bam_reader *r, uint64_t *n_chunks, uint64_t *n_byt
 
 int kbbq_bam_reader_read_groups(kbbq_bam_reader *r, uint32_t *table_index, uint32_t capacity, uint32_t *n) {
     if (!r || !n) return fail(KBBQ_EINVAL, "null argument");
-    *n = (uint32_t)r->order.size();
-    for (uint32_t i = 0; i < *n && i < capacity && table_index; ++i) table_index[i] = r->order[i];
+    *n = (uint32_t)r->groups.order.size();
+    for (uint32_t i = 0; i < *n && i < capacity && table_index; ++i) table_index[i] = r->groups.order[i];
     return KBBQ_OK;
 }
 
@@ -448,7 +388,7 @@ int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev) {
     HIP_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
     hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
                        (const uint64_t *)X.base_sz, n, r->use_oq, (uint8_t *)r->seq_text.p, (uint8_t *)q);
-    hipLaunchKernelGGL(k_bam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->dense.p, (uint8_t *)fl,
+    hipLaunchKernelGGL(k_bam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->groups.dense.p, (uint8_t *)fl,
                        (uint16_t *)rg);
     HIP_TRY(hipGetLastError());
     // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch and the counts are not read)

@@ -1,9 +1,9 @@
 // fastq_reader.hip -- the host side of kbbq_fastq_reader (include/kbbq_bgzf.h): a FASTQ file -- BGZF, plain gzip or text --
 // read on the device (MI355X, gfx950).  A chunk call reads top to bottom as: detect the container, obtain the text (BGZF
 // blocks through io_common.h's walk and inflate, a gzip stream through gzip_stream.h, or the bytes themselves), index the
-// lines, index the records (fastq_device.h), carry over what the chunk's end cut.
-#include "gzip_stream.h"
-#include "io_common.h"
+// lines -- all of that text_chunks.h's, which the SAM reader shares -- index the records (fastq_device.h), carry over what
+// the chunk's end cut.
+#include "text_chunks.h"
 
 #include "fastq_device.h"
 
@@ -17,21 +17,10 @@ struct FastqCounts {
     uint32_t longest = 0, shortest = 0;
 };
 
-struct kbbq_fastq_reader : FastqCounts {
-    Preload pre;
-    int device = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
-    Buf comp, text;                         // compressed chunk, inflated text (carry first)
-    Inflater inf;
-    Buf tile_counts, tile_sums, nl_pos;     // newline index
+struct kbbq_fastq_reader : FastqCounts, TextChunks {      // (the stream, the text, the newline index, the carry: TextChunks)
     Buf idx_u32, idx_second, base_sz, text_sz, flags;      // record index (FastqIndex)
-    Buf carry;                              // text of the record the previous chunk's end cut (device)
-    Buf h_small;                            // page-locked scratch for small read-backs
     Buf seq_text, counter;                  // scratch of kbbq_fastq_reader_batch (the chunk's sequence lines back to back)
-    uint64_t carry_bytes = 0;
     bool have_chunk = false;
-    double ms_inflate = 0, ms_index = 0;
     // chunks of the first scan that stay in device memory (kbbq_fastq_reader_keep): their text and record index
     // Two forms: the whole text with its record index, or -- when the chunk's batch was built and its sequence lines hold
     // nothing but ACGTN / acgt, so that the packed batch gives them back exactly -- only names and comments (a seventh of the
@@ -51,10 +40,6 @@ struct kbbq_fastq_reader : FastqCounts {
     bool keeping = false;
     int64_t selected = -1;      // the kept chunk that is the current one (pass 4), or -1: the live buffers
     uint64_t kept_bytes = 0;
-    // The container, decided by the first bytes after create / rewind: BGZF blocks, another gzip stream, or the text itself
-    enum { C_UNKNOWN, C_BGZF, C_GZIP, C_TEXT } container = C_UNKNOWN;
-    bool take_text = false;                 // kbbq_fastq_reader_take_text
-    GzStream gz;                            // the state of a gzip stream between chunk calls
 };
 
 namespace {
@@ -147,83 +132,14 @@ void stash_current(kbbq_fastq_reader *r) {
     r->batch_built = false;
 }
 
-// a new stream begins (create / rewind)
-void new_stream(kbbq_fastq_reader *r) {
-    r->container = kbbq_fastq_reader::C_UNKNOWN;
-    r->gz.reset();
-}
-
 // while chunks are kept, a buffer that no longer fits gives up the kept ones: pass 4 then inflates the file again
-int reserve_or_drop_kept(kbbq_fastq_reader *r, Buf &b, size_t need) {
-    return reserve_or_drop(b, need, [r] {
-        if (!r->keeping && r->kept.empty()) return false;
-        release_kept(r);
-        r->keeping = false;
-        return true;
-    });
+bool drop_kept(kbbq_fastq_reader *r) {
+    if (!r->keeping && r->kept.empty()) return false;
+    release_kept(r);
+    r->keeping = false;
+    return true;
 }
-
-// The container from the first bytes of a stream: 1 decided, 0 more bytes are needed
-int detect_container(kbbq_fastq_reader *r, const uint8_t *p, uint64_t n, bool last) {
-    using R = kbbq_fastq_reader;
-    if (n >= 1 && p[0] == '@') { r->container = r->take_text ? R::C_TEXT : R::C_BGZF; return 1; }
-    if (n >= 1 && p[0] != 0x1f) { r->container = R::C_BGZF; return 1; }      // (the BGZF path flags it)
-    if (n < 12) { if (!last) return 0; r->container = R::C_BGZF; return 1; }
-    if (p[1] != 0x8b || p[2] != 8) { r->container = R::C_BGZF; return 1; }
-    if (!(p[3] & 4)) { r->container = R::C_GZIP; return 1; }
-    const uint32_t xlen = p[10] | (p[11] << 8);
-    if (12 + (uint64_t)xlen > n) { if (!last) return 0; r->container = R::C_GZIP; return 1; }
-    r->container = bc_block_size(p + 12, xlen) ? R::C_BGZF : R::C_GZIP;
-    return 1;
-}
-
-// The text of a chunk call, two ways.  Both put it behind the carried bytes in r->text (queued on r->st, t0 recorded), set
-// *text to the total and fill info->consumed / n_blocks; info->flags bit 0: not this path's input, nothing was queued.
-
-// plain gzip (gzip_stream.h) or the text itself: every byte is taken, the reader keeps what it cannot decode yet
-int text_from_stream(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, bool last, kbbq_fastq_chunk *info, uint64_t *text) {
-    int rc;
-    HIP_TRY(hipEventRecord(r->t0, r->st));
-    (void)r->pre.take(file_bytes, n_bytes, r->st);      // (a piece copied ahead is not used: the stream's state comes first)
-    uint64_t produced = n_bytes;
-    const void *from = nullptr;      // (null: the caller's bytes)
-    if (r->container == kbbq_fastq_reader::C_GZIP) {
-        if ((rc = gz_decode(r->gz, r->st, r->device, file_bytes, n_bytes, last, false, &produced, &info->flags, &info->n_blocks))) return rc;
-        info->n_redecoded = (uint32_t)r->gz.redecoded;
-        from = r->gz.output();
-    }
-    info->consumed = n_bytes;
-    const uint64_t carried = r->carry_bytes;
-    if (carried + produced > TEXT_CAP) info->flags |= 1;
-    if (info->flags & 1) return KBBQ_OK;
-    if ((rc = reserve_or_drop_kept(r, r->text, carried + produced + 4096))) return rc;
-    if ((rc = r->h_small.reserve(4096))) return rc;
-    if (carried) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, carried, hipMemcpyDeviceToDevice, r->st));
-    if (produced) HIP_TRY(hipMemcpyAsync((char *)r->text.p + carried, from ? from : file_bytes, produced, from ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, r->st));
-    *text = carried + produced;
-    return KBBQ_OK;
-}
-
-// BGZF: the whole blocks at the front of the bytes, inflated; *nb blocks wait for inflate_check
-int text_from_bgzf(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, bool last, kbbq_fastq_chunk *info, uint64_t *text, uint32_t *nb) {
-    BlockTable T;
-    const WalkEnd end = walk_blocks(file_bytes, n_bytes, r->carry_bytes, TEXT_CAP, T);
-    info->consumed = T.consumed;
-    info->n_blocks = T.n_blocks();
-    if (end.why != WALK_END) { info->flags |= 1; return KBBQ_OK; }      // not BGZF: the blocks in front of it are left to the caller too
-    if (T.consumed == 0 && n_bytes && !last && !T.n_blocks()) return fail(KBBQ_EINVAL, "the chunk holds no complete BGZF block");
-    int rc;
-    void *d_comp = nullptr;
-    if ((rc = stage_compressed(r->pre, r->comp, file_bytes, n_bytes, T.consumed, r->st, [](Buf &b, size_t need) { return b.reserve(need); }, &d_comp))) return rc;
-    if ((rc = reserve_or_drop_kept(r, r->text, T.text + 4096))) return rc;
-    if ((rc = r->h_small.reserve(4096))) return rc;
-    if (r->carry_bytes) HIP_TRY(hipMemcpyAsync(r->text.p, r->carry.p, r->carry_bytes, hipMemcpyDeviceToDevice, r->st));
-    // (t0 behind the uploads: ms_inflate is the kernel alone, the compressed bytes' way to the device is not in its time)
-    if ((rc = inflate_queue(r->inf, r->device, r->st, T, d_comp, r->text.p, r->t0))) return rc;
-    *text = T.text;
-    *nb = T.n_blocks();
-    return KBBQ_OK;
-}
+int reserve_or_drop_kept(kbbq_fastq_reader *r, Buf &b, size_t need) { return r->reserve(b, need); }
 
 }  // namespace
 
@@ -236,13 +152,9 @@ int kbbq_fastq_reader_create(int32_t device, kbbq_fastq_reader **out) {
     KbbqDeviceGuard guard(device);
     HIP_TRY(guard.err);
     kbbq_fastq_reader *r = new kbbq_fastq_reader;
-    r->device = device;
-    r->h_small.host = true;
-    hipError_t he = hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipEventCreate(&r->t0);
-    if (he == hipSuccess) he = hipEventCreate(&r->t1);
-    if (he == hipSuccess) he = hipEventCreate(&r->t2);
-    if (he != hipSuccess) {
+    r->drop_kept = [r] { return drop_kept(r); };
+    hipError_t he;
+    if (!r->create(device, &he)) {
         kbbq_fastq_reader_destroy(r);
         return fail(KBBQ_EIO, "creating the reader's stream: %s", hipGetErrorString(he));
     }
@@ -254,16 +166,10 @@ void kbbq_fastq_reader_destroy(kbbq_fastq_reader *r) {
     if (!r) return;
     KbbqDeviceGuard guard(r->device);
     if (r->st) (void)hipStreamSynchronize(r->st);
-    Buf *all[] = {&r->comp, &r->text, &r->tile_counts, &r->tile_sums, &r->nl_pos, &r->idx_u32, &r->idx_second, &r->base_sz, &r->text_sz,
-                  &r->flags, &r->carry, &r->h_small, &r->seq_text, &r->counter};
+    Buf *all[] = {&r->idx_u32, &r->idx_second, &r->base_sz, &r->text_sz, &r->flags, &r->seq_text, &r->counter};
     for (Buf *b : all) b->release();
-    r->inf.release();
-    r->gz.release();
-    r->pre.release();
     release_kept(r);
-    hipEvent_t evs[] = {r->t0, r->t1, r->t2};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    if (r->st) (void)hipStreamDestroy(r->st);
+    r->destroy();
     delete r;
 }
 
@@ -274,9 +180,8 @@ int kbbq_fastq_reader_rewind(kbbq_fastq_reader *r) {
     stash_current(r);
     r->keeping = false;      // what was kept stays; a second scan keeps nothing more
     r->selected = -1;
-    r->carry_bytes = 0;
     r->have_chunk = false;
-    new_stream(r);
+    r->new_stream();
     return KBBQ_OK;
 }
 
@@ -333,38 +238,20 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     r->packed_is_exact = false;
     r->batch_built = false;
     int rc;
-    if (r->container == kbbq_fastq_reader::C_UNKNOWN && !detect_container(r, file_bytes, n_bytes, last != 0)) return KBBQ_OK;      // (consumed 0)
+    if (r->container == kbbq_fastq_reader::C_UNKNOWN && !r->detect_container(file_bytes, n_bytes, last != 0)) return KBBQ_OK;      // (consumed 0)
     // ---- the text: the carried bytes, then what this call's bytes hold
     uint64_t text = 0;
     uint32_t nb = 0;      // BGZF blocks whose status is still to be looked at
-    if (r->container == kbbq_fastq_reader::C_BGZF) rc = text_from_bgzf(r, file_bytes, n_bytes, last != 0, info, &text, &nb);
-    else rc = text_from_stream(r, file_bytes, n_bytes, last != 0, info, &text);
+    rc = r->obtain(file_bytes, n_bytes, last != 0, info, &text, &nb);
     if (rc || (info->flags & 1)) return rc;
-    HIP_TRY(hipMemsetAsync((char *)r->text.p + text, 0, 64, r->st));
-    HIP_TRY(hipEventRecord(r->t1, r->st));
     // ---- lines
-    const uint64_t n_tiles = (text + NL_TILE - 1) / NL_TILE;
     uint64_t n_lines = 0;
-    if (text) {
-        if ((rc = r->tile_counts.reserve((n_tiles + 2) * 8))) return rc;
-        uint64_t *tc = (uint64_t *)r->tile_counts.p;
-        hipLaunchKernelGGL(k_count_newlines, dim3((unsigned)n_tiles), dim3(256), 0, r->st, (const uint8_t *)r->text.p, text, tc);
-        HIP_TRY(hipGetLastError());
-        if ((rc = device_scan(r, tc, n_tiles, tc + n_tiles))) return rc;
-        HIP_TRY(hipMemcpyAsync(r->h_small.p, tc + n_tiles, 8, hipMemcpyDeviceToHost, r->st));
-        HIP_TRY(hipStreamSynchronize(r->st));
-        n_lines = *(const uint64_t *)r->h_small.p;
-        // (and whether every block inflated, read only now: the line count needed the wait anyway)
-        if ((rc = inflate_check(r->inf, r->st, nb, "chunk"))) return rc;
-    }
+    if ((rc = r->count_lines(0, text, nb, &n_lines))) return rc;
     const uint64_t n_rec = n_lines / 4;
     info->text_bytes = text - r->carry_bytes;
     uint64_t rec_end = 0;      // first byte behind the last complete record
     if (n_rec) {
-        if ((rc = r->nl_pos.reserve((n_lines + 4) * 4))) return rc;
-        hipLaunchKernelGGL(k_newline_positions, dim3((unsigned)n_tiles), dim3(256), 0, r->st, (const uint8_t *)r->text.p, text,
-                           (const uint64_t *)r->tile_counts.p, (uint32_t *)r->nl_pos.p, n_lines);
-        HIP_TRY(hipGetLastError());
+        if ((rc = r->line_positions(0, text, n_lines))) return rc;
         // ---- records
         if ((rc = reserve_or_drop_kept(r, r->idx_u32, n_rec * 7 * 4))) return rc;
         if ((rc = r->idx_second.reserve(n_rec))) return rc;
@@ -393,16 +280,8 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
         r->shortest = fl[2];
         rec_end = (uint64_t)(*(const uint32_t *)(hs + 4)) + 1;
     }
-    HIP_TRY(hipEventRecord(r->t2, r->st));
     // ---- what the chunk's end cut: kept for the next chunk
-    const uint64_t left = text - rec_end;
-    if (left) {
-        if (last) info->flags |= 4;      // the file ends inside a record (or without a final newline): the serial reader's case
-        if ((rc = r->carry.reserve(left + 64))) return rc;
-        HIP_TRY(hipMemcpyAsync(r->carry.p, (const char *)r->text.p + rec_end, left, hipMemcpyDeviceToDevice, r->st));
-    }
-    HIP_TRY(hipStreamSynchronize(r->st));
-    r->carry_bytes = left;
+    if ((rc = r->keep_rest(rec_end, text, last != 0, info))) return rc;
     r->text_bytes = text;
     r->n_records = n_rec;
     r->have_chunk = true;
@@ -410,9 +289,6 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     info->n_bases = n_rec ? r->n_bases : 0;
     info->longest = n_rec ? r->longest : 0;
     info->shortest = n_rec ? r->shortest : 0;
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, r->t0, r->t1) == hipSuccess) r->ms_inflate += a;
-    if (hipEventElapsedTime(&b, r->t1, r->t2) == hipSuccess) r->ms_index += b;
     return KBBQ_OK;
 }
 
@@ -425,7 +301,7 @@ int kbbq_fastq_reader_inflate(kbbq_fastq_reader *r, const uint8_t *file_bytes, u
     r->selected = -1;
     r->have_chunk = false;
     *consumed = *produced = 0;
-    if (r->container == kbbq_fastq_reader::C_UNKNOWN && n_bytes && !detect_container(r, file_bytes, n_bytes, false)) return KBBQ_OK;
+    if (r->container == kbbq_fastq_reader::C_UNKNOWN && n_bytes && !r->detect_container(file_bytes, n_bytes, false)) return KBBQ_OK;
     if (r->container == kbbq_fastq_reader::C_TEXT) {      // the bytes are the text
         const uint64_t n = std::min(n_bytes, capacity);
         memcpy(host_out, file_bytes, n);

@@ -1,7 +1,8 @@
 // io_common.h -- what the device I/O objects of include/kbbq_bgzf.h share (internal): growing buffers, pieces of a file
 // copied ahead of their chunk call, the walk over BGZF headers, the inflate launch, the exclusive scan, the packing of
 // sequence text into a batch, and the writer's submissions as far as the readers' write() needs them.  Host code only:
-// the kernels behind these functions live in io_common.hip and bgzf_writer.hip, nowhere else.
+// the kernels behind these functions live in io_common.hip and bgzf_writer.hip, nowhere else.  (text_chunks.h builds a
+// reader's way from file bytes to indexed lines out of them.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -148,6 +149,13 @@ int inflate_check(Inflater &I, hipStream_t st, uint32_t n_blocks, const char *un
 
 // exclusive scan of d[0, n) in place, the total to *d_total (device); tile_sums: the caller's scratch
 int device_scan_on(Buf &tile_sums, hipStream_t st, uint64_t *d, uint64_t n, uint64_t *d_total /* device */);
+
+// ---- where the lines of a text start (lines_device.h) -----------------------------------------------------------------
+// newlines per tile of 16 KB (256 lanes x 64 bytes) of text[0, n), queued on st; then -- behind the scan of the tile counts --
+// their positions, the first `capacity` of them.  text: 16-byte aligned, readable 64 bytes behind n.
+constexpr int NL_TILE = 16384;
+int newline_counts(hipStream_t st, const void *text, uint64_t n, uint64_t *tile_counts);
+int newline_positions(hipStream_t st, const void *text, uint64_t n, const uint64_t *tile_first, uint32_t *nl_pos, uint64_t capacity);
 
 // Sequence text into the engine's layout, queued on st: the 2-bit words, the non-ACGT mask and the off-case words of
 // seq_text[0, n_bases), 16 zero bytes behind each array, the two counts of k_pack_text in d_counts.  Then waits for st;

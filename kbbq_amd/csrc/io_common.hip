@@ -1,10 +1,12 @@
 // io_common.hip -- the host functions of io_common.h that both device readers use, with their kernels (MI355X, gfx950):
-// the BGZF block walk, the inflate launch and its status check, the exclusive scan, the packing of sequence text -- and
+// the BGZF block walk, the inflate launch and its status check, the exclusive scan, the newline index, the packing of
+// sequence text -- and
 // kbbq_reads_upload_text, which is that packing for a host batch.
 #include "io_common.h"
 
 #include "bgzf_inflate.h"
 #include "io_device.h"
+#include "lines_device.h"
 
 using namespace kbbq::dfl;
 
@@ -166,6 +168,22 @@ int device_scan_on(Buf &tile_sums, hipStream_t st, uint64_t *d, uint64_t n, uint
     hipLaunchKernelGGL(k_dscan_tiles, dim3((unsigned)n_tiles), dim3(256), 0, st, d, n, ts);
     hipLaunchKernelGGL(k_dscan_sums, dim3(1), dim3(1024), 0, st, ts, n_tiles, d_total);
     hipLaunchKernelGGL(k_dscan_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d, n, (const uint64_t *)ts);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int newline_counts(hipStream_t st, const void *text, uint64_t n, uint64_t *tile_counts) {
+    const uint64_t n_tiles = (n + NL_TILE - 1) / NL_TILE;
+    if (!n_tiles) return KBBQ_OK;
+    hipLaunchKernelGGL(k_count_newlines, dim3((unsigned)n_tiles), dim3(256), 0, st, (const uint8_t *)text, n, tile_counts);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int newline_positions(hipStream_t st, const void *text, uint64_t n, const uint64_t *tile_first, uint32_t *nl_pos, uint64_t capacity) {
+    const uint64_t n_tiles = (n + NL_TILE - 1) / NL_TILE;
+    if (!n_tiles) return KBBQ_OK;
+    hipLaunchKernelGGL(k_newline_positions, dim3((unsigned)n_tiles), dim3(256), 0, st, (const uint8_t *)text, n, tile_first, nl_pos, capacity);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }

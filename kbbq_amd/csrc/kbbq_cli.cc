@@ -8,8 +8,15 @@
 // what the reference also computes there (coverage, alpha, thresholds, the delta-Q model -- inside the library).
 //
 // Differences, all deliberate:
-//   * BAM goes through this tool's own codec (bam_io.*) because htslib is not in this image; CRAM and SAM
-//     text are refused (SURVEY risk R1);
+//   * BAM goes through this tool's own codec (bam_io.*) because htslib is not in this image; CRAM is refused
+//     (SURVEY risk R1);
+//   * SAM text is taken -- plain, gzip or BGZF, recognised by its "@HD", "@SQ", "@RG", "@PG" or "@CO" header line -- where the
+//     reference's main() refuses it (kbbq.cc:181-190) although its README promises "SAM/BAM or FASTQ": a widening.  No
+//     reference run defines it, so the BAM twin does (sam_io.h): the passes see of a line what they see of the BAM record
+//     sam_parse1 makes of it, and the output is the input's text with QUAL (and OQ:Z under --set-oq) changed, through BGZF
+//     like every other output.  It is read on the GPU like the other two formats (DeviceFastqInput::open_sam; from a pipe
+//     as well); the shapes that reader hands back, and every run that asks for the host parsers, go through the serial
+//     host reader (there is no block-parallel host parser for SAM);
 //   * one extra read-only scan of the input sizes the histograms (read groups, longest read) before
 //     the engine is created; the reference grows its tables on the fly;
 //   * the sampler seed can be fixed with KBBQ_SEED=<u32> (the reference always draws it from time+pid,
@@ -64,6 +71,7 @@
 #include "fastq_io.h"
 #include "host_model.h"
 #include "piece_reader.h"
+#include "sam_io.h"
 
 using namespace kbbq;
 
@@ -84,7 +92,7 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"genomelen", required_argument, 0, 'g'}, {"coverage", required_argument, 0, 'c'}, {"fixed", required_argument, 0, 'f'},
     {"alpha", required_argument, 0, 'a'},     {"threads", required_argument, 0, 't'},  {0, 0, 0, 0}};
 
-enum class Format { fastq, bam, cram, unknown };
+enum class Format { fastq, bam, sam, cram, unknown };
 
 // The value of an environment switch (what getenv returned): a number, or "set to this text"
 static long long env_num(const char *s, long long unset) { return s ? strtoll(s, nullptr, 10) : unset; }
@@ -112,6 +120,7 @@ struct CliOptions {
     int out_threads = 1;      // --threads, or "pick" (parse())
     int io_threads = 1;       // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
     bool is_bam = false;      // what sniff() found
+    bool is_sam = false;      // SAM text: the serial host reader (sam_io.h), whichever container it comes in
     bool timing = getenv("KBBQ_TIMING") != nullptr;                          // set to anything: wall-clock per phase on stderr at the end
     int write_threads = (int)env_num(getenv("KBBQ_WRITE_THREADS"), 4);       // threads writing ranges of a regular output file; 1: sequential always
     bool preload = env_num(getenv("KBBQ_PRELOAD"), 1) != 0;                  // =0: a piece of the device reader is not copied ahead of its chunk call
@@ -134,6 +143,7 @@ struct CliOptions {
     bool release = env_num(getenv("KBBQ_RELEASE"), 0) != 0;                  // =1: everything is freed in order at the end, no exit(0)
 
     bool fixed_mode() const { return !fixedinput.empty(); }
+    Format format() const { return is_bam ? Format::bam : is_sam ? Format::sam : Format::fastq; }
     bool host_io() const { return host_deflate; }
     // BGZF input that the host parsers read (BAM always) is inflated on the GPU as well
     bool inflate_on_device() const { return !host_deflate && device_inflate; }
@@ -141,7 +151,7 @@ struct CliOptions {
     bool may_read_on_device(bool resident_on) const {
         return (!fixed_mode() || fixed_on_device) && !host_io() && resident_on && device_reader && !serial_parse;
     }
-    bool fixed_may_read_on_device() const { return fixed_mode() && !is_bam && !host_io() && resident && device_reader && !serial_parse; }
+    bool fixed_may_read_on_device() const { return fixed_mode() && !is_bam && !is_sam && !host_io() && resident && device_reader && !serial_parse; }
     // What was asked for that reads the input more than once, which a stream does not allow; null: nothing
     const char *needs_a_file() const {
         if (fixed_mode()) return "--fixed reads two files side by side and starts over with the host parsers, which read both again, when the GPU readers hand one back";
@@ -233,6 +243,7 @@ static Format sniff(const std::string &path) {   // hts_detect_format, as far as
     unsigned char b[4] = {0, 0, 0, 0};
     const int n = gzread(f, b, 4);
     gzclose(f);
+    if (n >= 4 && looks_like_sam(b, 4)) return Format::sam;      // (before FASTQ's '@': "@HD" and a TAB is no read name)
     if (n >= 4 && b[0] == 'B' && b[1] == 'A' && b[2] == 'M' && b[3] == 1) return Format::bam;
     if (n >= 4 && b[0] == 'C' && b[1] == 'R' && b[2] == 'A' && b[3] == 'M') return Format::cram;
     if (n >= 1 && b[0] == '@') return Format::fastq;
@@ -297,6 +308,7 @@ struct Item {
     bool second = false;
     FastqRecord fq;
     BamRecord bam;
+    SamRecord sam;
 };
 
 enum { SRC_FATAL = -100 };        // an error the reference throws on; the message is already on stderr
@@ -352,6 +364,27 @@ private:
     bool use_oq_;
 };
 
+class SamSource : public Source {     // what BamSource is for the BAM twin of the text (sam_io.h)
+public:
+    SamSource(const std::string &path, bool use_oq, int threads) : in_(path, threads), use_oq_(use_oq) {}
+    bool ok() const override { return in_.ok(); }
+    const BamHeader &header() const { return in_.header(); }
+    int next(Item &it) override {
+        const int rc = in_.next(it.sam);
+        if (rc < 0) return rc;
+        std::string err;
+        if (!decode_sam_read(it.sam, use_oq_, it.seq, it.qual, it.rg, it.second, err)) {
+            std::cerr << err << std::flush;
+            return SRC_FATAL;
+        }
+        return rc;
+    }
+
+private:
+    SamReader in_;
+    bool use_oq_;
+};
+
 // KBBQ_TIMING=1: wall-clock per phase on stderr at the end ("[timing] scan 12.3 s ..."): where an end-to-end run goes
 struct PhaseClock {
     std::vector<std::pair<std::string, double>> phases;
@@ -377,6 +410,7 @@ struct PhaseClock {
 
 static std::unique_ptr<Source> open_source(const CliOptions &o, const std::string &path) {   // open_file, kbbq.cc:55-64
     if (o.is_bam) return std::unique_ptr<Source>(new BamSource(path, o.use_oq, o.io_threads));
+    if (o.is_sam) return std::unique_ptr<Source>(new SamSource(path, o.use_oq, o.io_threads));
     return std::unique_ptr<Source>(new FastqSource(path, o.io_threads));
 }
 
@@ -733,6 +767,9 @@ public:
     // in pass 4, the records rewritten around the new qualities are kernels (sam_read1, the BAM
     // constructor of CReadData and BamFile::recalibrate / write, htsiter.cc:5-45, readutils.cc:13-61)
     kbbq_bam_reader *bam = nullptr;
+    // SAM mode (open_sam): the chunks go to a kbbq_sam_reader -- the FASTQ reader's way to the lines of the text, then the
+    // BAM reader's fields of every line, and in pass 4 the lines written again around the new qualities (sam_io.h is the definition)
+    kbbq_sam_reader *sam = nullptr;
     bool oq_unwritable = false;               // some record's OQ tag bam_aux_update_str could not update (--set-oq: host path)
     double wait_s = 0, device_s = 0, batch_s = 0;
     const char *container = "BGZF";           // what the file is: BGZF, gzip (other gzip streams) or text
@@ -745,6 +782,14 @@ public:
         std::vector<const char *> ids;
         for (auto &id : rg_ids) ids.push_back(id.c_str());
         if (kbbq_bam_reader_create(0, use_oq ? 1 : 0, n_ref, header_bytes, ids.data(), (uint32_t)ids.size(), &bam) < 0) return false;
+        start_pass();
+        return true;
+    }
+    bool open_sam(const std::string &path, StreamInput *stream, bool use_oq, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
+        if (!open_file(path, stream, false)) return false;
+        std::vector<const char *> ids;
+        for (auto &id : rg_ids) ids.push_back(id.c_str());
+        if (kbbq_sam_reader_create(0, use_oq ? 1 : 0, header_bytes, ids.data(), (uint32_t)ids.size(), &sam) < 0) return false;
         start_pass();
         return true;
     }
@@ -792,6 +837,8 @@ public:
         reader = nullptr;
         if (bam) kbbq_bam_reader_destroy(bam);
         bam = nullptr;
+        if (sam) kbbq_sam_reader_destroy(sam);
+        sam = nullptr;
     }
     void close() {
         stop();
@@ -814,6 +861,7 @@ public:
         if (bgzf_ && preload_)
             ahead = [this](uint8_t *piece, uint64_t n) {
                 if (bam) (void)kbbq_bam_reader_preload(bam, piece, n, kFront);
+                else if (sam) (void)kbbq_sam_reader_preload(sam, piece, n, kFront);
                 else if (reader) (void)kbbq_fastq_reader_preload(reader, piece, n, kFront);
             };
         pieces_.start(src_, buf_[0] + kFront, buf_[1] + kFront, ahead);
@@ -831,15 +879,18 @@ public:
         uint8_t *data = piece.data - left_;
         if (left_) memcpy(data, carry_, left_);
         const auto t1 = std::chrono::steady_clock::now();
-        if ((bam ? kbbq_bam_reader_chunk(bam, data, left_ + n, last, &info) : kbbq_fastq_reader_chunk(reader, data, left_ + n, last, &info)) < 0) return -1;
+        if ((bam ? kbbq_bam_reader_chunk(bam, data, left_ + n, last, &info) : sam ? kbbq_sam_reader_chunk(sam, data, left_ + n, last, &info)
+                                                                            : kbbq_fastq_reader_chunk(reader, data, left_ + n, last, &info)) < 0) return -1;
         device_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-        if (bam && (info.flags & 8)) oq_unwritable = true;
+        if ((bam || sam) && (info.flags & 8)) oq_unwritable = true;
+        if (sam) info.flags &= ~2u;      // (bit 1 is the FASTQ reader's alone)
         const uint64_t rest = left_ + n - info.consumed;
         // (a read name that is too short included: the host path reports it)
         if (info.flags & 2) refusal = " Error: a read name is shorter than 2 characters before the first '_'.";
         else if (info.flags & 4) refusal = needs_host_parsers("an input that ends inside a record");
         else if (info.flags & 1)
             refusal = needs_host_parsers(bam ? "a BAM record the device reader hands back (no usable RG tag, no @RG line for it, or malformed)"
+                                         : sam ? "a SAM line the device reader hands back (SEQ or QUAL '*', no usable RG field, no @RG line for it, carriage returns, or malformed)"
                                              : "FASTQ the device reader hands back (multi-line records, RG: fields in read names, carriage returns, empty reads)");
         else if (rest > kFront || (rest && last)) refusal = needs_host_parsers("a compressed block that does not end");      // not a file this path reads
         if (!refusal.empty()) return -2;
@@ -853,21 +904,35 @@ public:
         return " Error: input from a pipe is read once, and " + what + " is left to the host parsers, which read it again: write the input to a file first.";
     }
     // The calls both readers have, whichever this one holds (include/kbbq_bgzf.h)
-    const char *format() const { return bam ? "BAM" : "FASTQ"; }
-    int keep(bool on) { return bam ? kbbq_bam_reader_keep(bam, on ? 1 : 0) : kbbq_fastq_reader_keep(reader, on ? 1 : 0); }
-    int kept(uint64_t *n_chunks, uint64_t *n_bytes) { return bam ? kbbq_bam_reader_kept(bam, n_chunks, n_bytes) : kbbq_fastq_reader_kept(reader, n_chunks, n_bytes); }
-    int batch(kbbq_reads *dev) { return bam ? kbbq_bam_reader_batch(bam, dev) : kbbq_fastq_reader_batch(reader, dev); }
-    int rewind() { return bam ? kbbq_bam_reader_rewind(bam) : kbbq_fastq_reader_rewind(reader); }
+    const char *format() const { return bam ? "BAM" : sam ? "SAM" : "FASTQ"; }
+    int keep(bool on) { return bam ? kbbq_bam_reader_keep(bam, on ? 1 : 0) : sam ? kbbq_sam_reader_keep(sam, on ? 1 : 0) : kbbq_fastq_reader_keep(reader, on ? 1 : 0); }
+    int kept(uint64_t *n_chunks, uint64_t *n_bytes) {
+        return bam ? kbbq_bam_reader_kept(bam, n_chunks, n_bytes) : sam ? kbbq_sam_reader_kept(sam, n_chunks, n_bytes) : kbbq_fastq_reader_kept(reader, n_chunks, n_bytes);
+    }
+    int batch(kbbq_reads *dev) { return bam ? kbbq_bam_reader_batch(bam, dev) : sam ? kbbq_sam_reader_batch(sam, dev) : kbbq_fastq_reader_batch(reader, dev); }
+    int rewind() { return bam ? kbbq_bam_reader_rewind(bam) : sam ? kbbq_sam_reader_rewind(sam) : kbbq_fastq_reader_rewind(reader); }
     // chunk i of the kept ones becomes the current chunk again (BAM: inflated and indexed again from the compressed bytes)
-    int select(uint64_t i, kbbq_fastq_chunk *info) { return bam ? kbbq_bam_reader_select(bam, i, info) : kbbq_fastq_reader_select(reader, i, info); }
-    // the kept text of the current chunk goes with this resident batch (FASTQ only: the BAM reader has no such call)
-    int attach(const kbbq_reads *batch) { return bam ? 0 : kbbq_fastq_reader_attach(reader, batch); }
-    void kernel_ms(double &inflate, double &index) { inflate = index = 0; if (bam) kbbq_bam_reader_kernel_ms(bam, &inflate, &index); else kbbq_fastq_reader_kernel_ms(reader, &inflate, &index); }
+    int select(uint64_t i, kbbq_fastq_chunk *info) {
+        return bam ? kbbq_bam_reader_select(bam, i, info) : sam ? kbbq_sam_reader_select(sam, i, info) : kbbq_fastq_reader_select(reader, i, info);
+    }
+    // the kept text of the current chunk goes with this resident batch (FASTQ only: the other readers have no such call)
+    int attach(const kbbq_reads *batch) { return bam || sam ? 0 : kbbq_fastq_reader_attach(reader, batch); }
+    // the read groups met, in dense-index order, as indices into the header's @RG ids (BAM and SAM)
+    int read_groups(uint32_t *table_index, uint32_t capacity, uint32_t *n) {
+        return bam ? kbbq_bam_reader_read_groups(bam, table_index, capacity, n) : kbbq_sam_reader_read_groups(sam, table_index, capacity, n);
+    }
+    void kernel_ms(double &inflate, double &index) {
+        inflate = index = 0;
+        if (bam) kbbq_bam_reader_kernel_ms(bam, &inflate, &index);
+        else if (sam) kbbq_sam_reader_kernel_ms(sam, &inflate, &index);
+        else kbbq_fastq_reader_kernel_ms(reader, &inflate, &index);
+    }
     // The current chunk with new qualities to the writer, text assembled from the device's own copy of the input
     // (kbbq_fastq_reader_write; kbbq_bam_reader_write: BamFile::recalibrate + write of every record on the device)
     bool write_chunk(DeviceBgzfWriter &out, const uint8_t *d_qual, bool set_oq, void *after_stream) {
         return out.submit([&](kbbq_bgzf *z) {
-            return bam ? kbbq_bam_reader_write(bam, z, d_qual, set_oq ? 1 : 0, after_stream) : kbbq_fastq_reader_write(reader, z, d_qual, after_stream);
+            return bam ? kbbq_bam_reader_write(bam, z, d_qual, set_oq ? 1 : 0, after_stream)
+                 : sam ? kbbq_sam_reader_write(sam, z, d_qual, set_oq ? 1 : 0, after_stream) : kbbq_fastq_reader_write(reader, z, d_qual, after_stream);
         });
     }
 
@@ -892,7 +957,7 @@ private:
 // the BAM alignment blocks.
 struct RecordStore {
     std::string blob;
-    std::vector<uint32_t> lens;     // FASTQ: name, comment, sequence length per record; BAM: block length
+    std::vector<uint32_t> lens;     // FASTQ: name, comment, sequence length per record; BAM: block length; SAM: line length
     size_t bytes() const { return blob.capacity() + lens.capacity() * 4; }
     void add(const FastqRecord &r) {
         blob += r.name; blob += r.comment; blob += r.seq;
@@ -902,12 +967,17 @@ struct RecordStore {
         blob.append((const char *)r.data.data(), r.data.size());
         lens.push_back((uint32_t)r.data.size());
     }
+    void add(const SamRecord &r) {
+        blob += r.line;
+        lens.push_back((uint32_t)r.line.size());
+    }
 };
 
 // One batch of reads in the engine's layout, plus the records themselves for the output pass.
 struct Batch {
     std::vector<FastqRecord> fq_recs;
     std::vector<BamRecord> bam_recs;
+    std::vector<SamRecord> sam_recs;
     std::vector<uint8_t> seq, qual, flags;
     std::vector<uint16_t> rg;
     std::vector<uint64_t> off, bases, nmask, offcase;
@@ -920,8 +990,8 @@ struct Batch {
     Item it;
 
     // returns false when no read was collected
-    bool fill(Source &in, ReadGroups &groups, size_t max_reads, bool keep_records, bool is_bam = false) {
-        fq_recs.clear(); bam_recs.clear(); seq.clear(); qual.clear(); flags.clear(); rg.clear();
+    bool fill(Source &in, ReadGroups &groups, size_t max_reads, bool keep_records, Format fmt = Format::fastq) {
+        fq_recs.clear(); bam_recs.clear(); sam_recs.clear(); seq.clear(); qual.clear(); flags.clear(); rg.clear();
         off.assign(1, 0);
         saw_empty = false;
         longest = 0;
@@ -939,7 +1009,9 @@ struct Batch {
             flags.push_back(it.second ? 1 : 0);
             rg.push_back((uint16_t)groups.index_of(it.rg));
             if (keep_records) {
-                if (is_bam) bam_recs.push_back(it.bam); else fq_recs.push_back(it.fq);
+                if (fmt == Format::bam) bam_recs.push_back(it.bam);
+                else if (fmt == Format::sam) sam_recs.push_back(it.sam);
+                else fq_recs.push_back(it.fq);
             }
         }
         return finish();
@@ -1154,6 +1226,46 @@ static int io_test(int argc, char *argv[], const CliOptions &o) {
         printf("#end %d\n", rc);
         return 0;
     }
+    if (what == "format" && argc > 3) {     // what sniff() makes of a file: --io-test format FILE
+        const char *names[] = {"fastq", "bam", "sam", "cram", "unknown"};
+        printf("%s\n", names[(int)sniff(argv[3])]);
+        return 0;
+    }
+    if (what == "sam" && argc > 3) {     // what the passes see of SAM text, in the lines of "bam": --io-test sam FILE [use-oq]
+        SamSource in(argv[3], argc > 4 && std::string(argv[4]) == "use-oq", io_threads);
+        if (!in.ok()) return 2;
+        printf("#text %zu genome %llu refs %zu\n", in.header().text.size(), (unsigned long long)in.header().genome_length(), in.header().refs.size());
+        Item it;
+        ReadGroups groups;
+        int rc;
+        while ((rc = in.next(it)) >= 0) {
+            std::string q(it.qual.size(), ' ');
+            for (size_t i = 0; i < q.size(); ++i) q[i] = (char)(it.qual[i] + 33);
+            printf("%s\t%d\t%s\t%d\t%d\t%s\t%s\n", it.sam.name().c_str(), (int)it.sam.flag, it.rg.c_str(), groups.index_of(it.rg), (int)it.second,
+                   it.seq.c_str(), q.c_str());
+        }
+        printf("#end %d\n", rc);
+        return 0;
+    }
+    if (what == "samcopy" && argc > 3) { // reader -> (OQ update) -> writer, the qualities as they are: --io-test samcopy FILE [set-oq]
+        SamReader in(argv[3], io_threads);
+        if (!in.ok()) return 2;
+        const bool set_oq = argc > 4 && std::string(argv[4]) == "set-oq";
+        BgzfWriter out(stdout);
+        if (!out.write(in.header().text.data(), in.header().text.size())) return 1;
+        SamRecord r;
+        std::string line;
+        std::vector<uint8_t> qual;
+        while (in.next(r) >= 0) {
+            // the stored qualities in sequencing orientation, which is what pass 4 hands the writer
+            qual.assign(r.l_seq, 0);
+            for (uint32_t i = 0; i < r.l_seq; ++i) qual[i] = r.qual_star ? 0xFF : (uint8_t)(r.line[r.qual_at + (r.reverse() ? r.l_seq - 1 - i : i)] - 33);
+            line.clear();
+            if (!rewrite_sam_record(r, qual.data(), set_oq, line)) return 3;
+            if (!out.write(line.data(), line.size())) return 1;
+        }
+        return out.close() ? 0 : 1;
+    }
     if (what == "bam-fast" && argc > 3) {     // the same lines from the block-parallel BAM parser: --io-test bam-fast FILE [use-oq] [threads]
         BamChunkParser in(argv[3], argc > 4 && std::string(argv[4]) == "use-oq", std::max(2, io_threads), argc > 5 ? atoi(argv[5]) : 4, true);
         if (!in.ok()) return 2;
@@ -1200,12 +1312,13 @@ static int io_test(int argc, char *argv[], const CliOptions &o) {
         }
         return out.close() ? 0 : 1;
     }
-    if ((what == "synth-fastq" || what == "synth-bam") && argc > 4) {
-        // The bench's own reads as a file on stdout: --io-test synth-fastq GENOME_LEN COVERAGE / synth-bam GENOME_LEN COVERAGE [oq]
+    if ((what == "synth-fastq" || what == "synth-bam" || what == "synth-sam") && argc > 4) {
+        // The bench's own reads as a file on stdout: --io-test synth-fastq GENOME_LEN COVERAGE / synth-bam GENOME_LEN COVERAGE [oq] /
+        // synth-sam GENOME_LEN COVERAGE [oq] (the lines whose BAM twins synth-bam writes)
         // (bench.py: seed 12345, 150-base reads, 100 N per million): k_synth -> record text / BAM records -> k_deflate, all on
         // the device.  The command line run on this file must log the bench's insert counts and write the bench's digest.
         const uint64_t G = strtoull(argv[3], nullptr, 10), cov = strtoull(argv[4], nullptr, 10);
-        const bool bam = what == "synth-bam", oq = bam && argc > 5 && std::string(argv[5]) == "oq";
+        const bool bam = what == "synth-bam", sam = what == "synth-sam", oq = (bam || sam) && argc > 5 && std::string(argv[5]) == "oq";
         kbbq_synth_params sp;
         memset(&sp, 0, sizeof sp);
         sp.seed = 12345; sp.genome_len = G; sp.read_len = 150; sp.n_reads = G * cov / 150; sp.n_rg = 1; sp.paired = 0; sp.n_per_million = 100;
@@ -1226,9 +1339,13 @@ static int io_test(int argc, char *argv[], const CliOptions &o) {
             BamWriter w(out);
             if (!w.write_header(h)) return 1;
         }
+        if (sam) {
+            const std::string text = "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:chr1\tLN:" + std::to_string(std::min<uint64_t>(G, 0xFFFFFFFFull)) + "\n@RG\tID:grp0\tSM:synth\n";
+            if (!out.write(text.data(), text.size())) return 1;
+        }
         const uint64_t step = (uint64_t)1 << 22;
         for (uint64_t first = 0; first < sp.n_reads; first += step)
-            if (!out.synth_batch(e, &sp, first, std::min(step, sp.n_reads - first), bam ? (oq ? 2 : 1) : 0)) return 1;
+            if (!out.synth_batch(e, &sp, first, std::min(step, sp.n_reads - first), bam ? (oq ? 2 : 1) : sam ? (oq ? 4 : 3) : 0)) return 1;
         return out.close() ? 0 : 1;
     }
     if (what == "bgzf") {   // stdin -> BGZF on stdout: --io-test bgzf [threads]
@@ -1360,7 +1477,8 @@ static std::vector<std::string> read_group_ids(const std::string &header_text) {
 
 // The first scan on the device.  A FASTQ file -- BGZF, any other gzip stream or uncompressed -- is read on the GPU
 // (DeviceFastqInput): the file's bytes go to the device, which inflates, finds the records and packs them; every chunk of the
-// file is one resident batch.  A BAM file takes the same road (DeviceFastqInput::open_bam; include/kbbq_bgzf.h:
+// file is one resident batch.  SAM text takes the same road in the same three containers (DeviceFastqInput::open_sam;
+// kbbq_sam_reader): its header -- the leading '@' lines -- is parsed here like a BAM file's.  A BAM file takes the same road (DeviceFastqInput::open_bam; include/kbbq_bgzf.h:
 // kbbq_bam_reader): the header is parsed here (its reference lengths are the genome length, kbbq.cc:196-216; its @RG ids are
 // the table the record kernel looks read groups up in), everything behind it on the device.  The inflated text (BAM: the
 // compressed bytes) of every chunk stays in HBM for pass 4 while it fits; otherwise pass 4 reads the file again.
@@ -1388,6 +1506,19 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceFastqInp
             ok = !rg_ids.empty() && rg_ids.size() < 65535;
             if (!ok) in.refusal = DeviceFastqInput::needs_host_parsers("a BAM header without @RG lines (or with 65535 of them)");
             ok = ok && in.open_bam(o.input, stream, o.use_oq, (int32_t)s.bam_header.refs.size(), header_bytes, rg_ids);
+        }
+    } else if (o.is_sam) {
+        // (a stream: from the head, which grows until a line that is no header line is in it)
+        std::unique_ptr<SamReader> head;
+        do head.reset(new SamReader(stream ? stream->head_path : o.input, 1));
+        while ((!head->ok() || !head->header_complete()) && stream && stream->grow_more());
+        ok = head->ok();
+        if (ok) {
+            s.bam_header = head->header();
+            rg_ids = read_group_ids(s.bam_header.text);
+            ok = !rg_ids.empty() && rg_ids.size() < 65535;
+            if (!ok) in.refusal = DeviceFastqInput::needs_host_parsers("a SAM header without @RG lines (or with 65535 of them)");
+            ok = ok && in.open_sam(o.input, stream, o.use_oq, s.bam_header.text.size(), rg_ids);
         }
     } else {
         ok = in.open(o.input, stream);
@@ -1417,7 +1548,7 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceFastqInp
         }
         in.chunk_records.push_back(info.n_records);
         if (!info.n_records) continue;
-        const uint64_t need = Resident::bytes_of(info.n_bases, info.n_records, o.is_bam ? 18 : 16);
+        const uint64_t need = Resident::bytes_of(info.n_bases, info.n_records, o.is_bam || o.is_sam ? 18 : 16);
         if (keeping) {
             uint64_t kept_chunks = 0, kept_bytes = 0;
             if (in.kept(&kept_chunks, &kept_bytes) < 0 || resident.bytes + need + kept_bytes > text_budget) {
@@ -1456,14 +1587,14 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceFastqInp
         in.refusal = DeviceFastqInput::needs_host_parsers("--set-oq on a record whose OQ tag cannot be updated");
         ok = false;
     }
-    if (ok && s.n_reads && o.is_bam) {
+    if (ok && s.n_reads && (o.is_bam || o.is_sam)) {
         // read groups in the order of their first records, as rg_to_int numbers them (readutils.cc:53-57)
         std::vector<uint32_t> order(rg_ids.size());
         uint32_t n_groups = 0;
-        if (kbbq_bam_reader_read_groups(in.bam, order.data(), (uint32_t)order.size(), &n_groups) < 0) ok = false;
+        if (in.read_groups(order.data(), (uint32_t)order.size(), &n_groups) < 0) ok = false;
         for (uint32_t g = 0; ok && g < n_groups; ++g) s.groups.index_of(rg_ids[order[g]]);
     }
-    if (ok && s.n_reads && !o.is_bam) s.groups.index_of(std::string());  // FASTQ without read-group fields: the one read group "" (readutils.cc:98-103)
+    if (ok && s.n_reads && !o.is_bam && !o.is_sam) s.groups.index_of(std::string());  // FASTQ without read-group fields: the one read group "" (readutils.cc:98-103)
     uint64_t kept_chunks = 0;
     if (ok && s.n_reads && in.rewind() == 0 && in.kept(&kept_chunks, &in.kept_bytes) == 0) in.text_kept = kept_chunks == resident.dev.size();
     if (ok && s.n_reads && stream && !in.text_kept) { in.refusal = does_not_fit(); ok = false; }      // (the reader gave its chunks up)
@@ -1506,7 +1637,7 @@ static int host_scan(const CliOptions &o, ScanState &s, Batch &batch) {
     ScopedSet<bool> packed_on_device(batch.pack_on_host, false);      // (the scan's batches only ever go to the device: packed there)
     Resident &resident = s.resident;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const bool fast = attempt == 0 && o.io_threads > 1 && !o.serial_parse;
+        const bool fast = attempt == 0 && o.io_threads > 1 && !o.serial_parse && !o.is_sam;      // (SAM: the serial reader only)
         if (attempt == 1) s.reset(o);
         std::unique_ptr<Source> in;
         Batch::Fast ff;
@@ -1517,12 +1648,13 @@ static int host_scan(const CliOptions &o, ScanState &s, Batch &batch) {
             if (!in->ok()) return give_up(" Error opening file " + o.filename);
         }
         if (!fast && o.is_bam) s.bam_header = static_cast<BamSource *>(in.get())->header();
+        if (o.is_sam) s.bam_header = static_cast<SamSource *>(in.get())->header();
         bool counting = true;    // the coverage pass stops at the first empty read; the other passes do not
         s.scan_fast = fast;
         for (;;) {
             const bool keep = resident.on && resident.keep_recs;
             RecordStore st;
-            if (!(fast ? batch.fill_fast(ff, s.groups, o.batch_reads, keep ? &st : nullptr) : batch.fill(*in, s.groups, o.batch_reads, keep, o.is_bam))) break;
+            if (!(fast ? batch.fill_fast(ff, s.groups, o.batch_reads, keep ? &st : nullptr) : batch.fill(*in, s.groups, o.batch_reads, keep, o.format()))) break;
             for (size_t r = 0; r < batch.c.n_reads && counting; ++r) {
                 const uint64_t l = batch.off[r + 1] - batch.off[r];
                 if (l == 0) counting = false; else s.seqlen += l;
@@ -1537,8 +1669,9 @@ static int host_scan(const CliOptions &o, ScanState &s, Batch &batch) {
             }
             if (resident.on && resident.keep_recs) {
                 if (!fast) {
-                    st.lens.reserve(batch.c.n_reads * (o.is_bam ? 1 : 3));
+                    st.lens.reserve(batch.c.n_reads * (o.is_bam || o.is_sam ? 1 : 3));
                     if (o.is_bam) for (auto &b : batch.bam_recs) st.add(b);
+                    else if (o.is_sam) for (auto &r : batch.sam_recs) st.add(r);
                     else for (auto &f : batch.fq_recs) st.add(f);
                 }
                 resident.rec_bytes += st.bytes();
@@ -1662,7 +1795,7 @@ static bool derive_sampling(const CliOptions &o, const ScanState &s, kbbq_params
     unsigned coverage = o.coverage;
     alpha = o.alpha;
     if (genomelen == 0) {   // kbbq.cc:196-216
-        if (!o.is_bam) return !give_up(" Error: --genomelen must be specified if input is not a bam.");
+        if (!o.is_bam && !o.is_sam) return !give_up(" Error: --genomelen must be specified if input is not a bam.");
         std::cerr << put_now << " Estimating genome length" << std::endl;
         genomelen = s.bam_header.genome_length();
         if (genomelen == 0)
@@ -1943,6 +2076,7 @@ struct Sink {
             if (!dev->ok()) return fail_engine("cannot create the BGZF writer");
         }
         bam.reset(new BamWriter(bytes()));
+        if (o.is_sam) return bytes().write(s.bam_header.text.data(), s.bam_header.text.size()) ? 0 : 1;      // the header text, verbatim
         return o.is_bam && !bam->write_header(s.bam_header) ? 1 : 0;      // BamFile::open_out, htsiter.cc:35-42
     }
     // FastqFile::write, htsiter.cc:75-86 (the comment goes on the '+' line); qualities as text, htsiter.cc:61-65
@@ -1969,6 +2103,12 @@ struct Sink {
     bool bam_record(BamRecord &b, const uint8_t *q, bool set_oq) {
         if (!rewrite_bam_record(b, q, set_oq, qtext)) return !corrupt_tags();
         return bam->write(b);
+    }
+    // the same for a SAM line (sam_io.h: rewrite_sam_record)
+    bool sam_record(const SamRecord &r, const uint8_t *q, bool set_oq) {
+        line.clear();
+        if (!rewrite_sam_record(r, q, set_oq, line)) return !corrupt_tags();
+        return bytes().write(line.data(), line.size());
     }
 };
 
@@ -2132,6 +2272,7 @@ static int write_resident_bam(kbbq_engine *e, ScanState &s, const CliOptions &o,
 static int write_resident_records(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink) {
     std::vector<uint8_t> newq;
     BamRecord b;
+    SamRecord sr;
     for (size_t bi = 0; bi < s.resident.dev.size(); ++bi) {
         const kbbq_reads &d = s.resident.dev[bi];
         const RecordStore &st = s.resident.recs[bi];
@@ -2146,6 +2287,12 @@ static int write_resident_records(kbbq_engine *e, ScanState &s, const CliOptions
                 const size_t len = b.l_seq();
                 if (!sink.bam_record(b, newq.data() + qa, o.set_oq)) return 1;
                 qa += len;
+            } else if (o.is_sam) {
+                sr.line.assign(st.blob.data() + at, st.lens[r]);
+                at += st.lens[r];
+                if (sr.parse() < 0) return input_changed();      // (the scan parsed this very line)
+                if (!sink.sam_record(sr, newq.data() + qa, o.set_oq)) return 1;
+                qa += sr.l_seq;
             } else {
                 const uint32_t nl = st.lens[3 * r], cl = st.lens[3 * r + 1], sl = st.lens[3 * r + 2];
                 const char *p = st.blob.data() + at;
@@ -2202,7 +2349,7 @@ static int write_serial(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink 
     std::unique_ptr<Source> in = open_source(o, o.input);
     std::vector<uint8_t> newq;
     size_t bi = 0;
-    while (batch.fill(*in, s.groups, o.batch_reads, true, o.is_bam)) {
+    while (batch.fill(*in, s.groups, o.batch_reads, true, o.format())) {
         newq.assign(batch.c.n_bases + 16, 0);
         if (s.resident.on) {
             const kbbq_reads *d = same_batch(s.resident, bi++, batch.c);
@@ -2215,6 +2362,8 @@ static int write_serial(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink 
             const uint8_t *q = newq.data() + batch.off[r];
             if (o.is_bam) {
                 if (!sink.bam_record(batch.bam_recs[r], q, o.set_oq)) return 1;
+            } else if (o.is_sam) {
+                if (!sink.sam_record(batch.sam_recs[r], q, o.set_oq)) return 1;
             } else {
                 const FastqRecord &f = batch.fq_recs[r];
                 if (!sink.fastq(f.name.data(), f.name.size(), f.comment.data(), f.comment.size(), f.seq.data(), f.seq.size(), q)) return 1;
@@ -2261,6 +2410,7 @@ int main(int argc, char *argv[]) {
     if (fmt == Format::unknown) return give_up(" Error opening file " + opt.filename);
     if (fmt == Format::cram) return give_up(" Error: CRAM input needs htslib, which this build does not have; use BAM or FASTQ.");
     opt.is_bam = fmt == Format::bam;
+    opt.is_sam = fmt == Format::sam;
     opt.fixed_on_device = opt.fixed_may_read_on_device();
     if (opt.stream || opt.fixed_stream) {
         if (const char *why = opt.needs_a_file())
@@ -2347,10 +2497,10 @@ int main(int argc, char *argv[]) {
     int rc = sink.open(opt, scan);
     if (rc) return rc;
     if (dev_in.active && sink.dev) rc = write_from_device_reader(e, scan, opt, sink, dev_in);
-    else if (resident.on && resident.keep_recs && !opt.is_bam && sink.dev) rc = write_resident_fastq(e, scan, opt, sink);
+    else if (resident.on && resident.keep_recs && !opt.is_bam && !opt.is_sam && sink.dev) rc = write_resident_fastq(e, scan, opt, sink);
     else if (resident.on && resident.keep_recs && opt.is_bam && sink.dev) rc = write_resident_bam(e, scan, opt, sink);
     else if (resident.on && resident.keep_recs) rc = write_resident_records(e, scan, opt, sink);
-    else if (scan.passes_fast() && !opt.is_bam && sink.dev) rc = write_reparsed_fastq(e, scan, opt, sink, batch);
+    else if (scan.passes_fast() && !opt.is_bam && !opt.is_sam && sink.dev) rc = write_reparsed_fastq(e, scan, opt, sink, batch);
     else rc = write_serial(e, scan, opt, sink, batch);
     if (rc || !sink.close()) return 1;
     clock.mark("pass4+format+deflate+write");

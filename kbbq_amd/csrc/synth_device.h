@@ -1,4 +1,4 @@
-// synth_device.h -- the synthetic data set formatted as FASTQ or BAM records on the device (gfx950), for
+// synth_device.h -- the synthetic data set formatted as FASTQ, BAM or SAM records on the device (gfx950), for
 // kbbq_bgzf_submit_synth.  Included once, by bgzf_writer.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,6 +95,43 @@ __global__ void __launch_bounds__(256) k_synth_bam(SynthBatch B, int oq, uint8_t
             const uint8_t q = B.qual[r * L + (rev ? L - 1 - i : i)];
             ql[i] = oq ? (uint8_t)11 : q;
             if (oq) aux[11 + i] = (uint8_t)(q + 33);
+        }
+    }
+}
+
+// The same unaligned records as SAM lines, field for field what k_synth_bam stores: FLAG 4 or 20 (two digits either way, so
+// that every line has the same size), SEQ reverse-complemented and QUAL reversed for the reverse-flagged half, RG:Z:grp0;
+// oq: the true qualities in OQ:Z and 11s (',') in QUAL.  The BAM records of the same reads are the twin of these lines.
+constexpr uint32_t synth_sam_record(uint32_t L, bool oq) { return 2 * L + 41 + (oq ? L + 6 : 0); }
+__global__ void __launch_bounds__(256) k_synth_sam(SynthBatch B, int oq, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    const uint32_t L = B.read_len, W = synth_sam_record(L, oq != 0);
+    // name (11) TAB FLAG (2), 15 bytes of "\t*\t0\t0\t*\t*\t0\t0\t" SEQ TAB QUAL TAB "RG:Z:grp0" [TAB "OQ:Z:" OQ] newline
+    const uint32_t seq0 = 29, qual0 = 30 + L, rg0 = 31 + 2 * L, oq0 = 46 + 2 * L;
+    for (uint64_t r = wave; r < B.n; r += n_waves) {
+        uint8_t *d = out + r * W;
+        const uint64_t idx = B.first + r;
+        const bool rev = ((idx * 2654435761ull) >> 7) & 1;
+        if (lane == 0) {
+            synth_name(d, idx);
+            d[11] = '\t';
+            d[12] = rev ? '2' : '0';
+            d[13] = rev ? '0' : '4';
+        }
+        if (lane >= 14 && lane < 29) d[lane] = (uint8_t)"\t*\t0\t0\t*\t*\t0\t0\t"[lane - 14];
+        if (lane == 30) { d[seq0 + L] = '\t'; d[qual0 + L] = '\t'; d[W - 1] = '\n'; }
+        if (lane >= 32 && lane < 41) d[rg0 + (lane - 32)] = (uint8_t)"RG:Z:grp0"[lane - 32];
+        if (oq && lane >= 41 && lane < 47) d[rg0 + 9 + (lane - 41)] = (uint8_t)"\tOQ:Z:"[lane - 41];
+        for (uint32_t i = lane; i < L; i += 64) {
+            const uint64_t g = r * L + (rev ? L - 1 - i : i);
+            uint32_t c; bool nn;
+            synth_base(B, g, c, nn);
+            if (rev) c = 3 - c;
+            d[seq0 + i] = nn ? 'N' : (uint8_t)"ACGT"[c];
+            const uint8_t q = B.qual[g];
+            d[qual0 + i] = (uint8_t)((oq ? 11 : q) + 33);
+            if (oq) d[oq0 + i] = (uint8_t)(q + 33);
         }
     }
 }
