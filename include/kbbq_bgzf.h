@@ -196,6 +196,22 @@ int kbbq_bam_reader_preload(kbbq_bam_reader *r, const uint8_t *file_bytes, uint6
 int kbbq_bam_reader_read_groups(kbbq_bam_reader *r, uint32_t *table_index, uint32_t capacity, uint32_t *n);
 /* The current chunk's records as a device batch (arrays owned by the library: kbbq_reads_free), rg = dense indices. */
 int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev);
+/* The records' read groups need no @RG line (the corrected file of --fixed is read for its sequence alone, and the host path
+ * asks of it only that every record HAS an RG tag, readutils.cc:41-53): with on != 0 a record must still carry a first RG
+ * tag of type Z or H -- without one it raises bit 0, the host path reports that file -- but its value is not looked up:
+ * every record gets table index 0, kbbq_bam_reader_read_groups reports no group, and rg_ids may be empty.  Every other flag
+ * is raised as before.  Before the first chunk; KBBQ_ESTATE afterwards. */
+int kbbq_bam_reader_any_read_group(kbbq_bam_reader *r, int32_t on);
+/* The current chunk's records as a SEQUENCE-ONLY device batch, what kbbq_fixed_errors_batch reads of a batch: n_reads,
+ * n_bases, bases and nmask (a spare zero word behind each), offsets (NULL and read_len for equally long reads) -- bit for bit
+ * those of kbbq_bam_reader_batch -- and nothing else: qual, flags, rg, offcase and the hints are NULL.  Packed straight from
+ * the records' 4-bit codes by one kernel: no text, no qualities.  kbbq_reads_free frees it. */
+int kbbq_bam_reader_batch_seq(kbbq_bam_reader *r, kbbq_reads *dev);
+/* Whether the batch built for the current chunk (kbbq_bam_reader_batch or _batch_seq) is exact: *exact = 1 when no
+ * forward-strand base of the chunk has a code other than A/C/G/T/N, so that the packed batch gives bam_seq_str's text back
+ * character for character (on the reverse strand every other code IS 'N', readutils.hh:35-36).  Valid until the next chunk,
+ * select or rewind; KBBQ_ESTATE before a batch was built.  As kbbq_fastq_reader_batch_exact. */
+int kbbq_bam_reader_batch_exact(kbbq_bam_reader *r, int32_t *exact);
 /* Pass 4: the current chunk's records with d_qual (device: the batch's new qualities in the batch's base order) in their
  * quality fields, submitted to writer z (kbbq_bgzf_collect returns the blocks).  after_stream as in kbbq_bgzf_submit. */
 int kbbq_bam_reader_write(kbbq_bam_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, int32_t set_oq, void *after_stream);
@@ -236,6 +252,11 @@ int kbbq_sam_reader_preload(kbbq_sam_reader *r, const uint8_t *file_bytes, uint6
 int kbbq_sam_reader_read_groups(kbbq_sam_reader *r, uint32_t *table_index, uint32_t capacity, uint32_t *n);
 /* The current chunk's records as a device batch (arrays owned by the library: kbbq_reads_free), rg = dense indices. */
 int kbbq_sam_reader_batch(kbbq_sam_reader *r, kbbq_reads *dev);
+/* As kbbq_bam_reader_any_read_group (an RG:Z: or RG:H: field must be there, its value is not looked up), kbbq_bam_reader_batch_seq
+ * (packed straight from the SEQ characters) and kbbq_bam_reader_batch_exact, with the same results on the twin text. */
+int kbbq_sam_reader_any_read_group(kbbq_sam_reader *r, int32_t on);
+int kbbq_sam_reader_batch_seq(kbbq_sam_reader *r, kbbq_reads *dev);
+int kbbq_sam_reader_batch_exact(kbbq_sam_reader *r, int32_t *exact);
 /* Pass 4: the current (or selected) chunk's lines with d_qual (device: the batch's new qualities in the batch's base order)
  * in their QUAL fields, submitted to writer z (kbbq_bgzf_collect returns the blocks).  after_stream as in kbbq_bgzf_submit. */
 int kbbq_sam_reader_write(kbbq_sam_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, int32_t set_oq, void *after_stream);

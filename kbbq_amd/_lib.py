@@ -200,6 +200,9 @@ SYMBOLS = {
     "kbbq_bam_reader_chunk": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int32, ctypes.POINTER(FastqChunk)]),
     "kbbq_bam_reader_read_groups": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "kbbq_bam_reader_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_bam_reader_any_read_group": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+    "kbbq_bam_reader_batch_seq": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_bam_reader_batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
     "kbbq_bam_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp]),
     "kbbq_bam_reader_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "kbbq_sam_reader_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32,
@@ -213,6 +216,9 @@ SYMBOLS = {
     "kbbq_sam_reader_preload": (ctypes.c_int, [c_vp, c_vp, c_u64, c_u64]),
     "kbbq_sam_reader_read_groups": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "kbbq_sam_reader_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_sam_reader_any_read_group": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+    "kbbq_sam_reader_batch_seq": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_sam_reader_batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
     "kbbq_sam_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp]),
     "kbbq_sam_reader_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

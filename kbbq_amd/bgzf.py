@@ -131,13 +131,20 @@ class FastqReader:
 class BamReader:
     """A BAM file read on the device (include/kbbq_bgzf.h: kbbq_bam_reader): inflate, record chain, field decode, and --
     pass 4 -- the records rewritten around the new qualities.  header_bytes / n_ref / rg_ids come from the caller's own
-    parse of the BAM header."""
+    parse of the BAM header.  any_read_group: every record must carry an RG tag but its value is not looked up (rg_ids may
+    be empty) -- the corrected file of --fixed, read for its sequence alone (batch_seq)."""
 
-    def __init__(self, header_bytes, n_ref, rg_ids, use_oq=False, device=0):
+    def __init__(self, header_bytes, n_ref, rg_ids, use_oq=False, device=0, any_read_group=False):
         self.L = _lib.lib()
         self.h = _lib.c_vp()
         ids = (ctypes.c_char_p * max(1, len(rg_ids)))(*[i.encode() if isinstance(i, str) else i for i in rg_ids])
         _lib.check(self.L.kbbq_bam_reader_create(device, 1 if use_oq else 0, n_ref, header_bytes, ids, len(rg_ids), ctypes.byref(self.h)))
+        if any_read_group:
+            self.any_read_group(True)
+
+    def any_read_group(self, on=True):
+        """Before the first chunk: RG tags are required but not looked up (kbbq_bam_reader_any_read_group)."""
+        _lib.check(self.L.kbbq_bam_reader_any_read_group(self.h, 1 if on else 0))
 
     def close(self):
         if getattr(self, "h", None):
@@ -182,6 +189,18 @@ class BamReader:
         _lib.check(self.L.kbbq_bam_reader_batch(self.h, ctypes.byref(d)))
         return d
 
+    def batch_seq(self):
+        """The current chunk as a sequence-only device batch: bases, nmask and lengths, nothing else (kbbq_bam_reader_batch_seq)."""
+        d = _lib.Reads()
+        _lib.check(self.L.kbbq_bam_reader_batch_seq(self.h, ctypes.byref(d)))
+        return d
+
+    def batch_exact(self):
+        """Whether no forward-strand base of the batch just built is anything but A/C/G/T/N (kbbq_bam_reader_batch_exact)."""
+        x = ctypes.c_int32()
+        _lib.check(self.L.kbbq_bam_reader_batch_exact(self.h, ctypes.byref(x)))
+        return bool(x.value)
+
     def write(self, writer, d_qual, set_oq=False, after_stream=None):
         _lib.check(self.L.kbbq_bam_reader_write(self.h, writer.h, d_qual, 1 if set_oq else 0, after_stream))
 
@@ -195,13 +214,19 @@ class SamReader:
     """SAM text -- BGZF, any other gzip stream or uncompressed, in pieces of any size -- read on the device
     (include/kbbq_bgzf.h: kbbq_sam_reader): the lines indexed, their fields decoded as the BAM twin's, and -- pass 4 -- the
     lines written again around the new qualities.  header_bytes (the size of the leading '@' lines) and rg_ids come from
-    the caller's own parse of the header."""
+    the caller's own parse of the header.  any_read_group: as BamReader's."""
 
-    def __init__(self, header_bytes, rg_ids, use_oq=False, device=0):
+    def __init__(self, header_bytes, rg_ids, use_oq=False, device=0, any_read_group=False):
         self.L = _lib.lib()
         self.h = _lib.c_vp()
         ids = (ctypes.c_char_p * max(1, len(rg_ids)))(*[i.encode() if isinstance(i, str) else i for i in rg_ids])
         _lib.check(self.L.kbbq_sam_reader_create(device, 1 if use_oq else 0, header_bytes, ids, len(rg_ids), ctypes.byref(self.h)))
+        if any_read_group:
+            self.any_read_group(True)
+
+    def any_read_group(self, on=True):
+        """Before the first chunk: RG tags are required but not looked up (kbbq_sam_reader_any_read_group)."""
+        _lib.check(self.L.kbbq_sam_reader_any_read_group(self.h, 1 if on else 0))
 
     def close(self):
         if getattr(self, "h", None):
@@ -245,6 +270,18 @@ class SamReader:
         d = _lib.Reads()
         _lib.check(self.L.kbbq_sam_reader_batch(self.h, ctypes.byref(d)))
         return d
+
+    def batch_seq(self):
+        """The current chunk as a sequence-only device batch: bases, nmask and lengths, nothing else (kbbq_sam_reader_batch_seq)."""
+        d = _lib.Reads()
+        _lib.check(self.L.kbbq_sam_reader_batch_seq(self.h, ctypes.byref(d)))
+        return d
+
+    def batch_exact(self):
+        """Whether no forward-strand base of the batch just built is anything but A/C/G/T/N (kbbq_sam_reader_batch_exact)."""
+        x = ctypes.c_int32()
+        _lib.check(self.L.kbbq_sam_reader_batch_exact(self.h, ctypes.byref(x)))
+        return bool(x.value)
 
     def write(self, writer, d_qual, set_oq=False, after_stream=None):
         _lib.check(self.L.kbbq_sam_reader_write(self.h, writer.h, d_qual, 1 if set_oq else 0, after_stream))

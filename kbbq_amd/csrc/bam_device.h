@@ -28,6 +28,9 @@
 //   k_bam_gather         one wavefront per record: 4-bit codes to sequence text (reverse-strand records complemented and
 //                        reversed, every non-ACGT code 'N' there, readutils.hh:35-36), qualities or OQ - 33 (reversed for
 //                        reverse-strand records, readutils.cc:36-39) into the batch's arrays; k_pack_text packs the text.
+//   k_bam_pack_seq       the sequence-only batch (kbbq_bam_reader_batch_seq: the corrected file of --fixed, read for its bases
+//                        alone): one lane per 64-base word of the batch, from the records' 4-bit codes straight to the 2-bit
+//                        words and the N mask (seq_pack.h) -- no byte of text and no quality is written or read back.
 //   k_bam_out_sizes / k_bam_rewrite
 //                        pass 4: every record again with the new qualities in its quality field (reversed back,
 //                        htsiter.cc:27-31) and -- --set-oq -- the old ones as OQ:Z, replaced in place or appended as
@@ -37,6 +40,7 @@
 #include <stdint.h>
 
 #include "rg_table.h"
+#include "seq_pack.h"
 
 namespace kbbq {
 namespace dfl {
@@ -287,7 +291,8 @@ __device__ __forceinline__ uint32_t bam_aux_size(const uint8_t *t, uint64_t a, u
 }
 
 // out: [0] flags, [1] longest, [2] shortest; first_seen[id] = smallest record ordinal (of the chunk) that carries it
-__global__ void __launch_bounds__(256) k_bam_records(const uint8_t *text, uint64_t n_records, int use_oq, BamRgTable T, BamIndex X,
+// any_rg (kbbq_bam_reader_any_read_group): the RG tag must be there, its value is not looked up -- table index 0, no first_seen
+__global__ void __launch_bounds__(256) k_bam_records(const uint8_t *text, uint64_t n_records, int use_oq, int any_rg, BamRgTable T, BamIndex X,
                                                       uint32_t *out, unsigned long long *first_seen) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_records) return;
@@ -322,6 +327,8 @@ __global__ void __launch_bounds__(256) k_bam_records(const uint8_t *text, uint64
     uint32_t rg = 0xFFFF;
     if (!rg_at || (text[rg_at] != 'Z' && text[rg_at] != 'H')) {
         fl |= BAMF_FALLBACK;
+    } else if (any_rg) {
+        rg = 0;
     } else {
         const uint64_t v = rg_at + 1;
         uint32_t len = 0;
@@ -387,6 +394,19 @@ __global__ void __launch_bounds__(256) k_bam_gather(const uint8_t *text, BamInde
             }
         }
     }
+}
+
+// The records' bases alone, packed: one lane per word of the batch (seq_pack.h).  counter[1] += the forward-strand bases
+// whose code is none of A/C/G/T/N (k_pack_text's second count).
+__global__ void __launch_bounds__(256) k_bam_pack_seq(const uint8_t *text, BamIndex X, const uint64_t *base_off, uint64_t n_records, uint64_t n_bases,
+                                                       uint64_t *bases, uint64_t *nmask, unsigned long long *counter) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_bases / 64 + 1) return;
+    const uint32_t inexact = seq_pack_word(
+        w, base_off, n_records, n_bases, [&](uint64_t r) { return (X.flag[r] & 16) != 0; },      // bam_is_rev
+        [&](uint64_t r, uint32_t j) { return (uint32_t)(text[(uint64_t)X.seq_off[r] + (j >> 1)] >> ((~j & 1) << 2)) & 15u; },      // bam_seqi
+        bases, nmask);
+    if (inexact) atomicAdd(counter + 1, (unsigned long long)inexact);
 }
 
 __global__ void __launch_bounds__(256) k_bam_out_sizes(const uint8_t *text, BamIndex X, uint64_t n_records, int set_oq) {

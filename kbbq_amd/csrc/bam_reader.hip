@@ -15,6 +15,8 @@ struct kbbq_bam_reader {
     hipStream_t st = nullptr;
     hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
     int use_oq = 0;
+    int any_rg = 0;                         // kbbq_bam_reader_any_read_group: RG tags are required, their values not looked up
+    bool fed = false;                       // a chunk call was made: the mode above no longer changes
     int32_t n_ref = 0;
     uint64_t header_left = 0;               // bytes of the BAM header still to skip at the front of the stream
     uint64_t header_bytes = 0;
@@ -30,6 +32,7 @@ struct kbbq_bam_reader {
     uint64_t text_bytes = 0, n_records = 0, n_bases = 0, idx_cap = 0;
     uint32_t longest = 0, shortest = 0, chunk_flags = 0;
     bool have_chunk = false;
+    bool batch_built = false, packed_is_exact = false;      // kbbq_bam_reader_batch_exact: of the current chunk's batch
     double ms_inflate = 0, ms_index = 0, ms_rewrite = 0;
     // chunks of the first scan kept for pass 4: the COMPRESSED bytes (a third of the stream) with their block table and the
     // bytes the chunk before them left over; pass 4 inflates and indexes them again (kbbq_bam_reader_select)
@@ -89,6 +92,7 @@ int bam_inflate(kbbq_bam_reader *r, const void *d_comp, const BlockTable &T) {
 int bam_index_stream(kbbq_bam_reader *r, uint64_t text, uint64_t skip, int32_t last, bool assign_groups, kbbq_bam_chunk *info) {
     int rc;
     r->n_records = 0; r->n_bases = 0; r->longest = r->shortest = 0;
+    r->batch_built = false;
     if ((rc = r->h_small.reserve(4096))) return rc;
     if ((rc = r->d_out.reserve(64))) return rc;
     uint64_t rec_end = skip;
@@ -143,7 +147,7 @@ int bam_index_stream(kbbq_bam_reader *r, uint64_t text, uint64_t skip, int32_t l
             }
             const BamIndex X = bam_index(r);
             hipLaunchKernelGGL(k_bam_rec_offsets, dim3(n_segs), dim3(256), 0, r->st, G, (const uint64_t *)counts, (uint32_t)bias, X.rec_off);
-            hipLaunchKernelGGL(k_bam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, t, n_rec, r->use_oq, r->groups.table(), X, out + 4,
+            hipLaunchKernelGGL(k_bam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, t, n_rec, r->use_oq, r->any_rg, r->groups.table(), X, out + 4,
                                (unsigned long long *)r->groups.first_seen.p);
             HIP_TRY(hipGetLastError());
             if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
@@ -237,6 +241,14 @@ int kbbq_bam_reader_rewind(kbbq_bam_reader *r) {
     r->carry_bytes = 0;
     r->header_left = r->header_bytes;
     r->have_chunk = false;
+    r->batch_built = false;
+    return KBBQ_OK;
+}
+
+int kbbq_bam_reader_any_read_group(kbbq_bam_reader *r, int32_t on) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (r->fed) return fail(KBBQ_ESTATE, "the read-group mode is set before the first chunk");
+    r->any_rg = on ? 1 : 0;
     return KBBQ_OK;
 }
 
@@ -275,6 +287,8 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
     HIP_TRY(guard.err);
     memset(info, 0, sizeof *info);
     r->have_chunk = false;
+    r->batch_built = false;
+    r->fed = true;
     BlockTable T;
     if (walk_blocks(file_bytes, n_bytes, r->carry_bytes, TEXT_CAP, T).why != WALK_END) { info->flags |= BAMF_FALLBACK; return KBBQ_OK; }      // (consumed 0)
     const uint64_t at = T.consumed, text = T.text;
@@ -347,6 +361,7 @@ int kbbq_bam_reader_select(kbbq_bam_reader *r, uint64_t i, kbbq_bam_chunk *info)
     if (!info) info = &local;
     memset(info, 0, sizeof *info);
     r->have_chunk = false;
+    r->batch_built = false;
     int rc;
     if ((rc = r->text.reserve(k.blocks.text + 4096))) return rc;
     if (k.carry_bytes) HIP_TRY(hipMemcpyAsync(r->text.p, k.carry.p, k.carry_bytes, hipMemcpyDeviceToDevice, r->st));
@@ -391,9 +406,13 @@ int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev) {
     hipLaunchKernelGGL(k_bam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->groups.dense.p, (uint8_t *)fl,
                        (uint16_t *)rg);
     HIP_TRY(hipGetLastError());
-    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch and the counts are not read)
-    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, nullptr))) return rc;
+    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch.  The second count is the
+    // forward-strand bases that are none of A/C/G/T/N: kbbq_bam_reader_batch_exact)
+    unsigned long long counts[2] = {0, 0};
+    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, counts))) return rc;
     arrays.release();
+    r->packed_is_exact = counts[1] == 0;
+    r->batch_built = true;
     dev->bases = (const uint64_t *)b;
     dev->nmask = (const uint64_t *)m;
     dev->qual = (const uint8_t *)q;
@@ -402,6 +421,55 @@ int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev) {
     dev->rg = (const uint16_t *)rg;
     dev->read_len = uniform ? r->longest : 0;
     dev->offcase = nullptr;
+    return KBBQ_OK;
+}
+
+int kbbq_bam_reader_batch_seq(kbbq_bam_reader *r, kbbq_reads *dev) {
+    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->chunk_flags & BAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host parser's", r->chunk_flags);
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    const uint64_t n = r->n_records, nbases = r->n_bases;
+    const BamIndex X = bam_index(r);
+    memset(dev, 0, sizeof *dev);
+    dev->n_reads = n;
+    dev->n_bases = nbases;
+    dev->on_device = 1;
+    void *b = nullptr, *m = nullptr, *off = nullptr;
+    BatchArrays arrays;
+    int rc;
+    const uint64_t words = nbases / 64 + 1;
+    if ((rc = r->counter.reserve(64))) return rc;
+    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
+    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
+    const bool uniform = r->longest == r->shortest;
+    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
+    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
+    // (the kernel writes every one of the `words` words; the spare words behind them are pack_text's)
+    HIP_TRY(hipMemsetAsync(r->counter.p, 0, 16, r->st));
+    HIP_TRY(hipMemsetAsync((char *)b + 2 * words * 8, 0, 16, r->st));
+    HIP_TRY(hipMemsetAsync((char *)m + words * 8, 0, 16, r->st));
+    hipLaunchKernelGGL(k_bam_pack_seq, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X, (const uint64_t *)X.base_sz, n,
+                       nbases, (uint64_t *)b, (uint64_t *)m, (unsigned long long *)r->counter.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, r->counter.p, 16, hipMemcpyDeviceToHost, r->st));
+    HIP_TRY(hipStreamSynchronize(r->st));
+    arrays.release();
+    r->packed_is_exact = counts[1] == 0;
+    r->batch_built = true;
+    dev->bases = (const uint64_t *)b;
+    dev->nmask = (const uint64_t *)m;
+    dev->offsets = (const uint64_t *)off;
+    dev->read_len = uniform ? r->longest : 0;
+    return KBBQ_OK;
+}
+
+int kbbq_bam_reader_batch_exact(kbbq_bam_reader *r, int32_t *exact) {
+    if (!r || !exact) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->batch_built) return fail(KBBQ_ESTATE, "no batch was built for the current chunk");
+    *exact = r->packed_is_exact ? 1 : 0;
     return KBBQ_OK;
 }
 

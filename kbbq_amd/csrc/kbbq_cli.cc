@@ -30,12 +30,17 @@
 //     reader, cut into the pieces of a file of the same bytes, and must fit in GPU memory with its text; whatever needs
 //     the input twice (KBBQ_RESIDENT=0, the host parsers, --fixed) is refused for it with one line.  "-" with a regular
 //     file on standard input is that file;
-//   * --fixed on FASTQ reads both files on the GPU (tally_fixed_on_device): the corrected file goes through a second device
-//     reader, its packed batches are compared with the resident ones by a kernel, record by record, and the tally runs from
-//     the error bits that leaves in HBM.  The reference compares the two files' characters on the host (kbbq.cc:371-375);
-//     the packed comparison is the same one while both files hold nothing but ACGTN / acgt, and anything else -- IUPAC
-//     codes, read groups in the names, records that are not four lines -- hands the run back to the host loop
-//     (tally_fixed), which stays the definition and is all a BAM input gets;
+//   * --fixed reads both files on the GPU, in all three formats (tally_fixed_on_device): the corrected file goes through a
+//     second device reader -- opened in the first file's format, kbbq.cc:370; for BAM and SAM with read groups that need no
+//     @RG line and as sequence-only batches, packed straight from the records -- its packed batches are compared with the
+//     resident ones by a kernel, record by record, and the tally runs from the error bits that leaves in HBM.  The reference
+//     compares the two files' characters on the host (kbbq.cc:371-375); the packed comparison is the same one while both
+//     files hold nothing but ACGTN (FASTQ: and acgt; BAM and SAM: on the forward strand -- on the reverse strand every other
+//     code is N anyway), and anything else hands the run back to the host loop (tally_fixed), which stays the definition:
+//     IUPAC codes, any shape a device reader flags (FASTQ: read groups in the names, records that are not four lines; BAM
+//     and SAM: a main file without @RG lines, a record without an RG tag, malformed records, --use-oq without a usable OQ),
+//     a corrected record without bases, a corrected file that does not open as the first file's format.  BAM and SAM
+//     have one timed run each, FASTQ none;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -114,7 +119,7 @@ struct CliOptions {
     // The input is not a regular file -- a pipe on standard input, a FIFO, /dev/stdin on a pipe: it is read once, front to
     // back, by the device reader (main(): StreamInput), and whatever would read it a second time is refused.
     bool stream = false, fixed_stream = false;
-    // --fixed may read both of its files on the GPU: FASTQ, and none of the switches below that ask for the host parsers
+    // --fixed may read both of its files on the GPU: none of the switches below that ask for the host parsers
     // (main() decides once the format is known, and clears it when the run is handed back to the host loop)
     bool fixed_on_device = false;
     int out_threads = 1;      // --threads, or "pick" (parse())
@@ -151,7 +156,7 @@ struct CliOptions {
     bool may_read_on_device(bool resident_on) const {
         return (!fixed_mode() || fixed_on_device) && !host_io() && resident_on && device_reader && !serial_parse;
     }
-    bool fixed_may_read_on_device() const { return fixed_mode() && !is_bam && !is_sam && !host_io() && resident && device_reader && !serial_parse; }
+    bool fixed_may_read_on_device() const { return fixed_mode() && !host_io() && resident && device_reader && !serial_parse; }
     // What was asked for that reads the input more than once, which a stream does not allow; null: nothing
     const char *needs_a_file() const {
         if (fixed_mode()) return "--fixed reads two files side by side and starts over with the host parsers, which read both again, when the GPU readers hand one back";
@@ -777,19 +782,24 @@ public:
     std::string refusal;
 
     // `stream`: the input when it is not a regular file (its head has been read), null for the file `path`
-    bool open_bam(const std::string &path, StreamInput *stream, bool use_oq, int32_t n_ref, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
+    // any_read_group: the records need an RG tag but no @RG line for it (the corrected file of --fixed; rg_ids may be empty)
+    bool open_bam(const std::string &path, StreamInput *stream, bool use_oq, int32_t n_ref, uint64_t header_bytes, const std::vector<std::string> &rg_ids,
+                  bool any_read_group = false) {
         if (!open_file(path, stream, true)) return false;
         std::vector<const char *> ids;
         for (auto &id : rg_ids) ids.push_back(id.c_str());
         if (kbbq_bam_reader_create(0, use_oq ? 1 : 0, n_ref, header_bytes, ids.data(), (uint32_t)ids.size(), &bam) < 0) return false;
+        if (any_read_group && kbbq_bam_reader_any_read_group(bam, 1) < 0) return false;
         start_pass();
         return true;
     }
-    bool open_sam(const std::string &path, StreamInput *stream, bool use_oq, uint64_t header_bytes, const std::vector<std::string> &rg_ids) {
+    bool open_sam(const std::string &path, StreamInput *stream, bool use_oq, uint64_t header_bytes, const std::vector<std::string> &rg_ids,
+                  bool any_read_group = false) {
         if (!open_file(path, stream, false)) return false;
         std::vector<const char *> ids;
         for (auto &id : rg_ids) ids.push_back(id.c_str());
         if (kbbq_sam_reader_create(0, use_oq ? 1 : 0, header_bytes, ids.data(), (uint32_t)ids.size(), &sam) < 0) return false;
+        if (any_read_group && kbbq_sam_reader_any_read_group(sam, 1) < 0) return false;
         start_pass();
         return true;
     }
@@ -910,6 +920,11 @@ public:
         return bam ? kbbq_bam_reader_kept(bam, n_chunks, n_bytes) : sam ? kbbq_sam_reader_kept(sam, n_chunks, n_bytes) : kbbq_fastq_reader_kept(reader, n_chunks, n_bytes);
     }
     int batch(kbbq_reads *dev) { return bam ? kbbq_bam_reader_batch(bam, dev) : sam ? kbbq_sam_reader_batch(sam, dev) : kbbq_fastq_reader_batch(reader, dev); }
+    // the sequence-only batch of the current chunk (BAM and SAM; FASTQ has the one batch) and whether the batch just built is exact
+    int batch_seq(kbbq_reads *dev) { return bam ? kbbq_bam_reader_batch_seq(bam, dev) : sam ? kbbq_sam_reader_batch_seq(sam, dev) : kbbq_fastq_reader_batch(reader, dev); }
+    int batch_exact(int32_t *exact) {
+        return bam ? kbbq_bam_reader_batch_exact(bam, exact) : sam ? kbbq_sam_reader_batch_exact(sam, exact) : kbbq_fastq_reader_batch_exact(reader, exact);
+    }
     int rewind() { return bam ? kbbq_bam_reader_rewind(bam) : sam ? kbbq_sam_reader_rewind(sam) : kbbq_fastq_reader_rewind(reader); }
     // chunk i of the kept ones becomes the current chunk again (BAM: inflated and indexed again from the compressed bytes)
     int select(uint64_t i, kbbq_fastq_chunk *info) {
@@ -1565,11 +1580,12 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceFastqInp
         }
         if (!resident.add(need, [&](kbbq_reads *d) { return in.batch(d); })) { in.refusal = does_not_fit(); ok = false; break; }
         in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
-        if (o.fixed_mode() && in.reader) {
+        if (o.fixed_mode()) {
             // --fixed compares the packed batches (kbbq_fixed_errors_batch), which is the comparison of the text only while the
-            // text holds nothing but ACGTN / acgt: any other character leaves the run to the host loop
+            // text holds nothing but ACGTN / acgt (BAM, SAM: on the forward strand): any other character leaves the run to the
+            // host loop
             int32_t exact = 0;
-            if (kbbq_fastq_reader_batch_exact(in.reader, &exact) < 0 || !exact) {
+            if (in.batch_exact(&exact) < 0 || !exact) {
                 in.refusal = DeviceFastqInput::needs_host_parsers("--fixed on reads with characters other than ACGTN");
                 ok = false;
                 break;
@@ -1970,13 +1986,29 @@ struct FixedOnDevice {
 // then the engine has counted nothing and the host loop can still take the whole run over.
 // The corrected file ends first: the batch with the last paired read is tallied up to that read, later ones not at all
 // (the reference stops consuming there).  The first file ends first: the rest of the corrected file is not read.
-// 0: tallied; 1: the message is on stderr; -1: handed back -- the corrected file cannot be opened here, a chunk of it has a
-// shape the device reader does not take or a character other than ACGTN / acgt -- and tally_fixed() does it all.
+// A BAM or SAM corrected file is read for its sequence alone: its records need an RG tag (readutils.cc:41-53) but its header
+// no @RG line (it is usually empty), and every chunk comes as a sequence-only batch, packed straight from the records.
+// 0: tallied; 1: the message is on stderr; -1: handed back -- the corrected file cannot be opened here in the first file's
+// format, a chunk of it has a shape the device reader does not take (any flag), a character other than ACGTN / acgt, or a
+// record without bases (what Batch::fill does with an empty read stays the host's business) -- and tally_fixed() does it all.
 static int tally_fixed_on_device(kbbq_engine *e, const CliOptions &o, ScanState &s, FixedOnDevice &rep) {
     std::vector<kbbq_reads> &main = s.resident.dev;
-    // the second file is opened in the FIRST file's format (kbbq.cc:370 passes is_bam): as FASTQ, whatever it holds
+    // the second file is opened in the FIRST file's format (kbbq.cc:370 passes is_bam), whatever it holds
     DeviceFastqInput fin(o);
-    if (!fin.open(o.fixed_path, nullptr)) return -1;
+    if (o.is_bam) {
+        BamReader head(o.fixed_path, 1);
+        if (!head.ok()) return -1;
+        const BamHeader h = head.header();
+        uint64_t header_bytes = 12 + h.text.size();
+        for (auto &r : h.refs) header_bytes += 8 + r.first.size() + 1;
+        if (!fin.open_bam(o.fixed_path, nullptr, o.use_oq, (int32_t)h.refs.size(), header_bytes, {}, true)) return -1;
+    } else if (o.is_sam) {
+        SamReader head(o.fixed_path, 1);
+        if (!head.ok()) return -1;
+        if (!fin.open_sam(o.fixed_path, nullptr, o.use_oq, head.header().text.size(), {}, true)) return -1;
+    } else if (!fin.open(o.fixed_path, nullptr)) {
+        return -1;
+    }
     size_t bi = 0;          // the resident batch the next record of the corrected file faces
     uint64_t done = 0;      // records of it that have their partners
     for (;;) {
@@ -1986,10 +2018,11 @@ static int tally_fixed_on_device(kbbq_engine *e, const CliOptions &o, ScanState 
         if (got < 0 || info.flags) return -1;
         ++rep.chunks;
         if (!info.n_records) continue;
+        if (info.shortest == 0) return -1;
         kbbq_reads fb;
         int32_t exact = 0;
-        if (fin.batch(&fb) < 0) return -1;
-        const bool usable = kbbq_fastq_reader_batch_exact(fin.reader, &exact) == 0 && exact;
+        if (fin.batch_seq(&fb) < 0) return -1;
+        const bool usable = fin.batch_exact(&exact) == 0 && exact;
         uint64_t at = 0, calls = 0;
         int rc = 0;
         while (usable && rc == 0 && at < fb.n_reads && bi < main.size()) {

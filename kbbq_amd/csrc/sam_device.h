@@ -18,6 +18,9 @@
 //                        bam_seq_str makes of the codes (reverse-strand records complemented and reversed, every code
 //                        that is not A/C/G/T 'N' there), qualities or the OQ value - 33 (reversed for reverse-strand
 //                        records) into the batch's arrays; k_pack_text packs the text.  Never an off-case bit.
+//   k_sam_pack_seq       the sequence-only batch (kbbq_sam_reader_batch_seq: the corrected file of --fixed, read for its bases
+//                        alone): one lane per 64-base word of the batch, from the SEQ characters through the same table
+//                        straight to the 2-bit words and the N mask (seq_pack.h: k_bam_pack_seq's rule and walk).
 //   k_sam_out_sizes / k_sam_rewrite
 //                        pass 4: every line again with the new qualities + 33 in QUAL (reversed back) and -- --set-oq -- the
 //                        stored QUAL text as the value of the first OQ:Z field, or "\tOQ:Z:<qual>" behind the line.
@@ -26,6 +29,7 @@
 #include <stdint.h>
 
 #include "rg_table.h"
+#include "seq_pack.h"
 
 namespace kbbq {
 namespace dfl {
@@ -69,8 +73,9 @@ __device__ __forceinline__ bool sam_aux_type(uint8_t c) {      // the types sam_
 
 // Line r of the text is record r: text[l0, e) with e the r-th newline; line 0 starts at first_start.
 // out: [0] flags, [1] longest, [2] shortest; first_seen[id] = smallest record ordinal (of the chunk) that carries it
+// any_rg (kbbq_sam_reader_any_read_group): the RG field must be there, its value is not looked up -- table index 0, no first_seen
 __global__ void __launch_bounds__(256) k_sam_records(const uint8_t *text, const uint32_t *nl_pos, uint64_t n_records, uint32_t first_start, int use_oq,
-                                                      RgTable T, SamIndex X, uint32_t *out, unsigned long long *first_seen) {
+                                                      int any_rg, RgTable T, SamIndex X, uint32_t *out, unsigned long long *first_seen) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_records) return;
     const uint32_t l0 = r ? nl_pos[r - 1] + 1 : first_start, e = nl_pos[r];
@@ -121,6 +126,8 @@ __global__ void __launch_bounds__(256) k_sam_records(const uint8_t *text, const 
         // RG (readutils.cc:41-58): there, type Z or H (bam_aux2Z), named by the header
         if (!rg_at || (text[rg_at + 3] != 'Z' && text[rg_at + 3] != 'H')) {
             fl |= SAMF_FALLBACK;
+        } else if (any_rg) {
+            rg = 0;
         } else {
             rg = rg_lookup(T, text + rg_at + 5, rg_len - 5);
             if (rg == 0xFFFF) fl |= SAMF_FALLBACK;      // a read group without an @RG line: the host path's dictionary handles it
@@ -185,6 +192,18 @@ __global__ void __launch_bounds__(256) k_sam_gather(const uint8_t *text, SamInde
             }
         }
     }
+}
+
+// The records' bases alone, packed: one lane per word of the batch (seq_pack.h).  counter[1] += the forward-strand bases
+// whose code is none of A/C/G/T/N (k_pack_text's second count).
+__global__ void __launch_bounds__(256) k_sam_pack_seq(const uint8_t *text, SamIndex X, const uint64_t *base_off, uint64_t n_records, uint64_t n_bases,
+                                                       uint64_t *bases, uint64_t *nmask, unsigned long long *counter) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_bases / 64 + 1) return;
+    const uint32_t inexact = seq_pack_word(
+        w, base_off, n_records, n_bases, [&](uint64_t r) { return (X.flag[r] & 16) != 0; },      // bam_is_rev
+        [&](uint64_t r, uint32_t j) { return sam_nt16(text[(uint64_t)X.seq_off[r] + j]); }, bases, nmask);
+    if (inexact) atomicAdd(counter + 1, (unsigned long long)inexact);
 }
 
 __global__ void __launch_bounds__(256) k_sam_out_sizes(SamIndex X, uint64_t n_records, int set_oq) {

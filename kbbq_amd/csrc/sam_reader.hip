@@ -19,6 +19,8 @@ struct SamCounts {
 
 struct kbbq_sam_reader : SamCounts, TextChunks {
     int use_oq = 0;
+    int any_rg = 0;                         // kbbq_sam_reader_any_read_group: RG fields are required, their values not looked up
+    bool fed = false;                       // a chunk call was made: the mode above no longer changes
     uint64_t header_bytes = 0, header_left = 0;      // the header's size in the text; what of it is still to come
     Buf idx_u32, idx_u16, idx_u64;          // SamIndex, idx_cap records long
     size_t idx_cap = 0;
@@ -26,6 +28,7 @@ struct kbbq_sam_reader : SamCounts, TextChunks {
     RgGroups groups;
     Buf seq_text, counter;                  // scratch of kbbq_sam_reader_batch
     bool have_chunk = false;
+    bool batch_built = false, packed_is_exact = false;      // kbbq_sam_reader_batch_exact: of the current chunk's batch
     // chunks of the first scan that stay in device memory (kbbq_sam_reader_keep): the whole text with its record index
     struct Kept : SamCounts {
         Buf text, idx_u32, idx_u16, idx_u64;
@@ -125,8 +128,16 @@ int kbbq_sam_reader_rewind(kbbq_sam_reader *r) {
     r->keeping = false;      // what was kept stays; a second scan keeps nothing more
     r->selected = -1;
     r->have_chunk = false;
+    r->batch_built = false;
     r->header_left = r->header_bytes;
     r->new_stream();
+    return KBBQ_OK;
+}
+
+int kbbq_sam_reader_any_read_group(kbbq_sam_reader *r, int32_t on) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (r->fed) return fail(KBBQ_ESTATE, "the read-group mode is set before the first chunk");
+    r->any_rg = on ? 1 : 0;
     return KBBQ_OK;
 }
 
@@ -160,6 +171,7 @@ int kbbq_sam_reader_select(kbbq_sam_reader *r, uint64_t i, kbbq_sam_chunk *info)
     const kbbq_sam_reader::Kept &k = r->kept[(size_t)i];
     r->selected = (int64_t)i;
     r->have_chunk = true;
+    r->batch_built = false;
     static_cast<SamCounts &>(*r) = k;
     if (info) {
         memset(info, 0, sizeof *info);
@@ -184,6 +196,8 @@ int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_
     stash_current(r);
     r->selected = -1;
     r->have_chunk = false;
+    r->batch_built = false;
+    r->fed = true;
     r->n_records = r->n_bases = 0;
     r->longest = r->shortest = r->chunk_flags = 0;
     int rc;
@@ -224,7 +238,7 @@ int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_
         const SamIndex X = index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap);
         const uint8_t *tb = (const uint8_t *)r->text.p + bias;
         hipLaunchKernelGGL(k_sam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, tb, (const uint32_t *)r->nl_pos.p, n_rec, first_start,
-                           r->use_oq, r->groups.table(), X, out, (unsigned long long *)r->groups.first_seen.p);
+                           r->use_oq, r->any_rg, r->groups.table(), X, out, (unsigned long long *)r->groups.first_seen.p);
         HIP_TRY(hipGetLastError());
         if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
         uint64_t *hs = (uint64_t *)r->h_small.p;
@@ -289,9 +303,13 @@ int kbbq_sam_reader_batch(kbbq_sam_reader *r, kbbq_reads *dev) {
     hipLaunchKernelGGL(k_sam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->groups.dense.p, (uint8_t *)fl,
                        (uint16_t *)rg);
     HIP_TRY(hipGetLastError());
-    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch and the counts are not read)
-    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, nullptr))) return rc;
+    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch.  The second count is the
+    // forward-strand bases that are none of A/C/G/T/N: kbbq_sam_reader_batch_exact)
+    unsigned long long counts[2] = {0, 0};
+    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, counts))) return rc;
     arrays.release();
+    r->packed_is_exact = counts[1] == 0;
+    r->batch_built = true;
     dev->bases = (const uint64_t *)b;
     dev->nmask = (const uint64_t *)m;
     dev->qual = (const uint8_t *)q;
@@ -300,6 +318,56 @@ int kbbq_sam_reader_batch(kbbq_sam_reader *r, kbbq_reads *dev) {
     dev->rg = (const uint16_t *)rg;
     dev->read_len = uniform ? r->longest : 0;
     dev->offcase = nullptr;
+    return KBBQ_OK;
+}
+
+int kbbq_sam_reader_batch_seq(kbbq_sam_reader *r, kbbq_reads *dev) {
+    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records || r->selected >= 0) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->chunk_flags & SAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host reader's", r->chunk_flags);
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    const uint64_t n = r->n_records, nbases = r->n_bases;
+    const SamIndex X = index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap);
+    const uint8_t *tb = (const uint8_t *)r->text.p + r->bias;
+    memset(dev, 0, sizeof *dev);
+    dev->n_reads = n;
+    dev->n_bases = nbases;
+    dev->on_device = 1;
+    void *b = nullptr, *m = nullptr, *off = nullptr;
+    BatchArrays arrays;
+    int rc;
+    const uint64_t words = nbases / 64 + 1;
+    if ((rc = r->counter.reserve(64))) return rc;
+    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
+    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
+    const bool uniform = r->longest == r->shortest;
+    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
+    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
+    // (the kernel writes every one of the `words` words; the spare words behind them are pack_text's)
+    HIP_TRY(hipMemsetAsync(r->counter.p, 0, 16, r->st));
+    HIP_TRY(hipMemsetAsync((char *)b + 2 * words * 8, 0, 16, r->st));
+    HIP_TRY(hipMemsetAsync((char *)m + words * 8, 0, 16, r->st));
+    hipLaunchKernelGGL(k_sam_pack_seq, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, tb, X, (const uint64_t *)X.base_sz, n, nbases, (uint64_t *)b,
+                       (uint64_t *)m, (unsigned long long *)r->counter.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, r->counter.p, 16, hipMemcpyDeviceToHost, r->st));
+    HIP_TRY(hipStreamSynchronize(r->st));
+    arrays.release();
+    r->packed_is_exact = counts[1] == 0;
+    r->batch_built = true;
+    dev->bases = (const uint64_t *)b;
+    dev->nmask = (const uint64_t *)m;
+    dev->offsets = (const uint64_t *)off;
+    dev->read_len = uniform ? r->longest : 0;
+    return KBBQ_OK;
+}
+
+int kbbq_sam_reader_batch_exact(kbbq_sam_reader *r, int32_t *exact) {
+    if (!r || !exact) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || r->selected >= 0 || !r->batch_built) return fail(KBBQ_ESTATE, "no batch was built for the current chunk");
+    *exact = r->packed_is_exact ? 1 : 0;
     return KBBQ_OK;
 }
 
