@@ -157,20 +157,11 @@ SYMBOLS = {
     "kbbq_bgzf_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "kbbq_host_bgzf_compress": (ctypes.c_int, [c_vp, c_u64, c_vp, c_u64, c_u64p]),
     "kbbq_fastq_reader_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(c_vp)]),
-    "kbbq_fastq_reader_destroy": (None, [c_vp]),
-    "kbbq_fastq_reader_rewind": (ctypes.c_int, [c_vp]),
-    "kbbq_fastq_reader_chunk": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int32, ctypes.POINTER(FastqChunk)]),
-    "kbbq_fastq_reader_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
-    "kbbq_fastq_reader_batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
     "kbbq_fastq_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
-    "kbbq_fastq_reader_keep": (ctypes.c_int, [c_vp, ctypes.c_int32]),
-    "kbbq_fastq_reader_kept": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
-    "kbbq_fastq_reader_select": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_void_p]),
     "kbbq_reads_upload_text": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.c_void_p, ctypes.POINTER(Reads)]),
     "kbbq_fastq_reader_inflate": (ctypes.c_int, [c_vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "kbbq_fastq_reader_attach": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
-    "kbbq_fastq_reader_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "kbbq_fastq_reader_gzip_ms": (ctypes.c_int, [c_vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
     "kbbq_fastq_reader_take_text": (ctypes.c_int, [c_vp, ctypes.c_int32]),
     "kbbq_reads_clone": (ctypes.c_int, [ctypes.POINTER(Reads), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Reads)]),
@@ -188,40 +179,33 @@ SYMBOLS = {
     "kbbq_digest_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64]),
     "kbbq_digest_get": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "kbbq_bgzf_submit_synth": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
-    "kbbq_fastq_reader_preload": (ctypes.c_int, [c_vp, c_vp, c_u64, c_u64]),
-    "kbbq_bam_reader_preload": (ctypes.c_int, [c_vp, c_vp, c_u64, c_u64]),
     "kbbq_bam_reader_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p),
                                               ctypes.c_uint32, ctypes.POINTER(c_vp)]),
-    "kbbq_bam_reader_destroy": (None, [c_vp]),
-    "kbbq_bam_reader_rewind": (ctypes.c_int, [c_vp]),
-    "kbbq_bam_reader_keep": (ctypes.c_int, [c_vp, ctypes.c_int32]),
-    "kbbq_bam_reader_kept": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
-    "kbbq_bam_reader_select": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_void_p]),
-    "kbbq_bam_reader_chunk": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int32, ctypes.POINTER(FastqChunk)]),
-    "kbbq_bam_reader_read_groups": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
-    "kbbq_bam_reader_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
-    "kbbq_bam_reader_any_read_group": (ctypes.c_int, [c_vp, ctypes.c_int32]),
-    "kbbq_bam_reader_batch_seq": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
-    "kbbq_bam_reader_batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
-    "kbbq_bam_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp]),
-    "kbbq_bam_reader_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "kbbq_sam_reader_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32,
                                               ctypes.POINTER(c_vp)]),
-    "kbbq_sam_reader_destroy": (None, [c_vp]),
-    "kbbq_sam_reader_rewind": (ctypes.c_int, [c_vp]),
-    "kbbq_sam_reader_keep": (ctypes.c_int, [c_vp, ctypes.c_int32]),
-    "kbbq_sam_reader_kept": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
-    "kbbq_sam_reader_select": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_void_p]),
-    "kbbq_sam_reader_chunk": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int32, ctypes.POINTER(FastqChunk)]),
-    "kbbq_sam_reader_preload": (ctypes.c_int, [c_vp, c_vp, c_u64, c_u64]),
-    "kbbq_sam_reader_read_groups": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
-    "kbbq_sam_reader_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
-    "kbbq_sam_reader_any_read_group": (ctypes.c_int, [c_vp, ctypes.c_int32]),
-    "kbbq_sam_reader_batch_seq": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
-    "kbbq_sam_reader_batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
-    "kbbq_sam_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp]),
-    "kbbq_sam_reader_kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
+
+# the device readers: what all three declare alike, and what the BAM and the SAM reader add
+for _kind in ("fastq", "bam", "sam"):
+    SYMBOLS.update({"kbbq_%s_reader_%s" % (_kind, _name): _sig for _name, _sig in {
+        "destroy": (None, [c_vp]),
+        "rewind": (ctypes.c_int, [c_vp]),
+        "preload": (ctypes.c_int, [c_vp, c_vp, c_u64, c_u64]),
+        "chunk": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int32, ctypes.POINTER(FastqChunk)]),
+        "batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+        "batch_exact": (ctypes.c_int, [c_vp, c_i32p]),
+        "keep": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+        "kept": (ctypes.c_int, [c_vp, c_u64p, c_u64p]),
+        "select": (ctypes.c_int, [c_vp, c_u64, c_vp]),
+        "kernel_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    }.items()})
+for _kind in ("bam", "sam"):
+    SYMBOLS.update({"kbbq_%s_reader_%s" % (_kind, _name): _sig for _name, _sig in {
+        "read_groups": (ctypes.c_int, [c_vp, c_u32p, ctypes.c_uint32, c_u32p]),
+        "any_read_group": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+        "batch_seq": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+        "write": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp]),
+    }.items()})
 
 _LIB = None
 

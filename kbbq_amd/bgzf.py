@@ -66,227 +66,134 @@ def host_compress(payload):
     return out[:n.value].tobytes()
 
 
-class FastqReader:
-    """A BGZF-compressed four-line FASTQ file read on the device (include/kbbq_bgzf.h: kbbq_fastq_reader)."""
+class _RecordReader:
+    """What the three device readers share (include/kbbq_bgzf.h): a chunk of the file, its batch, its records written again
+    around new qualities, and the chunks of a first scan kept for pass 4.  `kind` names the C functions:
+    kbbq_<kind>_reader_<name>."""
+    kind = None
 
-    def __init__(self, device=0):
+    def _create(self, *args):
         self.L = _lib.lib()
         self.h = _lib.c_vp()
-        _lib.check(self.L.kbbq_fastq_reader_create(device, ctypes.byref(self.h)))
+        self._call("create", *args, ctypes.byref(self.h), handle=False)
+
+    def _call(self, name, *args, handle=True):
+        fn = getattr(self.L, "kbbq_%s_reader_%s" % (self.kind, name))
+        return _lib.check(fn(self.h, *args) if handle else fn(*args))
+
+    def _chunk_info(self, name, *args):
+        info = _lib.FastqChunk()
+        self._call(name, *args, ctypes.byref(info))
+        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
+
+    def _batch(self, name):
+        d = _lib.Reads()
+        self._call(name, ctypes.byref(d))
+        return d
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.kbbq_fastq_reader_destroy(self.h)
+            getattr(self.L, "kbbq_%s_reader_destroy" % self.kind)(self.h)
             self.h = None
 
     def __del__(self):
         self.close()
 
     def rewind(self):
-        _lib.check(self.L.kbbq_fastq_reader_rewind(self.h))
+        self._call("rewind")
+
+    def keep(self, on=True):
+        self._call("keep", 1 if on else 0)
+
+    def kept(self):
+        n, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._call("kept", ctypes.byref(n), ctypes.byref(b))
+        return n.value, b.value
 
     def chunk(self, data, last):
         """Feed bytes of the file; returns the kbbq_fastq_chunk as a dict."""
         a = np.frombuffer(data, dtype=np.uint8)
-        info = _lib.FastqChunk()
-        _lib.check(self.L.kbbq_fastq_reader_chunk(self.h, a.ctypes.data if a.size else None, a.size, 1 if last else 0, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
+        return self._chunk_info("chunk", a.ctypes.data if a.size else None, a.size, 1 if last else 0)
+
+    def select(self, i):
+        return self._chunk_info("select", i)
 
     def batch(self):
-        d = _lib.Reads()
-        _lib.check(self.L.kbbq_fastq_reader_batch(self.h, ctypes.byref(d)))
-        return d
+        return self._batch("batch")
 
     def batch_exact(self):
-        """Whether the batch just built holds nothing but ACGTN / acgt (kbbq_fastq_reader_batch_exact)."""
+        """Whether the batch just built gives its sequence back exactly: FASTQ text of nothing but ACGTN / acgt, BAM or SAM
+        records without a forward-strand base that is none of A/C/G/T/N (kbbq_*_reader_batch_exact)."""
         x = ctypes.c_int32()
-        _lib.check(self.L.kbbq_fastq_reader_batch_exact(self.h, ctypes.byref(x)))
+        self._call("batch_exact", ctypes.byref(x))
         return bool(x.value)
 
-    def write(self, writer, d_qual, after_stream=None):
-        _lib.check(self.L.kbbq_fastq_reader_write(self.h, writer.h, d_qual, after_stream))
+    def write(self, writer, d_qual, set_oq=False, after_stream=None):
+        self._call("write", writer.h, d_qual, 1 if set_oq else 0, after_stream)
 
     def kernel_ms(self):
         a, b = ctypes.c_double(), ctypes.c_double()
-        _lib.check(self.L.kbbq_fastq_reader_kernel_ms(self.h, ctypes.byref(a), ctypes.byref(b)))
+        self._call("kernel_ms", ctypes.byref(a), ctypes.byref(b))
         return dict(inflate=a.value, index=b.value)
 
-    def keep(self, on=True):
-        _lib.check(self.L.kbbq_fastq_reader_keep(self.h, 1 if on else 0))
 
-    def kept(self):
-        n, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _lib.check(self.L.kbbq_fastq_reader_kept(self.h, ctypes.byref(n), ctypes.byref(b)))
-        return n.value, b.value
+class FastqReader(_RecordReader):
+    """A BGZF-compressed four-line FASTQ file read on the device (include/kbbq_bgzf.h: kbbq_fastq_reader)."""
+    kind = "fastq"
 
-    def select(self, i):
-        info = _lib.FastqChunk()
-        _lib.check(self.L.kbbq_fastq_reader_select(self.h, i, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
+    def __init__(self, device=0):
+        self._create(device)
+
+    def write(self, writer, d_qual, after_stream=None):
+        self._call("write", writer.h, d_qual, after_stream)
 
     def attach(self, batch):
-        _lib.check(self.L.kbbq_fastq_reader_attach(self.h, ctypes.byref(batch)))
+        self._call("attach", ctypes.byref(batch))
 
 
-class BamReader:
+class _AlignedReader(_RecordReader):
+    """What the BAM and the SAM reader have beyond the FASTQ reader's: read groups and the sequence-only batch."""
+
+    def _create(self, rg_ids, any_read_group, *args):
+        ids = (ctypes.c_char_p * max(1, len(rg_ids)))(*[i.encode() if isinstance(i, str) else i for i in rg_ids])
+        super()._create(*args, ids, len(rg_ids))
+        if any_read_group:
+            self.any_read_group(True)
+
+    def any_read_group(self, on=True):
+        """Before the first chunk: RG tags are required but not looked up (kbbq_*_reader_any_read_group)."""
+        self._call("any_read_group", 1 if on else 0)
+
+    def read_groups(self):
+        """Table indices (into rg_ids) of the read groups met so far, in dense-index order."""
+        n = ctypes.c_uint32()
+        self._call("read_groups", None, 0, ctypes.byref(n))
+        out = (ctypes.c_uint32 * max(1, n.value))()
+        self._call("read_groups", out, n.value, ctypes.byref(n))
+        return list(out[:n.value])
+
+    def batch_seq(self):
+        """The current chunk as a sequence-only device batch: bases, nmask and lengths, nothing else (kbbq_*_reader_batch_seq)."""
+        return self._batch("batch_seq")
+
+
+class BamReader(_AlignedReader):
     """A BAM file read on the device (include/kbbq_bgzf.h: kbbq_bam_reader): inflate, record chain, field decode, and --
     pass 4 -- the records rewritten around the new qualities.  header_bytes / n_ref / rg_ids come from the caller's own
     parse of the BAM header.  any_read_group: every record must carry an RG tag but its value is not looked up (rg_ids may
     be empty) -- the corrected file of --fixed, read for its sequence alone (batch_seq)."""
+    kind = "bam"
 
     def __init__(self, header_bytes, n_ref, rg_ids, use_oq=False, device=0, any_read_group=False):
-        self.L = _lib.lib()
-        self.h = _lib.c_vp()
-        ids = (ctypes.c_char_p * max(1, len(rg_ids)))(*[i.encode() if isinstance(i, str) else i for i in rg_ids])
-        _lib.check(self.L.kbbq_bam_reader_create(device, 1 if use_oq else 0, n_ref, header_bytes, ids, len(rg_ids), ctypes.byref(self.h)))
-        if any_read_group:
-            self.any_read_group(True)
-
-    def any_read_group(self, on=True):
-        """Before the first chunk: RG tags are required but not looked up (kbbq_bam_reader_any_read_group)."""
-        _lib.check(self.L.kbbq_bam_reader_any_read_group(self.h, 1 if on else 0))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.kbbq_bam_reader_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def rewind(self):
-        _lib.check(self.L.kbbq_bam_reader_rewind(self.h))
-
-    def keep(self, on=True):
-        _lib.check(self.L.kbbq_bam_reader_keep(self.h, 1 if on else 0))
-
-    def kept(self):
-        n, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _lib.check(self.L.kbbq_bam_reader_kept(self.h, ctypes.byref(n), ctypes.byref(b)))
-        return n.value, b.value
-
-    def chunk(self, data, last):
-        a = np.frombuffer(data, dtype=np.uint8)
-        info = _lib.FastqChunk()
-        _lib.check(self.L.kbbq_bam_reader_chunk(self.h, a.ctypes.data if a.size else None, a.size, 1 if last else 0, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
-
-    def select(self, i):
-        info = _lib.FastqChunk()
-        _lib.check(self.L.kbbq_bam_reader_select(self.h, i, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
-
-    def read_groups(self):
-        """Table indices (into rg_ids) of the read groups met so far, in dense-index order."""
-        n = ctypes.c_uint32()
-        _lib.check(self.L.kbbq_bam_reader_read_groups(self.h, None, 0, ctypes.byref(n)))
-        out = (ctypes.c_uint32 * max(1, n.value))()
-        _lib.check(self.L.kbbq_bam_reader_read_groups(self.h, out, n.value, ctypes.byref(n)))
-        return list(out[:n.value])
-
-    def batch(self):
-        d = _lib.Reads()
-        _lib.check(self.L.kbbq_bam_reader_batch(self.h, ctypes.byref(d)))
-        return d
-
-    def batch_seq(self):
-        """The current chunk as a sequence-only device batch: bases, nmask and lengths, nothing else (kbbq_bam_reader_batch_seq)."""
-        d = _lib.Reads()
-        _lib.check(self.L.kbbq_bam_reader_batch_seq(self.h, ctypes.byref(d)))
-        return d
-
-    def batch_exact(self):
-        """Whether no forward-strand base of the batch just built is anything but A/C/G/T/N (kbbq_bam_reader_batch_exact)."""
-        x = ctypes.c_int32()
-        _lib.check(self.L.kbbq_bam_reader_batch_exact(self.h, ctypes.byref(x)))
-        return bool(x.value)
-
-    def write(self, writer, d_qual, set_oq=False, after_stream=None):
-        _lib.check(self.L.kbbq_bam_reader_write(self.h, writer.h, d_qual, 1 if set_oq else 0, after_stream))
-
-    def kernel_ms(self):
-        a, b = ctypes.c_double(), ctypes.c_double()
-        _lib.check(self.L.kbbq_bam_reader_kernel_ms(self.h, ctypes.byref(a), ctypes.byref(b)))
-        return dict(inflate=a.value, index=b.value)
+        self._create(rg_ids, any_read_group, device, 1 if use_oq else 0, n_ref, header_bytes)
 
 
-class SamReader:
+class SamReader(_AlignedReader):
     """SAM text -- BGZF, any other gzip stream or uncompressed, in pieces of any size -- read on the device
     (include/kbbq_bgzf.h: kbbq_sam_reader): the lines indexed, their fields decoded as the BAM twin's, and -- pass 4 -- the
     lines written again around the new qualities.  header_bytes (the size of the leading '@' lines) and rg_ids come from
     the caller's own parse of the header.  any_read_group: as BamReader's."""
+    kind = "sam"
 
     def __init__(self, header_bytes, rg_ids, use_oq=False, device=0, any_read_group=False):
-        self.L = _lib.lib()
-        self.h = _lib.c_vp()
-        ids = (ctypes.c_char_p * max(1, len(rg_ids)))(*[i.encode() if isinstance(i, str) else i for i in rg_ids])
-        _lib.check(self.L.kbbq_sam_reader_create(device, 1 if use_oq else 0, header_bytes, ids, len(rg_ids), ctypes.byref(self.h)))
-        if any_read_group:
-            self.any_read_group(True)
-
-    def any_read_group(self, on=True):
-        """Before the first chunk: RG tags are required but not looked up (kbbq_sam_reader_any_read_group)."""
-        _lib.check(self.L.kbbq_sam_reader_any_read_group(self.h, 1 if on else 0))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.kbbq_sam_reader_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def rewind(self):
-        _lib.check(self.L.kbbq_sam_reader_rewind(self.h))
-
-    def keep(self, on=True):
-        _lib.check(self.L.kbbq_sam_reader_keep(self.h, 1 if on else 0))
-
-    def kept(self):
-        n, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _lib.check(self.L.kbbq_sam_reader_kept(self.h, ctypes.byref(n), ctypes.byref(b)))
-        return n.value, b.value
-
-    def chunk(self, data, last):
-        a = np.frombuffer(data, dtype=np.uint8)
-        info = _lib.FastqChunk()
-        _lib.check(self.L.kbbq_sam_reader_chunk(self.h, a.ctypes.data if a.size else None, a.size, 1 if last else 0, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
-
-    def select(self, i):
-        info = _lib.FastqChunk()
-        _lib.check(self.L.kbbq_sam_reader_select(self.h, i, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FastqChunk._fields_}
-
-    def read_groups(self):
-        """Table indices (into rg_ids) of the read groups met so far, in dense-index order."""
-        n = ctypes.c_uint32()
-        _lib.check(self.L.kbbq_sam_reader_read_groups(self.h, None, 0, ctypes.byref(n)))
-        out = (ctypes.c_uint32 * max(1, n.value))()
-        _lib.check(self.L.kbbq_sam_reader_read_groups(self.h, out, n.value, ctypes.byref(n)))
-        return list(out[:n.value])
-
-    def batch(self):
-        d = _lib.Reads()
-        _lib.check(self.L.kbbq_sam_reader_batch(self.h, ctypes.byref(d)))
-        return d
-
-    def batch_seq(self):
-        """The current chunk as a sequence-only device batch: bases, nmask and lengths, nothing else (kbbq_sam_reader_batch_seq)."""
-        d = _lib.Reads()
-        _lib.check(self.L.kbbq_sam_reader_batch_seq(self.h, ctypes.byref(d)))
-        return d
-
-    def batch_exact(self):
-        """Whether no forward-strand base of the batch just built is anything but A/C/G/T/N (kbbq_sam_reader_batch_exact)."""
-        x = ctypes.c_int32()
-        _lib.check(self.L.kbbq_sam_reader_batch_exact(self.h, ctypes.byref(x)))
-        return bool(x.value)
-
-    def write(self, writer, d_qual, set_oq=False, after_stream=None):
-        _lib.check(self.L.kbbq_sam_reader_write(self.h, writer.h, d_qual, 1 if set_oq else 0, after_stream))
-
-    def kernel_ms(self):
-        a, b = ctypes.c_double(), ctypes.c_double()
-        _lib.check(self.L.kbbq_sam_reader_kernel_ms(self.h, ctypes.byref(a), ctypes.byref(b)))
-        return dict(inflate=a.value, index=b.value)
+        self._create(rg_ids, any_read_group, device, 1 if use_oq else 0, header_bytes)

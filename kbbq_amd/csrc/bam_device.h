@@ -363,14 +363,6 @@ __global__ void __launch_bounds__(256) k_bam_records(const uint8_t *text, uint64
     if (__hip_atomic_load(&out[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > l_seq) atomicMin(&out[2], l_seq);
 }
 
-// second-in-pair flags (readutils.cc:59) and the dense read-group index of every record
-__global__ void __launch_bounds__(256) k_bam_read_meta(BamIndex X, uint64_t n_records, const uint16_t *dense, uint8_t *second, uint16_t *rg) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_records) return;
-    second[r] = (X.flag[r] & 0x80) ? 1 : 0;
-    rg[r] = dense[X.rg[r]];
-}
-
 __global__ void __launch_bounds__(256) k_bam_gather(const uint8_t *text, BamIndex X, const uint64_t *base_off, uint64_t n_records, int use_oq,
                                                      uint8_t *seq_text, uint8_t *qual) {
     const int lane = threadIdx.x & 63;
@@ -384,11 +376,11 @@ __global__ void __launch_bounds__(256) k_bam_gather(const uint8_t *text, BamInde
             const uint32_t code = (s[i >> 1] >> ((~i & 1) << 2)) & 15;      // bam_seqi
             const uint8_t qv = use_oq ? (uint8_t)(q[i] - 33) : q[i];
             if (!rev) {
-                seq_text[at + i] = (uint8_t)"=ACMGRSVTWYHKDBN"[code];       // seq_nt16_str
+                seq_text[at + i] = seq_str_char(code, false);
                 qual[at + i] = qv;
             } else {
-                // readutils.hh:35-36: the complement of A/C/G/T, 'N' for every other code; then reversed (with the qualities)
-                const uint8_t c = code == 1 ? 'T' : code == 2 ? 'G' : code == 4 ? 'C' : code == 8 ? 'A' : 'N';
+                // complemented, then reversed (with the qualities)
+                const uint8_t c = seq_str_char(code, true);
                 seq_text[at + (n - 1 - i)] = c;
                 qual[at + (n - 1 - i)] = qv;
             }

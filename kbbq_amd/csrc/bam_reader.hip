@@ -1,7 +1,11 @@
 // bam_reader.hip -- host side of kbbq_bam_reader (include/kbbq_bgzf.h): buffers, the chunk loop and the launches of
-// bam_device.h's kernels (MI355X, gfx950).  The BGZF walk, the inflate launch, the scan, the text packing and the hand-over
-// to the writer are io_common.h's.
-#include "io_common.h"
+// bam_device.h's kernels (MI355X, gfx950).  The stream and its scratch (ReaderStream), the BGZF walk, the inflate launch,
+// the scan and the text packing are io_common.h's; the batch builder, the pass-4 submission and the entry points every
+// reader has are record_batch.h's, shared with the FASTQ and the SAM reader; the read-group table is rg_table.h's.
+//
+// Unlike those two readers, this one keeps the COMPRESSED bytes of a chunk for pass 4: select inflates and indexes them
+// again, so a selected chunk is a current chunk like any other -- batch, batch_seq and batch_exact do not refuse it.
+#include "record_batch.h"
 #include "rg_table.h"
 
 #include "bam_device.h"
@@ -9,18 +13,12 @@
 using namespace kbbq::dfl;
 using namespace kbbq::io;
 
-struct kbbq_bam_reader {
-    Preload pre;                            // pieces of the file copied ahead of their chunk call (kbbq_bam_reader_preload)
-    int device = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+struct kbbq_bam_reader : ReaderStream, ChunkState {
     int use_oq = 0;
-    int any_rg = 0;                         // kbbq_bam_reader_any_read_group: RG tags are required, their values not looked up
-    bool fed = false;                       // a chunk call was made: the mode above no longer changes
     int32_t n_ref = 0;
     uint64_t header_left = 0;               // bytes of the BAM header still to skip at the front of the stream
     uint64_t header_bytes = 0;
-    Buf comp, text, h_small, carry, tile_sums;
+    Buf comp, text, carry;
     Inflater inf;
     Buf seg_u32, seg_slots, seg_counts;     // BamSegs
     Buf idx_u32, idx_u16, idx_u64;          // BamIndex
@@ -29,11 +27,9 @@ struct kbbq_bam_reader {
     Buf seq_text, counter;                  // scratch of kbbq_bam_reader_batch
     uint64_t carry_bytes = 0;
     // the current chunk
-    uint64_t text_bytes = 0, n_records = 0, n_bases = 0, idx_cap = 0;
+    uint64_t text_bytes = 0, n_records = 0, n_bases = 0;
+    size_t idx_cap = 0;
     uint32_t longest = 0, shortest = 0, chunk_flags = 0;
-    bool have_chunk = false;
-    bool batch_built = false, packed_is_exact = false;      // kbbq_bam_reader_batch_exact: of the current chunk's batch
-    double ms_inflate = 0, ms_index = 0, ms_rewrite = 0;
     // chunks of the first scan kept for pass 4: the COMPRESSED bytes (a third of the stream) with their block table and the
     // bytes the chunk before them left over; pass 4 inflates and indexes them again (kbbq_bam_reader_select)
     struct Kept {
@@ -48,7 +44,7 @@ struct kbbq_bam_reader {
 
 namespace {
 
-void bam_release_kept(kbbq_bam_reader *r) {
+void release_kept(kbbq_bam_reader *r) {
     for (auto &k : r->kept) { k.comp.release(); k.carry.release(); }
     r->kept.clear();
     r->kept_bytes = 0;
@@ -137,17 +133,16 @@ int bam_index_stream(kbbq_bam_reader *r, uint64_t text, uint64_t skip, int32_t l
         if (chain_flags & 6) info->flags |= BAMF_FALLBACK;      // too many repairs, or a malformed block: the host parsers' case
         if (rec_end > text) { info->flags |= BAMF_FALLBACK; rec_end = text; }
         if (n_rec && !(info->flags & BAMF_FALLBACK)) {
-            if (r->idx_cap < n_rec) {
-                const size_t cap = n_rec + n_rec / 8 + 1024;
-                r->idx_cap = 0;
-                if ((rc = r->idx_u32.reserve(cap * 7 * 4))) return rc;
-                if ((rc = r->idx_u16.reserve(cap * 2 * 2))) return rc;
-                if ((rc = r->idx_u64.reserve((cap + 2) * 2 * 8))) return rc;
-                r->idx_cap = cap;
-            }
+            rc = grow_index(r->idx_cap, n_rec, [r](size_t cap) {
+                int e;
+                if ((e = r->idx_u32.reserve(cap * 7 * 4))) return e;
+                if ((e = r->idx_u16.reserve(cap * 2 * 2))) return e;
+                return r->idx_u64.reserve((cap + 2) * 2 * 8);
+            });
+            if (rc) return rc;
             const BamIndex X = bam_index(r);
             hipLaunchKernelGGL(k_bam_rec_offsets, dim3(n_segs), dim3(256), 0, r->st, G, (const uint64_t *)counts, (uint32_t)bias, X.rec_off);
-            hipLaunchKernelGGL(k_bam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, t, n_rec, r->use_oq, r->any_rg, r->groups.table(), X, out + 4,
+            hipLaunchKernelGGL(k_bam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, t, n_rec, r->use_oq, r->groups.any_rg, r->groups.table(), X, out + 4,
                                (unsigned long long *)r->groups.first_seen.p);
             HIP_TRY(hipGetLastError());
             if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
@@ -181,11 +176,18 @@ int bam_index_stream(kbbq_bam_reader *r, uint64_t text, uint64_t skip, int32_t l
     info->n_bases = r->n_bases;
     info->longest = r->n_records ? r->longest : 0;
     info->shortest = r->n_records ? r->shortest : 0;
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, r->t0, r->t1) == hipSuccess) r->ms_inflate += a;
-    if (hipEventElapsedTime(&b, r->t1, r->t2) == hipSuccess) r->ms_index += b;
+    r->add_times();
     return KBBQ_OK;
 }
+
+// the argument and state checks of batch and batch_seq (a selected chunk was indexed again: it is not refused)
+int batchable(const kbbq_bam_reader *r, const kbbq_reads *dev) {
+    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->chunk_flags & BAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host parser's", r->chunk_flags);
+    return KBBQ_OK;
+}
+BatchShape batch_shape(const kbbq_bam_reader *r, const BamIndex &X) { return BatchShape{r->n_records, r->n_bases, r->longest, r->shortest, X.base_sz}; }
 
 }  // namespace
 
@@ -195,38 +197,28 @@ void kbbq_bam_reader_destroy(kbbq_bam_reader *r) {
     if (!r) return;
     KbbqDeviceGuard guard(r->device);
     if (r->st) (void)hipStreamSynchronize(r->st);
-    Buf *all[] = {&r->comp, &r->text, &r->h_small, &r->carry, &r->tile_sums, &r->seg_u32, &r->seg_slots,
-                  &r->seg_counts, &r->idx_u32, &r->idx_u16, &r->idx_u64, &r->d_out, &r->seq_text, &r->counter};
+    Buf *all[] = {&r->comp, &r->text, &r->carry, &r->seg_u32, &r->seg_slots, &r->seg_counts, &r->idx_u32, &r->idx_u16, &r->idx_u64, &r->d_out, &r->seq_text,
+                  &r->counter};
     for (Buf *b : all) b->release();
     r->groups.release();
     r->inf.release();
-    r->pre.release();
-    bam_release_kept(r);
-    hipEvent_t evs[] = {r->t0, r->t1, r->t2};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    if (r->st) (void)hipStreamDestroy(r->st);
+    release_kept(r);
+    r->destroy();
     delete r;
 }
 
 int kbbq_bam_reader_create(int32_t device, int32_t use_oq, int32_t n_ref, uint64_t header_bytes, const char *const *rg_ids, uint32_t n_rg_ids,
                            kbbq_bam_reader **out) {
-    if (!out || (n_rg_ids && !rg_ids)) return fail(KBBQ_EINVAL, "null argument");
-    if (n_rg_ids > 65535) return fail(KBBQ_ERANGE, "%u @RG lines: read-group indices travel in 16 bits", n_rg_ids);
-    int rc = device_exists(device);
-    if (rc) return rc;
+    int rc = RgGroups::check_args(out, rg_ids, n_rg_ids);
+    if (rc || (rc = device_exists(device))) return rc;
     KbbqDeviceGuard guard(device);
     HIP_TRY(guard.err);
     kbbq_bam_reader *r = new kbbq_bam_reader;
-    r->device = device;
     r->use_oq = use_oq ? 1 : 0;
     r->n_ref = n_ref;
     r->header_bytes = r->header_left = header_bytes;
-    r->h_small.host = true;
-    hipError_t he = hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipEventCreate(&r->t0);
-    if (he == hipSuccess) he = hipEventCreate(&r->t1);
-    if (he == hipSuccess) he = hipEventCreate(&r->t2);
-    if (he == hipSuccess) rc = r->groups.create(rg_ids, n_rg_ids);
+    hipError_t he = hipSuccess;
+    if (r->create(device, &he)) rc = r->groups.create(rg_ids, n_rg_ids);
     if (he != hipSuccess || rc) {
         kbbq_bam_reader_destroy(r);
         return rc ? rc : fail(KBBQ_EIO, "creating the BAM reader: %s", hipGetErrorString(he));
@@ -247,25 +239,10 @@ int kbbq_bam_reader_rewind(kbbq_bam_reader *r) {
 
 int kbbq_bam_reader_any_read_group(kbbq_bam_reader *r, int32_t on) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (r->fed) return fail(KBBQ_ESTATE, "the read-group mode is set before the first chunk");
-    r->any_rg = on ? 1 : 0;
-    return KBBQ_OK;
+    return r->groups.set_any(on);
 }
 
-int kbbq_bam_reader_keep(kbbq_bam_reader *r, int32_t on) {
-    if (!r) return fail(KBBQ_EINVAL, "null argument");
-    KbbqDeviceGuard guard(r->device);
-    HIP_TRY(guard.err);
-    if (on) {
-        if (r->have_chunk || !r->kept.empty()) return fail(KBBQ_ESTATE, "keeping starts before the first chunk of a scan");
-        r->keeping = true;
-    } else {
-        HIP_TRY(hipStreamSynchronize(r->st));
-        bam_release_kept(r);
-        r->keeping = false;
-    }
-    return KBBQ_OK;
-}
+int kbbq_bam_reader_keep(kbbq_bam_reader *r, int32_t on) { return reader_keep(r, on, release_kept); }
 
 int kbbq_bam_reader_kept(kbbq_bam_reader *r, uint64_t *n_chunks, uint64_t *n_bytes) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
@@ -276,9 +253,7 @@ int kbbq_bam_reader_kept(kbbq_bam_reader *r, uint64_t *n_chunks, uint64_t *n_byt
 
 int kbbq_bam_reader_read_groups(kbbq_bam_reader *r, uint32_t *table_index, uint32_t capacity, uint32_t *n) {
     if (!r || !n) return fail(KBBQ_EINVAL, "null argument");
-    *n = (uint32_t)r->groups.order.size();
-    for (uint32_t i = 0; i < *n && i < capacity && table_index; ++i) table_index[i] = r->groups.order[i];
-    return KBBQ_OK;
+    return r->groups.list(table_index, capacity, n);
 }
 
 int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, int32_t last, kbbq_bam_chunk *info) {
@@ -288,7 +263,7 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
     memset(info, 0, sizeof *info);
     r->have_chunk = false;
     r->batch_built = false;
-    r->fed = true;
+    r->groups.fed = true;
     BlockTable T;
     if (walk_blocks(file_bytes, n_bytes, r->carry_bytes, TEXT_CAP, T).why != WALK_END) { info->flags |= BAMF_FALLBACK; return KBBQ_OK; }      // (consumed 0)
     const uint64_t at = T.consumed, text = T.text;
@@ -298,7 +273,7 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
     int rc;
     auto drop_kept = [r] {
         if (!r->keeping && r->kept.empty()) return false;
-        bam_release_kept(r);
+        release_kept(r);
         r->keeping = false;
         return true;
     };
@@ -324,7 +299,7 @@ int kbbq_bam_reader_chunk(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_
         if (k.comp.reserve(at + 4096) || (carry_in && k.carry.reserve(carry_in + 64))) {
             (void)hipGetLastError();
             k.comp.release(); k.carry.release();
-            bam_release_kept(r);
+            release_kept(r);
             r->keeping = false;
             keep_this = false;
         } else {
@@ -375,102 +350,40 @@ int kbbq_bam_reader_select(kbbq_bam_reader *r, uint64_t i, kbbq_bam_chunk *info)
 }
 
 int kbbq_bam_reader_batch(kbbq_bam_reader *r, kbbq_reads *dev) {
-    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
-    if (r->chunk_flags & BAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host parser's", r->chunk_flags);
+    int rc = batchable(r, dev);
+    if (rc) return rc;
     KbbqDeviceGuard guard(r->device);
     HIP_TRY(guard.err);
-    const uint64_t n = r->n_records, nbases = r->n_bases;
     const BamIndex X = bam_index(r);
-    memset(dev, 0, sizeof *dev);
-    dev->n_reads = n;
-    dev->n_bases = nbases;
-    dev->on_device = 1;
-    void *b = nullptr, *m = nullptr, *q = nullptr, *off = nullptr, *fl = nullptr, *rg = nullptr;
-    BatchArrays arrays;
-    int rc;
-    const uint64_t words = nbases / 64 + 1;
-    if ((rc = r->seq_text.reserve(nbases + 64))) return rc;
-    if ((rc = r->counter.reserve((words + 2) * 8 + 64))) return rc;      // [0..1] counts, then the (always empty) off-case words
-    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&q, nbases + 16))) return rc;
-    if ((rc = arrays.alloc(&fl, n))) return rc;
-    if ((rc = arrays.alloc(&rg, n * 2 + 16))) return rc;
-    const bool uniform = r->longest == r->shortest;
-    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
-    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));      // (in front of the kernels, not between them)
-    HIP_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
-    hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
-                       (const uint64_t *)X.base_sz, n, r->use_oq, (uint8_t *)r->seq_text.p, (uint8_t *)q);
-    hipLaunchKernelGGL(k_bam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->groups.dense.p, (uint8_t *)fl,
-                       (uint16_t *)rg);
-    HIP_TRY(hipGetLastError());
-    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch.  The second count is the
-    // forward-strand bases that are none of A/C/G/T/N: kbbq_bam_reader_batch_exact)
-    unsigned long long counts[2] = {0, 0};
-    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, counts))) return rc;
-    arrays.release();
-    r->packed_is_exact = counts[1] == 0;
-    r->batch_built = true;
-    dev->bases = (const uint64_t *)b;
-    dev->nmask = (const uint64_t *)m;
-    dev->qual = (const uint8_t *)q;
-    dev->offsets = (const uint64_t *)off;
-    dev->flags = (const uint8_t *)fl;
-    dev->rg = (const uint16_t *)rg;
-    dev->read_len = uniform ? r->longest : 0;
-    dev->offcase = nullptr;
-    return KBBQ_OK;
+    const BatchShape S = batch_shape(r, X);
+    const uint64_t n = r->n_records;
+    // (no off-case bits; counter: [0..1] counts, then the always empty off-case words)
+    return build_batch(r->st, S, r->seq_text, r->counter, (S.words() + 2) * 8 + 64, true, false,
+                       [&](uint8_t *seq_text, uint8_t *q, uint8_t *fl, uint16_t *rg) {
+                           hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
+                                              (const uint64_t *)X.base_sz, n, r->use_oq, seq_text, q);
+                           return read_meta(r->st, X.flag, X.rg, n, (const uint16_t *)r->groups.dense.p, fl, rg);
+                       },
+                       dev, *r);
 }
 
 int kbbq_bam_reader_batch_seq(kbbq_bam_reader *r, kbbq_reads *dev) {
-    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
-    if (r->chunk_flags & BAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host parser's", r->chunk_flags);
+    int rc = batchable(r, dev);
+    if (rc) return rc;
     KbbqDeviceGuard guard(r->device);
     HIP_TRY(guard.err);
-    const uint64_t n = r->n_records, nbases = r->n_bases;
     const BamIndex X = bam_index(r);
-    memset(dev, 0, sizeof *dev);
-    dev->n_reads = n;
-    dev->n_bases = nbases;
-    dev->on_device = 1;
-    void *b = nullptr, *m = nullptr, *off = nullptr;
-    BatchArrays arrays;
-    int rc;
-    const uint64_t words = nbases / 64 + 1;
-    if ((rc = r->counter.reserve(64))) return rc;
-    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
-    const bool uniform = r->longest == r->shortest;
-    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
-    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
-    // (the kernel writes every one of the `words` words; the spare words behind them are pack_text's)
-    HIP_TRY(hipMemsetAsync(r->counter.p, 0, 16, r->st));
-    HIP_TRY(hipMemsetAsync((char *)b + 2 * words * 8, 0, 16, r->st));
-    HIP_TRY(hipMemsetAsync((char *)m + words * 8, 0, 16, r->st));
-    hipLaunchKernelGGL(k_bam_pack_seq, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X, (const uint64_t *)X.base_sz, n,
-                       nbases, (uint64_t *)b, (uint64_t *)m, (unsigned long long *)r->counter.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, r->counter.p, 16, hipMemcpyDeviceToHost, r->st));
-    HIP_TRY(hipStreamSynchronize(r->st));
-    arrays.release();
-    r->packed_is_exact = counts[1] == 0;
-    r->batch_built = true;
-    dev->bases = (const uint64_t *)b;
-    dev->nmask = (const uint64_t *)m;
-    dev->offsets = (const uint64_t *)off;
-    dev->read_len = uniform ? r->longest : 0;
-    return KBBQ_OK;
+    return build_batch_seq(r->st, batch_shape(r, X), r->counter,
+                           [&](uint64_t words, uint64_t *b, uint64_t *m, unsigned long long *counts) {
+                               hipLaunchKernelGGL(k_bam_pack_seq, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
+                                                  (const uint64_t *)X.base_sz, r->n_records, r->n_bases, b, m, counts);
+                           },
+                           dev, *r);
 }
 
 int kbbq_bam_reader_batch_exact(kbbq_bam_reader *r, int32_t *exact) {
     if (!r || !exact) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || !r->batch_built) return fail(KBBQ_ESTATE, "no batch was built for the current chunk");
-    *exact = r->packed_is_exact ? 1 : 0;
-    return KBBQ_OK;
+    return r->batch_exact(false, exact);      // (a selected chunk is no other than a live one)
 }
 
 int kbbq_bam_reader_write(kbbq_bam_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, int32_t set_oq, void *after_stream) {
@@ -483,44 +396,22 @@ int kbbq_bam_reader_write(kbbq_bam_reader *r, kbbq_bgzf *z, const uint8_t *d_qua
     HIP_TRY(guard.err);
     const uint64_t n = r->n_records;
     const BamIndex X = bam_index(r);
-    int rc;
-    // sizes of the rewritten records and where they go
-    hipLaunchKernelGGL(k_bam_out_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X, n, set_oq ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    if ((rc = device_scan_on(r->tile_sums, r->st, X.out_sz, n, X.out_sz + n))) return rc;
-    uint64_t *hs = (uint64_t *)r->h_small.p;
-    HIP_TRY(hipMemcpyAsync(hs, X.out_sz + n, 8, hipMemcpyDeviceToHost, r->st));
-    HIP_TRY(hipStreamSynchronize(r->st));
-    const uint64_t t = hs[0];
-    Submission *sp;
-    if ((rc = begin_submission(z, after_stream, &sp))) return rc;
-    Submission &s = *sp;
-    s.n = t;
-    s.formatted = true;
-    if ((rc = s.payload.reserve(t + 16))) return rc;
-    HIP_TRY(hipMemsetAsync((char *)s.payload.p + t, 0, 16, z->st));
-    HIP_TRY(hipEventRecord(s.t0, z->st));
-    hipLaunchKernelGGL(k_bam_rewrite, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, (const uint8_t *)r->text.p, X,
-                       (const uint64_t *)X.base_sz, (const uint64_t *)X.out_sz, n, set_oq ? 1 : 0, d_qual, (uint8_t *)s.payload.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = launch_deflate(z, s))) return rc;
-    // the reader's stream and index are read by the kernel just queued: the next chunk must not overwrite them before it has run
-    HIP_TRY(hipEventSynchronize(s.t1));
-    return KBBQ_OK;
+    const uint8_t *text = (const uint8_t *)r->text.p;
+    const int oq = set_oq ? 1 : 0;
+    uint64_t total = 0;
+    int rc = rewrite_total(*r, X.out_sz, n, [&] { hipLaunchKernelGGL(k_bam_out_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, text, X, n, oq); }, &total);
+    if (rc) return rc;
+    // (waits: the reader's stream and index are read by the kernel queued, the next chunk must not overwrite them before it has run)
+    return submit_rewrite(z, after_stream, total, true, [&](uint8_t *payload) {
+        hipLaunchKernelGGL(k_bam_rewrite, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, text, X, (const uint64_t *)X.base_sz,
+                           (const uint64_t *)X.out_sz, n, oq, d_qual, payload);
+    });
 }
 
 int kbbq_bam_reader_preload(kbbq_bam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint64_t front_room) {
-    if (!r || !file_bytes || !n_bytes) return fail(KBBQ_EINVAL, "bad argument");
-    KbbqDeviceGuard guard(r->device);
-    HIP_TRY(guard.err);
-    return r->pre.start(file_bytes, n_bytes, front_room);
+    return reader_preload(r, file_bytes, n_bytes, front_room);
 }
 
-int kbbq_bam_reader_kernel_ms(kbbq_bam_reader *r, double *inflate_ms, double *index_ms) {
-    if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (inflate_ms) *inflate_ms = r->ms_inflate;
-    if (index_ms) *index_ms = r->ms_index;
-    return KBBQ_OK;
-}
+int kbbq_bam_reader_kernel_ms(kbbq_bam_reader *r, double *inflate_ms, double *index_ms) { return reader_kernel_ms(r, inflate_ms, index_ms); }
 
 }  // extern "C"

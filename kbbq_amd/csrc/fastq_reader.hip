@@ -2,7 +2,11 @@
 // read on the device (MI355X, gfx950).  A chunk call reads top to bottom as: detect the container, obtain the text (BGZF
 // blocks through io_common.h's walk and inflate, a gzip stream through gzip_stream.h, or the bytes themselves), index the
 // lines -- all of that text_chunks.h's, which the SAM reader shares -- index the records (fastq_device.h), carry over what
-// the chunk's end cut.
+// the chunk's end cut.  The batch builder, the pass-4 submission and the entry points every reader has are record_batch.h's,
+// shared with the BAM and the SAM reader.
+//
+// A kept chunk is text and index, or names and comments alone, for write(): batch and batch_exact refuse a selected chunk.
+#include "record_batch.h"
 #include "text_chunks.h"
 
 #include "fastq_device.h"
@@ -17,10 +21,10 @@ struct FastqCounts {
     uint32_t longest = 0, shortest = 0;
 };
 
-struct kbbq_fastq_reader : FastqCounts, TextChunks {      // (the stream, the text, the newline index, the carry: TextChunks)
+// (the stream, the text, the newline index, the carry: TextChunks; packed_is_exact: the batch gives the sequence text back)
+struct kbbq_fastq_reader : FastqCounts, TextChunks, ChunkState {
     Buf idx_u32, idx_second, base_sz, text_sz, flags;      // record index (FastqIndex)
     Buf seq_text, counter;                  // scratch of kbbq_fastq_reader_batch (the chunk's sequence lines back to back)
-    bool have_chunk = false;
     // chunks of the first scan that stay in device memory (kbbq_fastq_reader_keep): their text and record index
     // Two forms: the whole text with its record index, or -- when the chunk's batch was built and its sequence lines hold
     // nothing but ACGTN / acgt, so that the packed batch gives them back exactly -- only names and comments (a seventh of the
@@ -30,8 +34,6 @@ struct kbbq_fastq_reader : FastqCounts, TextChunks {      // (the stream, the te
         Buf names, lens;            // the short form: names + comments back to back, (name, comment) lengths
         bool short_form = false;
     };
-    bool packed_is_exact = false;              // the current chunk's batch gives its sequence text back (set by batch())
-    bool batch_built = false;                  // batch() ran for the current chunk: packed_is_exact is known
     const uint64_t *att_bases = nullptr, *att_nmask = nullptr, *att_offcase = nullptr;      // kbbq_fastq_reader_attach
     std::vector<Kept> kept;
     // the short form's arrays are carved from slabs of 2 GB (four hipMalloc per chunk were four trips to the driver)
@@ -43,10 +45,6 @@ struct kbbq_fastq_reader : FastqCounts, TextChunks {      // (the stream, the te
 };
 
 namespace {
-
-int device_scan(kbbq_fastq_reader *r, uint64_t *d, uint64_t n, uint64_t *d_total /* device */) {
-    return device_scan_on(r->tile_sums, r->st, d, n, d_total);
-}
 
 FastqIndex index_from(void *idx_u32, void *second, void *base_sz, void *text_sz, void *flags, uint64_t cap) {
     FastqIndex X;
@@ -94,9 +92,11 @@ void *slab_piece(kbbq_fastq_reader *r, size_t bytes) {
     return p;
 }
 
+bool live_is_keepable(const kbbq_fastq_reader *r) { return r->keeping && r->selected < 0 && r->have_chunk && r->n_records; }
+
 // The live chunk moves into the kept list (its buffers with it: the next chunk allocates its own).
 void stash_current(kbbq_fastq_reader *r) {
-    if (!r->keeping || r->selected >= 0 || !r->have_chunk || !r->n_records) return;
+    if (!live_is_keepable(r)) return;
     kbbq_fastq_reader::Kept k;
     static_cast<FastqCounts &>(k) = *r;
     const uint64_t n = r->n_records;
@@ -139,7 +139,6 @@ bool drop_kept(kbbq_fastq_reader *r) {
     r->keeping = false;
     return true;
 }
-int reserve_or_drop_kept(kbbq_fastq_reader *r, Buf &b, size_t need) { return r->reserve(b, need); }
 
 }  // namespace
 
@@ -185,26 +184,13 @@ int kbbq_fastq_reader_rewind(kbbq_fastq_reader *r) {
     return KBBQ_OK;
 }
 
-int kbbq_fastq_reader_keep(kbbq_fastq_reader *r, int32_t on) {
-    if (!r) return fail(KBBQ_EINVAL, "null argument");
-    KbbqDeviceGuard guard(r->device);
-    HIP_TRY(guard.err);
-    if (on) {
-        if (r->have_chunk || !r->kept.empty()) return fail(KBBQ_ESTATE, "keeping starts before the first chunk of a scan");
-        r->keeping = true;
-    } else {
-        HIP_TRY(hipStreamSynchronize(r->st));
-        release_kept(r);
-        r->keeping = false;
-    }
-    return KBBQ_OK;
-}
+int kbbq_fastq_reader_keep(kbbq_fastq_reader *r, int32_t on) { return reader_keep(r, on, release_kept); }
 
 int kbbq_fastq_reader_kept(kbbq_fastq_reader *r, uint64_t *n_chunks, uint64_t *n_bytes) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (n_chunks) *n_chunks = r->kept.size() + ((r->keeping && r->selected < 0 && r->have_chunk && r->n_records) ? 1 : 0);
-    if (n_bytes) *n_bytes = r->kept_bytes + ((r->keeping && r->selected < 0 && r->have_chunk && r->n_records)
-                                                 ? r->text.bytes + r->idx_u32.bytes + r->base_sz.bytes + r->text_sz.bytes : 0);
+    const bool live = live_is_keepable(r);
+    if (n_chunks) *n_chunks = r->kept.size() + (live ? 1 : 0);
+    if (n_bytes) *n_bytes = r->kept_bytes + (live ? r->text.bytes + r->idx_u32.bytes + r->base_sz.bytes + r->text_sz.bytes : 0);
     return KBBQ_OK;
 }
 
@@ -253,10 +239,10 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     if (n_rec) {
         if ((rc = r->line_positions(0, text, n_lines))) return rc;
         // ---- records
-        if ((rc = reserve_or_drop_kept(r, r->idx_u32, n_rec * 7 * 4))) return rc;
+        if ((rc = r->reserve(r->idx_u32, n_rec * 7 * 4))) return rc;
         if ((rc = r->idx_second.reserve(n_rec))) return rc;
-        if ((rc = reserve_or_drop_kept(r, r->base_sz, (n_rec + 2) * 8))) return rc;
-        if ((rc = reserve_or_drop_kept(r, r->text_sz, (n_rec + 2) * 8))) return rc;
+        if ((rc = r->reserve(r->base_sz, (n_rec + 2) * 8))) return rc;
+        if ((rc = r->reserve(r->text_sz, (n_rec + 2) * 8))) return rc;
         if ((rc = r->flags.reserve(64))) return rc;
         const uint32_t init_flags[4] = {0, 0, 0xFFFFFFFFu, 0};
         HIP_TRY(hipMemcpyAsync(r->flags.p, init_flags, 16, hipMemcpyHostToDevice, r->st));
@@ -264,8 +250,8 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
         hipLaunchKernelGGL(k_fastq_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p,
                            (const uint32_t *)r->nl_pos.p, n_rec, X);
         HIP_TRY(hipGetLastError());
-        if ((rc = device_scan(r, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
-        if ((rc = device_scan(r, X.text_sz, n_rec, X.text_sz + n_rec))) return rc;
+        if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
+        if ((rc = device_scan_on(r->tile_sums, r->st, X.text_sz, n_rec, X.text_sz + n_rec))) return rc;
         uint64_t *hs = (uint64_t *)r->h_small.p;
         HIP_TRY(hipMemcpyAsync(hs, X.base_sz + n_rec, 8, hipMemcpyDeviceToHost, r->st));
         HIP_TRY(hipMemcpyAsync(hs + 1, X.flags, 16, hipMemcpyDeviceToHost, r->st));
@@ -369,60 +355,23 @@ int kbbq_fastq_reader_batch(kbbq_fastq_reader *r, kbbq_reads *dev) {
     if (!r->have_chunk || !r->n_records || r->selected >= 0) return fail(KBBQ_ESTATE, "no records in the current chunk");
     KbbqDeviceGuard guard(r->device);
     HIP_TRY(guard.err);
-    const uint64_t n = r->n_records, nbases = r->n_bases;
+    const uint64_t n = r->n_records;
     const FastqIndex X = index_of(r, n);
-    memset(dev, 0, sizeof *dev);
-    dev->n_reads = n;
-    dev->n_bases = nbases;
-    dev->on_device = 1;
-    void *b = nullptr, *m = nullptr, *q = nullptr, *oc = nullptr, *off = nullptr, *fl = nullptr;
-    BatchArrays arrays;
-    int rc;
-    const uint64_t words = nbases / 64 + 1;
-    if ((rc = r->seq_text.reserve(nbases + 64))) return rc;
-    // [0..1] the two counts of k_pack_text, behind them the off-case words: nearly every chunk has none, and an array
-    // allocated and freed again per chunk was a hipMalloc (which clears) and a hipFree (which waits for the device) for nothing
-    if ((rc = r->counter.reserve((words + 4) * 8 + 64))) return rc;
-    void *oc_scratch = (char *)r->counter.p + 16;
-    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&q, nbases + 16))) return rc;
-    if ((rc = arrays.alloc(&fl, n))) return rc;
-    const bool uniform = r->longest == r->shortest;
-    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
-    // (the copies in front of the kernels, not between them)
-    HIP_TRY(hipMemcpyAsync(fl, X.second, n, hipMemcpyDeviceToDevice, r->st));
-    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
-    HIP_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
-    hipLaunchKernelGGL(k_fastq_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p, X,
-                       (const uint64_t *)X.base_sz, n, (uint8_t *)r->seq_text.p, (uint8_t *)q);
-    HIP_TRY(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};      // off-case bases; characters the packed form cannot give back
-    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, oc_scratch, r->counter.p, counts))) return rc;
-    if (counts[0]) {      // soft-masked text: the batch gets its off-case bits
-        if ((rc = arrays.alloc(&oc, (words + 2) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(oc, oc_scratch, (words + 2) * 8, hipMemcpyDeviceToDevice, r->st));
-        HIP_TRY(hipStreamSynchronize(r->st));
-    }
-    arrays.release();
-    r->packed_is_exact = counts[1] == 0;
-    r->batch_built = true;
-    dev->bases = (const uint64_t *)b;
-    dev->nmask = (const uint64_t *)m;
-    dev->qual = (const uint8_t *)q;
-    dev->offsets = (const uint64_t *)off;
-    dev->flags = (const uint8_t *)fl;
-    dev->rg = nullptr;
-    dev->read_len = uniform ? r->longest : 0;
-    dev->offcase = (const uint64_t *)oc;
-    return KBBQ_OK;
+    const BatchShape S{n, r->n_bases, r->longest, r->shortest, X.base_sz};
+    // (no read groups; the batch of a soft-masked chunk gets the off-case words, and the counter two spare words more)
+    return build_batch(r->st, S, r->seq_text, r->counter, (S.words() + 4) * 8 + 64, false, true,
+                       [&](uint8_t *seq_text, uint8_t *q, uint8_t *fl, uint16_t *) {
+                           HIP_TRY(hipMemcpyAsync(fl, X.second, n, hipMemcpyDeviceToDevice, r->st));      // (a copy: in front of the kernel)
+                           hipLaunchKernelGGL(k_fastq_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, (const uint8_t *)r->text.p,
+                                              X, (const uint64_t *)X.base_sz, n, seq_text, q);
+                           return (int)KBBQ_OK;
+                       },
+                       dev, *r);
 }
 
 int kbbq_fastq_reader_batch_exact(kbbq_fastq_reader *r, int32_t *exact) {
     if (!r || !exact) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || r->selected >= 0 || !r->batch_built) return fail(KBBQ_ESTATE, "no batch was built for the current chunk");
-    *exact = r->packed_is_exact ? 1 : 0;
-    return KBBQ_OK;
+    return r->batch_exact(r->selected >= 0, exact);
 }
 
 int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, void *after_stream) {
@@ -433,34 +382,22 @@ int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d
     HIP_TRY(guard.err);
     if (r->selected >= 0 && r->kept[(size_t)r->selected].short_form && !r->att_bases)
         return fail(KBBQ_ESTATE, "the chunk was kept without its sequence text: attach its batch first (kbbq_fastq_reader_attach)");
-    Submission *sp;
-    int rc = begin_submission(z, after_stream, &sp);
-    if (rc) return rc;
-    Submission &s = *sp;
     const uint64_t n = r->n_records;
     const bool from_kept = r->selected >= 0;
     const kbbq_fastq_reader::Kept *k = from_kept ? &r->kept[(size_t)r->selected] : nullptr;
     const FastqIndex X = from_kept ? index_from(k->idx_u32.p, nullptr, k->base_sz.p, k->text_sz.p, nullptr, n) : index_of(r, n);
     const uint8_t *text = (const uint8_t *)(from_kept ? k->text.p : r->text.p);
-    const uint64_t t = r->out_text_bytes;      // (the scanned sizes' total, read back with the chunk's other counts)
-    s.n = t;
-    s.formatted = true;
-    if ((rc = s.payload.reserve(t + 16))) return rc;
-    HIP_TRY(hipMemsetAsync((char *)s.payload.p + t, 0, 16, z->st));
-    HIP_TRY(hipEventRecord(s.t0, z->st));
-    if (from_kept && k->short_form)
-        hipLaunchKernelGGL(k_fastq_text_packed, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, (const uint8_t *)k->names.p,
-                           (const uint32_t *)k->lens.p, (const uint64_t *)k->text_sz.p, (const uint64_t *)k->base_sz.p, r->att_bases, r->att_nmask,
-                           r->att_offcase, d_qual, n, (uint8_t *)s.payload.p);
-    else
-        hipLaunchKernelGGL(k_fastq_text_indexed, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, text, X,
-                           (const uint64_t *)X.text_sz, (const uint64_t *)X.base_sz, d_qual, n, (uint8_t *)s.payload.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = launch_deflate(z, s))) return rc;
-    // the reader's live text and index are read by the kernel just queued: the next kbbq_fastq_reader_chunk must not
-    // overwrite them before it has run (a kept chunk's buffers stay as they are)
-    if (!from_kept) HIP_TRY(hipEventSynchronize(s.t1));
-    return KBBQ_OK;
+    const dim3 grid((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32));
+    // The total is the scanned sizes', read back with the chunk's other counts.  Waits for the live chunk alone: its text and
+    // index are read by the kernel queued, and the next kbbq_fastq_reader_chunk must not overwrite them before it has run; a
+    // kept chunk's buffers stay as they are.
+    return submit_rewrite(z, after_stream, r->out_text_bytes, !from_kept, [&](uint8_t *payload) {
+        if (from_kept && k->short_form)
+            hipLaunchKernelGGL(k_fastq_text_packed, grid, dim3(256), 0, z->st, (const uint8_t *)k->names.p, (const uint32_t *)k->lens.p, (const uint64_t *)k->text_sz.p,
+                               (const uint64_t *)k->base_sz.p, r->att_bases, r->att_nmask, r->att_offcase, d_qual, n, payload);
+        else
+            hipLaunchKernelGGL(k_fastq_text_indexed, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)X.text_sz, (const uint64_t *)X.base_sz, d_qual, n, payload);
+    });
 }
 
 int kbbq_fastq_reader_attach(kbbq_fastq_reader *r, const kbbq_reads *batch) {
@@ -475,18 +412,10 @@ int kbbq_fastq_reader_attach(kbbq_fastq_reader *r, const kbbq_reads *batch) {
     return KBBQ_OK;
 }
 int kbbq_fastq_reader_preload(kbbq_fastq_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint64_t front_room) {
-    if (!r || !file_bytes || !n_bytes) return fail(KBBQ_EINVAL, "bad argument");
-    KbbqDeviceGuard guard(r->device);
-    HIP_TRY(guard.err);
-    return r->pre.start(file_bytes, n_bytes, front_room);
+    return reader_preload(r, file_bytes, n_bytes, front_room);
 }
 
-int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms) {
-    if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (inflate_ms) *inflate_ms = r->ms_inflate;      // (a gzip stream's stages included: kbbq_fastq_reader_gzip_ms splits them)
-    if (index_ms) *index_ms = r->ms_index;
-    return KBBQ_OK;
-}
+int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms) { return reader_kernel_ms(r, inflate_ms, index_ms); }
 
 int kbbq_fastq_reader_take_text(kbbq_fastq_reader *r, int32_t on) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");

@@ -1,8 +1,9 @@
 // io_common.h -- what the device I/O objects of include/kbbq_bgzf.h share (internal): growing buffers, pieces of a file
-// copied ahead of their chunk call, the walk over BGZF headers, the inflate launch, the exclusive scan, the packing of
-// sequence text into a batch, and the writer's submissions as far as the readers' write() needs them.  Host code only:
-// the kernels behind these functions live in io_common.hip and bgzf_writer.hip, nowhere else.  (text_chunks.h builds a
-// reader's way from file bytes to indexed lines out of them.)
+// copied ahead of their chunk call, the stream and scratch every reader has (ReaderStream), the walk over BGZF headers, the
+// inflate launch, the exclusive scan, the packing of sequence text into a batch, the per-read flags and read groups of a
+// BAM or SAM batch, and the writer's submissions as far as the readers' write() needs them.  Host code only: the kernels
+// behind these functions live in io_common.hip and bgzf_writer.hip, nowhere else.  (text_chunks.h builds a reader's way
+// from file bytes to indexed lines out of them, record_batch.h its batches and its pass-4 submissions.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -106,6 +107,44 @@ int stage_compressed(Preload &pre, Buf &comp, const uint8_t *file_bytes, uint64_
     return KBBQ_OK;
 }
 
+// What every device reader has: its stream, the events and sums of a chunk call's two times (t0 | text | t1 | index | t2),
+// the pieces copied ahead, page-locked scratch for small read-backs and the scan's scratch.
+struct ReaderStream {
+    Preload pre;
+    int device = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+    Buf h_small, tile_sums;
+    double ms_inflate = 0, ms_index = 0;
+    // the stream and the events; false with the HIP error in *he
+    bool create(int dev, hipError_t *he) {
+        device = dev;
+        h_small.host = true;
+        *he = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (*he == hipSuccess) *he = hipEventCreate(&t0);
+        if (*he == hipSuccess) *he = hipEventCreate(&t1);
+        if (*he == hipSuccess) *he = hipEventCreate(&t2);
+        return *he == hipSuccess;
+    }
+    // (the caller has waited for st)
+    void destroy() {
+        h_small.release();
+        tile_sums.release();
+        pre.release();
+        hipEvent_t evs[] = {t0, t1, t2};
+        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr;
+        t0 = t1 = t2 = nullptr;
+    }
+    // a chunk call's two times added up, its three events recorded and st waited for
+    void add_times() {
+        float a = 0, b = 0;
+        if (hipEventElapsedTime(&a, t0, t1) == hipSuccess) ms_inflate += a;
+        if (hipEventElapsedTime(&b, t1, t2) == hipSuccess) ms_index += b;
+    }
+};
+
 // ---- BGZF members: the walk over their headers --------------------------------------------------------------------------
 // The blocks at the front of a byte range: where their DEFLATE streams lie in it and where their bytes go in the output.
 struct BlockTable {
@@ -162,6 +201,10 @@ int newline_positions(hipStream_t st, const void *text, uint64_t n, const uint64
 // counts (or null: not read back) gets the off-case bases and the characters the packed form cannot give back.
 int pack_text(hipStream_t st, const void *seq_text, uint64_t n_bases, void *bases, void *nmask, void *offcase, void *d_counts,
               unsigned long long counts[2]);
+
+// Second-in-pair flags (readutils.cc:59) and dense read-group indices of the n records of a BAM or SAM chunk, queued on st:
+// second[r] = FLAG bit 0x80 of flag[r], rg[r] = dense[rg_index[r]] (flag, rg_index: the record index's arrays).
+int read_meta(hipStream_t st, const uint16_t *flag, const uint16_t *rg_index, uint64_t n, const uint16_t *dense, uint8_t *second, uint16_t *rg);
 
 // ---- the writer, as far as a reader's write() needs it (bgzf_writer.hip) -------------------------------------------------
 struct Submission {

@@ -1,7 +1,7 @@
-// io_common.hip -- the host functions of io_common.h that both device readers use, with their kernels (MI355X, gfx950):
+// io_common.hip -- the host functions of io_common.h that the device readers use, with their kernels (MI355X, gfx950):
 // the BGZF block walk, the inflate launch and its status check, the exclusive scan, the newline index, the packing of
-// sequence text -- and
-// kbbq_reads_upload_text, which is that packing for a host batch.
+// sequence text, the per-read flags and read groups (k_read_meta) -- and kbbq_reads_upload_text, which is that packing
+// for a host batch.
 #include "io_common.h"
 
 #include "bgzf_inflate.h"
@@ -200,6 +200,12 @@ int pack_text(hipStream_t st, const void *seq_text, uint64_t n_bases, void *base
     HIP_TRY(hipGetLastError());
     if (counts) HIP_TRY(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return KBBQ_OK;
+}
+
+int read_meta(hipStream_t st, const uint16_t *flag, const uint16_t *rg_index, uint64_t n, const uint16_t *dense, uint8_t *second, uint16_t *rg) {
+    hipLaunchKernelGGL(k_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, flag, rg_index, n, dense, second, rg);
+    HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
 

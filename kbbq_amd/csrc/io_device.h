@@ -1,5 +1,6 @@
-// io_device.h -- the kernels both device readers use (gfx950): an exclusive scan of 64-bit values and the packing of
-// sequence text into the engine's read layout.  Included once, by io_common.hip.
+// io_device.h -- the kernels the device readers share (gfx950): an exclusive scan of 64-bit values, the packing of
+// sequence text into the engine's read layout, and the per-read flags and read groups of a BAM or SAM batch.  Included
+// once, by io_common.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,6 +85,15 @@ __global__ void __launch_bounds__(256) k_pack_text(const uint8_t *seq_text, uint
     offcase[w] = oc;
     if (oc) atomicAdd(n_offcase, (unsigned long long)__popcll(oc));
     if (exotic) atomicAdd(n_offcase + 1, (unsigned long long)exotic);
+}
+
+// second-in-pair flags (readutils.cc:59) and the dense read-group index of every record of a BAM or SAM chunk
+__global__ void __launch_bounds__(256) k_read_meta(const uint16_t *flag, const uint16_t *rg_index, uint64_t n_records, const uint16_t *dense, uint8_t *second,
+                                                    uint16_t *rg) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_records) return;
+    second[r] = (flag[r] & 0x80) ? 1 : 0;
+    rg[r] = dense[rg_index[r]];
 }
 
 }  // namespace dfl

@@ -70,8 +70,28 @@ struct RgGroups {
     std::vector<uint32_t> h_id_off;
     std::vector<int32_t> dense_of;          // table index -> dense read-group index (first appearance), -1: not met
     std::vector<uint32_t> order;            // dense index -> table index
+    int any_rg = 0;                         // kbbq_*_reader_any_read_group: RG tags are required, their values not looked up
+    bool fed = false;                       // a chunk call was made: the mode above no longer changes
     size_t n_ids() const { return dense_of.size(); }
 
+    // the arguments of kbbq_{bam,sam}_reader_create that are about the table
+    static int check_args(const void *out, const char *const *rg_ids, uint32_t n_rg_ids) {
+        if (!out || (n_rg_ids && !rg_ids)) return fail(KBBQ_EINVAL, "null argument");
+        if (n_rg_ids > 65535) return fail(KBBQ_ERANGE, "%u @RG lines: read-group indices travel in 16 bits", n_rg_ids);
+        return KBBQ_OK;
+    }
+    // kbbq_*_reader_any_read_group
+    int set_any(int32_t on) {
+        if (fed) return fail(KBBQ_ESTATE, "the read-group mode is set before the first chunk");
+        any_rg = on ? 1 : 0;
+        return KBBQ_OK;
+    }
+    // kbbq_*_reader_read_groups: dense index -> table index of the groups met so far
+    int list(uint32_t *table_index, uint32_t capacity, uint32_t *n) const {
+        *n = (uint32_t)order.size();
+        for (uint32_t i = 0; i < *n && i < capacity && table_index; ++i) table_index[i] = order[i];
+        return KBBQ_OK;
+    }
     // the table to the device (plain copies: before the reader's first chunk)
     int create(const char *const *rg_ids, uint32_t n_rg_ids) {
         h_id_off.assign(1, 0);

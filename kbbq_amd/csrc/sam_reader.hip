@@ -1,7 +1,12 @@
 // sam_reader.hip -- the host side of kbbq_sam_reader (include/kbbq_bgzf.h): SAM text -- BGZF, plain gzip or uncompressed --
 // read on the device (MI355X, gfx950).  The way from the file's bytes to the lines of the text is text_chunks.h's, shared
-// with the FASTQ reader; the read-group table is rg_table.h's, shared with the BAM reader; the record index, the gather and
-// the pass-4 rewrite are sam_device.h's kernels.
+// with the FASTQ reader; the read-group table is rg_table.h's, shared with the BAM reader; the batch builder, the pass-4
+// submission and the entry points every reader has are record_batch.h's, shared with both; the record index, the gather
+// and the pass-4 rewrite are sam_device.h's kernels.
+//
+// A kept chunk is its whole text with its record index, for write() alone: batch, batch_seq and batch_exact refuse a
+// selected chunk (the BAM reader, which indexes a selected chunk again, does not).
+#include "record_batch.h"
 #include "text_chunks.h"
 #include "rg_table.h"
 
@@ -17,18 +22,14 @@ struct SamCounts {
     uint32_t longest = 0, shortest = 0, chunk_flags = 0;
 };
 
-struct kbbq_sam_reader : SamCounts, TextChunks {
+struct kbbq_sam_reader : SamCounts, TextChunks, ChunkState {
     int use_oq = 0;
-    int any_rg = 0;                         // kbbq_sam_reader_any_read_group: RG fields are required, their values not looked up
-    bool fed = false;                       // a chunk call was made: the mode above no longer changes
     uint64_t header_bytes = 0, header_left = 0;      // the header's size in the text; what of it is still to come
     Buf idx_u32, idx_u16, idx_u64;          // SamIndex, idx_cap records long
     size_t idx_cap = 0;
     Buf d_out;                              // small device words: record flags / longest / shortest
     RgGroups groups;
     Buf seq_text, counter;                  // scratch of kbbq_sam_reader_batch
-    bool have_chunk = false;
-    bool batch_built = false, packed_is_exact = false;      // kbbq_sam_reader_batch_exact: of the current chunk's batch
     // chunks of the first scan that stay in device memory (kbbq_sam_reader_keep): the whole text with its record index
     struct Kept : SamCounts {
         Buf text, idx_u32, idx_u16, idx_u64;
@@ -79,6 +80,16 @@ void stash_current(kbbq_sam_reader *r) {
     r->have_chunk = false;
 }
 
+// the argument and state checks of batch and batch_seq
+int batchable(const kbbq_sam_reader *r, const kbbq_reads *dev) {
+    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records || r->selected >= 0) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->chunk_flags & SAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host reader's", r->chunk_flags);
+    return KBBQ_OK;
+}
+SamIndex live_index(const kbbq_sam_reader *r) { return index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap); }
+BatchShape batch_shape(const kbbq_sam_reader *r, const SamIndex &X) { return BatchShape{r->n_records, r->n_bases, r->longest, r->shortest, X.base_sz}; }
+
 }  // namespace
 
 extern "C" {
@@ -96,10 +107,8 @@ void kbbq_sam_reader_destroy(kbbq_sam_reader *r) {
 }
 
 int kbbq_sam_reader_create(int32_t device, int32_t use_oq, uint64_t header_bytes, const char *const *rg_ids, uint32_t n_rg_ids, kbbq_sam_reader **out) {
-    if (!out || (n_rg_ids && !rg_ids)) return fail(KBBQ_EINVAL, "null argument");
-    if (n_rg_ids > 65535) return fail(KBBQ_ERANGE, "%u @RG lines: read-group indices travel in 16 bits", n_rg_ids);
-    int rc = device_exists(device);
-    if (rc) return rc;
+    int rc = RgGroups::check_args(out, rg_ids, n_rg_ids);
+    if (rc || (rc = device_exists(device))) return rc;
     KbbqDeviceGuard guard(device);
     HIP_TRY(guard.err);
     kbbq_sam_reader *r = new kbbq_sam_reader;
@@ -136,25 +145,10 @@ int kbbq_sam_reader_rewind(kbbq_sam_reader *r) {
 
 int kbbq_sam_reader_any_read_group(kbbq_sam_reader *r, int32_t on) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (r->fed) return fail(KBBQ_ESTATE, "the read-group mode is set before the first chunk");
-    r->any_rg = on ? 1 : 0;
-    return KBBQ_OK;
+    return r->groups.set_any(on);
 }
 
-int kbbq_sam_reader_keep(kbbq_sam_reader *r, int32_t on) {
-    if (!r) return fail(KBBQ_EINVAL, "null argument");
-    KbbqDeviceGuard guard(r->device);
-    HIP_TRY(guard.err);
-    if (on) {
-        if (r->have_chunk || !r->kept.empty()) return fail(KBBQ_ESTATE, "keeping starts before the first chunk of a scan");
-        r->keeping = true;
-    } else {
-        HIP_TRY(hipStreamSynchronize(r->st));
-        release_kept(r);
-        r->keeping = false;
-    }
-    return KBBQ_OK;
-}
+int kbbq_sam_reader_keep(kbbq_sam_reader *r, int32_t on) { return reader_keep(r, on, release_kept); }
 
 int kbbq_sam_reader_kept(kbbq_sam_reader *r, uint64_t *n_chunks, uint64_t *n_bytes) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
@@ -183,9 +177,7 @@ int kbbq_sam_reader_select(kbbq_sam_reader *r, uint64_t i, kbbq_sam_chunk *info)
 
 int kbbq_sam_reader_read_groups(kbbq_sam_reader *r, uint32_t *table_index, uint32_t capacity, uint32_t *n) {
     if (!r || !n) return fail(KBBQ_EINVAL, "null argument");
-    *n = (uint32_t)r->groups.order.size();
-    for (uint32_t i = 0; i < *n && i < capacity && table_index; ++i) table_index[i] = r->groups.order[i];
-    return KBBQ_OK;
+    return r->groups.list(table_index, capacity, n);
 }
 
 int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, int32_t last, kbbq_sam_chunk *info) {
@@ -197,7 +189,7 @@ int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_
     r->selected = -1;
     r->have_chunk = false;
     r->batch_built = false;
-    r->fed = true;
+    r->groups.fed = true;
     r->n_records = r->n_bases = 0;
     r->longest = r->shortest = r->chunk_flags = 0;
     int rc;
@@ -223,22 +215,21 @@ int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_
     uint64_t rec_end = skip;      // first byte behind the last complete line
     if (n_rec) {
         if ((rc = r->line_positions(bias, text, n_rec))) return rc;
-        if (r->idx_cap < n_rec) {
-            const size_t cap = n_rec + n_rec / 8 + 1024;
-            r->idx_cap = 0;
-            if ((rc = r->reserve(r->idx_u32, cap * 9 * 4))) return rc;
-            if ((rc = r->reserve(r->idx_u16, cap * 2 * 2))) return rc;
-            if ((rc = r->reserve(r->idx_u64, (cap + 2) * 2 * 8))) return rc;
-            r->idx_cap = cap;
-        }
+        rc = grow_index(r->idx_cap, n_rec, [r](size_t cap) {
+            int e;
+            if ((e = r->reserve(r->idx_u32, cap * 9 * 4))) return e;
+            if ((e = r->reserve(r->idx_u16, cap * 2 * 2))) return e;
+            return r->reserve(r->idx_u64, (cap + 2) * 2 * 8);
+        });
+        if (rc) return rc;
         if ((rc = r->d_out.reserve(64))) return rc;
         uint32_t *out = (uint32_t *)r->d_out.p;
         const uint32_t init_out[4] = {0, 0, 0xFFFFFFFFu, 0};
         HIP_TRY(hipMemcpyAsync(out, init_out, 16, hipMemcpyHostToDevice, r->st));
-        const SamIndex X = index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap);
+        const SamIndex X = live_index(r);
         const uint8_t *tb = (const uint8_t *)r->text.p + bias;
         hipLaunchKernelGGL(k_sam_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, tb, (const uint32_t *)r->nl_pos.p, n_rec, first_start,
-                           r->use_oq, r->any_rg, r->groups.table(), X, out, (unsigned long long *)r->groups.first_seen.p);
+                           r->use_oq, r->groups.any_rg, r->groups.table(), X, out, (unsigned long long *)r->groups.first_seen.p);
         HIP_TRY(hipGetLastError());
         if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
         uint64_t *hs = (uint64_t *)r->h_small.p;
@@ -271,104 +262,42 @@ int kbbq_sam_reader_chunk(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_
 }
 
 int kbbq_sam_reader_batch(kbbq_sam_reader *r, kbbq_reads *dev) {
-    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || !r->n_records || r->selected >= 0) return fail(KBBQ_ESTATE, "no records in the current chunk");
-    if (r->chunk_flags & SAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host reader's", r->chunk_flags);
+    int rc = batchable(r, dev);
+    if (rc) return rc;
     KbbqDeviceGuard guard(r->device);
     HIP_TRY(guard.err);
-    const uint64_t n = r->n_records, nbases = r->n_bases;
-    const SamIndex X = index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap);
+    const SamIndex X = live_index(r);
+    const BatchShape S = batch_shape(r, X);
     const uint8_t *tb = (const uint8_t *)r->text.p + r->bias;
-    memset(dev, 0, sizeof *dev);
-    dev->n_reads = n;
-    dev->n_bases = nbases;
-    dev->on_device = 1;
-    void *b = nullptr, *m = nullptr, *q = nullptr, *off = nullptr, *fl = nullptr, *rg = nullptr;
-    BatchArrays arrays;
-    int rc;
-    const uint64_t words = nbases / 64 + 1;
-    if ((rc = r->seq_text.reserve(nbases + 64))) return rc;
-    if ((rc = r->counter.reserve((words + 2) * 8 + 64))) return rc;      // [0..1] counts, then the (always empty) off-case words
-    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&q, nbases + 16))) return rc;
-    if ((rc = arrays.alloc(&fl, n))) return rc;
-    if ((rc = arrays.alloc(&rg, n * 2 + 16))) return rc;
-    const bool uniform = r->longest == r->shortest;
-    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
-    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));      // (in front of the kernels, not between them)
-    HIP_TRY(hipMemsetAsync((char *)q + nbases, 0, 16, r->st));
-    hipLaunchKernelGGL(k_sam_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, tb, X, (const uint64_t *)X.base_sz, n,
-                       (uint8_t *)r->seq_text.p, (uint8_t *)q);
-    hipLaunchKernelGGL(k_sam_read_meta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, (const uint16_t *)r->groups.dense.p, (uint8_t *)fl,
-                       (uint16_t *)rg);
-    HIP_TRY(hipGetLastError());
-    // (bam_seq_str gives upper-case letters only: no off-case bits; the words go to scratch.  The second count is the
-    // forward-strand bases that are none of A/C/G/T/N: kbbq_sam_reader_batch_exact)
-    unsigned long long counts[2] = {0, 0};
-    if ((rc = pack_text(r->st, r->seq_text.p, nbases, b, m, (char *)r->counter.p + 16, r->counter.p, counts))) return rc;
-    arrays.release();
-    r->packed_is_exact = counts[1] == 0;
-    r->batch_built = true;
-    dev->bases = (const uint64_t *)b;
-    dev->nmask = (const uint64_t *)m;
-    dev->qual = (const uint8_t *)q;
-    dev->offsets = (const uint64_t *)off;
-    dev->flags = (const uint8_t *)fl;
-    dev->rg = (const uint16_t *)rg;
-    dev->read_len = uniform ? r->longest : 0;
-    dev->offcase = nullptr;
-    return KBBQ_OK;
+    const uint64_t n = r->n_records;
+    // (no off-case bits; counter: [0..1] counts, then the always empty off-case words)
+    return build_batch(r->st, S, r->seq_text, r->counter, (S.words() + 2) * 8 + 64, true, false,
+                       [&](uint8_t *seq_text, uint8_t *q, uint8_t *fl, uint16_t *rg) {
+                           hipLaunchKernelGGL(k_sam_gather, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, r->st, tb, X,
+                                              (const uint64_t *)X.base_sz, n, seq_text, q);
+                           return read_meta(r->st, X.flag, X.rg, n, (const uint16_t *)r->groups.dense.p, fl, rg);
+                       },
+                       dev, *r);
 }
 
 int kbbq_sam_reader_batch_seq(kbbq_sam_reader *r, kbbq_reads *dev) {
-    if (!r || !dev) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || !r->n_records || r->selected >= 0) return fail(KBBQ_ESTATE, "no records in the current chunk");
-    if (r->chunk_flags & SAMF_FALLBACK) return fail(KBBQ_ESTATE, "the chunk holds a shape this reader does not take (flags %u): the host reader's", r->chunk_flags);
+    int rc = batchable(r, dev);
+    if (rc) return rc;
     KbbqDeviceGuard guard(r->device);
     HIP_TRY(guard.err);
-    const uint64_t n = r->n_records, nbases = r->n_bases;
-    const SamIndex X = index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap);
+    const SamIndex X = live_index(r);
     const uint8_t *tb = (const uint8_t *)r->text.p + r->bias;
-    memset(dev, 0, sizeof *dev);
-    dev->n_reads = n;
-    dev->n_bases = nbases;
-    dev->on_device = 1;
-    void *b = nullptr, *m = nullptr, *off = nullptr;
-    BatchArrays arrays;
-    int rc;
-    const uint64_t words = nbases / 64 + 1;
-    if ((rc = r->counter.reserve(64))) return rc;
-    if ((rc = arrays.alloc(&b, (2 * words + 2) * 8))) return rc;
-    if ((rc = arrays.alloc(&m, (words + 2) * 8))) return rc;
-    const bool uniform = r->longest == r->shortest;
-    if (!uniform && (rc = arrays.alloc(&off, (n + 1) * 8))) return rc;
-    if (!uniform) HIP_TRY(hipMemcpyAsync(off, X.base_sz, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
-    // (the kernel writes every one of the `words` words; the spare words behind them are pack_text's)
-    HIP_TRY(hipMemsetAsync(r->counter.p, 0, 16, r->st));
-    HIP_TRY(hipMemsetAsync((char *)b + 2 * words * 8, 0, 16, r->st));
-    HIP_TRY(hipMemsetAsync((char *)m + words * 8, 0, 16, r->st));
-    hipLaunchKernelGGL(k_sam_pack_seq, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, tb, X, (const uint64_t *)X.base_sz, n, nbases, (uint64_t *)b,
-                       (uint64_t *)m, (unsigned long long *)r->counter.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long counts[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, r->counter.p, 16, hipMemcpyDeviceToHost, r->st));
-    HIP_TRY(hipStreamSynchronize(r->st));
-    arrays.release();
-    r->packed_is_exact = counts[1] == 0;
-    r->batch_built = true;
-    dev->bases = (const uint64_t *)b;
-    dev->nmask = (const uint64_t *)m;
-    dev->offsets = (const uint64_t *)off;
-    dev->read_len = uniform ? r->longest : 0;
-    return KBBQ_OK;
+    return build_batch_seq(r->st, batch_shape(r, X), r->counter,
+                           [&](uint64_t words, uint64_t *b, uint64_t *m, unsigned long long *counts) {
+                               hipLaunchKernelGGL(k_sam_pack_seq, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r->st, tb, X, (const uint64_t *)X.base_sz,
+                                                  r->n_records, r->n_bases, b, m, counts);
+                           },
+                           dev, *r);
 }
 
 int kbbq_sam_reader_batch_exact(kbbq_sam_reader *r, int32_t *exact) {
     if (!r || !exact) return fail(KBBQ_EINVAL, "null argument");
-    if (!r->have_chunk || r->selected >= 0 || !r->batch_built) return fail(KBBQ_ESTATE, "no batch was built for the current chunk");
-    *exact = r->packed_is_exact ? 1 : 0;
-    return KBBQ_OK;
+    return r->batch_exact(r->selected >= 0, exact);
 }
 
 int kbbq_sam_reader_write(kbbq_sam_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, int32_t set_oq, void *after_stream) {
@@ -382,48 +311,25 @@ int kbbq_sam_reader_write(kbbq_sam_reader *r, kbbq_bgzf *z, const uint8_t *d_qua
     const uint64_t n = r->n_records;
     const bool from_kept = r->selected >= 0;
     const kbbq_sam_reader::Kept *k = from_kept ? &r->kept[(size_t)r->selected] : nullptr;
-    const SamIndex X = from_kept ? index_from(k->idx_u32.p, k->idx_u16.p, k->idx_u64.p, k->idx_cap) : index_from(r->idx_u32.p, r->idx_u16.p, r->idx_u64.p, r->idx_cap);
+    const SamIndex X = from_kept ? index_from(k->idx_u32.p, k->idx_u16.p, k->idx_u64.p, k->idx_cap) : live_index(r);
     const uint8_t *tb = (const uint8_t *)(from_kept ? k->text.p : r->text.p) + r->bias;
-    int rc;
-    // sizes of the output lines and where they go
-    hipLaunchKernelGGL(k_sam_out_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, set_oq ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    if ((rc = device_scan_on(r->tile_sums, r->st, X.out_sz, n, X.out_sz + n))) return rc;
-    if ((rc = r->h_small.reserve(4096))) return rc;
-    uint64_t *hs = (uint64_t *)r->h_small.p;
-    HIP_TRY(hipMemcpyAsync(hs, X.out_sz + n, 8, hipMemcpyDeviceToHost, r->st));
-    HIP_TRY(hipStreamSynchronize(r->st));
-    const uint64_t t = hs[0];
-    Submission *sp;
-    if ((rc = begin_submission(z, after_stream, &sp))) return rc;
-    Submission &s = *sp;
-    s.n = t;
-    s.formatted = true;
-    if ((rc = s.payload.reserve(t + 16))) return rc;
-    HIP_TRY(hipMemsetAsync((char *)s.payload.p + t, 0, 16, z->st));
-    HIP_TRY(hipEventRecord(s.t0, z->st));
-    hipLaunchKernelGGL(k_sam_rewrite, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, tb, X, (const uint64_t *)X.base_sz,
-                       (const uint64_t *)X.out_sz, n, set_oq ? 1 : 0, d_qual, (uint8_t *)s.payload.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = launch_deflate(z, s))) return rc;
-    // The text and the index are read by the kernel just queued.  The live ones: the next chunk must not overwrite them before it
-    // has run.  A kept chunk's: its output sizes are scanned again by the next write of the same chunk, on the reader's stream.
-    HIP_TRY(hipEventSynchronize(s.t1));
-    return KBBQ_OK;
+    const int oq = set_oq ? 1 : 0;
+    uint64_t total = 0;
+    int rc = rewrite_total(*r, X.out_sz, n, [&] { hipLaunchKernelGGL(k_sam_out_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, X, n, oq); }, &total);
+    if (rc) return rc;
+    // Waits, always: the text and the index are read by the kernel queued.  The live ones: the next chunk must not overwrite
+    // them before it has run.  A kept chunk's: its output sizes are scanned again by the next write of the same chunk, on the
+    // reader's stream.
+    return submit_rewrite(z, after_stream, total, true, [&](uint8_t *payload) {
+        hipLaunchKernelGGL(k_sam_rewrite, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, z->st, tb, X, (const uint64_t *)X.base_sz,
+                           (const uint64_t *)X.out_sz, n, oq, d_qual, payload);
+    });
 }
 
 int kbbq_sam_reader_preload(kbbq_sam_reader *r, const uint8_t *file_bytes, uint64_t n_bytes, uint64_t front_room) {
-    if (!r || !file_bytes || !n_bytes) return fail(KBBQ_EINVAL, "bad argument");
-    KbbqDeviceGuard guard(r->device);
-    HIP_TRY(guard.err);
-    return r->pre.start(file_bytes, n_bytes, front_room);
+    return reader_preload(r, file_bytes, n_bytes, front_room);
 }
 
-int kbbq_sam_reader_kernel_ms(kbbq_sam_reader *r, double *inflate_ms, double *index_ms) {
-    if (!r) return fail(KBBQ_EINVAL, "null argument");
-    if (inflate_ms) *inflate_ms = r->ms_inflate;      // (a gzip stream's stages included)
-    if (index_ms) *index_ms = r->ms_index;
-    return KBBQ_OK;
-}
+int kbbq_sam_reader_kernel_ms(kbbq_sam_reader *r, double *inflate_ms, double *index_ms) { return reader_kernel_ms(r, inflate_ms, index_ms); }
 
 }  // extern "C"

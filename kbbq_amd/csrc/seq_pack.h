@@ -1,13 +1,21 @@
-// seq_pack.h -- bam_seq_str's rule (readutils.hh:30-42) from htslib's 4-bit base codes straight to the engine's packed
-// layout, for the sequence-only batches of the BAM and the SAM reader (kbbq_*_reader_batch_seq): no text, no qualities.
-// No kernel in here: the rule and the walk of one 64-base word are __device__ functions for k_bam_pack_seq (bam_device.h)
-// and k_sam_pack_seq (sam_device.h), which differ only in where a record's 4-bit codes come from.
+// seq_pack.h -- bam_seq_str's rule (readutils.hh:30-42) over htslib's 4-bit base codes, once: to the character the rule
+// gives (k_bam_gather, k_sam_gather), and straight to the engine's packed layout for the sequence-only batches of the BAM
+// and the SAM reader (kbbq_*_reader_batch_seq): no text, no qualities.  No kernel in here: the rule and the walk of one
+// 64-base word are __device__ functions for the kernels of bam_device.h and sam_device.h, which differ only in where a
+// record's 4-bit codes come from.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace kbbq {
 namespace dfl {
+
+// The character bam_seq_str makes of base code `code4`: seq_nt16_str's letter on the forward strand; on the reverse strand
+// the complement of A/C/G/T and 'N' for every other code (readutils.hh:35-36)
+__device__ __forceinline__ uint8_t seq_str_char(uint32_t code4, bool rev) {
+    if (!rev) return (uint8_t)"=ACMGRSVTWYHKDBN"[code4];
+    return code4 == 1 ? 'T' : code4 == 2 ? 'G' : code4 == 4 ? 'C' : code4 == 8 ? 'A' : 'N';
+}
 
 // What base code `code4` (seq_nt16: 1/2/4/8 = A/C/G/T, 15 = N, the rest IUPAC and '=') of a record packs to:
 // bits 0-1 the 2-bit code, bit 2 the N bit, bit 3 "inexact" -- a character the packed form cannot give back.

@@ -1,6 +1,7 @@
 // text_chunks.h -- a text file read on the device chunk by chunk, up to its lines: what kbbq_fastq_reader and
-// kbbq_sam_reader (include/kbbq_bgzf.h) share.  Host code only, included by fastq_reader.hip and sam_reader.hip; the kernels
-// behind it are io_common.hip's (BGZF inflate, scan, newline index) and gzip_stream.hip's.
+// kbbq_sam_reader (include/kbbq_bgzf.h) share on top of io_common.h's ReaderStream, which every reader has.  Host code only,
+// included by fastq_reader.hip and sam_reader.hip; the kernels behind it are io_common.hip's (BGZF inflate, scan, newline
+// index) and gzip_stream.hip's.
 //
 // A chunk call reads top to bottom as: detect the container (BGZF, any other gzip stream, the text itself), obtain the
 // text behind the bytes the chunk before it left over, index the lines -- then the reader's own record index -- and carry
@@ -14,18 +15,12 @@
 namespace kbbq {
 namespace io {
 
-struct TextChunks {
-    Preload pre;
-    int device = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;      // a chunk call's timing: | text | index |
+struct TextChunks : ReaderStream {
     Buf comp, text;                         // compressed chunk, inflated text (carry first)
     Inflater inf;
-    Buf tile_counts, tile_sums, nl_pos;     // newline index
+    Buf tile_counts, nl_pos;                // newline index
     Buf carry;                              // text of the record the previous chunk's end cut (device)
-    Buf h_small;                            // page-locked scratch for small read-backs
     uint64_t carry_bytes = 0;
-    double ms_inflate = 0, ms_index = 0;
     // The container, decided by the first bytes after create / rewind: BGZF blocks, another gzip stream, or the text itself
     enum { C_UNKNOWN, C_BGZF, C_GZIP, C_TEXT } container = C_UNKNOWN;
     bool take_text = false;                 // a leading '@' is the text itself (otherwise it is reported as not BGZF)
@@ -33,28 +28,13 @@ struct TextChunks {
     // while the reader keeps chunks, a buffer that no longer fits gives them up (true: something was freed)
     std::function<bool()> drop_kept;
 
-    // the stream and the events; false with the HIP error in *he
-    bool create(int dev, hipError_t *he) {
-        device = dev;
-        h_small.host = true;
-        *he = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (*he == hipSuccess) *he = hipEventCreate(&t0);
-        if (*he == hipSuccess) *he = hipEventCreate(&t1);
-        if (*he == hipSuccess) *he = hipEventCreate(&t2);
-        return *he == hipSuccess;
-    }
     void destroy() {
         if (st) (void)hipStreamSynchronize(st);
-        Buf *all[] = {&comp, &text, &tile_counts, &tile_sums, &nl_pos, &carry, &h_small};
+        Buf *all[] = {&comp, &text, &tile_counts, &nl_pos, &carry};
         for (Buf *b : all) b->release();
         inf.release();
         gz.release();
-        pre.release();
-        hipEvent_t evs[] = {t0, t1, t2};
-        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-        st = nullptr;
-        t0 = t1 = t2 = nullptr;
+        ReaderStream::destroy();
     }
     // a new stream begins (create / rewind)
     void new_stream() {
@@ -127,9 +107,7 @@ struct TextChunks {
         }
         HIP_TRY(hipStreamSynchronize(st));
         carry_bytes = left;
-        float a = 0, b = 0;
-        if (hipEventElapsedTime(&a, t0, t1) == hipSuccess) ms_inflate += a;
-        if (hipEventElapsedTime(&b, t1, t2) == hipSuccess) ms_index += b;
+        add_times();
         return KBBQ_OK;
     }
 
