@@ -1,0 +1,252 @@
+// cli_options.h -- what a run of the `kbbq` command line is asked to do, before any pass: the options and every KBBQ_* switch
+// (CliOptions), the input formats and the one table of what differs between them (Format, FormatRow, kFormats), the stamped
+// log lines (put_now, give_up), what a file holds (sniff), an input that is not a regular file (StreamInput) and the phase
+// clock of KBBQ_TIMING.  Compiled into kbbq_cli.cc alone, which includes what this needs.
+#pragma once
+
+static std::ostream &put_now(std::ostream &os) {   // kbbq.cc:49-53
+    std::time_t t = std::time(nullptr);
+    std::tm tm = *std::localtime(&t);
+    return os << std::put_time(&tm, "[%F %T %Z]");
+}
+
+// a stamped line on stderr and the exit status that goes with it
+static int give_up(const std::string &text) {
+    std::cerr << put_now << text << std::endl;
+    return 1;
+}
+
+static struct option long_options[] = {   // kbbq.cc:66-79
+    {"ksize", required_argument, 0, 'k'},    {"use-oq", no_argument, 0, 'u'},     {"set-oq", no_argument, 0, 's'},
+    {"genomelen", required_argument, 0, 'g'}, {"coverage", required_argument, 0, 'c'}, {"fixed", required_argument, 0, 'f'},
+    {"alpha", required_argument, 0, 'a'},     {"threads", required_argument, 0, 't'},  {0, 0, 0, 0}};
+
+enum class Format { fastq, bam, sam, cram, unknown };
+
+class Source; struct ReaderCalls; struct Sink;
+
+// What differs between the input formats, a row of kFormats each.  What else differs is control flow and stands where it happens:
+// the header (open_device_input, Sink::open), BAM's record without bases and FASTQ's one read group (device_scan), pass 4's dispatch.
+struct FormatRow {
+    const char *name;                  // the device reader's name in the timing line
+    const char *handed_back;           // needs_host_parsers(...) of a chunk with flag bit 0
+    const char *header_without_rg;     // ... of a header whose @RG lines the device reader cannot use (null: no header)
+    bool bgzf_only;                    // no other container holds it
+    uint64_t reader_bytes_per_read;    // Resident::bytes_of, a batch of the device reader: offsets, flags, read groups
+    int lens_per_record;               // RecordStore's layout: FASTQ name, comment, sequence length; BAM block length; SAM line length + fields
+    bool block_parallel;               // there is a block-parallel host parser (open_fast)
+    std::unique_ptr<Source> (*open_source)(const std::string &path, bool use_oq, int threads);      // the serial host reader
+    const ReaderCalls *reader;         // the device reader's calls (cli_device_io.h)
+    // pass 4 of one record of a RecordStore (rec_bytes at `rec`, its entries at `lens`) with the new qualities q, n_bases of them; 0, or the exit status
+    int (Sink::*write_stored)(const char *rec, const uint32_t *lens, const uint8_t *q, bool set_oq, size_t &rec_bytes, size_t &n_bases);
+};
+extern const FormatRow kFormats[3];    // by Format: fastq, bam, sam (kbbq_cli.cc, behind everything a row points to)
+
+// The value of an environment switch (what getenv returned): a number, or "set to this text"
+static long long env_num(const char *s, long long unset) { return s ? strtoll(s, nullptr, 10) : unset; }
+static bool env_is(const char *s, const char *text) { return s && !strcmp(s, text); }
+
+// What the user asked for: the command line (kbbq.cc:81-150) and every KBBQ_* switch of the environment (README.md), each
+// read in one place -- here, when main() makes its CliOptions, before the first file is opened -- with its default beside it.
+struct CliOptions {
+    int k = 32;
+    long double alpha = 0;
+    uint64_t genomelen = 0;
+    unsigned coverage = 0;
+    bool set_oq = false, use_oq = false;
+    int nthreads = 0;
+    std::string filename = "-", fixedinput;
+    // What is opened for `filename` and for --fixed.  "-" with a regular file on standard input (kbbq ... < reads.fq.gz) is
+    // that file under a name that can be opened once per pass; the log lines keep saying "-".
+    std::string input = "-", fixed_path;
+    // The input is not a regular file -- a pipe on standard input, a FIFO, /dev/stdin on a pipe: it is read once, front to
+    // back, by the device reader (main(): StreamInput), and whatever would read it a second time is refused.
+    bool stream = false, fixed_stream = false;
+    // --fixed may read both of its files on the GPU: none of the switches below that ask for the host parsers
+    // (main() decides once the format is known, and clears it when the run is handed back to the host loop)
+    bool fixed_on_device = false;
+    int out_threads = 1;      // --threads, or "pick" (parse())
+    int io_threads = 1;       // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
+    Format format = Format::fastq;      // what sniff() found: fastq, bam or sam
+    bool timing = getenv("KBBQ_TIMING") != nullptr;                          // set to anything: wall-clock per phase on stderr at the end
+    int write_threads = (int)env_num(getenv("KBBQ_WRITE_THREADS"), 4);       // threads writing ranges of a regular output file; 1: sequential always
+    bool preload = env_num(getenv("KBBQ_PRELOAD"), 1) != 0;                  // =0: a piece of the device reader is not copied ahead of its chunk call
+    // bytes of the file per chunk of the device reader, reads per engine call: shrunk so that tests cross many boundaries with small files
+    uint64_t reader_piece = std::max<uint64_t>(64, (uint64_t)env_num(getenv("KBBQ_READER_PIECE_KB"), 256 << 10)) << 10;
+    size_t batch_reads = std::max<size_t>(1, (size_t)env_num(getenv("KBBQ_BATCH_READS"), 1 << 20));
+    long long host_cache_mb = env_num(getenv("KBBQ_HOST_CACHE_MB"), LLONG_MIN);   // host memory for the records of resident batches; unset: host_cache_budget()
+    int test_io_threads = (int)env_num(getenv("KBBQ_IO_THREADS"), 1);        // reader threads of the --io-test helpers
+    bool host_deflate = env_num(getenv("KBBQ_HOST_DEFLATE"), 0) != 0;        // =1: the zlib writer with the host readers, the A/B of the whole host I/O path
+    bool device_inflate = env_num(getenv("KBBQ_DEVICE_INFLATE"), 1) != 0;    // =0: the host parsers' BGZF input is inflated by their thread pool
+    bool resident = !env_is(getenv("KBBQ_RESIDENT"), "0");                   // =0: every pass reads the file again, nothing stays in HBM
+    bool device_reader = env_num(getenv("KBBQ_DEVICE_READER"), 1) != 0;      // =0: the host parsers at once
+    bool serial_parse = env_num(getenv("KBBQ_SERIAL_PARSE"), 0) != 0;        // =1: the serial readers at once
+    bool keep_text = env_num(getenv("KBBQ_KEEP_TEXT"), 1) != 0;              // =0: pass 4 of the device reader reads the file again (a stream: always 1)
+    long long text_budget_mb = env_num(getenv("KBBQ_TEXT_BUDGET_MB"), -1);   // HBM for resident reads + kept text; unset: 3/4 of the free memory
+    uint32_t seed = (uint32_t)env_num(getenv("KBBQ_SEED"), 0);               // the sampler's seed; 0: from time and pid like the reference
+    const char *devices = getenv("KBBQ_DEVICES");                            // 0,1,...: passes 1-3 sharded over these devices (run_on_devices)
+    bool exchange_local = env_is(getenv("KBBQ_EXCHANGE"), "local");          // in-process copies even between distinct devices
+    bool qual_digest = env_num(getenv("KBBQ_QUAL_DIGEST"), 0) != 0;          // =1: "[digest]" lines (bench.py's trusted_inserted and recal_qual_sum)
+    bool release = env_num(getenv("KBBQ_RELEASE"), 0) != 0;                  // =1: everything is freed in order at the end, no exit(0)
+
+    bool fixed_mode() const { return !fixedinput.empty(); }
+    const FormatRow &row() const { return kFormats[(int)format]; }
+    bool host_io() const { return host_deflate; }
+    // BGZF input that the host parsers read (BAM always) is inflated on the GPU as well
+    bool inflate_on_device() const { return !host_deflate && device_inflate; }
+    // The device reader (DeviceInput) may be tried: it makes resident batches of the input
+    bool may_read_on_device(bool resident_on) const {
+        return (!fixed_mode() || fixed_on_device) && !host_io() && resident_on && device_reader && !serial_parse;
+    }
+    bool fixed_may_read_on_device() const { return fixed_mode() && !host_io() && resident && device_reader && !serial_parse; }
+    // What was asked for that reads the input more than once, which a stream does not allow; null: nothing
+    const char *needs_a_file() const {
+        if (fixed_mode()) return "--fixed reads two files side by side and starts over with the host parsers, which read both again, when the GPU readers hand one back";
+        if (!resident) return "KBBQ_RESIDENT=0 reads it again in every pass";
+        if (!device_reader) return "KBBQ_DEVICE_READER=0 leaves it to the host parsers, which read it again for the output";
+        if (serial_parse) return "KBBQ_SERIAL_PARSE=1 leaves it to the host parsers, which read it again for the output";
+        if (host_deflate) return "KBBQ_HOST_DEFLATE=1 leaves it to the host parsers, which read it again for the output";
+        return nullptr;
+    }
+    // The name to open for a file argument, and whether it is a stream
+    static std::string resolve(const std::string &name, bool &is_stream) {
+        struct stat st;
+        is_stream = false;
+        if (name == "-") {
+            if (fstat(0, &st) == 0 && S_ISREG(st.st_mode)) return "/proc/self/fd/0";      // (a fresh description at offset 0 per open)
+            is_stream = true;
+        } else if (stat(name.c_str(), &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode)) {
+            is_stream = true;
+        }
+        return name;
+    }
+    uint64_t host_cache_budget() const {
+        if (host_cache_mb != LLONG_MIN) return (uint64_t)host_cache_mb << 20;
+        const long pages = sysconf(_SC_PHYS_PAGES), psize = sysconf(_SC_PAGE_SIZE);
+        const uint64_t ram = pages > 0 && psize > 0 ? (uint64_t)pages * (uint64_t)psize : 0;
+        return std::min<uint64_t>(ram / 4, 64ULL << 30);
+    }
+    // false: the message is on stderr, exit status 1
+    bool parse(int argc, char *argv[]) {
+        int opt = 0, opt_idx = 0;
+        while ((opt = getopt_long(argc, argv, "k:usg:c:f:a:t:", long_options, &opt_idx)) != -1) {
+            switch (opt) {
+                case 'k':
+                    k = std::stoi(std::string(optarg));
+                    // (the reference only prints this and goes on, kbbq.cc:102-104)
+                    if (k <= 0 || k > KBBQ_MAX_KMER) return !give_up("  Error: k must be <= " + std::to_string(KBBQ_MAX_KMER) + " and > 0.");
+                    break;
+                case 'u': use_oq = true; break;
+                case 's': set_oq = true; break;
+                case 'g': genomelen = std::stoull(std::string(optarg)); break;
+                case 'c': coverage = (unsigned)std::stoul(std::string(optarg)); break;
+                case 'f': fixedinput = std::string(optarg); break;
+                case 'a': alpha = std::stold(std::string(optarg)); break;
+                case 't':
+                    nthreads = std::stoi(std::string(optarg));
+                    if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
+                    break;
+                case '?':
+                default:
+                    return !give_up(std::string("  Unknown argument ") + (char)opt);
+            }
+        }
+        // --threads sizes the BGZF compression pool like the reference's htslib pool (kbbq.cc:159-168); unlike the
+        // reference, 0 does not mean "single-threaded" but "pick": the writer is the end-to-end bottleneck
+        out_threads = nthreads > 0 ? nthreads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        io_threads = out_threads;
+        if (optind < argc) {
+            filename = std::string(argv[optind]);
+            while (++optind < argc) std::cerr << put_now << " Warning: Extra argument " << argv[optind] << " ignored." << std::endl;
+        }
+        input = resolve(filename, stream);
+        if (fixed_mode()) fixed_path = resolve(fixedinput, fixed_stream);
+        return true;
+    }
+};
+
+static Format sniff(const std::string &path) {   // hts_detect_format, as far as this tool needs it
+    gzFile f = path == "-" ? nullptr : gzopen(path.c_str(), "rb");
+    if (!f) return Format::unknown;
+    unsigned char b[4] = {0, 0, 0, 0};
+    const int n = gzread(f, b, 4);
+    gzclose(f);
+    if (n >= 4 && looks_like_sam(b, 4)) return Format::sam;      // (before FASTQ's '@': "@HD" and a TAB is no read name)
+    if (n >= 4 && b[0] == 'B' && b[1] == 'A' && b[2] == 'M' && b[3] == 1) return Format::bam;
+    if (n >= 4 && b[0] == 'C' && b[1] == 'R' && b[2] == 'A' && b[3] == 'M') return Format::cram;
+    if (n >= 1 && b[0] == '@') return Format::fastq;
+    return Format::unknown;
+}
+
+// An input that is not a regular file (CliOptions::stream).  Its first bytes are read into host memory -- the head -- and
+// stand in for the input wherever a name is opened before the pieces flow: an in-memory file holds a copy of them, which
+// sniff() and BamReader open as /proc/self/fd/N.  The device reader then gets the head back as the first bytes of the
+// stream (piece_reader.h: PieceSource), so the input is read exactly once.
+struct StreamInput {
+    PieceSource src;
+    std::string head_path;      // the in-memory copy of the head, by name
+    StreamInput() = default;
+    StreamInput(const StreamInput &) = delete;
+    ~StreamInput() { if (memfd_ >= 0) ::close(memfd_); }
+    // false: nothing can be read from it (a terminal on standard input included: nobody is asked to type a file)
+    bool open(const CliOptions &o) {
+        src.stream = true;
+        if (o.filename == "-") {
+            if (isatty(0)) return false;
+            src.fd = 0;
+            src.owns_fd = false;
+        } else {
+            src.fd = ::open(o.input.c_str(), O_RDONLY);
+        }
+        if (src.fd < 0) return false;
+#ifdef F_SETPIPE_SZ
+        struct stat st;      // a pipe: as much buffer as the system grants, as on the output side (DeviceBgzfWriter)
+        if (fstat(src.fd, &st) == 0 && S_ISFIFO(st.st_mode)) (void)fcntl(src.fd, F_SETPIPE_SZ, 1 << 20);
+#endif
+        memfd_ = memfd_create("kbbq-head", MFD_CLOEXEC);
+        if (memfd_ < 0) return false;
+        head_path = "/proc/self/fd/" + std::to_string(memfd_);
+        return grow(kHead) && !src.head.empty();
+    }
+    // the head, and its copy, grown to `want` bytes or to the end of the stream
+    bool grow(size_t want) {
+        if (!src.grow_head(want)) return false;
+        while (copied_ < src.head.size()) {
+            const ssize_t w = pwrite(memfd_, src.head.data() + copied_, src.head.size() - copied_, (off_t)copied_);
+            if (w <= 0) return false;
+            copied_ += (size_t)w;
+        }
+        return true;
+    }
+    // A BAM header may be longer than any head chosen beforehand: the head is doubled until the header is in it
+    bool grow_more() { return !src.head_is_all && src.head.size() < kMaxHead && grow(2 * src.head.size()); }
+
+private:
+    // (a gzip header's fixed part and its longest extra field, or a whole first BGZF block, with room to spare)
+    static constexpr size_t kHead = (size_t)1 << 17, kMaxHead = (size_t)1 << 31;
+    int memfd_ = -1;
+    size_t copied_ = 0;
+};
+
+// KBBQ_TIMING=1: wall-clock per phase on stderr at the end ("[timing] scan 12.3 s ..."): where an end-to-end run goes
+struct PhaseClock {
+    std::vector<std::pair<std::string, double>> phases;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    bool on;
+    explicit PhaseClock(bool timing) : on(timing) {}
+    void mark(const char *name) {
+        const auto t1 = std::chrono::steady_clock::now();
+        phases.emplace_back(name, std::chrono::duration<double>(t1 - t0).count());
+        t0 = t1;
+    }
+    ~PhaseClock() { report(); }
+    void report() {
+        if (!on) return;
+        on = false;
+        std::cerr << "[timing]";
+        for (auto &p : phases) std::cerr << " " << p.first << " " << p.second << " s";
+        struct rusage ru;
+        if (getrusage(RUSAGE_SELF, &ru) == 0) std::cerr << " peak_host_rss_MB " << ru.ru_maxrss / 1024;
+        std::cerr << std::endl;
+    }
+};

@@ -38,7 +38,7 @@ std::unique_ptr<ByteSource> open_bytes(const std::string &path, int threads);
 // subfields -- or 0 if it is not one: what decides "BGZF" for every reader of this program (the device reader's own test
 // in kbbq_fastq_reader_chunk is the same rule).
 size_t bgzf_block_size(const unsigned char *h, size_t have);
-// Another inflater for BGZF files (the command line installs the one on the GPU, kbbq_cli.cc: DeviceBgzfSource): called by
+// Another inflater for BGZF files (the command line installs the one on the GPU, cli_device_io.h: DeviceBgzfSource): called by
 // open_bytes for a regular BGZF file, and for a regular file that is another gzip stream; a null result falls back to the
 // thread pool (BGZF) or to zlib.
 typedef std::unique_ptr<ByteSource> (*BgzfSourceFactory)(const std::string &path);
@@ -175,7 +175,7 @@ private:
 // reference would throw (name shorter than two characters, readutils.cc:90).
 bool parse_read_name(const std::string &fullname, std::string &rg, bool &second, std::string &first_name);
 
-// Where output bytes go: a BGZF writer -- host zlib (BgzfWriter below) or the device encoder (kbbq_cli.cc:
+// Where output bytes go: a BGZF writer -- host zlib (BgzfWriter below) or the device encoder (cli_device_io.h:
 // DeviceBgzfWriter over include/kbbq_bgzf.h).  The decompressed stream is the same through either.
 class ByteSink {
 public:

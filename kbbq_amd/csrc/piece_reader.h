@@ -1,4 +1,4 @@
-// piece_reader.h -- the input of the device readers as bytes in pieces (kbbq_cli.cc: DeviceFastqInput; --io-test pieces).
+// piece_reader.h -- the input of the device readers as bytes in pieces (cli_device_io.h: DeviceInput; --io-test pieces).
 // Host code only, no call into the engine library: what it does at the end of a stream is checked on a machine without a GPU.
 //   * PieceSource : where the bytes come from.  A regular file is read with pread at a running offset and may be read again
 //                   from its start.  Anything else -- a pipe, a FIFO, /dev/stdin on a pipe -- is a stream: read once with

@@ -391,7 +391,7 @@ def test_cli_output_does_not_depend_on_the_batch_size(tmp_path):
 
 
 def test_cli_output_into_a_file_is_written_in_ranges(tmp_path):
-    """Standard output that is a regular file gets its blocks by pwrite from several threads (kbbq_cli.cc:
+    """Standard output that is a regular file gets its blocks by pwrite from several threads (cli_device_io.h:
     DeviceBgzfWriter::put); the file must hold the bytes a pipe receives, behind whatever the file held before, and a file
     opened for appending or KBBQ_WRITE_THREADS=1 takes the sequential writes."""
     d, names, n_rg = named_dataset(seed=515, genome_len=30000, coverage=30, n_per_million=2000, ragged=True, extra_errors=80)

@@ -1,4 +1,4 @@
-"""`kbbq` reading its input from standard input, a pipe or a FIFO (kbbq_cli.cc: StreamInput, piece_reader.h): the stream
+"""`kbbq` reading its input from standard input, a pipe or a FIFO (cli_options.h: StreamInput, piece_reader.h): the stream
 is read once by the device reader, cut into the same pieces as a file of the same bytes, so the compressed output must be
 the named-file run's byte for byte -- and, since that only compares the program with itself, the oracle's qualities for the
 gzip and the BAM input.  What would need the input twice is refused with one line.  Every run uses 64 KB pieces, so these
