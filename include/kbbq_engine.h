@@ -343,6 +343,14 @@ int kbbq_recalibrate_batch(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qua
 /* Same, but qual_out is always HOST memory (a device-resident batch whose new qualities go to a writer). */
 int kbbq_recalibrate_batch_host(kbbq_engine *e, const kbbq_reads *reads, uint8_t *host_qual_out);
 
+/* Binned output qualities: map[q] stands for every quality q that pass 4 writes.  The map is engine state (NULL clears it):
+ * while one is set, every kbbq_recalibrate_batch* call -- the host-output and the submitted forms included -- passes its
+ * output through it before the caller sees it; with none set no kernel is launched and nothing changes. */
+int kbbq_set_quality_map(kbbq_engine *e, const uint8_t map[256]);
+/* The kernel alone: device_qual[i] = map[device_qual[i]] for i < n, in place, queued on the engine's stream.  device_qual
+ * needs no alignment and no byte outside [device_qual, device_qual + n) is touched; map is host memory. */
+int kbbq_map_qualities(kbbq_engine *e, uint8_t *device_qual, uint64_t n, const uint8_t map[256]);
+
 /* ---- asynchronous submission of host batches --------------------------------
  * The calls above return when their host batch has left the caller's memory, so batch i+1 is copied only after batch i
  * has landed: a bubble per batch on the link.  The *_submit forms only QUEUE the batch -- copy into a staging slot,
@@ -410,6 +418,26 @@ int kbbq_host_thresholds(int32_t k, uint64_t filter_bits, uint64_t inserted, uin
 /* CCovariateData::get_dqs (covariateutils.cc:204-230) on dense histograms; cov->rg and cov->q are
  * ignored (they are sums of cov->cycle). */
 int kbbq_host_train(const kbbq_covariates *cov, kbbq_dq *out);
+/* The recalibration table file: the covariate histograms of a training run as versioned, line-oriented text
+ * (kbbq_amd/csrc/host_table.cc has the format), from which kbbq_host_train gives the run's kbbq_dq again, integer for integer.
+ * write: all four arrays of cov, only cells whose total is not zero; rg_ids: cov->n_rg ids in dense-index order (the empty
+ * id is a value; none may hold a TAB or a line break, no two may be equal); info (may be NULL) goes into '#' lines that a
+ * reader ignores.  The same arguments give the same bytes.  KBBQ_EINVAL for a cell with errors > total, KBBQ_EIO for a file
+ * that cannot be written.
+ * read, in two steps like kbbq_covariates_get's callers: with cov's four arrays and rg_ids all NULL it checks the whole file
+ * and reports cov->n_rg, cov->n_cycle and in *rg_ids_bytes the room the ids need; with arrays of those dimensions and
+ * *rg_ids_bytes of room it fills them (cells the file does not name are zero) and writes the ids to rg_ids, each ended by
+ * a NUL, in dense-index order.  Nothing is indexed with a value that was not checked first: an unknown version, an index out
+ * of range, a row given twice, errors > total, a number that does not parse or overflows 64 bits, a file that ends early,
+ * more than 65534 read groups -- each is KBBQ_EINVAL with a text that names the line ("table <path>: line <n>: ..."). */
+typedef struct kbbq_table_info {
+    int32_t k;              /* --ksize of the run */
+    uint32_t seed;          /* its sampler seed */
+    uint64_t total_bases;   /* bases it read */
+    const char *command;    /* its command line, or NULL */
+} kbbq_table_info;
+int kbbq_host_table_write(const char *path, const kbbq_covariates *cov, const char *const *rg_ids, const kbbq_table_info *info);
+int kbbq_host_table_read(const char *path, kbbq_covariates *cov, char *rg_ids, uint64_t *rg_ids_bytes);
 /* Largest T with: std::bernoulli_distribution(p) accepts a 64-bit draw u  <=>  u < T. */
 uint64_t kbbq_host_bernoulli_threshold(double p, int32_t *always);
 

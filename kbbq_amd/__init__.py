@@ -6,5 +6,5 @@ functions), reads.py (batch packing), synth.py (seeded synthetic reads),
 dist.py (multi-GPU exchange steps over torch.distributed / RCCL).
 """
 from ._lib import KbbqError, LIB_PATH, build  # noqa: F401
-from .engine import Engine, plan_parameters  # noqa: F401
+from .engine import Engine, host_train, plan_parameters, read_table, write_table  # noqa: F401
 from .reads import ReadBatch  # noqa: F401

@@ -62,6 +62,10 @@ class Dq(ctypes.Structure):
                 ("cycledq", c_vp), ("dinucdq", c_vp)]
 
 
+class TableInfo(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("seed", ctypes.c_uint32), ("total_bases", c_u64), ("command", ctypes.c_char_p)]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -144,6 +148,11 @@ SYMBOLS = {
     "kbbq_host_thresholds": (ctypes.c_int, [ctypes.c_int32, c_u64, c_u64, ctypes.c_uint32, ctypes.c_char_p, c_i32p,
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t]),
     "kbbq_host_train": (ctypes.c_int, [ctypes.POINTER(Covariates), ctypes.POINTER(Dq)]),
+    "kbbq_host_table_write": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(Covariates), ctypes.POINTER(ctypes.c_char_p),
+                                             ctypes.POINTER(TableInfo)]),
+    "kbbq_host_table_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(Covariates), c_vp, c_u64p]),
+    "kbbq_set_quality_map": (ctypes.c_int, [c_vp, c_vp]),
+    "kbbq_map_qualities": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp]),
     "kbbq_host_bernoulli_threshold": (c_u64, [ctypes.c_double, c_i32p]),
     "kbbq_rng_state_at": (ctypes.c_int, [ctypes.c_uint32, c_u64, c_u64p]),
     # include/kbbq_bgzf.h: the BGZF writer on the device

@@ -146,6 +146,9 @@ public:
         if (fd_ >= 0 && lseek(fd_, (off_t)file_at_, SEEK_SET) < 0) return false;      // whoever writes next continues behind the blocks
         return fflush(out_) == 0;
     }
+    // The stream ends here without its end-of-file block, nothing more is collected or written: a run that has to stop after
+    // output has begun leaves a file every BGZF reader reports as truncated, not a short valid one.
+    void abandon() { closed_ = true; }
     int in_flight() const { return in_flight_; }
     uint64_t payload_bytes = 0, compressed_bytes = 0;
     void kernel_ms(double &format, double &deflate, double &gather) const { format = deflate = gather = 0; if (z_) kbbq_bgzf_kernel_ms(z_, &format, &deflate, &gather); }

@@ -19,7 +19,10 @@ static int give_up(const std::string &text) {
 static struct option long_options[] = {   // kbbq.cc:66-79
     {"ksize", required_argument, 0, 'k'},    {"use-oq", no_argument, 0, 'u'},     {"set-oq", no_argument, 0, 's'},
     {"genomelen", required_argument, 0, 'g'}, {"coverage", required_argument, 0, 'c'}, {"fixed", required_argument, 0, 'f'},
-    {"alpha", required_argument, 0, 'a'},     {"threads", required_argument, 0, 't'},  {0, 0, 0, 0}};
+    {"alpha", required_argument, 0, 'a'},     {"threads", required_argument, 0, 't'},
+    // not the reference's: the recalibration table (cli_table.h) and binned output qualities
+    {"save-table", required_argument, 0, 1001}, {"load-table", required_argument, 0, 1002}, {"quantize", required_argument, 0, 1003},
+    {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
 
@@ -65,6 +68,13 @@ struct CliOptions {
     // --fixed may read both of its files on the GPU: none of the switches below that ask for the host parsers
     // (main() decides once the format is known, and clears it when the run is handed back to the host loop)
     bool fixed_on_device = false;
+    // --save-table FILE: a training run also writes its covariate histograms there after pass 3; --load-table FILE: no
+    // training, the model comes from that file (cli_table.h); --quantize LIST: every written quality becomes the largest listed
+    // value that is not above it (one below the smallest listed value stays: a bad base is never rounded up)
+    std::string save_table, load_table, command_line;
+    bool quantize = false;
+    uint8_t quality_map[256];
+    const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
     int out_threads = 1;      // --threads, or "pick" (parse())
     int io_threads = 1;       // inflate pool of BGZF inputs (hts_set_thread_pool on the input handle, htsiter.hh:64-66,110-112)
     Format format = Format::fastq;      // what sniff() found: fastq, bam or sam
@@ -90,6 +100,25 @@ struct CliOptions {
     bool release = env_num(getenv("KBBQ_RELEASE"), 0) != 0;                  // =1: everything is freed in order at the end, no exit(0)
 
     bool fixed_mode() const { return !fixedinput.empty(); }
+    bool table_run() const { return !load_table.empty(); }
+    // --quantize's list into quality_map; false: not strictly increasing integers in 0..93, or none, or more than 93
+    bool parse_quantize(const char *list) {
+        std::vector<int> bins;
+        for (const char *q = list;;) {
+            if (*q < '0' || *q > '9') return false;
+            int v = 0;
+            for (; *q >= '0' && *q <= '9'; ++q) if ((v = v * 10 + (*q - '0')) > KBBQ_MAXQ) return false;
+            if ((!bins.empty() && v <= bins.back()) || bins.size() >= (size_t)KBBQ_MAXQ) return false;
+            bins.push_back(v);
+            if (!*q) break;
+            if (*q++ != ',') return false;
+        }
+        for (int q = 0, b = -1; q < 256; ++q) {
+            while (b + 1 < (int)bins.size() && bins[(size_t)b + 1] <= q) ++b;
+            quality_map[q] = (uint8_t)(b < 0 ? q : bins[(size_t)b]);
+        }
+        return quantize = true;
+    }
     const FormatRow &row() const { return kFormats[(int)format]; }
     bool host_io() const { return host_deflate; }
     // BGZF input that the host parsers read (BAM always) is inflated on the GPU as well
@@ -138,10 +167,16 @@ struct CliOptions {
                     break;
                 case 'u': use_oq = true; break;
                 case 's': set_oq = true; break;
-                case 'g': genomelen = std::stoull(std::string(optarg)); break;
-                case 'c': coverage = (unsigned)std::stoul(std::string(optarg)); break;
-                case 'f': fixedinput = std::string(optarg); break;
-                case 'a': alpha = std::stold(std::string(optarg)); break;
+                case 'g': genomelen = std::stoull(std::string(optarg)); if (!trains_with) trains_with = "--genomelen"; break;
+                case 'c': coverage = (unsigned)std::stoul(std::string(optarg)); if (!trains_with) trains_with = "--coverage"; break;
+                case 'f': fixedinput = std::string(optarg); if (!trains_with) trains_with = "--fixed"; break;
+                case 'a': alpha = std::stold(std::string(optarg)); if (!trains_with) trains_with = "--alpha"; break;
+                case 1001: save_table = std::string(optarg); if (!trains_with) trains_with = "--save-table"; break;
+                case 1002: load_table = std::string(optarg); break;
+                case 1003:
+                    if (!parse_quantize(optarg))
+                        return !give_up(std::string(" Error: --quantize takes up to 93 strictly increasing integers in 0..93, separated by commas, not \"") + optarg + "\".");
+                    break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -151,6 +186,9 @@ struct CliOptions {
                     return !give_up(std::string("  Unknown argument ") + (char)opt);
             }
         }
+        if (table_run() && trains_with)
+            return !give_up(std::string(" Error: --load-table with ") + trains_with + ": a table run does not train, it applies the model of the table.");
+        for (int i = 0; i < argc; ++i) command_line += (i ? " " : "") + std::string(argv[i]);
         // --threads sizes the BGZF compression pool like the reference's htslib pool (kbbq.cc:159-168); unlike the
         // reference, 0 does not mean "single-threaded" but "pick": the writer is the end-to-end bottleneck
         out_threads = nthreads > 0 ? nthreads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));

@@ -45,6 +45,7 @@ int kbbq_fail(int code, const char *fmt, ...) {      // (abi_internal.h: shared 
 #include "bucket.h"
 #include "long_reads.h"
 #include "fixed_compare.h"
+#include "quality_map.h"
 
 // ============================================================ engine object
 
@@ -273,6 +274,9 @@ struct kbbq_engine {
     int take_turn = 0;
     // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: what this engine has raised on ITS device
     size_t attr_lds_tally = 0, attr_lds_recal = 0;
+    // binned output qualities (kbbq_set_quality_map): pass 4's output goes through this map while one is set
+    QualityMap qmap;
+    bool qmap_set = false;
     std::map<const void *, size_t> attr_lds_correct;
 };
 
@@ -1173,6 +1177,30 @@ int kbbq_digest_add(kbbq_engine *e, const uint8_t *device_bytes, uint64_t n) {
     hipLaunchKernelGGL(k_sum_bytes, dim3((unsigned)std::min<uint64_t>((n / 16 + 256) / 256, 4096)), dim3(256), 0, e->stream, device_bytes, n, &e->d_totals->digest);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
+}
+
+// p[i] = map[p[i]] for i < n, queued on the engine's stream (quality_map.h)
+static int launch_quality_map(kbbq_engine *e, uint8_t *p, uint64_t n, const QualityMap &map) {
+    if (!n) return KBBQ_OK;
+    Timed t(e, "k_map_qualities");
+    hipLaunchKernelGGL(k_map_qualities, dim3((unsigned)std::min<uint64_t>((n / 16 + 256) / 256, 4096)), dim3(256), 0, e->stream, p, n, map);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int kbbq_set_quality_map(kbbq_engine *e, const uint8_t map[256]) {
+    ENGINE_DEVICE(e);
+    e->qmap_set = map != nullptr;
+    if (map) memcpy(e->qmap.w, map, 256);
+    return KBBQ_OK;
+}
+
+int kbbq_map_qualities(kbbq_engine *e, uint8_t *device_qual, uint64_t n, const uint8_t map[256]) {
+    ENGINE_DEVICE(e);
+    if (!map || (!device_qual && n)) return fail(KBBQ_EINVAL, "null argument");
+    QualityMap m;
+    memcpy(m.w, map, 256);
+    return launch_quality_map(e, device_qual, n, m);
 }
 
 int kbbq_digest_get(kbbq_engine *e, uint64_t *sum, int32_t reset) {
@@ -2347,12 +2375,17 @@ static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qu
     }
     const int vec_ok = (((uintptr_t)R.qual | (uintptr_t)d_out) & 15) == 0;
     auto launch = [&](uint64_t base0, uint64_t base1) -> int {      // the bases [base0, base1), base0 a multiple of 16
-        Timed t(e, "k_recalibrate");
-        const uint64_t lanes = (base1 - base0 + 15) / 16;
-        const unsigned blocks = (unsigned)std::min<uint64_t>((lanes + 1023) / 1024, lds > 76 * 1024 ? 256 : 256 * 2);
-        hipLaunchKernelGGL(k_recalibrate, dim3(blocks), dim3(1024), lds, e->stream,
-                           R, D, d_out, 6, vec_ok, lds_rgs, read_index, base0, base1);
-        HIP_TRY(hipGetLastError());
+        {
+            Timed t(e, "k_recalibrate");
+            const uint64_t lanes = (base1 - base0 + 15) / 16;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((lanes + 1023) / 1024, lds > 76 * 1024 ? 256 : 256 * 2);
+            hipLaunchKernelGGL(k_recalibrate, dim3(blocks), dim3(1024), lds, e->stream,
+                               R, D, d_out, 6, vec_ok, lds_rgs, read_index, base0, base1);
+            HIP_TRY(hipGetLastError());
+        }
+        // binned output (kbbq_set_quality_map): the bases this launch wrote, behind it on the same stream, before any copy
+        // out of d_out or any caller's work ordered behind the engine's stream sees them
+        if (e->qmap_set) return launch_quality_map(e, d_out + base0, base1 - base0, e->qmap);
         return KBBQ_OK;
     };
     if (pipelined) {

@@ -41,6 +41,11 @@
 //     and SAM: a main file without @RG lines, a record without an RG tag, malformed records, --use-oq without a usable OQ),
 //     a corrected record without bases, a corrected file that does not open as the first file's format.  BAM and SAM
 //     have one timed run each, FASTQ none;
+//   * --save-table FILE / --load-table FILE split a run in two, "make the table" and "apply the table" (cli_table.h): the first
+//     also writes the covariate histograms of its training passes, the second trains nothing, derives the model from such a
+//     file and applies it -- in one pass over the device reader, with nothing kept, where that reader may be tried (a stream
+//     of any size included), by the usual scan and pass 4 otherwise; --quantize LIST bins the written qualities
+//     (kbbq_set_quality_map).  The reference has none of the three;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -67,6 +72,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/kbbq_bgzf.h"
@@ -703,6 +709,7 @@ static int tally_fixed_on_device(kbbq_engine *e, const CliOptions &o, ScanState 
 }
 
 #include "cli_pass4.h"
+#include "cli_table.h"
 
 // What differs between the input formats and is no control flow (cli_options.h: FormatRow)
 const FormatRow kFormats[3] = {
@@ -715,7 +722,15 @@ const FormatRow kFormats[3] = {
 };
 
 // KBBQ_TIMING=1: what the device reader and the device writer did
-static void report_io_timing(DeviceInput &in, const Sink &w, const FixedOnDevice &fixed) {
+static void report_io_timing(DeviceInput &in, const Sink &w, const FixedOnDevice &fixed, const OnePass &one_pass) {
+    if (one_pass.used) {
+        double inf = 0, idx = 0;
+        in.kernel_ms(inf, idx);
+        std::cerr << "[timing] --load-table: applied in one pass over the " << in.format() << " reader on the GPU (" << in.container << "): " << one_pass.chunks
+                  << " chunks, " << one_pass.records << " records, " << one_pass.bases << " bases, nothing kept; the model installed " << one_pass.models
+                  << " times; waiting for file reads " << in.wait_s << " s, device calls " << in.device_s << " s; kernels: inflate " << inf
+                  << " ms, index + pack " << idx << " ms" << std::endl;
+    }
     if (fixed.used)
         std::cerr << "[timing] --fixed: both files read on the GPU (the fixed file: " << fixed.container << ", " << fixed.chunks << " chunks, " << fixed.records
                   << " records paired with " << fixed.batches << " resident batches in " << fixed.calls << " compare calls; " << fixed.straddled
@@ -732,6 +747,87 @@ static void report_io_timing(DeviceInput &in, const Sink &w, const FixedOnDevice
         std::cerr << "[timing] BGZF writer on the GPU: " << w.payload << " bytes -> " << w.compressed << " (ratio "
                   << (double)w.payload / (double)std::max<uint64_t>(1, w.compressed) << "); kernels: format " << w.ms_format
                   << " ms, deflate " << w.ms_deflate << " ms, gather " << w.ms_gather << " ms" << std::endl;
+}
+
+// Pass 4 by the one of cli_pass4.h's writers that fits what the scan left behind
+static int write_output(kbbq_engine *e, ScanState &scan, const CliOptions &opt, Sink &sink, DeviceInput &dev_in, Batch &batch) {
+    const Resident &resident = scan.resident;
+    if (dev_in.active && sink.dev) return write_from_device_reader(e, scan, opt, sink, dev_in);
+    if (resident.on && resident.keep_recs && opt.format == Format::fastq && sink.dev) return write_resident_fastq(e, scan, opt, sink);
+    if (resident.on && resident.keep_recs && opt.format == Format::bam && sink.dev) return write_resident_bam(e, scan, opt, sink);
+    if (resident.on && resident.keep_recs) return write_resident_records(e, scan, opt, sink);
+    if (scan.passes_fast() && opt.format == Format::fastq && sink.dev) return write_reparsed_fastq(e, scan, opt, sink, batch);
+    return write_serial(e, scan, opt, sink, batch);
+}
+
+// The end of a run whose output is written and closed: the timing report, then the process's exit
+static int end_run(const CliOptions &opt, PhaseClock &clock, DeviceInput &dev_in, const Sink &sink, const FixedOnDevice &fixed_report, const OnePass &one_pass,
+                   ScanState &scan, EngineOwner &engine) {
+    clock.mark("pass4+format+deflate+write");
+    if (clock.on) report_io_timing(dev_in, sink, fixed_report, one_pass);
+    // Everything is written and flushed.  Handing 200 GB of device memory back allocation by allocation takes 2.2 s at
+    // BASELINE size (every hipFree waits for the device); the process ends here and the driver takes it all back at once
+    // -- behind the device reader, whose I/O thread and streams must not be alive beside the runtime's own teardown (its
+    // two page-locked buffers of 256 MB, 60 ms to unpin, go with the rest).
+    // KBBQ_RELEASE=1: the orderly way (leak checkers), which is also what every early return above takes.
+    if (!opt.release) {
+        dev_in.stop();
+        clock.mark("end");
+        clock.report();
+        fflush(stdout);
+        fflush(stderr);
+        exit(0);      // (handlers registered with atexit still run: a profiler's, the runtime's)
+    }
+    scan.resident.drop();
+    engine.release();
+    clock.mark("release");
+    return 0;
+}
+
+// --load-table (cli_table.h): no sampling, no filters, no thresholds, no training passes.  The one-pass route wherever the
+// device reader may be tried; the general route -- the usual scan by the host parsers, the table's model with its rows in
+// the order that scan numbered the read groups, pass 4 by the writer main() would pick -- when the switches ask for the host
+// parsers or the one-pass route hands a file back (the device scan would hand the same file back: it is not tried again).
+static int run_table(CliOptions &opt, StreamInput *stream) {
+    LoadedTable table;
+    if (const int rc = table.load(opt.load_table)) return rc;
+    std::cerr << put_now << " Applying the recalibration table " << opt.load_table << " (" << table.n_rg << " read groups, " << table.n_cycle
+              << " cycles): no training passes." << std::endl;
+    if (opt.devices && *opt.devices) std::cerr << put_now << " KBBQ_DEVICES is ignored with --load-table: a table run uses one device." << std::endl;
+    PhaseClock clock(opt.timing);
+    DeviceInput dev_in(opt);
+    EngineOwner engine;
+    ScanState scan;
+    Batch batch;
+    OnePass one_pass;
+    scan.resident.init(opt);
+    Sink sink;
+    int rc = -1;
+    if (opt.may_read_on_device(scan.resident.on)) {
+        std::cerr << put_now << " Recalibrating file" << std::endl;
+        rc = apply_table_one_pass(opt, stream, dev_in, table, engine, scan, sink, one_pass);
+        if (rc > 0) return rc;
+        if (rc < 0) std::cerr << put_now << " The GPU reader hands the file back: starting over with the host parsers." << std::endl;
+    }
+    if (rc < 0) {
+        if (stream) return give_up(" Error: input from a pipe is read once, and the GPU reader cannot be used: write the input to a file first.");
+        scan.reset(opt);
+        if (host_scan(opt, scan, batch)) return 1;
+        if (scan.longest > table.n_cycle) return table.too_long(scan.longest);
+        clock.mark("scan+pack+upload");
+        if (scan.resident.on)
+            std::cerr << put_now << " Reads are resident on the GPU: " << scan.resident.dev.size() << " batches"
+                      << (scan.resident.keep_recs ? ", their records in host memory." : ".") << std::endl;
+        const uint64_t n_rg = std::max<size_t>(1, scan.groups.size());
+        if (create_table_engine(opt, table, n_rg, &engine.e)) return 1;
+        if (const int bad = table.install(engine.e, n_rg, scan.groups.names())) return bad;      // (the whole order is known: permuted once)
+        clock.mark("model");
+        std::cerr << put_now << " Recalibrating file" << std::endl;
+        if ((rc = sink.open(opt, scan))) return rc;
+        if (write_output(engine.e, scan, opt, sink, dev_in, batch)) return 1;
+    }
+    if (!sink.close()) return 1;
+    return end_run(opt, clock, dev_in, sink, FixedOnDevice(), one_pass, scan, engine);
 }
 
 int main(int argc, char *argv[]) {
@@ -757,6 +853,7 @@ int main(int argc, char *argv[]) {
             return give_up(std::string(" Error: input from a pipe is read once, and ") + why + ": write the input to a file first.");
     }
     if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
+    if (opt.table_run()) return run_table(opt, stream.get());
 
     // The one scan before the engine exists: on the device when that may be tried and takes the file, with the host parsers
     // otherwise.  An early return unwinds these in the reverse order: resident batches, engine, the device reader and its thread.
@@ -828,36 +925,16 @@ int main(int argc, char *argv[]) {
     }
     if (!trained && train_model(e, nullptr, true, clock, fail_engine)) return 1;
 
+    if (!opt.save_table.empty())
+        if (const int rc = save_table(e, opt, scan, p.seed)) return rc;
+
     // pass 4, kbbq.cc:455-457: recalibrate_and_write(file, dqs, "-")
     clock.mark("model");
     std::cerr << put_now << " Recalibrating file" << std::endl;
+    if (opt.quantize && kbbq_set_quality_map(e, opt.quality_map) < 0) return fail_engine("cannot set the quality map");
     Sink sink;
     int rc = sink.open(opt, scan);
     if (rc) return rc;
-    if (dev_in.active && sink.dev) rc = write_from_device_reader(e, scan, opt, sink, dev_in);
-    else if (resident.on && resident.keep_recs && opt.format == Format::fastq && sink.dev) rc = write_resident_fastq(e, scan, opt, sink);
-    else if (resident.on && resident.keep_recs && opt.format == Format::bam && sink.dev) rc = write_resident_bam(e, scan, opt, sink);
-    else if (resident.on && resident.keep_recs) rc = write_resident_records(e, scan, opt, sink);
-    else if (scan.passes_fast() && opt.format == Format::fastq && sink.dev) rc = write_reparsed_fastq(e, scan, opt, sink, batch);
-    else rc = write_serial(e, scan, opt, sink, batch);
-    if (rc || !sink.close()) return 1;
-    clock.mark("pass4+format+deflate+write");
-    if (clock.on) report_io_timing(dev_in, sink, fixed_report);
-    // Everything is written and flushed.  Handing 200 GB of device memory back allocation by allocation takes 2.2 s at
-    // BASELINE size (every hipFree waits for the device); the process ends here and the driver takes it all back at once
-    // -- behind the device reader, whose I/O thread and streams must not be alive beside the runtime's own teardown (its
-    // two page-locked buffers of 256 MB, 60 ms to unpin, go with the rest).
-    // KBBQ_RELEASE=1: the orderly way (leak checkers), which is also what every early return above takes.
-    if (!opt.release) {
-        dev_in.stop();
-        clock.mark("end");
-        clock.report();
-        fflush(stdout);
-        fflush(stderr);
-        exit(0);      // (handlers registered with atexit still run: a profiler's, the runtime's)
-    }
-    scan.resident.drop();
-    engine.release();
-    clock.mark("release");
-    return 0;
+    if (write_output(e, scan, opt, sink, dev_in, batch) || !sink.close()) return 1;
+    return end_run(opt, clock, dev_in, sink, fixed_report, OnePass(), scan, engine);
 }

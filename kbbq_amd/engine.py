@@ -286,6 +286,21 @@ class Engine:
         _lib.check(self.L.kbbq_recalibrate_batch(self.h, self._c(batch), out_device_ptr))
         return None
 
+    def set_quality_map(self, qmap):
+        """Binned output: every quality pass 4 writes becomes qmap[q] (256 bytes); None clears the map."""
+        if qmap is None:
+            _lib.check(self.L.kbbq_set_quality_map(self.h, None))
+            return
+        m = np.ascontiguousarray(qmap, dtype=np.uint8)
+        assert m.shape == (256,)
+        _lib.check(self.L.kbbq_set_quality_map(self.h, m.ctypes.data))
+
+    def map_qualities(self, device_ptr, n, qmap):
+        """The map kernel alone: n bytes at device_ptr become qmap[byte], in place, on the engine's stream."""
+        m = np.ascontiguousarray(qmap, dtype=np.uint8)
+        assert m.shape == (256,)
+        _lib.check(self.L.kbbq_map_qualities(self.h, device_ptr, int(n), m.ctypes.data))
+
     # ---- whole pipeline on one host batch (kbbq.cc:258-457)
     def run_all(self, batch):
         out = {}
@@ -332,6 +347,58 @@ def device_tensor(ptr, nbytes, dtype, device=0):
     import torch
     t = torch.as_tensor(_CudaArray(ptr, nbytes), device="cuda:%d" % device)
     return t.view(dtype)
+
+
+def _covariates_struct(cov):
+    """A kbbq_covariates over the arrays of a covariates dict (Engine.covariates()); the arrays it points into."""
+    R, C = int(cov["R"]), int(cov["C"])
+    a = {k: np.ascontiguousarray(cov[k], dtype=np.uint64) for k in ("rg", "q", "cycle", "dinuc")}
+    assert a["rg"].size == R * 2 and a["q"].size == R * NQ * 2 and a["cycle"].size == R * NQ * 2 * C * 2 and a["dinuc"].size == R * NQ * 32
+    c = _lib.Covariates()
+    c.n_rg, c.n_cycle = R, C
+    c.rg, c.q, c.cycle, c.dinuc = (a[k].ctypes.data for k in ("rg", "q", "cycle", "dinuc"))
+    return c, a
+
+
+def write_table(path, cov, rg_ids, k=0, seed=0, total_bases=0, command=None):
+    """The recalibration table file of a covariates dict (kbbq_host_table_write); rg_ids: one id per read group, in
+    dense-index order ("" is a value).  No GPU is touched."""
+    c, _keep = _covariates_struct(cov)
+    ids = [i.encode() if isinstance(i, str) else bytes(i) for i in rg_ids]
+    assert len(ids) == int(cov["R"])
+    arr = (ctypes.c_char_p * len(ids))(*ids)
+    info = _lib.TableInfo(k, seed & 0xFFFFFFFF, total_bases, command.encode() if isinstance(command, str) else command)
+    _lib.check(_lib.lib().kbbq_host_table_write(str(path).encode(), ctypes.byref(c), arr, ctypes.byref(info)))
+
+
+def read_table(path):
+    """A table file as a covariates dict with its read-group ids under "rg_ids" (kbbq_host_table_read: the dimensions
+    first, then the arrays).  A malformed file raises KbbqError with code -22 and the line number in the text."""
+    L = _lib.lib()
+    c = _lib.Covariates()
+    id_bytes = ctypes.c_uint64()
+    _lib.check(L.kbbq_host_table_read(str(path).encode(), ctypes.byref(c), None, ctypes.byref(id_bytes)))
+    R, C = int(c.n_rg), int(c.n_cycle)
+    out = dict(R=R, C=C, rg=np.zeros((R, 2), np.uint64), q=np.zeros((R, NQ, 2), np.uint64),
+               cycle=np.zeros((R, NQ, 2, C, 2), np.uint64), dinuc=np.zeros((R, NQ, 16, 2), np.uint64))
+    c.rg, c.q, c.cycle, c.dinuc = (out[k].ctypes.data for k in ("rg", "q", "cycle", "dinuc"))
+    ids = ctypes.create_string_buffer(max(1, id_bytes.value))
+    _lib.check(L.kbbq_host_table_read(str(path).encode(), ctypes.byref(c), ctypes.cast(ids, _lib.c_vp), ctypes.byref(id_bytes)))
+    out["rg_ids"] = [b.decode(errors="surrogateescape") for b in ids.raw[:id_bytes.value].split(b"\0")[:R]]
+    return out
+
+
+def host_train(cov):
+    """kbbq_host_train on a covariates dict (a loaded table): the delta-Q tables as Engine.dq() returns them."""
+    R, C = int(cov["R"]), int(cov["C"])
+    c, _keep = _covariates_struct(cov)
+    out = dict(R=R, C=C, meanq=np.zeros(R, np.int32), rg=np.zeros(R, np.int32), q=np.zeros((R, NQ), np.int32),
+               cycle=np.zeros((R, NQ, 2, C), np.int32), dinuc=np.zeros((R, NQ, 16), np.int32))
+    d = _lib.Dq()
+    d.n_rg, d.n_cycle = R, C
+    d.meanq, d.rgdq, d.qdq, d.cycledq, d.dinucdq = (out[k].ctypes.data for k in ("meanq", "rg", "q", "cycle", "dinuc"))
+    _lib.check(_lib.lib().kbbq_host_train(ctypes.byref(c), ctypes.byref(d)))
+    return out
 
 
 def rng_state_at(seed, ordinal):
