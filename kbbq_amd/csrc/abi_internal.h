@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// records the text (printf style) for kbbq_last_error() on this thread and returns `code` (engine.hip)
+// records the text (printf style) for kbbq_last_error() on this thread and returns `code` (engine_state.h)
 int kbbq_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // Every ABI entry works on its object's device and leaves the calling thread's current device as it found it

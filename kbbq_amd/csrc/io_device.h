@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256) k_dscan_add(uint64_t *data, uint64_t n, c
     if (i < n) data[i] += tile_sums[i / DSCAN_TILE];
 }
 
-// 64 bases per lane: the 2-bit words, the non-ACGT mask and the off-case bits (kbbq_pack_bases_case, engine.hip: same table)
+// 64 bases per lane: the 2-bit words, the non-ACGT mask and the off-case bits (kbbq_pack_bases_case, engine_misc.h: same table)
 // n_offcase[0] counts the off-case bases, n_offcase[1] the characters that the packed form cannot give back (anything but
 // ACGTN and acgt: digits, IUPAC codes, a lower-case n)
 __global__ void __launch_bounds__(256) k_pack_text(const uint8_t *seq_text, uint64_t n_bases, uint64_t *bases, uint64_t *nmask, uint64_t *offcase,

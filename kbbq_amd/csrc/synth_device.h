@@ -8,7 +8,7 @@ namespace kbbq {
 namespace dfl {
 
 // ---- the synthetic data set as files (tools: `kbbq --io-test synth-fastq / synth-bam`): the bench's own reads
-// (kbbq_synth_reads, engine.hip: k_synth) formatted on the device, so that a true 30x WGS-size FASTQ or BAM can be fed
+// (kbbq_synth_reads, engine_misc.h: k_synth) formatted on the device, so that a true 30x WGS-size FASTQ or BAM can be fed
 // to the command line and its digest compared with bench.py's.  Fixed-width names: every record has the same size.
 struct SynthBatch {
     const uint64_t *bases, *nmask;

@@ -780,7 +780,7 @@ def test_qualities_above_93_are_modelled_like_the_reference_s_growing_tables():
 @pytest.mark.parametrize("piece", ["64", "4160", "70000"])
 def test_pass4_of_a_host_batch_in_pieces(piece):
     """A large host batch with its result in host memory goes through pass 4 in pieces -- copy in, kernel and copy out of
-    successive pieces overlap on three streams (engine.hip: recalibrate_impl).  KBBQ_PASS4_PIECE shrinks the pieces so
+    successive pieces overlap on three streams (recalibrate_impl).  KBBQ_PASS4_PIECE shrinks the pieces so
     that small batches cross many piece boundaries (inside reads, between reads, at 64-base word boundaries): same
     qualities as the oracle's for uniform, ragged and many-read-group batches.  (The switch is read once per process.)"""
     import os

@@ -4,7 +4,7 @@ counters near their bound, mapped and identity quality plans, qualities without 
 launches, cycle windows, unaligned quality / output pointers, delta-Q tables beyond the LDS and the clamps, and the
 range check of kbbq_set_dq.  Every comparison is exact.
 
-Each case states the engine rule that sends it down its branch (engine.hip / kernels.h, cited) as a check of its
+Each case states the engine rule that sends it down its branch (engine_pass3.h, engine_pass4.h / kernels.h, cited) as a check of its
 own, and test_engine_rules_are_the_ones_the_cases_rely_on fails loudly if one of those rules is no longer in the sources."""
 import ctypes
 import os
@@ -29,19 +29,19 @@ CSRC = os.path.join(common.ROOT, "kbbq_amd", "csrc")
 # ---- the engine's rules, as the cases below rely on them -------------------------------------------------------------
 # (file, source text) pairs; the Python mirrors below restate them.
 RULES = (
-    ("engine.hip", "const int ccap = std::min(((max_len + 31) / 32) * 32, 192);"),                 # run_tally: cycles per window
-    ("engine.hip", "constexpr int kTallyMaxWindows = 24;"),                                        # above: direct cycle counts
-    ("engine.hip", "const size_t per_slot = (direct_cycles ? 0 : (size_t)8 * ccap) + 128;"),
-    ("engine.hip", "plan_tally_slots(P, e->qpresent, (int)((152 * 1024 - 512) / per_slot), n_rg);"),
-    ("engine.hip", "if (top >= 0 && top + 1 <= max_slots && (n_rg <= 1 || 2 * distinct >= top + 1)) {"),
-    ("engine.hip", "const size_t budget = (size_t)n_rg * per_rg <= 70 * 1024 ? 70 * 1024 : 140 * 1024;"),
-    ("engine.hip", "const int blocks = (int)std::min<uint64_t>((groups + 1023) / 1024, lds <= 76 * 1024 ? 512 : 256);"),
-    ("engine.hip", "if (!e->opt.tally_general && !R.offsets && n_rg == 1 && n_windows == 1 && R.read_len >= 16 && (int)R.read_len <= ccap && R.n_bases < (1ULL << 32) && vec_ok &&"),
+    ("engine_pass3.h", "const int ccap = std::min(((max_len + 31) / 32) * 32, 192);"),             # run_tally: cycles per window
+    ("engine_pass3.h", "constexpr int kTallyMaxWindows = 24;"),                                    # above: direct cycle counts
+    ("engine_pass3.h", "const size_t per_slot = (direct_cycles ? 0 : (size_t)8 * ccap) + 128;"),
+    ("engine_pass3.h", "plan_tally_slots(P, e->qpresent, (int)((152 * 1024 - 512) / per_slot), n_rg);"),
+    ("engine_pass3.h", "if (top >= 0 && top + 1 <= max_slots && (n_rg <= 1 || 2 * distinct >= top + 1)) {"),
+    ("engine_pass3.h", "const size_t budget = (size_t)n_rg * per_rg <= 70 * 1024 ? 70 * 1024 : 140 * 1024;"),
+    ("engine_pass3.h", "const int blocks = (int)std::min<uint64_t>((groups + 1023) / 1024, lds <= 76 * 1024 ? 512 : 256);"),
+    ("engine_pass3.h", "if (!e->opt.tally_general && !R.offsets && n_rg == 1 && n_windows == 1 && R.read_len >= 16 && (int)R.read_len <= ccap && R.n_bases < (1ULL << 32) && vec_ok &&"),
     ("kernels.h", "const uint64_t flush_every = max((uint64_t)1, (uint64_t)40000 / ((uint64_t)16384 / (uint64_t)L + 2));"),
     ("kernels.h", "const bool flush = (direct ? (it & 0xFFFF) == 0xFFFF : *l_reads >= 40000u) || it + 1 == iters;"),
-    ("engine.hip", "const int per_rg = (D.n_slots * (4 * D.n_cycle + 16) + KBBQ_NQ * 2 + 3) & ~3;"),
-    ("engine.hip", "const int budget = per_rg + 256 <= 64 * 1024 ? 64 * 1024 - 256 : 152 * 1024 - 256;"),
-    ("engine.hip", "const int lds_rgs = D.n_slots > 255 ? 0 : std::max(0, std::min(D.n_rg, budget / per_rg));"),
+    ("engine_pass4.h", "const int per_rg = (D.n_slots * (4 * D.n_cycle + 16) + KBBQ_NQ * 2 + 3) & ~3;"),
+    ("engine_pass4.h", "const int budget = per_rg + 256 <= 64 * 1024 ? 64 * 1024 - 256 : 152 * 1024 - 256;"),
+    ("engine_pass4.h", "const int lds_rgs = D.n_slots > 255 ? 0 : std::max(0, std::min(D.n_rg, budget / per_rg));"),
 )
 UNIFORM_FLUSH_READS = 40000      # kernels.h, k_tally_uniform's flush_every
 GENERAL_FLUSH_READS = 40000      # kernels.h, k_tally's l_reads bound
@@ -70,7 +70,7 @@ def n_windows_of(max_len):
 
 
 def tally_plan(quals, max_len, n_rg):
-    """plan_tally_slots + run_tally's launch split (engine.hip:238-261, 1965-1976): (identity, n_slots, per_launch, lds)."""
+    """plan_tally_slots + run_tally's launch split (engine_pass3.h): (identity, n_slots, per_launch, lds)."""
     direct = n_windows_of(max_len) > 24
     per_slot = (0 if direct else 8 * ccap_of(max_len)) + 128
     max_slots = max(1, min((152 * 1024 - 512) // per_slot, 255))
@@ -87,13 +87,13 @@ def tally_plan(quals, max_len, n_rg):
 
 
 def uniform_kernel_taken(read_len, n_rg, ragged, qual_aligned, general=False):
-    """engine.hip:1998: k_tally_uniform serves the batch (else k_tally)."""
+    """run_tally: k_tally_uniform serves the batch (else k_tally)."""
     return (not general and not ragged and n_rg == 1 and n_windows_of(read_len) == 1 and 16 <= read_len <= ccap_of(read_len)
             and qual_aligned)
 
 
 def recal_lds_rgs(n_slots, n_cycle, n_rg):
-    """recalibrate_impl (engine.hip:2277-2282): read groups whose delta-Q tables k_recalibrate holds in LDS."""
+    """recalibrate_impl: read groups whose delta-Q tables k_recalibrate holds in LDS."""
     per_rg = (n_slots * (4 * n_cycle + 16) + NQ * 2 + 3) & ~3
     budget = 64 * 1024 - 256 if per_rg + 256 <= 64 * 1024 else 152 * 1024 - 256
     return 0 if n_slots > 255 else max(0, min(n_rg, budget // per_rg))
@@ -284,7 +284,7 @@ def test_cycle_windows(M, monkeypatch):
 @pytest.mark.parametrize("shift", [1, 7, 15])
 @pytest.mark.parametrize("shape", ["uniform", "ragged"])
 def test_unaligned_qual(shape, shift, monkeypatch):
-    """qual 1-15 bytes past a 16-byte boundary (vec_ok == 0, engine.hip:1986): byte loads in k_tally; n_bases is no
+    """qual 1-15 bytes past a 16-byte boundary (vec_ok == 0, run_tally): byte loads in k_tally; n_bases is no
     multiple of 16."""
     rng = np.random.RandomState(shift)
     lens = np.full(20001, 150) if shape == "uniform" else np.concatenate([[0, 1, 150], rng.randint(0, 151, 20000)])
