@@ -157,7 +157,9 @@ int kbbq_engine_sync(kbbq_engine *e);
  * = 1 / 0 (KBBQ_INFER_SUBSET), "pass2_side" = 0 / 1 / 2: where the insert side of pass 2 runs (KBBQ_PASS2_SIDE; waits likewise),
  * "scan_blocks" / "walk_blocks" / "infer_blocks" = workgroups per CU of the kernels that stay resident for a whole batch while
  * the other stream has work (0 = as many as fit ... 16, 17 = the engine's own choice; KBBQ_SCAN_BLOCKS, KBBQ_WALK_BLOCKS,
- * KBBQ_INFER_BLOCKS).  KBBQ_EINVAL for an unknown name or a value out of range.
+ * KBBQ_INFER_BLOCKS), "report_flush" = bases a block of the quality-report kernel counts in LDS before it flushes to the
+ * global tables (1 .. 65535, the bound at which no LDS counter can overflow; 0 = that bound), "report_grid" = most workgroups of that kernel (1 .. 512,
+ * 0 = the default: a small grid makes a small batch cross many flushes).  KBBQ_EINVAL for an unknown name or a value out of range.
  * The engine runs kernels of neighbouring batches on two streams of its own: in a host process with more streams than the
  * runtime's hardware queues (GPU_MAX_HW_QUEUES) the two may share a queue and then run in order. */
 int kbbq_engine_tune(kbbq_engine *e, const char *name, uint64_t value);
@@ -351,6 +353,23 @@ int kbbq_set_quality_map(kbbq_engine *e, const uint8_t map[256]);
  * needs no alignment and no byte outside [device_qual, device_qual + n) is touched; map is host memory. */
 int kbbq_map_qualities(kbbq_engine *e, uint8_t *device_qual, uint64_t n, const uint8_t map[256]);
 
+/* What pass 4 did to the qualities, summed over every kbbq_recalibrate_batch* call while the report is on.
+ *   transfer [n_rg][256][KBBQ_MAXQ + 1]   bases of the read group with input quality i that were written as quality o
+ *   cycle    [n_rg][2][n_cycle][3]        per (pair, cycle): bases, sum of input qualities, sum of written qualities
+ *   above_maxq                            bases written above KBBQ_MAXQ (a caller's own quality map can do that; such a
+ *                                         base is counted in column KBBQ_MAXQ, and here; the cycle sums take the value written,
+ *                                         so such a report has sum_out > KBBQ_MAXQ * bases somewhere and the report FILE, whose
+ *                                         reader refuses that, cannot hold it: kbbq_host_report_write returns KBBQ_EINVAL)
+ * Every base of a batch is counted exactly once, whatever pass 4 did with it: N bases, bases below the minimum quality
+ * that pass 4 leaves alone, input qualities up to 255.  The counts are integer sums: they do not depend on how the
+ * batches were cut, on the piece size of a host batch or on the flush bound.  The report is engine state like the
+ * histograms: kbbq_engine_reset zeroes it.  While it is on, the launch behind pass 4 reads the batch's qual and qual_out
+ * both, so a qual_out that overlaps the batch's qual (in the same memory) is refused with KBBQ_EINVAL. */
+typedef struct kbbq_quality_report { uint64_t n_rg, n_cycle; uint64_t *transfer, *cycle; uint64_t above_maxq; } kbbq_quality_report;
+int kbbq_report_enable(kbbq_engine *e, int32_t on);   /* allocates and zeroes the device tables on first use; off: no kernel is launched, nothing changes */
+int kbbq_report_batch(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual_out);  /* the kernel alone, queued on the engine's stream */
+int kbbq_report_get(kbbq_engine *e, kbbq_quality_report *out, int32_t reset);   /* waits; caller-allocated arrays of kbbq_engine_dims' sizes */
+
 /* ---- asynchronous submission of host batches --------------------------------
  * The calls above return when their host batch has left the caller's memory, so batch i+1 is copied only after batch i
  * has landed: a bubble per batch on the link.  The *_submit forms only QUEUE the batch -- copy into a staging slot,
@@ -438,6 +457,19 @@ typedef struct kbbq_table_info {
 } kbbq_table_info;
 int kbbq_host_table_write(const char *path, const kbbq_covariates *cov, const char *const *rg_ids, const kbbq_table_info *info);
 int kbbq_host_table_read(const char *path, kbbq_covariates *cov, char *rg_ids, uint64_t *rg_ids_bytes);
+/* The quality report file: a kbbq_quality_report as versioned, line-oriented text in the manner of the table file
+ * (kbbq_amd/csrc/host_report.cc has the format).  write: only non-zero cells; rg_ids as for the table; observed (may be NULL):
+ * covariate histograms of the report's dimensions whose q array -- the calibration curve before recalibration -- goes into
+ * `observed` rows; info (may be NULL) and a summary per read group go into '#' lines that a reader ignores.  The same
+ * arguments give the same bytes.  KBBQ_EINVAL for a report the reader would refuse, KBBQ_EIO for a file that cannot be written.
+ * read, in two steps like kbbq_host_table_read: with report's two arrays, observed_q and rg_ids all NULL it checks the whole
+ * file and reports n_rg, n_cycle and the room the ids need; with arrays of those dimensions it fills them (observed_q:
+ * [n_rg][256][2] {errors, total}, may be NULL in step two).  Refused, each with its line number ("report <path>: line <n>:
+ * ..."): everything the table reader refuses, q_out > KBBQ_MAXQ, sum_in > 255 * bases, sum_out > KBBQ_MAXQ * bases, a read
+ * group whose transfer total differs from its cycle total, a row given twice, a missing end line. */
+int kbbq_host_report_write(const char *path, const kbbq_quality_report *report, const char *const *rg_ids,
+                           const kbbq_covariates *observed, const kbbq_table_info *info);
+int kbbq_host_report_read(const char *path, kbbq_quality_report *report, uint64_t *observed_q, char *rg_ids, uint64_t *rg_ids_bytes);
 /* Largest T with: std::bernoulli_distribution(p) accepts a 64-bit draw u  <=>  u < T. */
 uint64_t kbbq_host_bernoulli_threshold(double p, int32_t *always);
 

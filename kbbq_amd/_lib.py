@@ -66,6 +66,10 @@ class TableInfo(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("seed", ctypes.c_uint32), ("total_bases", c_u64), ("command", ctypes.c_char_p)]
 
 
+class QualityReport(ctypes.Structure):
+    _fields_ = [("n_rg", c_u64), ("n_cycle", c_u64), ("transfer", c_vp), ("cycle", c_vp), ("above_maxq", c_u64)]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -153,6 +157,12 @@ SYMBOLS = {
     "kbbq_host_table_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(Covariates), c_vp, c_u64p]),
     "kbbq_set_quality_map": (ctypes.c_int, [c_vp, c_vp]),
     "kbbq_map_qualities": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp]),
+    "kbbq_report_enable": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+    "kbbq_report_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp]),
+    "kbbq_report_get": (ctypes.c_int, [c_vp, ctypes.POINTER(QualityReport), ctypes.c_int32]),
+    "kbbq_host_report_write": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(QualityReport), ctypes.POINTER(ctypes.c_char_p),
+                                              ctypes.POINTER(Covariates), ctypes.POINTER(TableInfo)]),
+    "kbbq_host_report_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(QualityReport), c_vp, c_vp, c_u64p]),
     "kbbq_host_bernoulli_threshold": (c_u64, [ctypes.c_double, c_i32p]),
     "kbbq_rng_state_at": (ctypes.c_int, [ctypes.c_uint32, c_u64, c_u64p]),
     # include/kbbq_bgzf.h: the BGZF writer on the device

@@ -22,6 +22,7 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"alpha", required_argument, 0, 'a'},     {"threads", required_argument, 0, 't'},
     // not the reference's: the recalibration table (cli_table.h) and binned output qualities
     {"save-table", required_argument, 0, 1001}, {"load-table", required_argument, 0, 1002}, {"quantize", required_argument, 0, 1003},
+    {"report", required_argument, 0, 1004},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -72,6 +73,9 @@ struct CliOptions {
     // training, the model comes from that file (cli_table.h); --quantize LIST: every written quality becomes the largest listed
     // value that is not above it (one below the smallest listed value stays: a bad base is never rounded up)
     std::string save_table, load_table, command_line;
+    // --report FILE: what pass 4 did to the qualities, tallied on the GPU behind it (kbbq_quality_report), written there after
+    // the last batch; no training-only option: it goes with --load-table, --fixed and --quantize alike
+    std::string report;
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -177,6 +181,7 @@ struct CliOptions {
                     if (!parse_quantize(optarg))
                         return !give_up(std::string(" Error: --quantize takes up to 93 strictly increasing integers in 0..93, separated by commas, not \"") + optarg + "\".");
                     break;
+                case 1004: report = std::string(optarg); break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;

@@ -23,6 +23,44 @@ static int save_table(kbbq_engine *e, const CliOptions &o, const ScanState &s, u
     return 0;
 }
 
+// --report: the quality report of the pass-4 engine (include/kbbq_engine.h: kbbq_report_get) into its file, once the last
+// batch has drained.  names: the ids of the read groups that records carried, by dense index, where save_table gets them.  The
+// file lists those groups: the one-pass table run's engine also has an index for every group its header declares and no record
+// carries -- they come last and have counted nothing -- and a training run on the same input never numbers them, so leaving them
+// out is what makes every way through the program write the same rows.  observed_q: the error counts by input quality of
+// those groups, [names.size()][256][2] -- a table run's come from the table -- or null: the engine's own histograms (a training
+// run's; with --fixed the tally it made).  0, or the exit status.
+static int write_quality_report(kbbq_engine *e, const CliOptions &o, std::vector<std::string> names, const uint64_t *observed_q, uint32_t seed, uint64_t seqlen) {
+    uint64_t n_rg = 0, n_cycle = 0;
+    if (kbbq_engine_dims(e, &n_rg, &n_cycle) < 0) return fail_engine("writing the quality report");
+    std::vector<uint64_t> transfer(n_rg * KBBQ_NQ * (KBBQ_MAXQ + 1)), cycle(n_rg * 2 * n_cycle * 3), q;
+    kbbq_quality_report rep = {n_rg, n_cycle, transfer.data(), cycle.data(), 0};
+    if (kbbq_report_get(e, &rep, 0) < 0) return fail_engine("writing the quality report");
+    kbbq_covariates cov = {n_rg, n_cycle, nullptr, nullptr, nullptr, nullptr};
+    if (observed_q) {
+        cov.q = const_cast<uint64_t *>(observed_q);
+    } else {
+        q.resize(n_rg * KBBQ_NQ * 2);
+        cov.q = q.data();
+        if (kbbq_covariates_get(e, &cov) < 0) return fail_engine("writing the quality report");
+    }
+    if (names.empty()) names.resize(1);      // (an input without reads: the engine's one group, with the empty id)
+    if (names.size() > n_rg) names.resize(n_rg);
+    const uint64_t per_rg_t = (uint64_t)KBBQ_NQ * (KBBQ_MAXQ + 1);
+    for (uint64_t i = names.size() * per_rg_t; i < transfer.size(); ++i)
+        if (transfer[i]) return give_up(" Error: the quality report counted bases in a read group that no record was seen to carry.");
+    rep.n_rg = cov.n_rg = names.size();      // (the read group is the outermost index of every array: the first groups are a prefix)
+    std::vector<const char *> ids;
+    for (auto &n : names) ids.push_back(n.c_str());
+    const kbbq_table_info info = {o.k, seed, seqlen, o.command_line.c_str()};
+    if (kbbq_host_report_write(o.report.c_str(), &rep, ids.data(), &cov, &info) < 0)
+        return give_up(std::string(" Error: cannot write the quality report: ") + kbbq_last_error());
+    uint64_t bases = 0;
+    for (uint64_t n : transfer) bases += n;
+    std::cerr << put_now << " Wrote the quality report " << o.report << " (" << names.size() << " read groups, " << n_cycle << " cycles, " << bases << " bases)." << std::endl;
+    return 0;
+}
+
 // --load-table: the file's histograms, the delta-Q tables kbbq_host_train makes of them, and those tables with the rows of
 // the read groups in the order the input numbers them.
 struct LoadedTable {
@@ -30,6 +68,7 @@ struct LoadedTable {
     std::vector<std::string> ids;
     std::unordered_map<std::string, size_t> row_of;
     std::vector<int32_t> meanq, rgdq, qdq, cycledq, dinucdq;      // [n_rg]..., in the table's order
+    std::vector<uint64_t> q_hist;      // the table's q histogram, [n_rg][256][2]: the `observed` rows of --report
 
     // 0, or the exit status with the line on stderr
     int load(const std::string &path) {
@@ -53,7 +92,17 @@ struct LoadedTable {
         meanq.resize(n_rg); rgdq.resize(n_rg); qdq.resize(nq); cycledq.resize(nq * 2 * n_cycle); dinucdq.resize(nq * 16);
         kbbq_dq dq = {n_rg, n_cycle, meanq.data(), rgdq.data(), qdq.data(), cycledq.data(), dinucdq.data()};
         if (kbbq_host_train(&cov, &dq) < 0) return give_up(std::string(" Error: the table's model: ") + kbbq_last_error());
+        q_hist = q;
         return 0;
+    }
+    // the table's q histogram with the row of order[g] as read group g (groups without a row stay zero), [order.size()][256][2]
+    std::vector<uint64_t> observed(const std::vector<std::string> &order, uint64_t engine_rg) const {
+        std::vector<uint64_t> out(engine_rg * KBBQ_NQ * 2, 0);
+        for (size_t g = 0; g < order.size() && g < engine_rg; ++g) {
+            const auto it = row_of.find(order[g]);
+            if (it != row_of.end()) std::copy(q_hist.begin() + it->second * KBBQ_NQ * 2, q_hist.begin() + (it->second + 1) * KBBQ_NQ * 2, out.begin() + g * KBBQ_NQ * 2);
+        }
+        return out;
     }
     static int no_row(const std::string &id) { return give_up(" Error: a record's read group \"" + id + "\" has no row in the table."); }
     int too_long(uint64_t longest) const {
@@ -95,6 +144,7 @@ static int create_table_engine(const CliOptions &o, const LoadedTable &t, uint64
     p.alpha = 0.5; p.seed = 1; p.approx_kmers = 1000;
     if (kbbq_engine_create(&p, e) < 0) return fail_engine("cannot create the engine");
     if (o.quantize && kbbq_set_quality_map(*e, o.quality_map) < 0) return fail_engine("cannot set the quality map");
+    if (!o.report.empty() && kbbq_report_enable(*e, 1) < 0) return fail_engine("cannot switch the quality report on");
     return 0;
 }
 
@@ -102,6 +152,7 @@ static int create_table_engine(const CliOptions &o, const LoadedTable &t, uint64
 struct OnePass {
     bool used = false;
     uint64_t chunks = 0, records = 0, bases = 0, models = 0;
+    std::vector<std::string> rg_ids;      // the read groups that records carried, in the order of their first records: the engine's dense indices (--report)
 };
 
 // --load-table, the one-pass route: whatever the device reader may read -- a file or a stream, of any size -- is inflated,
@@ -213,6 +264,7 @@ static int apply_table_one_pass(const CliOptions &o, StreamInput *stream, Device
     }
     s.n_reads = rep.records;
     s.seqlen = rep.bases;
+    rep.rg_ids = order;
     rep.used = true;
     return 0;
 }

@@ -30,9 +30,10 @@ using namespace kbbq;
 #include "long_reads.h"
 #include "fixed_compare.h"
 #include "quality_map.h"
+#include "quality_report.h"
 
 // The order of these is fixed.  Each header uses what the ones above it define (the state, then the helpers every pass
-// shares, then the passes in their order: pass 3's read index serves pass 4, pass 4's tables the host-only training in
+// shares, then the passes in their order: pass 3's read index serves pass 4 and the report behind it, pass 4's tables the host-only training in
 // engine_misc.h).  And the compiler emits a kernel template's instantiations in the order of their first use, so the order
 // of the pass headers is also the order of the kernels in the code object: pass 1's inserts, the emits, k_infer, the scan,
 // the walks.  A header moved up or down changes the object although no kernel changed.
@@ -43,6 +44,7 @@ using namespace kbbq;
 #include "engine_pass1.h"
 #include "engine_pass2.h"
 #include "engine_pass3.h"
+#include "engine_report.h"
 #include "engine_pass4.h"
 #include "engine_misc.h"
 
@@ -152,6 +154,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->p4.d_dq_base);
     hipFree(e->p4.d_dq_cycle);
     hipFree(e->p4.d_dq_dinuc);
+    hipFree(e->rep.d_tables);
     hipFree(e->d_counters);
     hipFree(e->d_tickets);
     hipFree(e->d_totals);
@@ -181,6 +184,7 @@ int kbbq_engine_reset(kbbq_engine *e) {
     if ((rc = reset_counters(e))) return rc;
     if ((rc = e->bk.reset(e->stream))) return rc;
     e->p4.reset();
+    if ((rc = e->rep.reset(e->stream))) return rc;
     e->profile.reset();
     return sync_engine(e);
 }
@@ -206,6 +210,12 @@ int kbbq_engine_tune(kbbq_engine *e, const char *name, uint64_t value) {
         e->opt.bucket_records = value;
     } else if (!strcmp(name, "pass4_piece")) {
         e->opt.pass4_piece = value;
+    } else if (!strcmp(name, "report_flush")) {
+        if (value > kReportFlushBases) return fail(KBBQ_EINVAL, "report_flush: 1 to %llu bases, 0 = default", (unsigned long long)kReportFlushBases);
+        e->opt.report_flush = value;
+    } else if (!strcmp(name, "report_grid")) {
+        if (value > 512) return fail(KBBQ_EINVAL, "report_grid: 1 to 512 blocks, 0 = default");
+        e->opt.report_grid = value;
     } else if (!strcmp(name, "scan_blocks") || !strcmp(name, "walk_blocks") || !strcmp(name, "infer_blocks")) {
         // (17 = the default: the measured setting for short reads, none otherwise)
         if (value > 17) return fail(KBBQ_EINVAL, "%s: 0 (as many as fit) to 16 workgroups per CU, 17 = default", name);

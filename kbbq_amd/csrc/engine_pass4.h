@@ -62,6 +62,10 @@ static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qu
     ENGINE_DEVICE(e);
     if (!qual_out || !reads) return fail(KBBQ_EINVAL, "null argument");
     if (!e->p4.dq_set) return fail(KBBQ_ESTATE, "no delta-Q tables yet");
+    // the report kernel reads the old qualities after pass 4 has written the new ones.  (A host batch with a host output is
+    // refused alike, on purpose: its device copies never alias, but one rule for both memories is the one the header states)
+    if (e->rep.on && reads->qual && (reads->on_device != 0) == !out_on_host && ranges_overlap(reads->qual, qual_out, reads->n_bases))
+        return fail(KBBQ_EINVAL, "qual_out overlaps the batch's qual: not while the quality report is on");
     HostBatchDone host_done(e, reads);
     ReadsDev R; int max_len;
     // a large host batch with its result in host memory goes through in pieces (below): 64 Ki-base multiples, at least 2^23
@@ -110,7 +114,9 @@ static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qu
         }
         // binned output (kbbq_set_quality_map): the bases this launch wrote, behind it on the same stream, before any copy
         // out of d_out or any caller's work ordered behind the engine's stream sees them
-        if (e->p4.qmap_set) return launch_quality_map(e, d_out + base0, base1 - base0, e->p4.qmap);
+        if (e->p4.qmap_set && (rc = launch_quality_map(e, d_out + base0, base1 - base0, e->p4.qmap))) return rc;
+        // the quality report (kbbq_report_enable): the same bases, behind the map -- it counts what the caller will see
+        if (e->rep.on) return launch_quality_report(e, R, d_out, read_index, base0, base1);
         return KBBQ_OK;
     };
     if (pipelined) {

@@ -67,6 +67,8 @@ struct Options {
     int bucket = -1;                  // KBBQ_F_BUCKET_ON / _OFF, KBBQ_BUCKET=1/0: bucketed / direct inserts; -1: by filter size
     uint64_t bucket_records = 0;      // KBBQ_BUCKET_RECORDS: records gathered per flush (0: a share of the free HBM)
     uint64_t pass4_piece = 0;         // KBBQ_PASS4_PIECE: piece size of pass 4's pipeline in bases (0: about a quarter of a batch)
+    uint64_t report_flush = 0;        // kbbq_engine_tune("report_flush", n): bases a block of k_quality_report counts between two flushes (0: kReportFlushBases)
+    uint64_t report_grid = 0;         // kbbq_engine_tune("report_grid", n): most blocks of k_quality_report (0: the cap of k_recalibrate)
     // Workgroups per CU of the persistent kernels while two streams are in use (0: as many as fit).  k_scan_trusted, k_infer
     // and k_correct_wave take their reads from a global counter, so a grid of any size finishes the batch; a kernel that
     // fills every wave slot keeps the other stream's kernel out until its own last read is done.
@@ -233,6 +235,17 @@ struct Pass4State {
     void reset() { dq_set = false; }
 };
 
+// the quality report (include/kbbq_engine.h: kbbq_quality_report; engine_report.h): what pass 4 did, tallied behind it while `on`
+struct ReportState {
+    bool on = false;
+    unsigned long long *d_tables = nullptr;     // transfer, then cycle, then the above-93 count: one allocation, made when first switched on
+    uint64_t transfer_words = 0, cycle_words = 0;
+    int reset(hipStream_t stream) {
+        if (d_tables) HIP_TRY(hipMemsetAsync(d_tables, 0, (transfer_words + cycle_words + 1) * 8, stream));
+        return KBBQ_OK;
+    }
+};
+
 // Host batches: a ring of device staging slots owned by the engine and a copy stream.  A host batch is copied
 // into the next slot with hipMemcpyAsync on the copy stream (DMA straight from the caller's memory when that is
 // page-locked), the pass's kernels wait for the copy by event, and the entry point returns as soon as the COPY
@@ -320,6 +333,7 @@ struct kbbq_engine {
     Pass2State p2;
     Pass3State p3;
     Pass4State p4;
+    ReportState rep;
     Staging stage;
     Buckets bk;
     Profile profile;

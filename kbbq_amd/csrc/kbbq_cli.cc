@@ -57,6 +57,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <climits>
 #include <condition_variable>
@@ -827,6 +828,11 @@ static int run_table(CliOptions &opt, StreamInput *stream) {
         if (write_output(engine.e, scan, opt, sink, dev_in, batch)) return 1;
     }
     if (!sink.close()) return 1;
+    if (!opt.report.empty()) {
+        const std::vector<std::string> names = one_pass.used ? one_pass.rg_ids : scan.groups.names();
+        const std::vector<uint64_t> observed = table.observed(names, std::max<size_t>(1, names.size()));
+        if (const int bad = write_quality_report(engine.e, opt, names, observed.data(), 0, scan.seqlen)) return bad;
+    }
     return end_run(opt, clock, dev_in, sink, FixedOnDevice(), one_pass, scan, engine);
 }
 
@@ -851,6 +857,14 @@ int main(int argc, char *argv[]) {
     if (opt.stream || opt.fixed_stream) {
         if (const char *why = opt.needs_a_file())
             return give_up(std::string(" Error: input from a pipe is read once, and ") + why + ": write the input to a file first.");
+    }
+    // --report: behind the checks of the input and before the first pass, so that a run of hours does not end on a path that
+    // cannot be written; opened for appending, which proves the same and leaves an earlier report as it is until the new one
+    // is written (kbbq_host_report_write truncates)
+    if (!opt.report.empty()) {
+        FILE *f = fopen(opt.report.c_str(), "ab");
+        if (!f) return give_up(" Error: --report: cannot open " + opt.report + " for writing: " + strerror(errno));
+        fclose(f);
     }
     if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
     if (opt.table_run()) return run_table(opt, stream.get());
@@ -932,9 +946,12 @@ int main(int argc, char *argv[]) {
     clock.mark("model");
     std::cerr << put_now << " Recalibrating file" << std::endl;
     if (opt.quantize && kbbq_set_quality_map(e, opt.quality_map) < 0) return fail_engine("cannot set the quality map");
+    if (!opt.report.empty() && kbbq_report_enable(e, 1) < 0) return fail_engine("cannot switch the quality report on");
     Sink sink;
     int rc = sink.open(opt, scan);
     if (rc) return rc;
     if (write_output(e, scan, opt, sink, dev_in, batch) || !sink.close()) return 1;
+    if (!opt.report.empty())
+        if (const int bad = write_quality_report(e, opt, scan.groups.names(), nullptr, p.seed, scan.seqlen)) return bad;
     return end_run(opt, clock, dev_in, sink, fixed_report, OnePass(), scan, engine);
 }

@@ -13,6 +13,7 @@ from . import _lib
 from .reads import ReadBatch, unpack_bits
 
 NQ = _lib.NQ
+MAXQ = 93      # KBBQ_MAXQ
 
 
 def long_double_text(x):
@@ -301,6 +302,25 @@ class Engine:
         assert m.shape == (256,)
         _lib.check(self.L.kbbq_map_qualities(self.h, device_ptr, int(n), m.ctypes.data))
 
+    # ---- the quality report: what pass 4 did, tallied on the GPU
+    def report_enable(self, on=True):
+        """While on, every recalibrate() is followed by the report kernel on the same stream; off: nothing is launched."""
+        _lib.check(self.L.kbbq_report_enable(self.h, 1 if on else 0))
+
+    def report_batch(self, dreads, out_device_ptr):
+        """The report kernel alone: a device batch and the device array of its new qualities, on the engine's stream."""
+        _lib.check(self.L.kbbq_report_batch(self.h, self._c(dreads), out_device_ptr))
+
+    def report(self, reset=False):
+        """The report so far (waits): transfer [R][256][94], cycle [R][2][C][3] = bases, sum in, sum out; above_maxq."""
+        R, C = self.n_rg, self.max_read_len
+        out = dict(R=R, C=C, transfer=np.zeros((R, NQ, MAXQ + 1), np.uint64), cycle=np.zeros((R, 2, C, 3), np.uint64))
+        q = _lib.QualityReport()
+        q.transfer, q.cycle = out["transfer"].ctypes.data, out["cycle"].ctypes.data
+        _lib.check(self.L.kbbq_report_get(self.h, ctypes.byref(q), 1 if reset else 0))
+        out["above_maxq"] = int(q.above_maxq)
+        return out
+
     # ---- whole pipeline on one host batch (kbbq.cc:258-457)
     def run_all(self, batch):
         out = {}
@@ -384,6 +404,41 @@ def read_table(path):
     c.rg, c.q, c.cycle, c.dinuc = (out[k].ctypes.data for k in ("rg", "q", "cycle", "dinuc"))
     ids = ctypes.create_string_buffer(max(1, id_bytes.value))
     _lib.check(L.kbbq_host_table_read(str(path).encode(), ctypes.byref(c), ctypes.cast(ids, _lib.c_vp), ctypes.byref(id_bytes)))
+    out["rg_ids"] = [b.decode(errors="surrogateescape") for b in ids.raw[:id_bytes.value].split(b"\0")[:R]]
+    return out
+
+
+def write_report(path, report, rg_ids, observed=None, k=0, seed=0, total_bases=0, command=None):
+    """The quality report file of a report dict (Engine.report(); kbbq_host_report_write); observed: a covariates dict
+    whose q histogram goes into `observed` rows, or None.  No GPU is touched."""
+    R, C = int(report["R"]), int(report["C"])
+    a = {k_: np.ascontiguousarray(report[k_], dtype=np.uint64) for k_ in ("transfer", "cycle")}
+    assert a["transfer"].size == R * NQ * (MAXQ + 1) and a["cycle"].size == R * 2 * C * 3
+    q = _lib.QualityReport(R, C, a["transfer"].ctypes.data, a["cycle"].ctypes.data, int(report.get("above_maxq", 0)))
+    ids = [i.encode() if isinstance(i, str) else bytes(i) for i in rg_ids]
+    assert len(ids) == R
+    arr = (ctypes.c_char_p * len(ids))(*ids)
+    c, _keep = _covariates_struct(observed) if observed is not None else (None, None)
+    info = _lib.TableInfo(k, seed & 0xFFFFFFFF, total_bases, command.encode() if isinstance(command, str) else command)
+    _lib.check(_lib.lib().kbbq_host_report_write(str(path).encode(), ctypes.byref(q), arr, ctypes.byref(c) if c is not None else None,
+                                                 ctypes.byref(info)))
+
+
+def read_report(path):
+    """A report file as a report dict, with "rg_ids" and "observed" ([R][256][2] {errors, total}, zero where the file has
+    no such row).  A malformed file raises KbbqError with code -22 and the line number in the text."""
+    L = _lib.lib()
+    q = _lib.QualityReport()
+    id_bytes = ctypes.c_uint64()
+    _lib.check(L.kbbq_host_report_read(str(path).encode(), ctypes.byref(q), None, None, ctypes.byref(id_bytes)))
+    R, C = int(q.n_rg), int(q.n_cycle)
+    out = dict(R=R, C=C, transfer=np.zeros((R, NQ, MAXQ + 1), np.uint64), cycle=np.zeros((R, 2, C, 3), np.uint64),
+               observed=np.zeros((R, NQ, 2), np.uint64))
+    q.transfer, q.cycle = out["transfer"].ctypes.data, out["cycle"].ctypes.data
+    ids = ctypes.create_string_buffer(max(1, id_bytes.value))
+    _lib.check(L.kbbq_host_report_read(str(path).encode(), ctypes.byref(q), out["observed"].ctypes.data, ctypes.cast(ids, _lib.c_vp),
+                                       ctypes.byref(id_bytes)))
+    out["above_maxq"] = int(q.above_maxq)
     out["rg_ids"] = [b.decode(errors="surrogateescape") for b in ids.raw[:id_bytes.value].split(b"\0")[:R]]
     return out
 
