@@ -386,6 +386,60 @@ int kbbq_errors_batch_submit(kbbq_engine *e, const kbbq_reads *reads, kbbq_ticke
 int kbbq_recalibrate_batch_submit(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qual_out, kbbq_ticket *ticket);
 int kbbq_batch_wait(kbbq_engine *e, kbbq_ticket ticket);
 
+/* ---- the k-mer spectrum of the reads: genome length without a reference --------
+ * How many distinct k-mers occur once, twice, ... in the reads: an error spike at 1, a coverage peak, and the genome length is
+ * the k-mer mass above the valley between them divided by the peak's mean multiplicity (kbbq_host_spectrum_estimate).  The
+ * count needs no engine -- a driver takes it between its first scan and the engine whose filters the answer sizes -- and the
+ * table is returned by kbbq_spectrum_destroy before those are allocated.
+ *   Counted: the canonical key (as every pass forms it) of every window of k bases that lies inside one read and holds no
+ *   non-ACGT base; reads shorter than k contribute nothing; offcase, qualities, flags, read groups and hints are neither read
+ *   nor written.  With sample_shift s > 0 a k-mer is counted iff the top s bits of its mixed key (splitmix64's finaliser) are
+ *   zero: EVERY occurrence of a chosen k-mer is counted, so its multiplicity is exact and the histogram is that of a 2^-s
+ *   sample of the distinct k-mers, not of the occurrences (which would move the peak).
+ *   The table: 2^slots_log2 slots of open addressing in device memory, a u64 key and a u32 count per slot (12 bytes; a k-mer
+ *   seen 2^32 times or more wraps its count), linear probing bounded by the slot count.  A k-mer that finds no slot is
+ *   dropped and kbbq_spectrum_finish returns KBBQ_ERANGE: an error return, nothing waits or spins.
+ *   The result is a multiset of (key, count): it does not depend on the launch shape, on how the reads were cut into batches
+ *   or on the order of the inserts. */
+#define KBBQ_SPECTRUM_BINS 1024
+typedef struct kbbq_spectrum kbbq_spectrum;
+typedef struct kbbq_spectrum_result {
+    uint64_t hist[KBBQ_SPECTRUM_BINS];  /* [0] = 0; [m], 1 <= m <= BINS-2: distinct counted k-mers seen m times; [BINS-1]: seen >= BINS-1 times */
+    uint64_t tail_mass;                 /* sum of the multiplicities of the k-mers in the last bin */
+    uint64_t distinct, counted;         /* sum of hist; sum of all multiplicities */
+    uint64_t valid_positions;           /* k-mer starts whose k bases hold no non-ACGT base, before sampling */
+    uint32_t k, sample_shift;
+} kbbq_spectrum_result;
+/* k in 1..KBBQ_MAX_KMER, slots_log2 in 6..32, sample_shift <= 32, else KBBQ_EINVAL; KBBQ_ENOMEM when the table does not fit. */
+int kbbq_spectrum_create(int32_t device, int32_t k, uint32_t slots_log2, uint32_t sample_shift, kbbq_spectrum **out);
+/* A device batch (on the handle's device) is only queued, on the handle's own stream: its arrays stay valid until
+ * kbbq_spectrum_finish.  A host batch is copied to the device first (bases, N mask and offsets alone) and the call
+ * returns when its launch is done and the copy is freed. */
+int kbbq_spectrum_batch(kbbq_spectrum *s, const kbbq_reads *reads);
+/* Waits; the spectrum of every batch so far (more may follow).  KBBQ_ERANGE: the table was full, the result is not valid. */
+int kbbq_spectrum_finish(kbbq_spectrum *s, kbbq_spectrum_result *out);
+int kbbq_spectrum_destroy(kbbq_spectrum *s);
+
+/* Host side of the spectrum (no GPU touched; kbbq_amd/csrc/host_spectrum.cc).
+ * shift: the smallest s with positions >> s <= 2^(slots_log2 - 1).  `positions` is an upper bound on the distinct k-mers (the
+ * bases scanned), so the table never passes half full.  KBBQ_ERANGE if s would exceed 32.
+ * estimate, in integers (products in 128 bits), B = KBBQ_SPECTRUM_BINS: the valley v is the smallest m in 1..B-3 with
+ * hist[m+1] > hist[m]; the peak p the m in v+1..B-2 with the largest hist[m] (the smallest on ties); over lo = max(v+1, p - p/2)
+ * .. hi = min(B-2, p + p/2), W = sum hist[m] and S = sum m*hist[m]; M = sum of m*hist[m] over v+1..B-2, plus tail_mass;
+ * genome_length = (M*W / S) << sample_shift, kmer_coverage_milli = 1000*S / W, window_kmers = W.  Returns 1 with *out zeroed
+ * when there is no valley, when W < 512 (too few k-mers under the peak for its mean to be trusted) or when the length would
+ * not fit 63 bits; 0 otherwise.
+ * The file: '#' lines (#kbbq-spectrum 1, #k, #sample_shift, #valid_kmers, #distinct, #counted, #tail_mass, #valley, #peak,
+ * #genome_length; the last three 0 without an estimate), then "m<TAB>hist[m]" for m = 1 .. the last non-zero bin: without
+ * its '#' lines, the two-column histogram that spectrum plotters read.  read gives back what write was given (est may be
+ * NULL in both; of an estimate the file holds valley, peak and genome_length, the other two fields are derived from the
+ * histogram again) and refuses with KBBQ_EINVAL, naming the line, whatever write cannot have written. */
+typedef struct kbbq_spectrum_estimate { uint64_t genome_length, valley, peak, window_kmers, kmer_coverage_milli; } kbbq_spectrum_estimate;
+int kbbq_host_spectrum_shift(uint64_t positions, uint32_t slots_log2, uint32_t *shift);
+int kbbq_host_spectrum_estimate(const kbbq_spectrum_result *r, kbbq_spectrum_estimate *out);
+int kbbq_host_spectrum_write(const char *path, const kbbq_spectrum_result *r, const kbbq_spectrum_estimate *est);
+int kbbq_host_spectrum_read(const char *path, kbbq_spectrum_result *r, kbbq_spectrum_estimate *est);
+
 /* ---- synthetic input and measurement ------------------------------------- */
 
 typedef struct kbbq_synth_params {

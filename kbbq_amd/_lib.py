@@ -70,6 +70,19 @@ class QualityReport(ctypes.Structure):
     _fields_ = [("n_rg", c_u64), ("n_cycle", c_u64), ("transfer", c_vp), ("cycle", c_vp), ("above_maxq", c_u64)]
 
 
+SPECTRUM_BINS = 1024      # KBBQ_SPECTRUM_BINS
+
+
+class SpectrumResult(ctypes.Structure):
+    _fields_ = [("hist", c_u64 * SPECTRUM_BINS), ("tail_mass", c_u64), ("distinct", c_u64), ("counted", c_u64),
+                ("valid_positions", c_u64), ("k", ctypes.c_uint32), ("sample_shift", ctypes.c_uint32)]
+
+
+class SpectrumEstimate(ctypes.Structure):
+    _fields_ = [("genome_length", c_u64), ("valley", c_u64), ("peak", c_u64), ("window_kmers", c_u64),
+                ("kmer_coverage_milli", c_u64)]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -163,6 +176,14 @@ SYMBOLS = {
     "kbbq_host_report_write": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(QualityReport), ctypes.POINTER(ctypes.c_char_p),
                                               ctypes.POINTER(Covariates), ctypes.POINTER(TableInfo)]),
     "kbbq_host_report_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(QualityReport), c_vp, c_vp, c_u64p]),
+    "kbbq_spectrum_create": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(c_vp)]),
+    "kbbq_spectrum_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
+    "kbbq_spectrum_finish": (ctypes.c_int, [c_vp, ctypes.POINTER(SpectrumResult)]),
+    "kbbq_spectrum_destroy": (ctypes.c_int, [c_vp]),
+    "kbbq_host_spectrum_shift": (ctypes.c_int, [c_u64, ctypes.c_uint32, c_u32p]),
+    "kbbq_host_spectrum_estimate": (ctypes.c_int, [ctypes.POINTER(SpectrumResult), ctypes.POINTER(SpectrumEstimate)]),
+    "kbbq_host_spectrum_write": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(SpectrumResult), ctypes.POINTER(SpectrumEstimate)]),
+    "kbbq_host_spectrum_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(SpectrumResult), ctypes.POINTER(SpectrumEstimate)]),
     "kbbq_host_bernoulli_threshold": (c_u64, [ctypes.c_double, c_i32p]),
     "kbbq_rng_state_at": (ctypes.c_int, [ctypes.c_uint32, c_u64, c_u64p]),
     # include/kbbq_bgzf.h: the BGZF writer on the device

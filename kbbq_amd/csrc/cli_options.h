@@ -23,6 +23,8 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     // not the reference's: the recalibration table (cli_table.h) and binned output qualities
     {"save-table", required_argument, 0, 1001}, {"load-table", required_argument, 0, 1002}, {"quantize", required_argument, 0, 1003},
     {"report", required_argument, 0, 1004},
+    // the genome length from the reads' own k-mer spectrum, and that spectrum as a file (cli_spectrum.h)
+    {"estimate-genomelen", no_argument, 0, 1005}, {"spectrum", required_argument, 0, 1006},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -76,6 +78,12 @@ struct CliOptions {
     // --report FILE: what pass 4 did to the qualities, tallied on the GPU behind it (kbbq_quality_report), written there after
     // the last batch; no training-only option: it goes with --load-table, --fixed and --quantize alike
     std::string report;
+    // --estimate-genomelen: where the run would stop for lack of a genome length (FASTQ without -g, a BAM or SAM header without
+    // reference lengths), it comes from the k-mer spectrum of the reads; --spectrum FILE: that spectrum is written there.
+    // Training options both: they size the filters, which --load-table and --fixed do not use
+    bool estimate_genomelen = false;
+    std::string spectrum;
+    const char *spectrum_option = nullptr;      // the first of the two that was given
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -102,6 +110,9 @@ struct CliOptions {
     bool exchange_local = env_is(getenv("KBBQ_EXCHANGE"), "local");          // in-process copies even between distinct devices
     bool qual_digest = env_num(getenv("KBBQ_QUAL_DIGEST"), 0) != 0;          // =1: "[digest]" lines (bench.py's trusted_inserted and recal_qual_sum)
     bool release = env_num(getenv("KBBQ_RELEASE"), 0) != 0;                  // =1: everything is freed in order at the end, no exit(0)
+    // slots of the k-mer spectrum's table, 6..32 (12 bytes each: 805 MB).  Unlike the switches above it changes a result: a
+    // smaller table takes a thinner sample of the distinct k-mers, and the estimate is that sample's
+    long long spectrum_slots_log2 = env_num(getenv("KBBQ_SPECTRUM_SLOTS_LOG2"), 26);
 
     bool fixed_mode() const { return !fixedinput.empty(); }
     bool table_run() const { return !load_table.empty(); }
@@ -182,6 +193,16 @@ struct CliOptions {
                         return !give_up(std::string(" Error: --quantize takes up to 93 strictly increasing integers in 0..93, separated by commas, not \"") + optarg + "\".");
                     break;
                 case 1004: report = std::string(optarg); break;
+                case 1005:
+                    estimate_genomelen = true;
+                    if (!trains_with) trains_with = "--estimate-genomelen";
+                    if (!spectrum_option) spectrum_option = "--estimate-genomelen";
+                    break;
+                case 1006:
+                    spectrum = std::string(optarg);
+                    if (!trains_with) trains_with = "--spectrum";
+                    if (!spectrum_option) spectrum_option = "--spectrum";
+                    break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -193,6 +214,10 @@ struct CliOptions {
         }
         if (table_run() && trains_with)
             return !give_up(std::string(" Error: --load-table with ") + trains_with + ": a table run does not train, it applies the model of the table.");
+        if (fixed_mode() && spectrum_option)
+            return !give_up(std::string(" Error: ") + spectrum_option + " with --fixed: the genome length sizes the filters, which are not used there.");
+        if (estimate_genomelen && genomelen)
+            return !give_up(" Error: --estimate-genomelen with --genomelen: the genome length is either given or estimated, not both.");
         for (int i = 0; i < argc; ++i) command_line += (i ? " " : "") + std::string(argv[i]);
         // --threads sizes the BGZF compression pool like the reference's htslib pool (kbbq.cc:159-168); unlike the
         // reference, 0 does not mean "single-threaded" but "pick": the writer is the end-to-end bottleneck

@@ -46,6 +46,9 @@
 //     file and applies it -- in one pass over the device reader, with nothing kept, where that reader may be tried (a stream
 //     of any size included), by the usual scan and pass 4 otherwise; --quantize LIST bins the written qualities
 //     (kbbq_set_quality_map).  The reference has none of the three;
+//   * --estimate-genomelen supplies the genome length from the k-mer spectrum of the reads, counted on the GPU between the scan
+//     and derive_sampling (cli_spectrum.h), where the reference stops for lack of one (kbbq.cc:196-218); --spectrum FILE writes
+//     that spectrum.  Training options both; without them no byte of either output changes;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -461,10 +464,13 @@ static int train_model(kbbq_engine *e, kbbq_group *grp, bool prints, PhaseClock 
     return 0;
 }
 
+#include "cli_spectrum.h"
+
 // What the reference derives before it samples (kbbq.cc:196-270): genome length, coverage, the sampling rate `alpha`, and
-// with them the engine's alpha, approx_kmers and seed.  false: the message is on stderr.
-static bool derive_sampling(const CliOptions &o, const ScanState &s, kbbq_params &p, long double &alpha) {
-    uint64_t genomelen = o.genomelen;
+// with them the engine's alpha, approx_kmers and seed.  estimated: the genome length --estimate-genomelen found (0: none),
+// which stands where --genomelen would.  false: the message is on stderr.
+static bool derive_sampling(const CliOptions &o, const ScanState &s, uint64_t estimated, kbbq_params &p, long double &alpha) {
+    uint64_t genomelen = o.genomelen ? o.genomelen : estimated;
     unsigned coverage = o.coverage;
     alpha = o.alpha;
     if (genomelen == 0) {   // kbbq.cc:196-216
@@ -866,6 +872,11 @@ int main(int argc, char *argv[]) {
         if (!f) return give_up(" Error: --report: cannot open " + opt.report + " for writing: " + strerror(errno));
         fclose(f);
     }
+    if (!opt.spectrum.empty()) {      // --spectrum: likewise
+        FILE *f = fopen(opt.spectrum.c_str(), "ab");
+        if (!f) return give_up(" Error: --spectrum: cannot open " + opt.spectrum + " for writing: " + strerror(errno));
+        fclose(f);
+    }
     if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
     if (opt.table_run()) return run_table(opt, stream.get());
 
@@ -903,10 +914,20 @@ int main(int argc, char *argv[]) {
     bool trained = false;      // KBBQ_DEVICES: the model was trained and broadcast among the ranks
     if (!opt.fixed_mode()) {
         long double alpha = 0;
-        if (!derive_sampling(opt, scan, p, alpha)) return 1;
+        const PassBatches reads{&resident.dev, nullptr, resident.on ? nullptr : &batch, &opt, &scan};
+        // --estimate-genomelen, --spectrum: the k-mer spectrum, counted only where the run lacks a genome length -- a header that
+        // gives one wins as without the option -- or the file is asked for
+        uint64_t estimated = 0;
+        if (opt.spectrum_option) {
+            const bool need_length = opt.estimate_genomelen && !(opt.format != Format::fastq && scan.bam_header.genome_length());
+            if (need_length || !opt.spectrum.empty()) {
+                if (const int rc = count_spectrum(opt, scan, reads, need_length, &estimated)) return rc;
+                clock.mark("spectrum");
+            }
+        }
+        if (!derive_sampling(opt, scan, estimated, p, alpha)) return 1;
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
         const std::vector<int> devices = device_list(opt, scan);
-        const PassBatches reads{&resident.dev, nullptr, resident.on ? nullptr : &batch, &opt, &scan};
         if (devices.size() > 1) {
             if (run_on_devices(devices, e, p, opt, alpha, scan, clock)) return 1;
             trained = true;

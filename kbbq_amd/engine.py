@@ -443,6 +443,96 @@ def read_report(path):
     return out
 
 
+SPECTRUM_FIELDS = ("tail_mass", "distinct", "counted", "valid_positions", "k", "sample_shift")
+ESTIMATE_FIELDS = ("genome_length", "valley", "peak", "window_kmers", "kmer_coverage_milli")
+
+
+def _spectrum_dict(res):
+    out = {f: int(getattr(res, f)) for f in SPECTRUM_FIELDS}
+    out["hist"] = np.array(res.hist[:], dtype=np.uint64)
+    return out
+
+
+def _spectrum_struct(result):
+    res = _lib.SpectrumResult()
+    hist = np.ascontiguousarray(result["hist"], dtype=np.uint64)
+    assert hist.shape == (_lib.SPECTRUM_BINS,)
+    ctypes.memmove(res.hist, hist.ctypes.data, hist.nbytes)
+    for f in SPECTRUM_FIELDS:
+        setattr(res, f, int(result[f]))
+    return res
+
+
+class Spectrum:
+    """The k-mer spectrum of the reads, counted on the GPU (kbbq_spectrum_*): a table of 2^slots_log2 slots on `device`, no
+    engine.  With sample_shift s > 0 one in 2^s of the distinct k-mers is counted, each with all its occurrences."""
+
+    def __init__(self, k, slots_log2, sample_shift=0, device=0):
+        self.L = _lib.lib()
+        h = _lib.c_vp()
+        _lib.check(self.L.kbbq_spectrum_create(device, k, slots_log2, sample_shift, ctypes.byref(h)))
+        self.h = h
+
+    def add(self, batch):
+        """A ReadBatch (copied to the device for the launch) or DeviceReads (only queued: keep it until finish())."""
+        _lib.check(self.L.kbbq_spectrum_batch(self.h, ctypes.byref(batch.c)))
+
+    def finish(self):
+        """The spectrum of every batch so far (waits) as a dict: hist (uint64[1024]) and the fields of kbbq_spectrum_result.
+        A full table raises KbbqError with code -34 (KBBQ_ERANGE)."""
+        res = _lib.SpectrumResult()
+        _lib.check(self.L.kbbq_spectrum_finish(self.h, ctypes.byref(res)))
+        return _spectrum_dict(res)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.kbbq_spectrum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def spectrum_shift(positions, slots_log2):
+    """The smallest sample shift that keeps a table of 2^slots_log2 slots at most half full for `positions` k-mer starts."""
+    s = ctypes.c_uint32()
+    _lib.check(_lib.lib().kbbq_host_spectrum_shift(int(positions), int(slots_log2), ctypes.byref(s)))
+    return s.value
+
+
+def estimate_genome_length(result):
+    """kbbq_host_spectrum_estimate on a spectrum dict: a dict of the estimate's fields, or None where the spectrum shows no
+    coverage peak.  No GPU is touched."""
+    res = _spectrum_struct(result)
+    est = _lib.SpectrumEstimate()
+    if _lib.check(_lib.lib().kbbq_host_spectrum_estimate(ctypes.byref(res), ctypes.byref(est))):
+        return None
+    return {f: int(getattr(est, f)) for f in ESTIMATE_FIELDS}
+
+
+def write_spectrum(path, result, estimate=None):
+    """The spectrum file of a spectrum dict and, optionally, its estimate (kbbq_host_spectrum_write)."""
+    res = _spectrum_struct(result)
+    est = _lib.SpectrumEstimate(*(int(estimate[f]) for f in ESTIMATE_FIELDS)) if estimate is not None else None
+    _lib.check(_lib.lib().kbbq_host_spectrum_write(str(path).encode(), ctypes.byref(res), ctypes.byref(est) if est is not None else None))
+
+
+def read_spectrum(path):
+    """A spectrum file as (spectrum dict, estimate dict or None).  A malformed file raises KbbqError with code -22 and the
+    line number in the text."""
+    res = _lib.SpectrumResult()
+    est = _lib.SpectrumEstimate()
+    _lib.check(_lib.lib().kbbq_host_spectrum_read(str(path).encode(), ctypes.byref(res), ctypes.byref(est)))
+    e = {f: int(getattr(est, f)) for f in ESTIMATE_FIELDS}
+    return _spectrum_dict(res), (e if e["genome_length"] else None)
+
+
 def host_train(cov):
     """kbbq_host_train on a covariates dict (a loaded table): the delta-Q tables as Engine.dq() returns them."""
     R, C = int(cov["R"]), int(cov["C"])
