@@ -153,6 +153,14 @@ int kbbq_fastq_reader_batch_exact(kbbq_fastq_reader *r, int32_t *exact);
  * d_qual (device: the batch's new qualities, in the batch's base order) on the quality lines, submitted to writer z
  * (kbbq_bgzf_collect returns the blocks).  after_stream as in kbbq_bgzf_submit. */
 int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, void *after_stream);
+/* The same with corrected sequence lines, in both forms (the chunk's text, or -- a chunk kept in the short form -- the attached
+ * packed batch): d_fix_mask / d_fix_bases are kbbq_correct_batch's outputs for the chunk's batch (device; nmask's and bases'
+ * layouts, in the batch's base order).  Where the mask bit of a base is set its character is "ACGT"[code]; every other character
+ * of the sequence line passes as kbbq_fastq_reader_write passes it (lower case and IUPAC codes included), and names, '+' lines
+ * and quality lines are byte for byte the same.  Both arrays are read by the kernel queued behind after_stream: keep them as
+ * long as d_qual. */
+int kbbq_fastq_reader_write_corrected(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint64_t *d_fix_mask,
+                                      const uint64_t *d_fix_bases, void *after_stream);
 /* Milliseconds the device spent inflating / indexing + packing since creation (a gzip stream's stages are in inflate_ms). */
 int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms);
 /* A gzip stream's stages since creation, in milliseconds of wall time (each stage waits for its kernels): block finding,

@@ -230,6 +230,9 @@ int kbbq_host_free(void *p);
  * whose new qualities stay on the GPU for the BGZF writer, kbbq_bgzf.h). */
 int kbbq_device_alloc(kbbq_engine *e, size_t bytes, void **out);
 int kbbq_device_free(kbbq_engine *e, void *p);
+/* Zeroes `bytes` of device memory, queued on the engine's stream: how a caller without device code of its own clears the
+ * arrays that kbbq_correct_batch and kbbq_errors_batch want zeroed. */
+int kbbq_device_zero(kbbq_engine *e, void *p, size_t bytes);
 int kbbq_measure_host_link(int32_t device, uint64_t bytes, double *h2d_gbps, double *d2h_gbps);
 /* The same with both directions running at once (three copies each way on two streams): the rates pass 4 of the
  * host-batch mode, which copies in and out at the same time, can hope for. */
@@ -297,6 +300,26 @@ int kbbq_tally_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *er
 int kbbq_fixed_errors_batch(kbbq_engine *e, const kbbq_reads *reads, uint64_t first_read,
                             const kbbq_reads *fixed, uint64_t fixed_first_read, uint64_t n_reads,
                             uint64_t *errors /* device, nmask's layout for `reads`: n_bases/64+2 words, zeroed by the caller before the first call */);
+
+/* ---- base correction: from "this base is wrong" to "this base should be X" --------
+ * The reference writes no corrected reads; the rule is this project's own.  For every read of L >= k
+ * bases and every position i of it whose bit in `errors` is set: the windows are the k-mer starts s = max(0, i-k+1) ..
+ * min(i, L-k); a window is usable iff it holds no other flagged position and no base with its nmask bit set, other than i
+ * itself; the candidates are the bases whose 2-bit code differs from the base's (all four for a base with its nmask bit);
+ * support(c) = usable windows whose canonical key with c put at i is in the trusted filter; the base is fixed iff the largest
+ * support is >= 1 and exactly one candidate has it, otherwise it stays and counts as ambiguous (a tie at the top) or
+ * unsupported (top support 0, no usable window included).  Reads shorter than k are not looked at and their flags are not
+ * counted.  The result depends on (reads, errors, filter, k) alone: not on how the batches were cut, on uniform or ragged
+ * batches, on hints or on the offcase array (an off-case letter has its folded code).
+ *   errors    1 bit per base in nmask's layout (what kbbq_errors_batch hands out as errors_out, or any array of the caller's)
+ *   fix_mask  nmask's layout (n_bases/64+2 words): set where a base is fixed
+ *   fix_bases bases' layout (n_bases/32+2 words): the new 2-bit code where fix_mask is set, 0 elsewhere
+ * Device batch, device arrays, both outputs zeroed by the caller; the kernel is queued on the engine's stream.
+ * KBBQ_ESTATE before kbbq_trusted_finish; KBBQ_EINVAL for a host batch. */
+typedef struct kbbq_fix_counts { uint64_t flagged, fixed, ambiguous, unsupported; } kbbq_fix_counts;
+int kbbq_correct_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *errors, uint64_t *fix_mask, uint64_t *fix_bases);
+/* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
+int kbbq_correct_counts(kbbq_engine *e, kbbq_fix_counts *out, int32_t reset);
 
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]

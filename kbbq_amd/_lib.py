@@ -83,6 +83,10 @@ class SpectrumEstimate(ctypes.Structure):
                 ("kmer_coverage_milli", c_u64)]
 
 
+class FixCounts(ctypes.Structure):
+    _fields_ = [("flagged", c_u64), ("fixed", c_u64), ("ambiguous", c_u64), ("unsupported", c_u64)]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -132,6 +136,8 @@ SYMBOLS = {
     "kbbq_errors_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp]),
     "kbbq_tally_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp]),
     "kbbq_fixed_errors_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_vp]),
+    "kbbq_correct_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, c_vp, c_vp]),
+    "kbbq_correct_counts": (ctypes.c_int, [c_vp, ctypes.POINTER(FixCounts), ctypes.c_int32]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),
@@ -151,6 +157,7 @@ SYMBOLS = {
     "kbbq_host_free": (ctypes.c_int, [c_vp]),
     "kbbq_device_alloc": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp)]),
     "kbbq_device_free": (ctypes.c_int, [c_vp, c_vp]),
+    "kbbq_device_zero": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t]),
     "kbbq_measure_host_link": (ctypes.c_int, [ctypes.c_int32, c_u64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "kbbq_measure_host_link_duplex": (ctypes.c_int, [ctypes.c_int32, c_u64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "kbbq_synth_tables": (ctypes.c_int, [ctypes.POINTER(SynthParams), c_u32p, c_u32p]),
@@ -198,6 +205,7 @@ SYMBOLS = {
     "kbbq_host_bgzf_compress": (ctypes.c_int, [c_vp, c_u64, c_vp, c_u64, c_u64p]),
     "kbbq_fastq_reader_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(c_vp)]),
     "kbbq_fastq_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "kbbq_fastq_reader_write_corrected": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "kbbq_reads_upload_text": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.c_void_p, ctypes.POINTER(Reads)]),
     "kbbq_fastq_reader_inflate": (ctypes.c_int, [c_vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

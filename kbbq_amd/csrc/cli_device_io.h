@@ -24,6 +24,9 @@ struct ReaderCalls {
     int (*any_read_group)(void *h, int32_t on);
     int (*take_text)(void *h, int32_t on);
     uint32_t oq_unwritable_bit;      // the chunk flag "some record's OQ tag cannot be updated" (BAM and SAM)
+    // --correct: write with the fixes of kbbq_correct_batch in the sequence lines (FASTQ's: changing SEQ in a BAM or SAM record
+    // would falsify its CIGAR, MD and NM, and this tool does not re-align)
+    int (*write_corrected)(void *h, kbbq_bgzf *z, const uint8_t *d_qual, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases, void *after_stream);
 };
 // f, whose first argument is a reader of type R, as a call on the opaque handle
 template <auto f> struct Thunk;
@@ -33,7 +36,8 @@ static const ReaderCalls kFastqReaderCalls = {
     Thunk<kbbq_fastq_reader_destroy>::call, Thunk<kbbq_fastq_reader_chunk>::call, Thunk<kbbq_fastq_reader_preload>::call, Thunk<kbbq_fastq_reader_keep>::call, Thunk<kbbq_fastq_reader_kept>::call,
     Thunk<kbbq_fastq_reader_select>::call, Thunk<kbbq_fastq_reader_rewind>::call, Thunk<kbbq_fastq_reader_batch>::call, nullptr /* batch */, Thunk<kbbq_fastq_reader_batch_exact>::call, Thunk<kbbq_fastq_reader_kernel_ms>::call,
     [](void *h, kbbq_bgzf *z, const uint8_t *q, int32_t, void *after) { return kbbq_fastq_reader_write((kbbq_fastq_reader *)h, z, q, after); },
-    Thunk<kbbq_fastq_reader_attach>::call, nullptr, nullptr, Thunk<kbbq_fastq_reader_take_text>::call, 0};
+    Thunk<kbbq_fastq_reader_attach>::call, nullptr, nullptr, Thunk<kbbq_fastq_reader_take_text>::call, 0,
+    Thunk<kbbq_fastq_reader_write_corrected>::call};
 // (sam_read1, the BAM constructor of CReadData, BamFile::recalibrate / write are kernels: htsiter.cc:5-45, readutils.cc:13-61)
 static const ReaderCalls kBamReaderCalls = {
     [](bool use_oq, int32_t n_ref, uint64_t header_bytes, const char *const *ids, uint32_t n_ids, void **out) {
@@ -538,6 +542,10 @@ public:
     // The current chunk with new qualities to the writer, assembled from the device's own copy of the input (BamFile::recalibrate + write)
     bool write_chunk(DeviceBgzfWriter &out, const uint8_t *d_qual, bool set_oq, void *after_stream) {
         return out.submit([&](kbbq_bgzf *z) { return r_->write(h_, z, d_qual, set_oq ? 1 : 0, after_stream); });
+    }
+    // ... and with the fixed bases in its sequence lines (--correct: FASTQ)
+    bool write_chunk_corrected(DeviceBgzfWriter &out, const uint8_t *d_qual, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases, void *after_stream) {
+        return out.submit([&](kbbq_bgzf *z) { return r_->write_corrected(h_, z, d_qual, d_fix_mask, d_fix_bases, after_stream); });
     }
 
 private:

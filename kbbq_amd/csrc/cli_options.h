@@ -25,6 +25,8 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"report", required_argument, 0, 1004},
     // the genome length from the reads' own k-mer spectrum, and that spectrum as a file (cli_spectrum.h)
     {"estimate-genomelen", no_argument, 0, 1005}, {"spectrum", required_argument, 0, 1006},
+    // the output's sequence lines with the flagged bases repaired that the trusted filter can repair (cli_pass4.h)
+    {"correct", no_argument, 0, 1007},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -84,6 +86,10 @@ struct CliOptions {
     bool estimate_genomelen = false;
     std::string spectrum;
     const char *spectrum_option = nullptr;      // the first of the two that was given
+    // --correct: pass 3 keeps every resident batch's error flags, pass 4 asks the trusted filter for the base each flagged base
+    // should be (kbbq_correct_batch) and writes the FASTQ with those bases in its sequence lines.  A training option (the filter is
+    // a training run's), FASTQ through the device reader on one device only: whatever leads elsewhere is refused (correct_refusal)
+    bool correct = false;
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -115,6 +121,24 @@ struct CliOptions {
     long long spectrum_slots_log2 = env_num(getenv("KBBQ_SPECTRUM_SLOTS_LOG2"), 26);
 
     bool fixed_mode() const { return !fixedinput.empty(); }
+    // What was asked for beside --correct that it cannot go with, known before the input is opened; null: nothing
+    const char *correct_refusal() const {
+        if (fixed_mode()) return "--fixed: the errors of a fixed run come from the corrected file, and no trusted filter is built to repair them from";
+        if (!device_reader) return "KBBQ_DEVICE_READER=0: the corrected sequence lines are written by the GPU reader's writer, not by the host parsers";
+        if (serial_parse) return "KBBQ_SERIAL_PARSE=1: the corrected sequence lines are written by the GPU reader's writer, not by the host parsers";
+        if (host_deflate) return "KBBQ_HOST_DEFLATE=1: the corrected sequence lines are written by the GPU reader's writer, not by the host parsers";
+        if (!resident) return "KBBQ_RESIDENT=0: the error flags of pass 3 stay with the resident batches";
+        int entries = 0;
+        for (const char *q = devices ? devices : ""; *q;) {
+            char *end = nullptr;
+            (void)strtol(q, &end, 10);
+            if (end == q) break;
+            ++entries;
+            q = *end == ',' ? end + 1 : end;
+        }
+        if (entries > 1) return "KBBQ_DEVICES with more than one device: the error flags of the other devices' shards do not reach the device that writes";
+        return nullptr;
+    }
     bool table_run() const { return !load_table.empty(); }
     // --quantize's list into quality_map; false: not strictly increasing integers in 0..93, or none, or more than 93
     bool parse_quantize(const char *list) {
@@ -203,6 +227,7 @@ struct CliOptions {
                     if (!trains_with) trains_with = "--spectrum";
                     if (!spectrum_option) spectrum_option = "--spectrum";
                     break;
+                case 1007: correct = true; if (!trains_with) trains_with = "--correct"; break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -212,8 +237,12 @@ struct CliOptions {
                     return !give_up(std::string("  Unknown argument ") + (char)opt);
             }
         }
+        if (table_run() && correct)      // (whatever training option came first: the line names this one)
+            return !give_up(" Error: --load-table with --correct: a table run builds no trusted filter, and the corrections come from that.");
         if (table_run() && trains_with)
             return !give_up(std::string(" Error: --load-table with ") + trains_with + ": a table run does not train, it applies the model of the table.");
+        if (correct)
+            if (const char *why = correct_refusal()) return !give_up(std::string(" Error: --correct with ") + why + ".");
         if (fixed_mode() && spectrum_option)
             return !give_up(std::string(" Error: ") + spectrum_option + " with --fixed: the genome length sizes the filters, which are not used there.");
         if (estimate_genomelen && genomelen)

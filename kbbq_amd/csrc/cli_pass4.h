@@ -1,5 +1,5 @@
 // cli_pass4.h -- pass 4 of the command line (kbbq.cc:455-457: recalibrate_and_write): the output's BGZF layer and the record
-// writers of the three formats (Sink), the device quality arrays of the batches in flight (QualSlots) and the six ways from
+// writers of the three formats (Sink), the device quality arrays of the batches in flight (QualSlots; --correct: their fix arrays, FixSlots) and the six ways from
 // what the first scan left behind to the output, of which main() picks one.  Compiled into kbbq_cli.cc alone.
 #pragma once
 
@@ -127,12 +127,40 @@ struct QualSlots {
     }
 };
 
+// --correct: pass 4's pair of fix arrays (kbbq_correct_batch's fix_mask and fix_bases of one batch, one allocation), handled as
+// QualSlots handles the qualities: batch n fills slot n & 1 while the writer still reads the other one.
+struct FixSlots {
+    kbbq_engine *e;
+    void *p[2] = {nullptr, nullptr};
+    size_t bytes[2] = {0, 0};
+    ~FixSlots() { for (int i = 0; i < 2; ++i) if (p[i]) kbbq_device_free(e, p[i]); }
+    // The fixes of batch d, whose error flags pass 3 left in `errors`, into slot t; call behind QualSlots::recalibrate of the
+    // same batch, which has waited for the writer to be through with the slot.  0 and the two arrays, or the exit status.
+    int correct(int t, const kbbq_reads &d, const uint64_t *errors, const uint64_t **mask, const uint64_t **bases) {
+        const size_t mask_bytes = (d.n_bases / 64 + 2) * 8, need = mask_bytes + (d.n_bases / 32 + 2) * 8;
+        if (bytes[t] < need) {
+            if (p[t] && kbbq_device_free(e, p[t]) < 0) return fail_engine("correcting");
+            p[t] = nullptr;
+            bytes[t] = need + need / 8 + 4096;
+            if (kbbq_device_alloc(e, bytes[t], &p[t]) < 0) return fail_engine("correcting");
+        }
+        if (kbbq_device_zero(e, p[t], need) < 0) return fail_engine("correcting");
+        *mask = (const uint64_t *)p[t];
+        *bases = (const uint64_t *)((const char *)p[t] + mask_bytes);
+        if (kbbq_correct_batch(e, &d, errors, (uint64_t *)*mask, (uint64_t *)*bases) < 0) return fail_engine("correcting");
+        return 0;
+    }
+};
+
 // Pass 4, the device path: the file's chunks again (inflate + record index, as in the first scan) or the chunks kept in HBM,
 // pass 4 into a device array, the text assembled from the device's own copy of the input, deflated, written.  Nothing but
 // compressed bytes crosses the host link in either direction.
 static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in) {
     DeviceBgzfWriter &out = *sink.dev;
     QualSlots slots{e};
+    FixSlots fixes{e};
+    const bool correct = o.correct;
+    if (correct && s.error_flags.of.size() != s.resident.dev.size()) return give_up(" Error: --correct: pass 3 left no error flags for the resident batches.");
     size_t bi = 0;
     if (!in.text_kept) {
         in.start_pass();
@@ -150,15 +178,26 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
         if (!info.n_records) continue;
         const kbbq_reads &d = s.resident.dev[bi];
         const int t = (int)(bi & 1);
+        const uint64_t *errors = correct ? s.error_flags.of[bi] : nullptr;
         ++bi;
         const uint8_t *q = nullptr;
         if (const int rc = slots.recalibrate(out, t, d, &q)) return rc;
         // KBBQ_QUAL_DIGEST=1: the sum of every recalibrated quality, taken on the device from the array the writer reads
         // (the number bench.py prints as recal_qual_sum for the same reads)
         if (o.qual_digest && kbbq_digest_add(e, q, d.n_bases) < 0) return fail_engine("recalibrating");
-        if (!in.write_chunk(out, q, o.set_oq, kbbq_engine_stream(e))) return 1;
+        if (correct) {
+            const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
+            if (const int rc = fixes.correct(t, d, errors, &fix_mask, &fix_bases)) return rc;
+            if (!in.write_chunk_corrected(out, q, fix_mask, fix_bases, kbbq_engine_stream(e))) return 1;
+        } else if (!in.write_chunk(out, q, o.set_oq, kbbq_engine_stream(e))) return 1;
     }
     if (!out.drain()) return 1;
+    if (correct) {
+        kbbq_fix_counts c;
+        if (kbbq_correct_counts(e, &c, 0) < 0) return fail_engine("correcting");
+        std::cerr << put_now << " Corrected bases: " << c.flagged << " flagged, " << c.fixed << " fixed, " << c.ambiguous << " ambiguous, " << c.unsupported
+                  << " unsupported." << std::endl;
+    }
     if (o.qual_digest) {
         uint64_t sum = 0;
         if (kbbq_digest_get(e, &sum, 1) < 0) return fail_engine("recalibrating");

@@ -47,6 +47,7 @@ using namespace kbbq;
 #include "engine_report.h"
 #include "engine_pass4.h"
 #include "engine_misc.h"
+#include "engine_correct.h"
 
 extern "C" {
 
@@ -158,6 +159,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->d_counters);
     hipFree(e->d_tickets);
     hipFree(e->d_totals);
+    hipFree(e->d_fix_counts);
     hipFree(e->p4.d_dq_qslot);
     hipFree(e->d_qpresent);
     hipFree(e->p3.d_rg_present[0]);

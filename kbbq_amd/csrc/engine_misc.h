@@ -325,6 +325,13 @@ int kbbq_device_alloc(kbbq_engine *e, size_t bytes, void **out) {
     return KBBQ_OK;
 }
 
+int kbbq_device_zero(kbbq_engine *e, void *p, size_t bytes) {
+    ENGINE_DEVICE(e);
+    if (!p) return fail(KBBQ_EINVAL, "null argument");
+    HIP_TRY(hipMemsetAsync(p, 0, bytes, e->stream));
+    return KBBQ_OK;
+}
+
 int kbbq_device_free(kbbq_engine *e, void *p) {
     ENGINE_DEVICE(e);
     if (p) {

@@ -149,7 +149,7 @@ struct Counters {                   // kbbq_engine::d_counters
     SideCounters *side(int s) { return s ? &side1 : &side0; }      // (on the device pointer: address arithmetic only)
 };
 struct Tickets {                    // kbbq_engine::d_tickets: chunk counters of the kernels that hand their reads out dynamically (ReadChunks)
-    unsigned int infer, scan[2], walk[2], unused[11];      // k_infer; k_scan_trusted and k_correct_wave per side of pass 3
+    unsigned int infer, scan[2], walk[2], fix, unused[10];      // k_infer; k_scan_trusted and k_correct_wave per side of pass 3; k_fix_bases
 };
 struct Totals {                     // kbbq_engine::d_totals
     unsigned long long walk_reads, walk_queries;   // pass 3: reads sent to the correction kernels, Bloom queries there (k_add_counters)
@@ -348,6 +348,9 @@ struct kbbq_engine {
     Counters *d_counters = nullptr;
     Tickets *d_tickets = nullptr;
     Totals *d_totals = nullptr;
+    // kbbq_fix_counts of k_fix_bases (engine_correct.h): flagged, fixed, ambiguous, unsupported.  Allocated by the first kbbq_correct_batch:
+    // an engine that never corrects makes exactly the allocations, in the order, that it made before there was such a call
+    unsigned long long *d_fix_counts = nullptr;
     // a kernel's MaxDynamicSharedMemorySize is set per device: what this engine has raised on ITS device, per kernel (raise_dynamic_lds)
     std::map<const void *, size_t> dyn_lds;
     // synthetic reads (kbbq_synth_reads): the quality and error tables of the last read length asked for
@@ -362,6 +365,7 @@ int reset_counters(kbbq_engine *e) {
     HIP_TRY(hipMemsetAsync(e->d_counters, 0, sizeof(Counters), e->stream));
     HIP_TRY(hipMemsetAsync(e->d_totals, 0, offsetof(Totals, digest), e->stream));      // (the digest has its own reset: kbbq_digest_get)
     HIP_TRY(hipMemsetAsync(e->d_qpresent, 0, 32, e->stream));
+    if (e->d_fix_counts) HIP_TRY(hipMemsetAsync(e->d_fix_counts, 0, 32, e->stream));
     memset(e->qpresent, 0, sizeof e->qpresent);
     e->qpresent_known = false;
     return KBBQ_OK;

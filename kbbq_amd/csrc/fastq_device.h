@@ -8,6 +8,9 @@
 //   k_fastq_gather       sequence text and qualities (- 33) of the records into the batch's contiguous arrays
 //   k_fastq_text_indexed / k_fastq_keep_names / k_fastq_text_packed
 //                        pass 4: the records' text from the device copy of the input, or from the kept names and the packed batch
+//   k_fastq_text_indexed_fixed / k_fastq_text_packed_fixed
+//                        the same two with corrected sequence lines (kbbq_fastq_reader_write_corrected): kernels of their own, so
+//                        that the two above stay what they are
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -129,6 +132,36 @@ __global__ void __launch_bounds__(256) k_fastq_text_packed(const uint8_t *names,
         const uint8_t *name = names + (text_off[r] - 2 * b0 - 6 * r);
         const SeqSource from = {nullptr, bases, nmask, offcase, b0};
         emit_fastq_record(lane, name, nl, name + nl, cl, from, sl, new_qual + b0, out + text_off[r]);
+    }
+}
+
+// The two text kernels again, with the fixes of kbbq_correct_batch (include/kbbq_engine.h) written into the sequence lines:
+// fix_mask / fix_bases are relative to the chunk's batch, as base_off is.
+__global__ void __launch_bounds__(256) k_fastq_text_indexed_fixed(const uint8_t *text, FastqIndex X, const uint64_t *text_off, const uint64_t *base_off,
+                                                                   const uint8_t *new_qual, const uint64_t *fix_mask, const uint64_t *fix_bases,
+                                                                   uint64_t n_records, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t r = wave; r < n_records; r += n_waves) {
+        const uint32_t nl = X.name_len[r], cl = X.com_len[r], sl = X.seq_len[r];
+        const uint8_t *name = text + X.name_off[r], *comment = text + X.com_off[r], *seq = text + X.seq_off[r];
+        const SeqSource from = {seq, nullptr, nullptr, nullptr, 0, fix_mask, fix_bases, base_off[r]};
+        emit_fastq_record<true>(lane, name, nl, comment, cl, from, sl, new_qual + base_off[r], out + text_off[r]);
+    }
+}
+__global__ void __launch_bounds__(256) k_fastq_text_packed_fixed(const uint8_t *names, const uint32_t *lens, const uint64_t *text_off, const uint64_t *base_off,
+                                                                  const uint64_t *bases, const uint64_t *nmask, const uint64_t *offcase,
+                                                                  const uint8_t *new_qual, const uint64_t *fix_mask, const uint64_t *fix_bases,
+                                                                  uint64_t n_records, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t r = wave; r < n_records; r += n_waves) {
+        const uint32_t nl = lens[2 * r], cl = lens[2 * r + 1];
+        const uint64_t b0 = base_off[r];
+        const uint32_t sl = (uint32_t)(base_off[r + 1] - b0);
+        const uint8_t *name = names + (text_off[r] - 2 * b0 - 6 * r);
+        const SeqSource from = {nullptr, bases, nmask, offcase, b0, fix_mask, fix_bases, b0};
+        emit_fastq_record<true>(lane, name, nl, name + nl, cl, from, sl, new_qual + b0, out + text_off[r]);
     }
 }
 

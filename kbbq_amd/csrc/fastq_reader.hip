@@ -374,7 +374,8 @@ int kbbq_fastq_reader_batch_exact(kbbq_fastq_reader *r, int32_t *exact) {
     return r->batch_exact(r->selected >= 0, exact);
 }
 
-int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, void *after_stream) {
+// both forms of the write; fix_mask / fix_bases (both or neither): the corrected form's kernels instead of the plain ones
+static int fastq_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint64_t *fix_mask, const uint64_t *fix_bases, void *after_stream) {
     if (!r || !z || !d_qual) return fail(KBBQ_EINVAL, "null argument");
     if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
     if (r->device != z->device) return fail(KBBQ_EINVAL, "reader and writer are on different devices");
@@ -392,12 +393,28 @@ int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d
     // index are read by the kernel queued, and the next kbbq_fastq_reader_chunk must not overwrite them before it has run; a
     // kept chunk's buffers stay as they are.
     return submit_rewrite(z, after_stream, r->out_text_bytes, !from_kept, [&](uint8_t *payload) {
-        if (from_kept && k->short_form)
+        if (from_kept && k->short_form && fix_mask)
+            hipLaunchKernelGGL(k_fastq_text_packed_fixed, grid, dim3(256), 0, z->st, (const uint8_t *)k->names.p, (const uint32_t *)k->lens.p, (const uint64_t *)k->text_sz.p,
+                               (const uint64_t *)k->base_sz.p, r->att_bases, r->att_nmask, r->att_offcase, d_qual, fix_mask, fix_bases, n, payload);
+        else if (from_kept && k->short_form)
             hipLaunchKernelGGL(k_fastq_text_packed, grid, dim3(256), 0, z->st, (const uint8_t *)k->names.p, (const uint32_t *)k->lens.p, (const uint64_t *)k->text_sz.p,
                                (const uint64_t *)k->base_sz.p, r->att_bases, r->att_nmask, r->att_offcase, d_qual, n, payload);
+        else if (fix_mask)
+            hipLaunchKernelGGL(k_fastq_text_indexed_fixed, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)X.text_sz, (const uint64_t *)X.base_sz, d_qual,
+                               fix_mask, fix_bases, n, payload);
         else
             hipLaunchKernelGGL(k_fastq_text_indexed, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)X.text_sz, (const uint64_t *)X.base_sz, d_qual, n, payload);
     });
+}
+
+int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, void *after_stream) {
+    return fastq_write(r, z, d_qual, nullptr, nullptr, after_stream);
+}
+
+int kbbq_fastq_reader_write_corrected(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases,
+                                      void *after_stream) {
+    if (!d_fix_mask || !d_fix_bases) return fail(KBBQ_EINVAL, "null argument");
+    return fastq_write(r, z, d_qual, d_fix_mask, d_fix_bases, after_stream);
 }
 
 int kbbq_fastq_reader_attach(kbbq_fastq_reader *r, const kbbq_reads *batch) {

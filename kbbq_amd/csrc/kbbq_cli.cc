@@ -181,6 +181,19 @@ struct ScanState {
     size_t longest = 0;
     BamHeader bam_header;
     Resident resident;
+    // --correct: the error flags of every resident batch (device arrays of engine e, nmask's layout), which pass 3 fills and
+    // pass 4 reads; freed before the engine goes (main() declares the engine's owner first)
+    struct ErrorFlags {
+        kbbq_engine *e = nullptr;
+        std::vector<uint64_t *> of;      // by resident batch
+        ErrorFlags() = default;
+        ErrorFlags(const ErrorFlags &) = delete;
+        ~ErrorFlags() { drop(); }
+        void drop() {
+            for (uint64_t *p : of) kbbq_device_free(e, p);
+            of.clear();
+        }
+    } error_flags;
     bool scan_fast = false;      // the block-parallel parser read the whole stream
     bool any_empty = false;      // some read was empty
     // forget what a scan found: the next way of reading the input starts over
@@ -189,6 +202,7 @@ struct ScanState {
         seqlen = n_reads = 0;
         longest = 0;
         scan_fast = any_empty = false;
+        error_flags.drop();
         resident.drop();
         resident.init(o);
     }
@@ -370,6 +384,7 @@ struct PassBatches {
     Batch *host;
     const CliOptions *opt;
     ScanState *scan;
+    std::vector<uint64_t *> *flags = nullptr;      // --correct (device batches): where pass 3 leaves every batch's error flags
     bool fatal() const { return host && host->fatal; }      // a parser gave up; its message is on stderr
     // f(batch, index) for every batch; false when f said so.  stop_at_empty: pass 1 ends at the first empty read (kbbq.cc:234).
     template <class F> bool each(bool stop_at_empty, F f) const {
@@ -446,7 +461,19 @@ static int run_passes(kbbq_engine *e, const CliOptions &o, long double alpha, co
         clock.mark("pass2");
         std::cerr << put_now << " Finding errors" << std::endl;
     }
-    ok = reads.each(false, [&](const kbbq_reads &b, size_t) { return kbbq_errors_batch(e, &b, nullptr) >= 0; });
+    if (!reads.flags) {
+        ok = reads.each(false, [&](const kbbq_reads &b, size_t) { return kbbq_errors_batch(e, &b, nullptr) >= 0; });
+    } else {
+        // --correct: every resident batch gets a device array for its flags, which stays for pass 4; such a call completes before
+        // it returns (kbbq_engine.h: kbbq_errors_batch), so pass 3 of this run goes batch by batch
+        ok = reads.each(false, [&](const kbbq_reads &b, size_t) {
+            void *p = nullptr;
+            const size_t bytes = (b.n_bases / 64 + 2) * 8;
+            if (kbbq_device_alloc(e, bytes, &p) < 0) return false;
+            reads.flags->push_back((uint64_t *)p);
+            return kbbq_device_zero(e, p, bytes) >= 0 && kbbq_errors_batch(e, &b, (uint64_t *)p) >= 0;
+        });
+    }
     if (!ok) return die("finding errors");
     if (reads.fatal()) return 1;
     if (grp && kbbq_exchange_histograms(e, grp) < 0) return die("summing the histograms");
@@ -785,6 +812,7 @@ static int end_run(const CliOptions &opt, PhaseClock &clock, DeviceInput &dev_in
         fflush(stderr);
         exit(0);      // (handlers registered with atexit still run: a profiler's, the runtime's)
     }
+    scan.error_flags.drop();
     scan.resident.drop();
     engine.release();
     clock.mark("release");
@@ -859,6 +887,9 @@ int main(int argc, char *argv[]) {
     if (fmt == Format::unknown) return give_up(" Error opening file " + opt.filename);
     if (fmt == Format::cram) return give_up(" Error: CRAM input needs htslib, which this build does not have; use BAM or FASTQ.");
     opt.format = fmt;
+    if (opt.correct && fmt != Format::fastq)
+        return give_up(std::string(" Error: --correct with ") + (fmt == Format::bam ? "BAM" : "SAM") +
+                       " input: changing SEQ there would falsify CIGAR, MD and NM, and this tool does not re-align.  Corrected reads are written for FASTQ.");
     opt.fixed_on_device = opt.fixed_may_read_on_device();
     if (opt.stream || opt.fixed_stream) {
         if (const char *why = opt.needs_a_file())
@@ -890,6 +921,8 @@ int main(int argc, char *argv[]) {
     FixedOnDevice fixed_report;
     scan.resident.init(opt);
     const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, stream.get(), dev_in, scan);
+    if (!read_on_device && opt.correct)      // (no host parsers behind --correct, as behind a stream)
+        return give_up(" Error: --correct: the GPU reader hands this input back to the host parsers (or the reads do not stay in GPU memory), and they write no corrected reads.");
     if (!read_on_device && stream) {
         // no host parsers behind a stream; without a reason the stream held no read at all, and nothing is left to read
         if (!scan.resident.on) return give_up(" Error: input from a pipe is read once, and the reads cannot stay in GPU memory: write the input to a file first.");
@@ -914,7 +947,8 @@ int main(int argc, char *argv[]) {
     bool trained = false;      // KBBQ_DEVICES: the model was trained and broadcast among the ranks
     if (!opt.fixed_mode()) {
         long double alpha = 0;
-        const PassBatches reads{&resident.dev, nullptr, resident.on ? nullptr : &batch, &opt, &scan};
+        PassBatches reads{&resident.dev, nullptr, resident.on ? nullptr : &batch, &opt, &scan};
+        if (opt.correct) reads.flags = &scan.error_flags.of;
         // --estimate-genomelen, --spectrum: the k-mer spectrum, counted only where the run lacks a genome length -- a header that
         // gives one wins as without the option -- or the file is asked for
         uint64_t estimated = 0;
@@ -927,6 +961,7 @@ int main(int argc, char *argv[]) {
         }
         if (!derive_sampling(opt, scan, estimated, p, alpha)) return 1;
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
+        scan.error_flags.e = e;
         const std::vector<int> devices = device_list(opt, scan);
         if (devices.size() > 1) {
             if (run_on_devices(devices, e, p, opt, alpha, scan, clock)) return 1;

@@ -74,6 +74,16 @@ struct SeqSource {
     const uint8_t *text;           // the sequence characters, or null: from the packed arrays at base index `first`
     const uint64_t *bases, *nmask, *offcase;
     uint64_t first;
+    // Optional (the corrected output, emit_fastq_record<true> alone): where bit fix_first + j of fix_mask (nmask's layout) is set,
+    // character j is "ACGT"[the 2-bit code at that index of fix_bases (bases' layout)] instead of the source's
+    const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
+    uint64_t fix_first = 0;
+    __device__ __forceinline__ bool fixed_at(uint32_t j, uint8_t &c) const {
+        const uint64_t g = fix_first + j;
+        if (!((fix_mask[g >> 6] >> (g & 63)) & 1)) return false;
+        c = (uint8_t)((0x54474341u >> (8 * ((uint32_t)(fix_bases[g >> 5] >> ((g & 31) * 2)) & 3u))) & 0xFFu);      // "ACGT"
+        return true;
+    }
     __device__ __forceinline__ uint8_t at(uint32_t j) const {
         if (text) return text[j];
         const uint64_t g = first + j;
@@ -83,6 +93,8 @@ struct SeqSource {
         return low ? (uint8_t)(c | 0x20) : c;
     }
 };
+// FIX: the sequence line takes the fixes of seq.fix_mask / fix_bases; every other byte, and every unfixed character, as without
+template <bool FIX = false>
 __device__ __forceinline__ void emit_fastq_record(int lane, const uint8_t *name, uint32_t nl, const uint8_t *comment, uint32_t cl, const SeqSource &seq,
                                                   uint32_t sl, const uint8_t *q, uint8_t *out) {
     const uint32_t a_seq = 1 + nl + 1, a_plus = a_seq + sl, a_com = a_plus + 2, a_q = a_com + cl + 1, total = a_q + sl + 1;
@@ -96,7 +108,11 @@ __device__ __forceinline__ void emit_fastq_record(int lane, const uint8_t *name,
             if (i == 0) k = '@';
             else if (i < 1 + nl) sp = name + (i - 1);
             else if (i < a_seq) k = '\n';
-            else if (i < a_plus) { if (seq.text) sp = seq.text + (i - a_seq); else k = seq.at(i - a_seq); }
+            else if (i < a_plus) {
+                if (FIX && seq.fixed_at(i - a_seq, k)) {}
+                else if (seq.text) sp = seq.text + (i - a_seq);
+                else k = seq.at(i - a_seq);
+            }
             else if (i == a_plus) k = '\n';
             else if (i == a_plus + 1) k = '+';
             else if (i < a_com + cl) sp = comment + (i - a_com);

@@ -248,6 +248,32 @@ class Engine:
         _lib.check(self.L.kbbq_fixed_errors_batch(self.h, self._c(batch), first_read, self._c(fixed), fixed_first_read, n_reads,
                                                   errors_device_ptr))
 
+    # ---- base correction: which flagged bases the trusted filter can repair, and to what
+    def correct_bases(self, batch, error_words):
+        """kbbq_correct_batch on a device batch (DeviceReads) and an error bit array in nmask's layout (host words, e.g.
+        pack_bits of pass 3's flags): (fix_mask, fix_bases) as NumPy uint64 arrays of n_bases/64+2 and n_bases/32+2 words --
+        a bit where a base is fixed, its new 2-bit code.  Waits for the kernel."""
+        import torch
+        nb = int(batch.c.n_bases)
+        words = np.zeros(nb // 64 + 2, dtype=np.uint64)
+        given = np.ascontiguousarray(error_words, dtype=np.uint64)
+        assert len(given) <= len(words), "error_words: at most n_bases/64+2 words"
+        words[:len(given)] = given
+        dev = "cuda:%d" % self.params.device
+        d_err = torch.from_numpy(words.view(np.int64)).to(dev)
+        d_mask = torch.zeros(nb // 64 + 2, dtype=torch.int64, device=dev)
+        d_bases = torch.zeros(nb // 32 + 2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_correct_batch(self.h, self._c(batch), d_err.data_ptr(), d_mask.data_ptr(), d_bases.data_ptr()))
+        self.sync()
+        return d_mask.cpu().numpy().view(np.uint64), d_bases.cpu().numpy().view(np.uint64)
+
+    def fix_counts(self, reset=False):
+        """What correct_bases did since the last reset (waits): flagged, fixed, ambiguous, unsupported."""
+        c = _lib.FixCounts()
+        _lib.check(self.L.kbbq_correct_counts(self.h, ctypes.byref(c), 1 if reset else 0))
+        return dict(flagged=int(c.flagged), fixed=int(c.fixed), ambiguous=int(c.ambiguous), unsupported=int(c.unsupported))
+
     def covariates(self):
         R, C = self.n_rg, self.max_read_len
         out = dict(R=R, C=C, rg=np.zeros((R, 2), np.uint64), q=np.zeros((R, NQ, 2), np.uint64),
