@@ -167,6 +167,45 @@ int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double
  * speculative decode with the re-decodes of false starts, the window chain, resolve + CRC-32. */
 int kbbq_fastq_reader_gzip_ms(kbbq_fastq_reader *r, double *find_ms, double *decode_ms, double *chain_ms, double *resolve_ms);
 
+/* ---- paired FASTQ: who is second-in-pair when the names do not say, and whether two files (or the neighbours of an
+ * interleaved one) are in step.  The reference knows second-in-pair from a "/2" name suffix alone (readutils.cc:74-97), which
+ * stays the default; data whose mate number stands in the comment ("@name 2:N:0:ACGT"), or nowhere, needs the caller's word. */
+#define KBBQ_MATES_FROM_NAMES 0     /* the part of the name before the first '_' ends in "/2": the reference's rule, the default */
+#define KBBQ_MATES_ALL_FIRST 1      /* every record is first-in-pair, whatever its name says */
+#define KBBQ_MATES_ALL_SECOND 2     /* every record is second-in-pair */
+#define KBBQ_MATES_INTERLEAVED 3    /* record 0, 2, 4 ... of the WHOLE input is first, 1, 3, 5 ... second */
+/* How the chunks indexed from now on get their second-in-pair flags (kbbq_reads.flags of kbbq_fastq_reader_batch).  The reader
+ * counts the records of the chunks it has indexed since create or rewind, so that the parity of an interleaved input runs over
+ * the whole input and not per chunk; a kept chunk remembers its first record's ordinal. */
+int kbbq_fastq_reader_set_mates(kbbq_fastq_reader *r, int32_t mode);
+/* The second-in-pair flags of the current chunk's records, one byte each, into d_flags (device memory of the caller's,
+ * n_records bytes): of the live chunk what its batch gets, of a selected kept chunk the same again, in either kept form.
+ * Returns when they are written. */
+int kbbq_fastq_reader_mates(kbbq_fastq_reader *r, uint8_t *d_flags);
+/* The pair keys of the current chunk's records into d_keys (device memory of the caller's, n_records values): a record's key
+ * is the FNV-1a 64 hash of its name -- the header line behind '@' up to the first white-space character -- without its last two
+ * bytes when the name is longer than two bytes and they are "/1" or "/2"; nothing else is stripped.  Mates have equal keys;
+ * two different names have equal keys with probability 2^-64.  On the live chunk and on a selected kept chunk, in either kept
+ * form (the short form keeps the names).  Returns when they are written. */
+int kbbq_fastq_reader_pair_keys(kbbq_fastq_reader *r, uint64_t *d_keys);
+/* Milliseconds the device spent in kbbq_fastq_reader_pair_keys' kernel since creation (the mates kernel of a chunk call is in
+ * kbbq_fastq_reader_kernel_ms' index_ms). */
+int kbbq_fastq_reader_pair_keys_ms(kbbq_fastq_reader *r, double *keys_ms);
+/* The name of record i of the current chunk (live or selected) into out[0, capacity), not terminated; *len gets its whole
+ * length.  For the one line a run ends with when its pairs are out of step: it waits for the device and copies a few bytes. */
+int kbbq_fastq_reader_record_name(kbbq_fastq_reader *r, uint64_t i, char *out, uint32_t capacity, uint32_t *len);
+/* Two key arrays on `device` compared: n comparisons, a[i] with b[i] -- or, adjacent != 0, a[2i] with a[2i + 1] (the keys of
+ * an interleaved input; b is not read).  *n_mismatch: how many differ; *first: the lowest such i (UINT64_MAX: none).  Two
+ * counters on the device take them (atomicAdd, atomicMin) and nothing but those two words crosses the host link.  Queued on
+ * the device's null stream and waited for.  *kernel_ms (may be NULL) gets the kernel's time. */
+int kbbq_pair_keys_check(int32_t device, const uint64_t *d_a, const uint64_t *d_b, uint64_t n, int32_t adjacent, uint64_t *n_mismatch,
+                         uint64_t *first, double *kernel_ms);
+/* Device memory for key arrays where no engine exists yet (the first scan): n keys; a device-to-device copy of n keys (queued
+ * on the null stream and waited for); free. */
+int kbbq_pair_keys_alloc(int32_t device, uint64_t n, uint64_t **d_out);
+int kbbq_pair_keys_copy(int32_t device, uint64_t *d_dst, const uint64_t *d_src, uint64_t n);
+int kbbq_pair_keys_free(int32_t device, uint64_t *d_keys);
+
 /* ---- the input side: a BAM file read on the device (round 4) ----------------------------------------------------------
  * What it replaces: sam_read1 (BamFile::next, htsiter.cc:5), the BAM constructor of CReadData (readutils.cc:13-61, with
  * bam_seq_str, readutils.hh:30-42) and -- pass 4 -- BamFile::recalibrate + sam_write1 (htsiter.cc:11-45), once per chunk of

@@ -212,6 +212,15 @@ SYMBOLS = {
     "kbbq_fastq_reader_attach": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads)]),
     "kbbq_fastq_reader_gzip_ms": (ctypes.c_int, [c_vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
     "kbbq_fastq_reader_take_text": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+    "kbbq_fastq_reader_set_mates": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+    "kbbq_fastq_reader_mates": (ctypes.c_int, [c_vp, c_vp]),
+    "kbbq_fastq_reader_pair_keys": (ctypes.c_int, [c_vp, c_vp]),
+    "kbbq_fastq_reader_pair_keys_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
+    "kbbq_fastq_reader_record_name": (ctypes.c_int, [c_vp, c_u64, ctypes.c_char_p, ctypes.c_uint32, c_u32p]),
+    "kbbq_pair_keys_check": (ctypes.c_int, [ctypes.c_int32, c_vp, c_vp, c_u64, ctypes.c_int32, c_u64p, c_u64p, ctypes.POINTER(ctypes.c_double)]),
+    "kbbq_pair_keys_alloc": (ctypes.c_int, [ctypes.c_int32, c_u64, ctypes.POINTER(c_vp)]),
+    "kbbq_pair_keys_copy": (ctypes.c_int, [ctypes.c_int32, c_vp, c_vp, c_u64]),
+    "kbbq_pair_keys_free": (ctypes.c_int, [ctypes.c_int32, c_vp]),
     "kbbq_reads_clone": (ctypes.c_int, [ctypes.POINTER(Reads), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Reads)]),
     "kbbq_engine_dims": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "kbbq_group_rccl_unique_id": (ctypes.c_int, [ctypes.c_void_p]),

@@ -150,6 +150,42 @@ class FastqReader(_RecordReader):
     def attach(self, batch):
         self._call("attach", ctypes.byref(batch))
 
+    def set_mates(self, mode):
+        """How the chunks indexed from now on get their second-in-pair flags: one of the MATES_* values."""
+        self._call("set_mates", mode)
+
+    def mates(self, d_flags):
+        """The current chunk's second-in-pair flags, a byte per record, into device memory (a pointer)."""
+        self._call("mates", d_flags)
+
+    def pair_keys(self, d_keys):
+        """The pair keys of the current chunk's records, a uint64 each, into device memory (a pointer)."""
+        self._call("pair_keys", d_keys)
+
+    def pair_keys_ms(self):
+        ms = ctypes.c_double()
+        self._call("pair_keys_ms", ctypes.byref(ms))
+        return ms.value
+
+    def record_name(self, i):
+        """The name of record i of the current chunk."""
+        n = ctypes.c_uint32()
+        buf = ctypes.create_string_buffer(1 << 16)
+        self._call("record_name", i, buf, len(buf), ctypes.byref(n))
+        return buf.raw[:min(n.value, len(buf))]
+
+
+# kbbq_fastq_reader_set_mates (include/kbbq_bgzf.h)
+MATES_FROM_NAMES, MATES_ALL_FIRST, MATES_ALL_SECOND, MATES_INTERLEAVED = 0, 1, 2, 3
+
+
+def pair_keys_check(d_a, d_b, n, adjacent=False, device=0):
+    """n comparisons of pair keys in device memory (pointers): d_a[i] with d_b[i], or -- adjacent -- d_a[2i] with d_a[2i + 1].
+    (number of mismatches, lowest mismatching i or None)."""
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    _lib.check(_lib.lib().kbbq_pair_keys_check(device, d_a, d_b, n, 1 if adjacent else 0, ctypes.byref(bad), ctypes.byref(first), None))
+    return bad.value, (first.value if bad.value else None)
+
 
 class _AlignedReader(_RecordReader):
     """What the BAM and the SAM reader have beyond the FASTQ reader's: read groups and the sequence-only batch."""

@@ -27,6 +27,11 @@ struct ReaderCalls {
     // --correct: write with the fixes of kbbq_correct_batch in the sequence lines (FASTQ's: changing SEQ in a BAM or SAM record
     // would falsify its CIGAR, MD and NM, and this tool does not re-align)
     int (*write_corrected)(void *h, kbbq_bgzf *z, const uint8_t *d_qual, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases, void *after_stream);
+    // paired FASTQ (cli_pairs.h): who is second-in-pair by the caller's word, the pair keys of the current chunk, a record's name
+    int (*set_mates)(void *h, int32_t mode);
+    int (*pair_keys)(void *h, uint64_t *d_keys);
+    int (*pair_keys_ms)(void *h, double *keys_ms);
+    int (*record_name)(void *h, uint64_t i, char *out, uint32_t capacity, uint32_t *len);
 };
 // f, whose first argument is a reader of type R, as a call on the opaque handle
 template <auto f> struct Thunk;
@@ -37,7 +42,8 @@ static const ReaderCalls kFastqReaderCalls = {
     Thunk<kbbq_fastq_reader_select>::call, Thunk<kbbq_fastq_reader_rewind>::call, Thunk<kbbq_fastq_reader_batch>::call, nullptr /* batch */, Thunk<kbbq_fastq_reader_batch_exact>::call, Thunk<kbbq_fastq_reader_kernel_ms>::call,
     [](void *h, kbbq_bgzf *z, const uint8_t *q, int32_t, void *after) { return kbbq_fastq_reader_write((kbbq_fastq_reader *)h, z, q, after); },
     Thunk<kbbq_fastq_reader_attach>::call, nullptr, nullptr, Thunk<kbbq_fastq_reader_take_text>::call, 0,
-    Thunk<kbbq_fastq_reader_write_corrected>::call};
+    Thunk<kbbq_fastq_reader_write_corrected>::call,
+    Thunk<kbbq_fastq_reader_set_mates>::call, Thunk<kbbq_fastq_reader_pair_keys>::call, Thunk<kbbq_fastq_reader_pair_keys_ms>::call, Thunk<kbbq_fastq_reader_record_name>::call};
 // (sam_read1, the BAM constructor of CReadData, BamFile::recalibrate / write are kernels: htsiter.cc:5-45, readutils.cc:13-61)
 static const ReaderCalls kBamReaderCalls = {
     [](bool use_oq, int32_t n_ref, uint64_t header_bytes, const char *const *ids, uint32_t n_ids, void **out) {
@@ -415,6 +421,8 @@ public:
     const char *container = "BGZF";           // what the file is: BGZF, gzip (other gzip streams) or text
     // why the scan could not go on (device_scan): a file starts over with the host parsers, a stream's run ends with this line
     std::string refusal;
+    // who is second-in-pair (--in2, --interleaved; KBBQ_MATES_*), set before open(): the default leaves it to the names
+    int32_t mates = KBBQ_MATES_FROM_NAMES;
 
     // `stream`: the input when it is not a regular file (its head has been read), null for the file `path`; n_ref, header_bytes,
     // rg_ids: what a BAM or SAM header says (open_device_input); any_read_group: the records need an RG tag but no @RG line
@@ -429,6 +437,7 @@ public:
         if (r_->create(use_oq, n_ref, header_bytes, ids.data(), (uint32_t)ids.size(), &h_) < 0) return false;
         if (r_->take_text && r_->take_text(h_, 1) < 0) return false;
         if (any_read_group && r_->any_read_group && r_->any_read_group(h_, 1) < 0) return false;
+        if (mates != KBBQ_MATES_FROM_NAMES && (!r_->set_mates || r_->set_mates(h_, mates) < 0)) return false;
         start_pass();
         return true;
     }
@@ -539,6 +548,15 @@ public:
     // the read groups met, in dense-index order, as indices into the header's @RG ids (BAM and SAM)
     int read_groups(uint32_t *table_index, uint32_t capacity, uint32_t *n) { return r_->read_groups(h_, table_index, capacity, n); }
     void kernel_ms(double &inflate, double &index) { inflate = index = 0; r_->kernel_ms(h_, &inflate, &index); }
+    // paired FASTQ: the pair keys of the current chunk's records into device memory, their kernel's time, the name of record i
+    int pair_keys(uint64_t *d_keys) { return r_->pair_keys(h_, d_keys); }
+    double pair_keys_ms() { double ms = 0; if (h_ && r_->pair_keys_ms) r_->pair_keys_ms(h_, &ms); return ms; }
+    std::string record_name(uint64_t i) {
+        std::vector<char> buf(1 << 16);
+        uint32_t len = 0;
+        if (!h_ || r_->record_name(h_, i, buf.data(), (uint32_t)buf.size(), &len) < 0) return "?";
+        return std::string(buf.data(), std::min<size_t>(len, buf.size()));
+    }
     // The current chunk with new qualities to the writer, assembled from the device's own copy of the input (BamFile::recalibrate + write)
     bool write_chunk(DeviceBgzfWriter &out, const uint8_t *d_qual, bool set_oq, void *after_stream) {
         return out.submit([&](kbbq_bgzf *z) { return r_->write(h_, z, d_qual, set_oq ? 1 : 0, after_stream); });

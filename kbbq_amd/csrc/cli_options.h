@@ -27,6 +27,8 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"estimate-genomelen", no_argument, 0, 1005}, {"spectrum", required_argument, 0, 1006},
     // the output's sequence lines with the flagged bases repaired that the trusted filter can repair (cli_pass4.h)
     {"correct", no_argument, 0, 1007},
+    // paired FASTQ (cli_pairs.h): the second-in-pair file and where its records go, or one input whose records alternate
+    {"in2", required_argument, 0, 1008}, {"out2", required_argument, 0, 1009}, {"interleaved", no_argument, 0, 1010},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -90,6 +92,13 @@ struct CliOptions {
     // should be (kbbq_correct_batch) and writes the FASTQ with those bases in its sequence lines.  A training option (the filter is
     // a training run's), FASTQ through the device reader on one device only: whatever leads elsewhere is refused (correct_refusal)
     bool correct = false;
+    // --in2 FILE --out2 FILE: the positional input holds the first-in-pair reads, FILE the second-in-pair ones, record for record;
+    // one scan reads both on the GPU, one model is trained on all reads, and the second file's records go to --out2 as BGZF.
+    // --interleaved: one input whose records alternate first, second.  Either way the mate flag is the file's or the ordinal's
+    // word, whatever the names say, and the run checks that the pairs are in step (cli_pairs.h).  Both go through the device
+    // reader alone: whatever leads elsewhere is refused (pairs_refusal)
+    std::string in2, out2, in2_path;
+    bool in2_stream = false, interleaved = false;
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -137,6 +146,29 @@ struct CliOptions {
             q = *end == ',' ? end + 1 : end;
         }
         if (entries > 1) return "KBBQ_DEVICES with more than one device: the error flags of the other devices' shards do not reach the device that writes";
+        return nullptr;
+    }
+    bool paired_files() const { return !in2.empty(); }
+    const char *pairs_option() const { return paired_files() ? "--in2" : !out2.empty() ? "--out2" : interleaved ? "--interleaved" : nullptr; }
+    // What was asked for beside --in2 / --out2 or --interleaved that they cannot go with, known before the input is opened; null: nothing
+    const char *pairs_refusal() const {
+        if (in2.empty() != out2.empty())
+            return in2.empty() ? "out --in2: --out2 names the output of the second-in-pair file, which --in2 gives"
+                               : "out --out2: the second file's records are written to a file of their own, which --out2 names";
+        if (paired_files() && interleaved) return " --interleaved: the pairs come in two files or in one, not both";
+        if (paired_files() && fixed_mode()) return " --fixed: a fixed run of two files would read four, which is not built";
+        if (paired_files() && table_run()) return " --load-table: the one-pass table run reads one file";
+        if (!device_reader) return " KBBQ_DEVICE_READER=0: the host parsers know second-in-pair from the names alone, as the reference does";
+        if (serial_parse) return " KBBQ_SERIAL_PARSE=1: the host parsers know second-in-pair from the names alone, as the reference does";
+        if (host_deflate) return " KBBQ_HOST_DEFLATE=1: the host parsers know second-in-pair from the names alone, as the reference does";
+        if (!resident) return " KBBQ_RESIDENT=0: every pass would read the input again through the host parsers, which know second-in-pair from the names alone";
+        if (paired_files() && (stream || in2_stream)) return " an input that is not a regular file: two streams would need two kept heads, which is not built";
+        return nullptr;
+    }
+    // the same once the format of the inputs is known (main(): sniff)
+    const char *pairs_format_refusal(Format first, Format second) const {
+        if (first == Format::bam || first == Format::sam) return first == Format::bam ? " BAM input: its records carry their mate in FLAG" : " SAM input: its records carry their mate in FLAG";
+        if (paired_files() && second != Format::fastq) return " a second file that is not FASTQ";
         return nullptr;
     }
     bool table_run() const { return !load_table.empty(); }
@@ -228,6 +260,9 @@ struct CliOptions {
                     if (!spectrum_option) spectrum_option = "--spectrum";
                     break;
                 case 1007: correct = true; if (!trains_with) trains_with = "--correct"; break;
+                case 1008: in2 = std::string(optarg); break;
+                case 1009: out2 = std::string(optarg); break;
+                case 1010: interleaved = true; break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -258,6 +293,9 @@ struct CliOptions {
         }
         input = resolve(filename, stream);
         if (fixed_mode()) fixed_path = resolve(fixedinput, fixed_stream);
+        if (paired_files()) in2_path = resolve(in2, in2_stream);
+        if (const char *option = pairs_option())
+            if (const char *why = pairs_refusal()) return !give_up(std::string(" Error: ") + option + " with" + why + ".");
         return true;
     }
 };

@@ -51,6 +51,11 @@ struct Sink {
         if (o.format == Format::sam) return bytes().write(s.bam_header.text.data(), s.bam_header.text.size()) ? 0 : 1;      // the header text, verbatim
         return o.format == Format::bam && !bam->write_header(s.bam_header) ? 1 : 0;      // BamFile::open_out, htsiter.cc:35-42
     }
+    // --out2: FASTQ through the encoder on the GPU into a file of its own (no header, no host writer: the device path's alone)
+    int open_file(FILE *out, const CliOptions &o) {
+        dev.reset(new DeviceBgzfWriter(out, 0, o.write_threads));
+        return dev->ok() ? 0 : fail_engine("cannot create the BGZF writer");
+    }
     // One record of a RecordStore with its new qualities (FormatRow::write_stored).  FASTQ: FastqFile::write, htsiter.cc:75-86
     // (the comment goes on the '+' line); qualities as text, htsiter.cc:61-65
     int stored_fastq(const char *rec, const uint32_t *lens, const uint8_t *q, bool, size_t &rec_bytes, size_t &n_bases) {
@@ -155,13 +160,16 @@ struct FixSlots {
 // Pass 4, the device path: the file's chunks again (inflate + record index, as in the first scan) or the chunks kept in HBM,
 // pass 4 into a device array, the text assembled from the device's own copy of the input, deflated, written.  Nothing but
 // compressed bytes crosses the host link in either direction.
-static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in) {
+// first_batch: the resident batch of the reader's first chunk with records -- 0, or, for the second file of --in2, the number of
+// batches the first file made; totals: the "Corrected bases" and "[digest]" lines, which count every batch written so far (the
+// last reader's call prints them: one line each, over both files).
+static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in, size_t first_batch = 0, bool totals = true) {
     DeviceBgzfWriter &out = *sink.dev;
     QualSlots slots{e};
     FixSlots fixes{e};
     const bool correct = o.correct;
     if (correct && s.error_flags.of.size() != s.resident.dev.size()) return give_up(" Error: --correct: pass 3 left no error flags for the resident batches.");
-    size_t bi = 0;
+    size_t bi = first_batch;
     if (!in.text_kept) {
         in.start_pass();
         if (in.rewind() < 0) return fail_engine("recalibrating");
@@ -171,11 +179,12 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
         if (in.text_kept) {
             // the chunk's text and index (BAM: its compressed bytes, inflated and indexed again) are still on the device
             if (!in.chunk_records[ci]) continue;
-            if (in.select(bi, &info) < 0 || info.n_records != in.chunk_records[ci] || in.attach(&s.resident.dev[bi]) < 0) return fail_engine("recalibrating");
+            if (in.select(bi - first_batch, &info) < 0 || info.n_records != in.chunk_records[ci] || in.attach(&s.resident.dev[bi]) < 0) return fail_engine("recalibrating");
         } else if (in.next_chunk(info) != 1 || info.n_records != in.chunk_records[ci]) {
             return input_changed();
         }
         if (!info.n_records) continue;
+        if (bi >= s.resident.dev.size()) return input_changed();
         const kbbq_reads &d = s.resident.dev[bi];
         const int t = (int)(bi & 1);
         const uint64_t *errors = correct ? s.error_flags.of[bi] : nullptr;
@@ -192,6 +201,7 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
         } else if (!in.write_chunk(out, q, o.set_oq, kbbq_engine_stream(e))) return 1;
     }
     if (!out.drain()) return 1;
+    if (!totals) return 0;
     if (correct) {
         kbbq_fix_counts c;
         if (kbbq_correct_counts(e, &c, 0) < 0) return fail_engine("correcting");

@@ -175,6 +175,8 @@ struct OnePass {
 static int apply_table_one_pass(const CliOptions &o, StreamInput *stream, DeviceInput &in, const LoadedTable &table, EngineOwner &engine, ScanState &s,
                                 Sink &sink, OnePass &rep) {
     std::vector<std::string> rg_ids;
+    // --interleaved: second-in-pair by the record's ordinal, which changes the cycle pass 4 looks up, and the pairs checked chunk by chunk
+    if (o.interleaved) { in.mates = KBBQ_MATES_INTERLEAVED; s.pairs.interleaved = true; }
     if (!open_device_input(o, o.input, stream, false, in, s.bam_header, rg_ids)) {
         in.close();
         if (!stream) return -1;
@@ -226,6 +228,8 @@ static int apply_table_one_pass(const CliOptions &o, StreamInput *stream, Device
         kbbq_reads d;
         if (in.batch(&d) < 0) return cut_short(fail_engine("packing a chunk"));
         live.push_back(d);
+        // (pairs out of step in a later chunk, when output has begun: the run ends like every other trouble met there)
+        if (s.pairs.on() && !s.pairs.chunk(0, in, in, o.filename, o.in2, info)) return cut_short(give_up(s.pairs.failure));
         // the model, when this chunk brought a read group's first record (FASTQ: the first chunk)
         std::vector<std::string> now;
         if (o.format == Format::fastq) {
@@ -256,6 +260,7 @@ static int apply_table_one_pass(const CliOptions &o, StreamInput *stream, Device
         e = engine.e;
         if (const int rc = sink.open(o, s)) return rc;
     }
+    if (s.pairs.on() && !s.pairs.finish(o.filename, o.in2)) return cut_short(give_up(s.pairs.failure));
     if (!sink.dev->drain()) return 1;
     if (o.qual_digest) {
         uint64_t sum = 0;

@@ -6,10 +6,13 @@
 // shared with the BAM and the SAM reader.
 //
 // A kept chunk is text and index, or names and comments alone, for write(): batch and batch_exact refuse a selected chunk.
+// Paired FASTQ (pairs_device.h) -- the mate flags by the caller's word, the pair keys of the names, the comparison of two key
+// arrays -- reads the names of the live chunk and of a kept one in either form.
 #include "record_batch.h"
 #include "text_chunks.h"
 
 #include "fastq_device.h"
+#include "pairs_device.h"
 
 using namespace kbbq::dfl;
 using namespace kbbq::io;
@@ -19,6 +22,7 @@ struct FastqCounts {
     uint64_t text_bytes = 0, n_records = 0, n_bases = 0;
     uint64_t out_text_bytes = 0;            // bytes of the chunk's records written out as FASTQ text
     uint32_t longest = 0, shortest = 0;
+    uint64_t first_record = 0;              // the ordinal of the chunk's first record in the whole input (KBBQ_MATES_INTERLEAVED)
 };
 
 // (the stream, the text, the newline index, the carry: TextChunks; packed_is_exact: the batch gives the sequence text back)
@@ -42,6 +46,10 @@ struct kbbq_fastq_reader : FastqCounts, TextChunks, ChunkState {
     bool keeping = false;
     int64_t selected = -1;      // the kept chunk that is the current one (pass 4), or -1: the live buffers
     uint64_t kept_bytes = 0;
+    // paired FASTQ (kbbq_fastq_reader_set_mates): the mode, the records of the chunks indexed since create / rewind, the key kernel's time
+    int32_t mates = KBBQ_MATES_FROM_NAMES;
+    uint64_t records_seen = 0;
+    double ms_keys = 0;
 };
 
 namespace {
@@ -90,6 +98,20 @@ void *slab_piece(kbbq_fastq_reader *r, size_t bytes) {
     r->slab_used += bytes;
     r->kept_bytes += bytes;
     return p;
+}
+
+// where the names of the current chunk's records are (pairs_device.h): the live text, a kept text, or the short form's names
+NameSource names_of(kbbq_fastq_reader *r) {
+    const uint64_t n = r->n_records;
+    if (r->selected >= 0) {
+        const kbbq_fastq_reader::Kept &k = r->kept[(size_t)r->selected];
+        if (k.short_form)
+            return NameSource{nullptr, nullptr, nullptr, (const uint8_t *)k.names.p, (const uint32_t *)k.lens.p, (const uint64_t *)k.text_sz.p, (const uint64_t *)k.base_sz.p};
+        const FastqIndex X = index_from(k.idx_u32.p, nullptr, k.base_sz.p, k.text_sz.p, nullptr, n);
+        return NameSource{(const uint8_t *)k.text.p, X.name_off, X.name_len, nullptr, nullptr, nullptr, nullptr};
+    }
+    const FastqIndex X = index_of(r, n);
+    return NameSource{(const uint8_t *)r->text.p, X.name_off, X.name_len, nullptr, nullptr, nullptr, nullptr};
 }
 
 bool live_is_keepable(const kbbq_fastq_reader *r) { return r->keeping && r->selected < 0 && r->have_chunk && r->n_records; }
@@ -180,6 +202,7 @@ int kbbq_fastq_reader_rewind(kbbq_fastq_reader *r) {
     r->keeping = false;      // what was kept stays; a second scan keeps nothing more
     r->selected = -1;
     r->have_chunk = false;
+    r->records_seen = 0;
     r->new_stream();
     return KBBQ_OK;
 }
@@ -250,6 +273,10 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
         hipLaunchKernelGGL(k_fastq_records, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, (const uint8_t *)r->text.p,
                            (const uint32_t *)r->nl_pos.p, n_rec, X);
         HIP_TRY(hipGetLastError());
+        if (r->mates != KBBQ_MATES_FROM_NAMES) {      // the caller's word instead of the names': a kernel of its own behind the records'
+            hipLaunchKernelGGL(k_fastq_mates, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, r->st, X.second, n_rec, r->mates, r->records_seen);
+            HIP_TRY(hipGetLastError());
+        }
         if ((rc = device_scan_on(r->tile_sums, r->st, X.base_sz, n_rec, X.base_sz + n_rec))) return rc;
         if ((rc = device_scan_on(r->tile_sums, r->st, X.text_sz, n_rec, X.text_sz + n_rec))) return rc;
         uint64_t *hs = (uint64_t *)r->h_small.p;
@@ -270,6 +297,8 @@ int kbbq_fastq_reader_chunk(kbbq_fastq_reader *r, const uint8_t *file_bytes, uin
     if ((rc = r->keep_rest(rec_end, text, last != 0, info))) return rc;
     r->text_bytes = text;
     r->n_records = n_rec;
+    r->first_record = r->records_seen;
+    r->records_seen += n_rec;
     r->have_chunk = true;
     info->n_records = n_rec;
     info->n_bases = n_rec ? r->n_bases : 0;
@@ -437,6 +466,149 @@ int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double
 int kbbq_fastq_reader_take_text(kbbq_fastq_reader *r, int32_t on) {
     if (!r) return fail(KBBQ_EINVAL, "null argument");
     r->take_text = on != 0;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_set_mates(kbbq_fastq_reader *r, int32_t mode) {
+    if (!r) return fail(KBBQ_EINVAL, "null argument");
+    if (mode < KBBQ_MATES_FROM_NAMES || mode > KBBQ_MATES_INTERLEAVED) return fail(KBBQ_EINVAL, "mates mode %d", (int)mode);
+    r->mates = mode;
+    return KBBQ_OK;
+}
+
+// the current chunk for the calls that read its names: 0, or the error
+static int chunk_with_records(kbbq_fastq_reader *r) {
+    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_mates(kbbq_fastq_reader *r, uint8_t *d_flags) {
+    if (!r || !d_flags) return fail(KBBQ_EINVAL, "null argument");
+    int rc = chunk_with_records(r);
+    if (rc) return rc;
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    const uint64_t n = r->n_records;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (r->selected < 0) HIP_TRY(hipMemcpyAsync(d_flags, r->idx_second.p, n, hipMemcpyDeviceToDevice, r->st));      // what the batch gets
+    else if (r->mates != KBBQ_MATES_FROM_NAMES) hipLaunchKernelGGL(k_fastq_mates, grid, dim3(256), 0, r->st, d_flags, n, r->mates, r->first_record);
+    else hipLaunchKernelGGL(k_fastq_mates_names, grid, dim3(256), 0, r->st, names_of(r), n, d_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r->st));
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_pair_keys(kbbq_fastq_reader *r, uint64_t *d_keys) {
+    if (!r || !d_keys) return fail(KBBQ_EINVAL, "null argument");
+    int rc = chunk_with_records(r);
+    if (rc) return rc;
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    const uint64_t n = r->n_records;
+    HIP_TRY(hipEventRecord(r->t0, r->st));      // (a chunk call's events, free between two of them)
+    hipLaunchKernelGGL(k_pair_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, names_of(r), n, d_keys);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r->t1, r->st));
+    HIP_TRY(hipStreamSynchronize(r->st));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, r->t0, r->t1) == hipSuccess) r->ms_keys += ms;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_pair_keys_ms(kbbq_fastq_reader *r, double *keys_ms) {
+    if (!r || !keys_ms) return fail(KBBQ_EINVAL, "null argument");
+    *keys_ms = r->ms_keys;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_record_name(kbbq_fastq_reader *r, uint64_t i, char *out, uint32_t capacity, uint32_t *len) {
+    if (!r || !len || (!out && capacity)) return fail(KBBQ_EINVAL, "null argument");
+    int rc = chunk_with_records(r);
+    if (rc) return rc;
+    if (i >= r->n_records) return fail(KBBQ_EINVAL, "record %llu of %llu", (unsigned long long)i, (unsigned long long)r->n_records);
+    KbbqDeviceGuard guard(r->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(hipStreamSynchronize(r->st));
+    const NameSource S = names_of(r);
+    const uint8_t *from = nullptr;
+    uint32_t nl = 0;
+    if (S.text) {
+        uint32_t off = 0;
+        HIP_TRY(hipMemcpy(&off, S.name_off + i, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&nl, S.name_len + i, 4, hipMemcpyDeviceToHost));
+        from = S.text + off;
+    } else {
+        uint64_t t = 0, b = 0;
+        HIP_TRY(hipMemcpy(&nl, S.lens + 2 * i, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&t, S.text_off + i, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&b, S.base_off + i, 8, hipMemcpyDeviceToHost));
+        from = S.names + (t - 2 * b - 6 * i);
+    }
+    *len = nl;
+    if (std::min(nl, capacity)) HIP_TRY(hipMemcpy(out, from, std::min(nl, capacity), hipMemcpyDeviceToHost));
+    return KBBQ_OK;
+}
+
+int kbbq_pair_keys_check(int32_t device, const uint64_t *d_a, const uint64_t *d_b, uint64_t n, int32_t adjacent, uint64_t *n_mismatch, uint64_t *first,
+                         double *kernel_ms) {
+    if (!n_mismatch || !first || (n && (!d_a || (!adjacent && !d_b)))) return fail(KBBQ_EINVAL, "null argument");
+    *n_mismatch = 0;
+    *first = UINT64_MAX;
+    if (kernel_ms) *kernel_ms = 0;
+    if (!n) return KBBQ_OK;
+    if (n > ((uint64_t)1 << 39)) return fail(KBBQ_EINVAL, "%llu comparisons in one call", (unsigned long long)n);      // (the grid's blocks travel in 31 bits)
+    int rc = device_exists(device);
+    if (rc) return rc;
+    KbbqDeviceGuard guard(device);
+    HIP_TRY(guard.err);
+    // (two counters, allocated and freed per call: a call per chunk of some hundred MB)
+    Buf counters;
+    if ((rc = counters.reserve(16))) return rc;
+    struct Free { Buf &b; hipEvent_t e0 = nullptr, e1 = nullptr; ~Free() { b.release(); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); } } owned{counters};
+    unsigned long long init[2] = {0, ~0ull}, got[2] = {0, 0};
+    HIP_TRY(hipMemcpy(counters.p, init, 16, hipMemcpyHostToDevice));
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&owned.e0));
+        HIP_TRY(hipEventCreate(&owned.e1));
+        HIP_TRY(hipEventRecord(owned.e0, nullptr));
+    }
+    hipLaunchKernelGGL(k_pair_keys_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_a, d_b, n, adjacent ? 1 : 0, (unsigned long long *)counters.p);
+    HIP_TRY(hipGetLastError());
+    if (kernel_ms) HIP_TRY(hipEventRecord(owned.e1, nullptr));
+    HIP_TRY(hipMemcpy(got, counters.p, 16, hipMemcpyDeviceToHost));
+    if (kernel_ms) {
+        float ms = 0;
+        if (hipEventSynchronize(owned.e1) == hipSuccess && hipEventElapsedTime(&ms, owned.e0, owned.e1) == hipSuccess) *kernel_ms = ms;
+    }
+    *n_mismatch = got[0];
+    *first = got[1];
+    return KBBQ_OK;
+}
+
+int kbbq_pair_keys_alloc(int32_t device, uint64_t n, uint64_t **d_out) {
+    if (!d_out || !n) return fail(KBBQ_EINVAL, "bad argument");
+    *d_out = nullptr;
+    int rc = device_exists(device);
+    if (rc) return rc;
+    KbbqDeviceGuard guard(device);
+    HIP_TRY(guard.err);
+    HIP_TRY(hipMalloc((void **)d_out, n * 8));
+    return KBBQ_OK;
+}
+
+int kbbq_pair_keys_copy(int32_t device, uint64_t *d_dst, const uint64_t *d_src, uint64_t n) {
+    if (!d_dst || !d_src) return fail(KBBQ_EINVAL, "null argument");
+    KbbqDeviceGuard guard(device);
+    HIP_TRY(guard.err);
+    if (n) HIP_TRY(hipMemcpy(d_dst, d_src, n * 8, hipMemcpyDeviceToDevice));
+    return KBBQ_OK;
+}
+
+int kbbq_pair_keys_free(int32_t device, uint64_t *d_keys) {
+    if (!d_keys) return KBBQ_OK;
+    KbbqDeviceGuard guard(device);
+    HIP_TRY(guard.err);
+    HIP_TRY(hipFree(d_keys));
     return KBBQ_OK;
 }
 

@@ -49,6 +49,10 @@
 //   * --estimate-genomelen supplies the genome length from the k-mer spectrum of the reads, counted on the GPU between the scan
 //     and derive_sampling (cli_spectrum.h), where the reference stops for lack of one (kbbq.cc:196-218); --spectrum FILE writes
 //     that spectrum.  Training options both; without them no byte of either output changes;
+//   * --in2 FILE --out2 FILE and --interleaved take paired-end FASTQ (cli_pairs.h): a second file read in the same scan, its
+//     records written to a file of its own, or one input whose records alternate; second-in-pair is then the file's or the
+//     ordinal's word instead of the "/2" name suffix that the reference alone knows (readutils.cc:74-97, still the default), and
+//     the run checks on the GPU that the pairs are in step.  Through the device reader only; without them nothing changes;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -93,6 +97,7 @@ using namespace kbbq;
 // (headers of this unit alone, in this order: each uses what the ones before it define)
 #include "cli_options.h"
 #include "cli_device_io.h"
+#include "cli_pairs.h"
 #include "cli_host_batch.h"
 
 // minion::create_seed_seq().GenerateOne() (minion.hpp:320-345, 377-408; the chrono/random_device branch
@@ -194,6 +199,10 @@ struct ScanState {
             of.clear();
         }
     } error_flags;
+    // --in2, --interleaved: the check that the pairs are in step, made while the device reader scans (cli_pairs.h), and the
+    // resident batch the second file's first chunk became
+    PairCheck pairs;
+    size_t in2_first_batch = 0;
     bool scan_fast = false;      // the block-parallel parser read the whole stream
     bool any_empty = false;      // some read was empty
     // forget what a scan found: the next way of reading the input starts over
@@ -203,6 +212,8 @@ struct ScanState {
         longest = 0;
         scan_fast = any_empty = false;
         error_flags.drop();
+        pairs.release();
+        in2_first_batch = 0;
         resident.drop();
         resident.init(o);
     }
@@ -229,11 +240,20 @@ struct EngineOwner {
 // state is as it was before: the caller starts over with the host parsers.  `stream`: the input is not a regular file but
 // this stream, read once -- the BAM header comes from its head, its text must stay in HBM, and in.refusal is the line the
 // run ends with where a file would start over (empty: the stream held no read).
-static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceInput &in, ScanState &s) {
+// in2: --in2's file, or null.  Its chunks become resident batches behind those of the first file (s.in2_first_batch), its kept text
+// counts with the first file's, and what ends its scan is told in in.refusal like the first file's.  With --in2 or --interleaved
+// every chunk's pair keys are checked on the way (s.pairs); pairs out of step end the scan like any refusal, with s.pairs.failure set.
+static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceInput &in, DeviceInput *in2, ScanState &s) {
     Resident &resident = s.resident;
     std::vector<std::string> rg_ids;
     bool ok = open_device_input(o, o.input, stream, false, in, s.bam_header, rg_ids);
     if (!ok && in.refusal.empty()) in.refusal = " Error opening file " + o.filename;
+    if (ok && in2) {
+        BamHeader no_header;
+        std::vector<std::string> no_ids;
+        ok = open_device_input(o, o.in2_path, nullptr, false, *in2, no_header, no_ids);
+        if (!ok) in.refusal = in2->refusal.empty() ? " Error opening file " + o.in2 : in2->refusal;
+    }
     // the line of a stream whose reads and text do not both stay in HBM
     auto does_not_fit = [&] {
         uint64_t free_b = 0, total_b = 0;
@@ -244,56 +264,68 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceInput &i
     // The text stays in HBM beside the packed reads while both fit in three quarters of the free memory
     // (resident.budget is 60 %): pass 4 then takes the record text from there and the file is read and inflated once.
     // KBBQ_KEEP_TEXT=0: pass 4 reads the file again.  KBBQ_TEXT_BUDGET_MB: that share, set by hand.  A stream cannot be read again: its text is kept or the run ends.
-    bool keeping = ok && (o.keep_text || stream) && in.keep(true) == 0;
+    bool keeping = ok && (o.keep_text || stream) && in.keep(true) == 0 && (!in2 || in2->keep(true) == 0);
     if (ok && stream && !keeping) { ok = false; in.refusal = std::string(" Error: ") + kbbq_last_error(); }
     const uint64_t text_budget = o.text_budget_mb >= 0 ? (uint64_t)o.text_budget_mb << 20 : resident.budget / 4 * 5;
-    while (ok) {
-        kbbq_fastq_chunk info;
-        const int rc = in.next_chunk(info);
-        if (rc == 0) break;
-        if (rc < 0) {
-            if (rc == -1) in.refusal = std::string(" Error: reading the input: ") + kbbq_last_error();
-            ok = false;
-            break;
-        }
-        in.chunk_records.push_back(info.n_records);
-        if (!info.n_records) continue;
-        const uint64_t need = Resident::bytes_of(info.n_bases, info.n_records, o.row().reader_bytes_per_read);
-        if (keeping) {
-            uint64_t kept_chunks = 0, kept_bytes = 0;
-            if (in.kept(&kept_chunks, &kept_bytes) < 0 || resident.bytes + need + kept_bytes > text_budget) {
-                in.keep(false);
-                keeping = false;
-                if (stream) { in.refusal = does_not_fit(); ok = false; break; }
-            }
-        }
-        const auto tb = std::chrono::steady_clock::now();
-        if (info.longest > KBBQ_MAX_READ_LEN) {
-            in.refusal = reads_too_long();
-            ok = false;
-            break;
-        }
-        if (!resident.add(need, [&](kbbq_reads *d) { return in.batch(d); })) { in.refusal = does_not_fit(); ok = false; break; }
-        in.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
-        if (o.fixed_mode()) {
-            // --fixed compares the packed batches (kbbq_fixed_errors_batch), which is the comparison of the text only while the
-            // text holds nothing but ACGTN / acgt (BAM, SAM: on the forward strand): any other character leaves the run to the
-            // host loop
-            int32_t exact = 0;
-            if (in.batch_exact(&exact) < 0 || !exact) {
-                in.refusal = DeviceInput::needs_host_parsers("--fixed on reads with characters other than ACGTN");
+    // the chunks of one input (which: 0 the first or only one, 1 --in2's) into resident batches
+    auto scan_input = [&](DeviceInput &cur, int which) {
+        while (ok) {
+            kbbq_fastq_chunk info;
+            const int rc = cur.next_chunk(info);
+            if (rc == 0) break;
+            if (rc < 0) {
+                if (rc == -1) in.refusal = std::string(" Error: reading the input: ") + kbbq_last_error();
+                else if (which) in.refusal = cur.refusal;
                 ok = false;
                 break;
             }
+            cur.chunk_records.push_back(info.n_records);
+            if (!info.n_records) continue;
+            const uint64_t need = Resident::bytes_of(info.n_bases, info.n_records, o.row().reader_bytes_per_read);
+            if (keeping) {
+                uint64_t kept_chunks = 0, kept_bytes = 0, kept_bytes2 = 0;
+                if (in.kept(&kept_chunks, &kept_bytes) < 0 || (in2 && in2->kept(&kept_chunks, &kept_bytes2) < 0) ||
+                    resident.bytes + need + kept_bytes + kept_bytes2 > text_budget) {
+                    in.keep(false);
+                    if (in2) in2->keep(false);
+                    keeping = false;
+                    if (stream) { in.refusal = does_not_fit(); ok = false; break; }
+                }
+            }
+            const auto tb = std::chrono::steady_clock::now();
+            if (info.longest > KBBQ_MAX_READ_LEN) {
+                in.refusal = reads_too_long();
+                ok = false;
+                break;
+            }
+            if (!resident.add(need, [&](kbbq_reads *d) { return cur.batch(d); })) { in.refusal = does_not_fit(); ok = false; break; }
+            cur.batch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
+            if (s.pairs.on() && !s.pairs.chunk(which, cur, in, o.filename, o.in2, info)) { ok = false; break; }
+            if (o.fixed_mode()) {
+                // --fixed compares the packed batches (kbbq_fixed_errors_batch), which is the comparison of the text only while the
+                // text holds nothing but ACGTN / acgt (BAM, SAM: on the forward strand): any other character leaves the run to the
+                // host loop
+                int32_t exact = 0;
+                if (cur.batch_exact(&exact) < 0 || !exact) {
+                    in.refusal = DeviceInput::needs_host_parsers("--fixed on reads with characters other than ACGTN");
+                    ok = false;
+                    break;
+                }
+            }
+            s.seqlen += info.n_bases;
+            s.n_reads += info.n_records;
+            s.longest = std::max<size_t>(s.longest, info.longest);
+            if (o.format == Format::bam && info.shortest == 0) {      // an empty read ends the reference's coverage and sampling loops: the host path's case
+                in.refusal = DeviceInput::needs_host_parsers("a BAM record without bases");
+                ok = false;
+            }
         }
-        s.seqlen += info.n_bases;
-        s.n_reads += info.n_records;
-        s.longest = std::max<size_t>(s.longest, info.longest);
-        if (o.format == Format::bam && info.shortest == 0) {      // an empty read ends the reference's coverage and sampling loops: the host path's case
-            in.refusal = DeviceInput::needs_host_parsers("a BAM record without bases");
-            ok = false;
-        }
-    }
+    };
+    scan_input(in, 0);
+    s.in2_first_batch = resident.dev.size();
+    if (in2) scan_input(*in2, 1);
+    if (ok && s.pairs.on() && !s.pairs.finish(o.filename, o.in2)) ok = false;
+    s.pairs.release();      // (the keys go before the engine and its filters come)
     if (ok && o.set_oq && in.oq_unwritable) {      // bam_aux_update_str would fail on some record: the host path reports it
         in.refusal = DeviceInput::needs_host_parsers("--set-oq on a record whose OQ tag cannot be updated");
         ok = false;
@@ -307,15 +339,22 @@ static bool device_scan(const CliOptions &o, StreamInput *stream, DeviceInput &i
     }
     if (ok && s.n_reads && o.format == Format::fastq) s.groups.index_of(std::string());  // FASTQ without read-group fields: the one read group "" (readutils.cc:98-103)
     uint64_t kept_chunks = 0;
-    if (ok && s.n_reads && in.rewind() == 0 && in.kept(&kept_chunks, &in.kept_bytes) == 0) in.text_kept = kept_chunks == resident.dev.size();
+    if (ok && s.n_reads && in.rewind() == 0 && in.kept(&kept_chunks, &in.kept_bytes) == 0) in.text_kept = kept_chunks == s.in2_first_batch;
+    if (ok && s.n_reads && in2 && in2->rewind() == 0 && in2->kept(&kept_chunks, &in2->kept_bytes) == 0)
+        in2->text_kept = kept_chunks == resident.dev.size() - s.in2_first_batch;
     if (ok && s.n_reads && stream && !in.text_kept) { in.refusal = does_not_fit(); ok = false; }      // (the reader gave its chunks up)
     if (!ok || !s.n_reads) {
         s.reset(o);
         in.close();
+        if (in2) in2->close();
         return false;
     }
     in.active = true;
     if (!in.text_kept) { in.keep(false); in.kept_bytes = 0; }
+    if (in2) {
+        in2->active = true;
+        if (!in2->text_kept) { in2->keep(false); in2->kept_bytes = 0; }
+    }
     resident.keep_recs = false;      // the records come from the device's own copy of the input in pass 4
     return true;
 }
@@ -842,6 +881,8 @@ static int run_table(CliOptions &opt, StreamInput *stream) {
         std::cerr << put_now << " Recalibrating file" << std::endl;
         rc = apply_table_one_pass(opt, stream, dev_in, table, engine, scan, sink, one_pass);
         if (rc > 0) return rc;
+        if (rc < 0 && opt.interleaved)      // (as a training run: no host parsers behind --interleaved)
+            return give_up(" Error: --interleaved: the GPU reader hands this input back to the host parsers, and they know second-in-pair from the names alone.");
         if (rc < 0) std::cerr << put_now << " The GPU reader hands the file back: starting over with the host parsers." << std::endl;
     }
     if (rc < 0) {
@@ -890,6 +931,9 @@ int main(int argc, char *argv[]) {
     if (opt.correct && fmt != Format::fastq)
         return give_up(std::string(" Error: --correct with ") + (fmt == Format::bam ? "BAM" : "SAM") +
                        " input: changing SEQ there would falsify CIGAR, MD and NM, and this tool does not re-align.  Corrected reads are written for FASTQ.");
+    if (const char *option = opt.pairs_option())
+        if (const char *why = opt.pairs_format_refusal(fmt, opt.paired_files() ? sniff(opt.in2_path) : Format::fastq))
+            return give_up(std::string(" Error: ") + option + " with" + why + ".");
     opt.fixed_on_device = opt.fixed_may_read_on_device();
     if (opt.stream || opt.fixed_stream) {
         if (const char *why = opt.needs_a_file())
@@ -908,19 +952,36 @@ int main(int argc, char *argv[]) {
         if (!f) return give_up(" Error: --spectrum: cannot open " + opt.spectrum + " for writing: " + strerror(errno));
         fclose(f);
     }
+    if (opt.paired_files()) {      // --out2: likewise, but a file this made is gone again until pass 4 writes it: a run that fails leaves none
+        const bool was_there = access(opt.out2.c_str(), F_OK) == 0;
+        FILE *f = fopen(opt.out2.c_str(), "ab");
+        if (!f) return give_up(" Error: --out2: cannot open " + opt.out2 + " for writing: " + strerror(errno));
+        fclose(f);
+        if (!was_there) unlink(opt.out2.c_str());
+    }
     if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
     if (opt.table_run()) return run_table(opt, stream.get());
 
     // The one scan before the engine exists: on the device when that may be tried and takes the file, with the host parsers
     // otherwise.  An early return unwinds these in the reverse order: resident batches, engine, the device reader and its thread.
     PhaseClock clock(opt.timing);
-    DeviceInput dev_in(opt);
+    DeviceInput dev_in(opt), dev_in2(opt);
     EngineOwner engine;
     ScanState scan;
     Batch batch;
     FixedOnDevice fixed_report;
     scan.resident.init(opt);
-    const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, stream.get(), dev_in, scan);
+    // --in2, --interleaved: the mate flags by the file's or the ordinal's word, and the pairs checked while the reader scans
+    scan.pairs.two_files = opt.paired_files();
+    scan.pairs.interleaved = opt.interleaved;
+    if (opt.paired_files()) { dev_in.mates = KBBQ_MATES_ALL_FIRST; dev_in2.mates = KBBQ_MATES_ALL_SECOND; }
+    if (opt.interleaved) dev_in.mates = KBBQ_MATES_INTERLEAVED;
+    const bool read_on_device = opt.may_read_on_device(scan.resident.on) && device_scan(opt, stream.get(), dev_in, opt.paired_files() ? &dev_in2 : nullptr, scan);
+    if (!scan.pairs.failure.empty()) return give_up(scan.pairs.failure);
+    if (!read_on_device && opt.pairs_option())      // (no host parsers behind the pair options: they know second-in-pair from the names alone)
+        return give_up(std::string(" Error: ") + opt.pairs_option() + ": the GPU reader hands " + (opt.paired_files() ? "one of these inputs" : "this input") +
+                       " back to the host parsers (or the reads do not stay in GPU memory), and they know second-in-pair from the names alone" +
+                       (dev_in.refusal.empty() ? "." : ":" + dev_in.refusal));
     if (!read_on_device && opt.correct)      // (no host parsers behind --correct, as behind a stream)
         return give_up(" Error: --correct: the GPU reader hands this input back to the host parsers (or the reads do not stay in GPU memory), and they write no corrected reads.");
     if (!read_on_device && stream) {
@@ -976,6 +1037,8 @@ int main(int argc, char *argv[]) {
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
         const int on_device = read_on_device ? tally_fixed_on_device(e, opt, scan, fixed_report) : -1;
         if (on_device > 0) return 1;
+        if (on_device < 0 && read_on_device && opt.interleaved)      // (as in the scan: no host parsers behind --interleaved)
+            return give_up(" Error: --interleaved: --fixed hands this run back to the host parsers, and they know second-in-pair from the names alone.");
         if (on_device < 0 && read_on_device) {
             // Handed back: the run starts over as it would have without the device readers -- nothing resident, the scan by the
             // host parsers, a new engine for what that scan found (the first one has tallied nothing).
@@ -1006,7 +1069,30 @@ int main(int argc, char *argv[]) {
     Sink sink;
     int rc = sink.open(opt, scan);
     if (rc) return rc;
-    if (write_output(e, scan, opt, sink, dev_in, batch) || !sink.close()) return 1;
+    if (!opt.paired_files()) {
+        if (write_output(e, scan, opt, sink, dev_in, batch) || !sink.close()) return 1;
+    } else {
+        // the first file's records to stdout as ever, then the second file's -- the resident batches behind the first file's --
+        // to --out2 through a writer of its own; a run that fails on the way leaves no --out2 file
+        if (write_from_device_reader(e, scan, opt, sink, dev_in, 0, false)) return 1;
+        FILE *f2 = fopen(opt.out2.c_str(), "wb");
+        if (!f2) return give_up(" Error: --out2: cannot open " + opt.out2 + " for writing: " + strerror(errno));
+        Sink sink2;
+        const bool ok2 = sink2.open_file(f2, opt) == 0 && write_from_device_reader(e, scan, opt, sink2, dev_in2, scan.in2_first_batch, true) == 0;
+        const bool closed2 = sink2.close();      // (the writer goes before its file)
+        if ((fclose(f2) != 0) | !ok2 | !closed2) {
+            unlink(opt.out2.c_str());
+            return ok2 ? give_up(" Error: --out2: writing " + opt.out2 + " failed.") : 1;
+        }
+        if (!sink.close()) { unlink(opt.out2.c_str()); return 1; }
+        if (clock.on)
+            std::cerr << "[timing] pairs: " << dev_in2.format() << " reader of --in2 on the GPU (" << dev_in2.container << "; "
+                      << (dev_in2.text_kept ? "the text kept in HBM" : "both scans") << "); key kernel " << dev_in.pair_keys_ms() << " + " << dev_in2.pair_keys_ms()
+                      << " ms, " << scan.pairs.checks << " checks " << scan.pairs.ms_check << " ms" << std::endl;
+        dev_in2.close();      // (its I/O thread and streams must not be alive at the exit of end_run, like the first reader's)
+    }
+    if (opt.interleaved && clock.on)
+        std::cerr << "[timing] pairs: interleaved; key kernel " << dev_in.pair_keys_ms() << " ms, " << scan.pairs.checks << " checks " << scan.pairs.ms_check << " ms" << std::endl;
     if (!opt.report.empty())
         if (const int bad = write_quality_report(e, opt, scan.groups.names(), nullptr, p.seed, scan.seqlen)) return bad;
     return end_run(opt, clock, dev_in, sink, fixed_report, OnePass(), scan, engine);
