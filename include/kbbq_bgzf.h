@@ -161,6 +161,22 @@ int kbbq_fastq_reader_write(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d
  * long as d_qual. */
 int kbbq_fastq_reader_write_corrected(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint64_t *d_fix_mask,
                                       const uint64_t *d_fix_bases, void *after_stream);
+/* Records whose output is shorter than their input, or absent (kbbq_trim_batch, include/kbbq_engine.h).  d_keep (device): per
+ * record of the current chunk the kept length, 0 for a record that is not written.  Record r is written as "@name\n" + the
+ * first keep[r] sequence characters + "\n+comment\n" + the first keep[r] qualities + "\n"; a keep above the record's length
+ * counts as the length.  d_fix_mask / d_fix_bases: both set (the corrected form, as kbbq_fastq_reader_write_corrected) or both
+ * NULL.  All three forms of a chunk: live, kept whole, kept in the short form with its batch attached.  The sizes of what is
+ * written are scanned into offsets of their own on the reader's stream, behind after_stream, and the call waits for their
+ * total: *out_bytes = the bytes of text submitted.  A chunk of which nothing is kept submits nothing (*out_bytes = 0: there is
+ * nothing to collect).  The call returns when the text kernel has run. */
+int kbbq_fastq_reader_write_trimmed(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint32_t *d_keep, const uint64_t *d_fix_mask,
+                                    const uint64_t *d_fix_bases, void *after_stream, uint64_t *out_bytes);
+/* Milliseconds the device spent on the size pass and scan of kbbq_fastq_reader_write_trimmed since creation (its text kernels
+ * are in the writer's format time: kbbq_bgzf_kernel_ms). */
+int kbbq_fastq_reader_trim_ms(kbbq_fastq_reader *r, double *sizes_ms);
+/* The records kbbq_fastq_reader_write_trimmed has written since creation, and those of them that were written shorter than
+ * they stand in the input (what a caller that applied kbbq_trim_mates cannot learn from kbbq_trim_counts). */
+int kbbq_fastq_reader_trim_written(kbbq_fastq_reader *r, uint64_t *records, uint64_t *shortened);
 /* Milliseconds the device spent inflating / indexing + packing since creation (a gzip stream's stages are in inflate_ms). */
 int kbbq_fastq_reader_kernel_ms(kbbq_fastq_reader *r, double *inflate_ms, double *index_ms);
 /* A gzip stream's stages since creation, in milliseconds of wall time (each stage waits for its kernels): block finding,

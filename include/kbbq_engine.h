@@ -321,6 +321,45 @@ int kbbq_correct_batch(kbbq_engine *e, const kbbq_reads *reads, const uint64_t *
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_correct_counts(kbbq_engine *e, kbbq_fix_counts *out, int32_t reset);
 
+/* ---- trimming and filtering reads by the qualities pass 4 writes ------------------
+ * The rule is this project's own, exact and all integers.  q[0..n) are the qualities written for one
+ * read (after the delta-Q apply and after a quality map: the bytes of the quality line minus 33).
+ *   1. cut      kept = n.  With tail_q = Q > 0 (the BWA/cutadapt rule): s = 0, best = 0, then i = n-1 down to 0:
+ *               s += Q - q[i]; if s < 0 stop; if s > best { best = s; kept = i }.  The stop matters (this is not the global
+ *               maximum of the suffix sums) and the comparison is strict (of equal sums the largest index wins).
+ *   2. errors   ee = sum over i < kept of EE[q[i]], EE[v] = round(10^(-v/10) * 2^32) as uint64 (kbbq_trim_ee_table: built once
+ *               on the host in long double); the sum is a uint64 (8 388 607 bases stay below 2^56).  A bound of E expected
+ *               errors is floor(E * 2^32) (kbbq_trim_ee_bound).
+ *   3. verdict  exactly one, in this order: kept < max(1, min_length): too short; else has_ee and ee > ee_bound: over the
+ *               expected errors; else kept with length `kept` -- "shortened" when kept < n.
+ *   4. mates    in a paired run a kept read whose mate's verdict is a drop is dropped with its mate (kbbq_trim_mates).
+ * The result depends on the read's written qualities, on the parameters and -- step 4 -- on its mate alone: not on how the
+ * batches were cut or on uniform or ragged batches. */
+typedef struct kbbq_trim_params {
+    int32_t tail_q;         /* 0: no cut; else 1..93 */
+    int32_t has_ee;         /* 0: no expected-error bound */
+    uint64_t min_length;    /* 0 counts as 1: a read cut to nothing is always dropped */
+    uint64_t ee_bound;      /* floor(E * 2^32) */
+} kbbq_trim_params;
+/* Sums since the last reset.  reads_in = reads_kept + too_short + over_ee + with_mate.  `shortened` counts the reads whose own
+ * verdict was "kept" with kept < n; kbbq_trim_mates does not know a read's length and leaves it alone. */
+typedef struct kbbq_trim_counts { uint64_t reads_in, bases_in, shortened, too_short, over_ee, reads_kept, bases_kept, with_mate; } kbbq_trim_counts;
+/* keep[r] (device, n_reads words) = the kept length of read r of the device batch, or 0 for a dropped read; device_qual: the
+ * batch's written qualities (the array kbbq_recalibrate_batch filled; the batch's own qual is not read).  Uniform or ragged
+ * batches, reads of any length the engine takes.  Queued on the engine's stream.  KBBQ_EINVAL for a host batch or
+ * parameters out of range. */
+int kbbq_trim_batch(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p, uint32_t *keep);
+/* Step 4 on device arrays of kept lengths: where exactly one of a[i], b[i] (i < n) is 0 both become 0; with adjacent != 0 the
+ * pair is a[2i], a[2i+1] (i < n/2), b is not read and an odd n is KBBQ_EINVAL.  Each read dropped here is counted as
+ * with_mate and taken out of reads_kept and bases_kept.  Queued on the engine's stream. */
+int kbbq_trim_mates(kbbq_engine *e, uint32_t *keep_a, uint32_t *keep_b, uint64_t n, int32_t adjacent);
+/* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
+int kbbq_trim_counts_get(kbbq_engine *e, kbbq_trim_counts *out, int32_t reset);
+/* The table EE[0..256) the kernel uses, and the bound of E expected errors (E > 0, finite and below 2^32, else KBBQ_EINVAL).
+ * Host code; no GPU is touched. */
+int kbbq_trim_ee_table(uint64_t out[256]);
+int kbbq_trim_ee_bound(double max_ee, uint64_t *bound);
+
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]
  *   cycle [n_rg][256][2][max_read_len][2]   (third index: 0 first-in-pair, 1 second)

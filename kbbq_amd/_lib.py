@@ -87,6 +87,14 @@ class FixCounts(ctypes.Structure):
     _fields_ = [("flagged", c_u64), ("fixed", c_u64), ("ambiguous", c_u64), ("unsupported", c_u64)]
 
 
+class TrimParams(ctypes.Structure):
+    _fields_ = [("tail_q", ctypes.c_int32), ("has_ee", ctypes.c_int32), ("min_length", c_u64), ("ee_bound", c_u64)]
+
+
+class TrimCounts(ctypes.Structure):
+    _fields_ = [(n, c_u64) for n in ("reads_in", "bases_in", "shortened", "too_short", "over_ee", "reads_kept", "bases_kept", "with_mate")]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -138,6 +146,11 @@ SYMBOLS = {
     "kbbq_fixed_errors_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_vp]),
     "kbbq_correct_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, c_vp, c_vp]),
     "kbbq_correct_counts": (ctypes.c_int, [c_vp, ctypes.POINTER(FixCounts), ctypes.c_int32]),
+    "kbbq_trim_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp]),
+    "kbbq_trim_mates": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u64, ctypes.c_int32]),
+    "kbbq_trim_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(TrimCounts), ctypes.c_int32]),
+    "kbbq_trim_ee_table": (ctypes.c_int, [c_u64p]),
+    "kbbq_trim_ee_bound": (ctypes.c_int, [ctypes.c_double, c_u64p]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),
@@ -206,6 +219,9 @@ SYMBOLS = {
     "kbbq_fastq_reader_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(c_vp)]),
     "kbbq_fastq_reader_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "kbbq_fastq_reader_write_corrected": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "kbbq_fastq_reader_write_trimmed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u64p]),
+    "kbbq_fastq_reader_trim_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
+    "kbbq_fastq_reader_trim_written": (ctypes.c_int, [c_vp, c_u64p, c_u64p]),
     "kbbq_reads_upload_text": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.c_void_p, ctypes.POINTER(Reads)]),
     "kbbq_fastq_reader_inflate": (ctypes.c_int, [c_vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

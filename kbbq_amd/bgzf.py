@@ -147,6 +147,27 @@ class FastqReader(_RecordReader):
     def write(self, writer, d_qual, after_stream=None):
         self._call("write", writer.h, d_qual, after_stream)
 
+    def write_corrected(self, writer, d_qual, d_fix_mask, d_fix_bases, after_stream=None):
+        self._call("write_corrected", writer.h, d_qual, d_fix_mask, d_fix_bases, after_stream)
+
+    def write_trimmed(self, writer, d_qual, d_keep, d_fix_mask=None, d_fix_bases=None, after_stream=None):
+        """The current chunk's records cut to d_keep[r] bases each (device uint32 per record; 0: not written), with the fixes of
+        the two arrays when they are given.  Returns the bytes of text submitted: 0 means nothing was, so nothing is to collect."""
+        n = ctypes.c_uint64()
+        self._call("write_trimmed", writer.h, d_qual, d_keep, d_fix_mask, d_fix_bases, after_stream, ctypes.byref(n))
+        return n.value
+
+    def trim_written(self):
+        """(records written, those of them written shorter than they were) by write_trimmed since the reader was made."""
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        self._call("trim_written", ctypes.byref(n), ctypes.byref(m))
+        return n.value, m.value
+
+    def trim_ms(self):
+        ms = ctypes.c_double()
+        self._call("trim_ms", ctypes.byref(ms))
+        return ms.value
+
     def attach(self, batch):
         self._call("attach", ctypes.byref(batch))
 

@@ -32,6 +32,12 @@ struct ReaderCalls {
     int (*pair_keys)(void *h, uint64_t *d_keys);
     int (*pair_keys_ms)(void *h, double *keys_ms);
     int (*record_name)(void *h, uint64_t i, char *out, uint32_t capacity, uint32_t *len);
+    // --trim-tail, --min-length, --max-ee (cli_trim.h): records cut to d_keep bases each or left out, with or without fixes, and
+    // what was written that way (FASTQ's: clipping SEQ in a BAM or SAM record would falsify CIGAR, MD and NM, and mates are in FLAG)
+    int (*write_trimmed)(void *h, kbbq_bgzf *z, const uint8_t *d_qual, const uint32_t *d_keep, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases,
+                         void *after_stream, uint64_t *out_bytes);
+    int (*trim_written)(void *h, uint64_t *records, uint64_t *shortened);
+    int (*trim_ms)(void *h, double *sizes_ms);
 };
 // f, whose first argument is a reader of type R, as a call on the opaque handle
 template <auto f> struct Thunk;
@@ -43,7 +49,8 @@ static const ReaderCalls kFastqReaderCalls = {
     [](void *h, kbbq_bgzf *z, const uint8_t *q, int32_t, void *after) { return kbbq_fastq_reader_write((kbbq_fastq_reader *)h, z, q, after); },
     Thunk<kbbq_fastq_reader_attach>::call, nullptr, nullptr, Thunk<kbbq_fastq_reader_take_text>::call, 0,
     Thunk<kbbq_fastq_reader_write_corrected>::call,
-    Thunk<kbbq_fastq_reader_set_mates>::call, Thunk<kbbq_fastq_reader_pair_keys>::call, Thunk<kbbq_fastq_reader_pair_keys_ms>::call, Thunk<kbbq_fastq_reader_record_name>::call};
+    Thunk<kbbq_fastq_reader_set_mates>::call, Thunk<kbbq_fastq_reader_pair_keys>::call, Thunk<kbbq_fastq_reader_pair_keys_ms>::call, Thunk<kbbq_fastq_reader_record_name>::call,
+    Thunk<kbbq_fastq_reader_write_trimmed>::call, Thunk<kbbq_fastq_reader_trim_written>::call, Thunk<kbbq_fastq_reader_trim_ms>::call};
 // (sam_read1, the BAM constructor of CReadData, BamFile::recalibrate / write are kernels: htsiter.cc:5-45, readutils.cc:13-61)
 static const ReaderCalls kBamReaderCalls = {
     [](bool use_oq, int32_t n_ref, uint64_t header_bytes, const char *const *ids, uint32_t n_ids, void **out) {
@@ -124,6 +131,15 @@ public:
         if (!make_room()) return false;
         if (call(z_) < 0) return fail_here();
         ++in_flight_;
+        return true;
+    }
+    // The same for a call that may find nothing to submit: it answers 0 then, above 0 when a submission was made
+    template <class F> bool submit_if_any(F call) {
+        if (!flush_host()) return false;
+        if (!make_room()) return false;
+        const int rc = call(z_);
+        if (rc < 0) return fail_here();
+        if (rc > 0) ++in_flight_;
         return true;
     }
     // One batch of FASTQ records (RecordStore layout) whose quality lines come from device memory: the device assembles the text.
@@ -565,6 +581,19 @@ public:
     bool write_chunk_corrected(DeviceBgzfWriter &out, const uint8_t *d_qual, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases, void *after_stream) {
         return out.submit([&](kbbq_bgzf *z) { return r_->write_corrected(h_, z, d_qual, d_fix_mask, d_fix_bases, after_stream); });
     }
+    // ... and cut to d_keep[r] bases each, or left out (--trim-tail, --min-length, --max-ee: FASTQ); the fix arrays both or neither.
+    // A chunk of which nothing is kept submits nothing
+    bool write_chunk_trimmed(DeviceBgzfWriter &out, const uint8_t *d_qual, const uint32_t *d_keep, const uint64_t *d_fix_mask, const uint64_t *d_fix_bases,
+                             void *after_stream) {
+        return out.submit_if_any([&](kbbq_bgzf *z) {
+            uint64_t bytes = 0;
+            const int rc = r_->write_trimmed(h_, z, d_qual, d_keep, d_fix_mask, d_fix_bases, after_stream, &bytes);
+            return rc < 0 ? rc : bytes ? 1 : 0;
+        });
+    }
+    bool can_trim() const { return r_ && r_->write_trimmed; }
+    void trim_written(uint64_t &records, uint64_t &shortened) { records = shortened = 0; if (h_ && r_->trim_written) r_->trim_written(h_, &records, &shortened); }
+    double trim_ms() { double ms = 0; if (h_ && r_->trim_ms) r_->trim_ms(h_, &ms); return ms; }
 
 private:
     void stop_io() { pieces_.stop(); }

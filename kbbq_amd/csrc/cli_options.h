@@ -29,6 +29,8 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"correct", no_argument, 0, 1007},
     // paired FASTQ (cli_pairs.h): the second-in-pair file and where its records go, or one input whose records alternate
     {"in2", required_argument, 0, 1008}, {"out2", required_argument, 0, 1009}, {"interleaved", no_argument, 0, 1010},
+    // the output's reads cut and dropped by the qualities that are written (cli_trim.h); any of the three turns it on
+    {"trim-tail", required_argument, 0, 1011}, {"min-length", required_argument, 0, 1012}, {"max-ee", required_argument, 0, 1013},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -99,6 +101,12 @@ struct CliOptions {
     // reader alone: whatever leads elsewhere is refused (pairs_refusal)
     std::string in2, out2, in2_path;
     bool in2_stream = false, interleaved = false;
+    // --trim-tail Q, --min-length L, --max-ee E: pass 4 cuts the 3' end of every read by the BWA/cutadapt rule on the qualities it
+    // writes, drops a read whose kept length is below L (a read cut to nothing always) or whose kept bases carry more than E
+    // expected errors, and -- a paired run -- the mate of a dropped read (include/kbbq_engine.h: kbbq_trim_batch).  FASTQ through
+    // the device reader with the reads resident: whatever leads elsewhere is refused (trim_refusal)
+    kbbq_trim_params trim = {0, 0, 0, 0};
+    const char *trim_option = nullptr;      // the first of the three that was given: trimming is on
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -146,6 +154,17 @@ struct CliOptions {
             q = *end == ',' ? end + 1 : end;
         }
         if (entries > 1) return "KBBQ_DEVICES with more than one device: the error flags of the other devices' shards do not reach the device that writes";
+        return nullptr;
+    }
+    bool trim_on() const { return trim_option != nullptr; }
+    // What was asked for beside --trim-tail, --min-length or --max-ee that they cannot go with, known before the input is opened; null: nothing
+    const char *trim_refusal() const {
+        if (fixed_mode()) return "--fixed: reads are cut and dropped by the GPU reader's writer in a training run, and a fixed run may be handed back to the host parsers";
+        if (table_run()) return "--load-table: the one-pass table run forgets a chunk before its mate's chunk arrives";
+        if (!device_reader) return "KBBQ_DEVICE_READER=0: reads are cut and dropped by the GPU reader's writer, not by the host parsers";
+        if (serial_parse) return "KBBQ_SERIAL_PARSE=1: reads are cut and dropped by the GPU reader's writer, not by the host parsers";
+        if (host_deflate) return "KBBQ_HOST_DEFLATE=1: reads are cut and dropped by the GPU reader's writer, not by the host parsers";
+        if (!resident) return "KBBQ_RESIDENT=0: the verdicts are taken on the resident batches";
         return nullptr;
     }
     bool paired_files() const { return !in2.empty(); }
@@ -263,6 +282,27 @@ struct CliOptions {
                 case 1008: in2 = std::string(optarg); break;
                 case 1009: out2 = std::string(optarg); break;
                 case 1010: interleaved = true; break;
+                case 1011: {
+                    uint64_t q = 0;
+                    if (!trim_parse_integer(optarg, 1, KBBQ_MAXQ, &q))
+                        return !give_up(std::string(" Error: --trim-tail takes an integer in 1..93, not \"") + optarg + "\".");
+                    trim.tail_q = (int32_t)q;
+                    if (!trim_option) trim_option = "--trim-tail";
+                    break;
+                }
+                case 1012:
+                    if (!trim_parse_integer(optarg, 1, KBBQ_MAX_READ_LEN, &trim.min_length))
+                        return !give_up(std::string(" Error: --min-length takes an integer in 1..") + std::to_string(KBBQ_MAX_READ_LEN) + ", not \"" + optarg + "\".");
+                    if (!trim_option) trim_option = "--min-length";
+                    break;
+                case 1013: {
+                    double value = 0;
+                    if (!trim_parse_max_ee(optarg, &value, &trim.ee_bound))
+                        return !give_up(std::string(" Error: --max-ee takes a decimal number above 0 and below 4294967296, not \"") + optarg + "\".");
+                    trim.has_ee = 1;
+                    if (!trim_option) trim_option = "--max-ee";
+                    break;
+                }
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -278,6 +318,10 @@ struct CliOptions {
             return !give_up(std::string(" Error: --load-table with ") + trains_with + ": a table run does not train, it applies the model of the table.");
         if (correct)
             if (const char *why = correct_refusal()) return !give_up(std::string(" Error: --correct with ") + why + ".");
+        if (trim_on()) {
+            if (!trim.min_length) trim.min_length = 1;
+            if (const char *why = trim_refusal()) return !give_up(std::string(" Error: ") + trim_option + " with " + why + ".");
+        }
         if (fixed_mode() && spectrum_option)
             return !give_up(std::string(" Error: ") + spectrum_option + " with --fixed: the genome length sizes the filters, which are not used there.");
         if (estimate_genomelen && genomelen)

@@ -163,13 +163,19 @@ struct FixSlots {
 // first_batch: the resident batch of the reader's first chunk with records -- 0, or, for the second file of --in2, the number of
 // batches the first file made; totals: the "Corrected bases" and "[digest]" lines, which count every batch written so far (the
 // last reader's call prints them: one line each, over both files).
-static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in, size_t first_batch = 0, bool totals = true) {
+// trim (--trim-tail, --min-length, --max-ee: cli_trim.h; null: none): the records are written cut to their kept lengths or left
+// out -- the verdicts taken here, batch by batch behind pass 4, unless a paired run's pre-pass has taken them all; which: the
+// file whose array of kept lengths this reader's records stand in (1: --in2's).
+static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in, size_t first_batch = 0, bool totals = true,
+                                    TrimRun *trim = nullptr, int which = 0) {
     DeviceBgzfWriter &out = *sink.dev;
     QualSlots slots{e};
     FixSlots fixes{e};
     const bool correct = o.correct;
     if (correct && s.error_flags.of.size() != s.resident.dev.size()) return give_up(" Error: --correct: pass 3 left no error flags for the resident batches.");
     size_t bi = first_batch;
+    uint64_t ordinal = 0;      // (trim: the first record of the next batch, in its file)
+    if (trim && !in.can_trim()) return give_up(std::string(" Error: ") + o.trim_option + ": this input's reader on the GPU writes no trimmed records.");
     if (!in.text_kept) {
         in.start_pass();
         if (in.rewind() < 0) return fail_engine("recalibrating");
@@ -194,14 +200,28 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
         // KBBQ_QUAL_DIGEST=1: the sum of every recalibrated quality, taken on the device from the array the writer reads
         // (the number bench.py prints as recal_qual_sum for the same reads)
         if (o.qual_digest && kbbq_digest_add(e, q, d.n_bases) < 0) return fail_engine("recalibrating");
-        if (correct) {
+        if (trim) {
+            // (--correct: the fixes first, then the cut; the writer call returns when its text kernel has run, so the arrays of
+            // slot t are free again whether or not this chunk made a submission)
+            const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
+            if (correct)
+                if (const int rc = fixes.correct(t, d, errors, &fix_mask, &fix_bases)) return rc;
+            if (!trim->have_verdicts)
+                if (const int rc = trim->batch(which, ordinal, d, q)) return rc;
+            if (ordinal + d.n_reads > trim->n[which]) return input_changed();
+            if (!in.write_chunk_trimmed(out, q, trim->keep[which] + ordinal, fix_mask, fix_bases, kbbq_engine_stream(e))) return 1;
+            ordinal += d.n_reads;
+        } else if (correct) {
             const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
             if (const int rc = fixes.correct(t, d, errors, &fix_mask, &fix_bases)) return rc;
             if (!in.write_chunk_corrected(out, q, fix_mask, fix_bases, kbbq_engine_stream(e))) return 1;
         } else if (!in.write_chunk(out, q, o.set_oq, kbbq_engine_stream(e))) return 1;
     }
     if (!out.drain()) return 1;
+    if (trim) trim->wrote(in);
     if (!totals) return 0;
+    if (trim)
+        if (const int rc = trim->line()) return rc;
     if (correct) {
         kbbq_fix_counts c;
         if (kbbq_correct_counts(e, &c, 0) < 0) return fail_engine("correcting");

@@ -48,6 +48,8 @@ using namespace kbbq;
 #include "engine_pass4.h"
 #include "engine_misc.h"
 #include "engine_correct.h"
+#include "trim.h"      // (its two kernels are no templates: defined here, behind every kernel above)
+#include "engine_trim.h"
 
 extern "C" {
 
@@ -160,6 +162,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->d_tickets);
     hipFree(e->d_totals);
     hipFree(e->d_fix_counts);
+    hipFree(e->trim.d_counts);
     hipFree(e->p4.d_dq_qslot);
     hipFree(e->d_qpresent);
     hipFree(e->p3.d_rg_present[0]);
@@ -187,6 +190,7 @@ int kbbq_engine_reset(kbbq_engine *e) {
     if ((rc = e->bk.reset(e->stream))) return rc;
     e->p4.reset();
     if ((rc = e->rep.reset(e->stream))) return rc;
+    if ((rc = e->trim.reset(e->stream))) return rc;
     e->profile.reset();
     return sync_engine(e);
 }

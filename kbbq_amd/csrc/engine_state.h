@@ -246,6 +246,18 @@ struct ReportState {
     }
 };
 
+// trimming and filtering (include/kbbq_engine.h: kbbq_trim_batch; engine_trim.h): the kbbq_trim_counts of k_trim_reads and
+// k_trim_mates and, behind them in the same allocation, the expected-error table.  Allocated by the first trimming call, as
+// d_fix_counts is: an engine that never trims makes exactly the allocations it made before there was such a call
+struct TrimState {
+    unsigned long long *d_counts = nullptr;
+    const unsigned long long *d_ee = nullptr;
+    int reset(hipStream_t stream) {
+        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 8 * 8, stream));      // (TRIM_COUNTS words: trim.h)
+        return KBBQ_OK;
+    }
+};
+
 // Host batches: a ring of device staging slots owned by the engine and a copy stream.  A host batch is copied
 // into the next slot with hipMemcpyAsync on the copy stream (DMA straight from the caller's memory when that is
 // page-locked), the pass's kernels wait for the copy by event, and the entry point returns as soon as the COPY
@@ -334,6 +346,7 @@ struct kbbq_engine {
     Pass3State p3;
     Pass4State p4;
     ReportState rep;
+    TrimState trim;
     Staging stage;
     Buckets bk;
     Profile profile;

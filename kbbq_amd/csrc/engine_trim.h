@@ -1,0 +1,79 @@
+// engine_trim.h -- trimming and filtering reads by the qualities pass 4 wrote (include/kbbq_engine.h: kbbq_trim_batch,
+// kbbq_trim_mates, kbbq_trim_counts_get): the launches of trim.h's two kernels and the counters.  Part of engine.hip; behind
+// engine_correct.h, so that every kernel before it keeps its place in the code object.
+#pragma once
+
+namespace {
+
+// the first trimming call of this engine: the counters and the expected-error table (engine_state.h: TrimState)
+int trim_state(kbbq_engine *e) {
+    if (e->trim.d_counts) return KBBQ_OK;
+    uint64_t table[256];
+    int rc = kbbq_trim_ee_table(table);
+    if (rc) return rc;
+    unsigned long long *d = nullptr;
+    HIP_TRY(hipMalloc(&d, (TRIM_COUNTS + 256) * 8));
+    hipError_t he = hipMemsetAsync(d, 0, TRIM_COUNTS * 8, e->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(d + TRIM_COUNTS, table, sizeof table, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);      // (the table is on this call's stack)
+    if (he != hipSuccess) { hipFree(d); HIP_TRY(he); }
+    e->trim.d_counts = d;
+    e->trim.d_ee = d + TRIM_COUNTS;
+    return KBBQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbbq_trim_batch(kbbq_engine *e, const kbbq_reads *reads, const uint8_t *device_qual, const kbbq_trim_params *p, uint32_t *keep) {
+    ENGINE_DEVICE(e);
+    if (!reads || !device_qual || !p || !keep) return fail(KBBQ_EINVAL, "null argument");
+    if (!reads->on_device) return fail(KBBQ_EINVAL, "not a device batch");
+    if (p->tail_q < 0 || p->tail_q > KBBQ_MAXQ) return fail(KBBQ_EINVAL, "tail_q must be in 1..%d (0: no cut)", KBBQ_MAXQ);
+    if (p->min_length > 0xFFFFFFFFull) return fail(KBBQ_EINVAL, "min_length must be below 2^32");
+    ReadsDev R; int max_len;
+    int rc = device_view(e, reads, &R, &max_len);
+    if (rc) return rc;
+    if ((rc = trim_state(e))) return rc;
+    TrimDev P;
+    P.tail_q = p->tail_q;
+    P.has_ee = p->has_ee != 0;
+    P.min_len = (uint32_t)std::max<uint64_t>(1, p->min_length);
+    P.ee_bound = p->ee_bound;
+    Timed t(e, "k_trim_reads");
+    hipLaunchKernelGGL(k_trim_reads, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, device_qual, P, e->trim.d_ee, keep, e->trim.d_counts);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int kbbq_trim_mates(kbbq_engine *e, uint32_t *keep_a, uint32_t *keep_b, uint64_t n, int32_t adjacent) {
+    ENGINE_DEVICE(e);
+    if (!keep_a || (!adjacent && !keep_b)) return fail(KBBQ_EINVAL, "null argument");
+    if (adjacent && (n & 1)) return fail(KBBQ_EINVAL, "an odd number of reads cannot be adjacent pairs");
+    int rc = trim_state(e);
+    if (rc) return rc;
+    const uint64_t n_pairs = adjacent ? n / 2 : n;
+    if (!n_pairs) return KBBQ_OK;
+    Timed t(e, "k_trim_mates");
+    hipLaunchKernelGGL(k_trim_mates, dim3((unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 4096)), dim3(256), 0, e->stream, keep_a, keep_b, n_pairs,
+                       adjacent ? 1 : 0, e->trim.d_counts);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int kbbq_trim_counts_get(kbbq_engine *e, kbbq_trim_counts *out, int32_t reset) {
+    ENGINE_DEVICE(e);
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
+    int rc = sync_engine(e);
+    if (rc) return rc;
+    unsigned long long c[TRIM_COUNTS] = {};
+    if (e->trim.d_counts) HIP_TRY(hipMemcpy(c, e->trim.d_counts, sizeof c, hipMemcpyDeviceToHost));
+    out->reads_in = c[TRIM_READS_IN]; out->bases_in = c[TRIM_BASES_IN]; out->shortened = c[TRIM_SHORTENED];
+    out->too_short = c[TRIM_TOO_SHORT]; out->over_ee = c[TRIM_OVER_EE]; out->reads_kept = c[TRIM_READS_KEPT];
+    out->bases_kept = c[TRIM_BASES_KEPT]; out->with_mate = c[TRIM_WITH_MATE];
+    if (reset && e->trim.d_counts) HIP_TRY(hipMemset(e->trim.d_counts, 0, sizeof c));
+    return KBBQ_OK;
+}
+
+}  // extern "C"

@@ -11,6 +11,9 @@
 //   k_fastq_text_indexed_fixed / k_fastq_text_packed_fixed
 //                        the same two with corrected sequence lines (kbbq_fastq_reader_write_corrected): kernels of their own, so
 //                        that the two above stay what they are
+//   k_fastq_trim_sizes / k_fastq_text_indexed_trimmed / k_fastq_text_packed_trimmed
+//                        records whose output is shorter than their input, or absent (kbbq_fastq_reader_write_trimmed): the sizes
+//                        of what is kept, and the two text kernels again around offsets of their own -- behind the seven above
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -162,6 +165,62 @@ __global__ void __launch_bounds__(256) k_fastq_text_packed_fixed(const uint8_t *
         const uint8_t *name = names + (text_off[r] - 2 * b0 - 6 * r);
         const SeqSource from = {nullptr, bases, nmask, offcase, b0, fix_mask, fix_bases, b0};
         emit_fastq_record<true>(lane, name, nl, name + nl, cl, from, sl, new_qual + b0, out + text_off[r]);
+    }
+}
+
+// ---- trimmed and filtered records (kbbq_fastq_reader_write_trimmed) ----------------------------------------------------
+// keep[r]: how much of record r's sequence and quality lines is written, 0: the record is not written at all.  A record's
+// output is then name + comment + 2 x keep + 6 bytes, so the offsets of the output are an array of their own (out_off, the
+// scanned sizes); text_off and base_off stay the chunk's, which is where the short form finds its names and every form its
+// qualities.  A keep above the record's length counts as the length.
+// name_len / com_len: X.name_len, X.com_len with stride 1, or the short form's lens, lens + 1 with stride 2.
+// written[0] += the records that are written, written[1] += those of them that are shorter than they were: once per wavefront.
+__global__ void __launch_bounds__(256) k_fastq_trim_sizes(const uint32_t *name_len, const uint32_t *com_len, uint32_t stride, const uint64_t *base_off,
+                                                           const uint32_t *keep, uint64_t n_records, uint64_t *out_sz, unsigned long long *written) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t sl = 0, kl = 0;
+    if (r < n_records) {
+        sl = base_off[r + 1] - base_off[r];
+        kl = keep[r] < sl ? keep[r] : sl;
+        out_sz[r] = kl ? (uint64_t)name_len[r * stride] + com_len[r * stride] + 2 * kl + 6 : 0;
+    }
+    const int n_written = __popcll(__ballot(kl != 0)), n_cut = __popcll(__ballot(kl != 0 && kl < sl));
+    if ((threadIdx.x & 63) == 0) {
+        if (n_written) atomicAdd(&written[0], (unsigned long long)n_written);
+        if (n_cut) atomicAdd(&written[1], (unsigned long long)n_cut);
+    }
+}
+
+template <bool FIX>
+__global__ void __launch_bounds__(256) k_fastq_text_indexed_trimmed(const uint8_t *text, FastqIndex X, const uint64_t *out_off, const uint64_t *base_off,
+                                                                     const uint32_t *keep, const uint8_t *new_qual, const uint64_t *fix_mask,
+                                                                     const uint64_t *fix_bases, uint64_t n_records, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t r = wave; r < n_records; r += n_waves) {
+        const uint32_t nl = X.name_len[r], cl = X.com_len[r], sl = X.seq_len[r], kl = keep[r] < sl ? keep[r] : sl;
+        if (!kl) continue;
+        const uint8_t *name = text + X.name_off[r], *comment = text + X.com_off[r], *seq = text + X.seq_off[r];
+        const SeqSource from = {seq, nullptr, nullptr, nullptr, 0, fix_mask, fix_bases, base_off[r]};
+        emit_fastq_record<FIX>(lane, name, nl, comment, cl, from, kl, new_qual + base_off[r], out + out_off[r]);
+    }
+}
+
+template <bool FIX>
+__global__ void __launch_bounds__(256) k_fastq_text_packed_trimmed(const uint8_t *names, const uint32_t *lens, const uint64_t *text_off, const uint64_t *out_off,
+                                                                    const uint64_t *base_off, const uint32_t *keep, const uint64_t *bases, const uint64_t *nmask,
+                                                                    const uint64_t *offcase, const uint8_t *new_qual, const uint64_t *fix_mask,
+                                                                    const uint64_t *fix_bases, uint64_t n_records, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t r = wave; r < n_records; r += n_waves) {
+        const uint32_t nl = lens[2 * r], cl = lens[2 * r + 1];
+        const uint64_t b0 = base_off[r];
+        const uint32_t sl = (uint32_t)(base_off[r + 1] - b0), kl = keep[r] < sl ? keep[r] : sl;
+        if (!kl) continue;
+        const uint8_t *name = names + (text_off[r] - 2 * b0 - 6 * r);      // (the chunk's own text offsets: where the names were put)
+        const SeqSource from = {nullptr, bases, nmask, offcase, b0, fix_mask, fix_bases, b0};
+        emit_fastq_record<FIX>(lane, name, nl, name + nl, cl, from, kl, new_qual + b0, out + out_off[r]);
     }
 }
 

@@ -50,6 +50,11 @@ struct kbbq_fastq_reader : FastqCounts, TextChunks, ChunkState {
     int32_t mates = KBBQ_MATES_FROM_NAMES;
     uint64_t records_seen = 0;
     double ms_keys = 0;
+    // trimmed output (kbbq_fastq_reader_write_trimmed): the offsets of the records that are written, the time of their size pass and
+    // scan.  Reserved by the first such call: a reader that never writes trimmed records allocates what it did before
+    Buf trim_off;
+    double ms_trim_sizes = 0;
+    uint64_t trim_written = 0, trim_shortened = 0;      // records written by such calls, and those of them that were cut
 };
 
 namespace {
@@ -187,7 +192,7 @@ void kbbq_fastq_reader_destroy(kbbq_fastq_reader *r) {
     if (!r) return;
     KbbqDeviceGuard guard(r->device);
     if (r->st) (void)hipStreamSynchronize(r->st);
-    Buf *all[] = {&r->idx_u32, &r->idx_second, &r->base_sz, &r->text_sz, &r->flags, &r->seq_text, &r->counter};
+    Buf *all[] = {&r->idx_u32, &r->idx_second, &r->base_sz, &r->text_sz, &r->flags, &r->seq_text, &r->counter, &r->trim_off};
     for (Buf *b : all) b->release();
     release_kept(r);
     r->destroy();
@@ -444,6 +449,84 @@ int kbbq_fastq_reader_write_corrected(kbbq_fastq_reader *r, kbbq_bgzf *z, const 
                                       void *after_stream) {
     if (!d_fix_mask || !d_fix_bases) return fail(KBBQ_EINVAL, "null argument");
     return fastq_write(r, z, d_qual, d_fix_mask, d_fix_bases, after_stream);
+}
+
+int kbbq_fastq_reader_write_trimmed(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint32_t *d_keep, const uint64_t *fix_mask,
+                                    const uint64_t *fix_bases, void *after_stream, uint64_t *out_bytes) {
+    if (!r || !z || !d_qual || !d_keep || !out_bytes) return fail(KBBQ_EINVAL, "null argument");
+    if ((fix_mask == nullptr) != (fix_bases == nullptr)) return fail(KBBQ_EINVAL, "the two fix arrays are both set or both null");
+    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->device != z->device) return fail(KBBQ_EINVAL, "reader and writer are on different devices");
+    KbbqDeviceGuard guard(z->device);
+    HIP_TRY(guard.err);
+    if (r->selected >= 0 && r->kept[(size_t)r->selected].short_form && !r->att_bases)
+        return fail(KBBQ_ESTATE, "the chunk was kept without its sequence text: attach its batch first (kbbq_fastq_reader_attach)");
+    *out_bytes = 0;
+    const uint64_t n = r->n_records;
+    const bool from_kept = r->selected >= 0;
+    const kbbq_fastq_reader::Kept *k = from_kept ? &r->kept[(size_t)r->selected] : nullptr;
+    const bool packed = from_kept && k->short_form;
+    const FastqIndex X = from_kept ? index_from(k->idx_u32.p, nullptr, k->base_sz.p, k->text_sz.p, nullptr, n) : index_of(r, n);
+    const uint8_t *text = (const uint8_t *)(from_kept ? k->text.p : r->text.p);
+    // ---- the sizes of what is written, scanned into offsets of their own, and their total: on the reader's stream, behind the
+    // caller's (which fills d_keep)
+    int rc;
+    if ((rc = r->trim_off.reserve((n + 4) * 8))) return rc;      // the offsets, their total, the two counts of k_fastq_trim_sizes
+    if ((rc = r->h_small.reserve(4096))) return rc;
+    uint64_t *out_off = (uint64_t *)r->trim_off.p;
+    if (after_stream) {
+        HIP_TRY(hipEventRecord(r->t2, (hipStream_t)after_stream));      // (a chunk call's events, free between two of them)
+        HIP_TRY(hipStreamWaitEvent(r->st, r->t2, 0));
+    }
+    HIP_TRY(hipEventRecord(r->t0, r->st));
+    HIP_TRY(hipMemsetAsync(out_off + n + 1, 0, 16, r->st));
+    const uint32_t *lens = packed ? (const uint32_t *)k->lens.p : nullptr;
+    hipLaunchKernelGGL(k_fastq_trim_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, packed ? lens : X.name_len, packed ? lens + 1 : X.com_len,
+                       packed ? 2u : 1u, (const uint64_t *)X.base_sz, d_keep, n, out_off, (unsigned long long *)(out_off + n + 1));
+    HIP_TRY(hipGetLastError());
+    if ((rc = device_scan_on(r->tile_sums, r->st, out_off, n, out_off + n))) return rc;
+    HIP_TRY(hipEventRecord(r->t1, r->st));
+    uint64_t *hs = (uint64_t *)r->h_small.p;
+    HIP_TRY(hipMemcpyAsync(hs, out_off + n, 24, hipMemcpyDeviceToHost, r->st));
+    HIP_TRY(hipStreamSynchronize(r->st));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, r->t0, r->t1) == hipSuccess) r->ms_trim_sizes += ms;
+    const uint64_t total = hs[0];
+    r->trim_written += hs[1];
+    r->trim_shortened += hs[2];
+    *out_bytes = total;
+    if (!total) return KBBQ_OK;      // nothing of this chunk is written: nothing is submitted
+    const dim3 grid((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32));
+    // (waits for the live chunk alone, as kbbq_fastq_reader_write does; out_off is read by the kernel queued and overwritten by
+    // the next call, which for a kept chunk may come before that kernel has run: a kept chunk waits too)
+    return submit_rewrite(z, after_stream, total, true, [&](uint8_t *payload) {
+        const uint64_t *base_off = (const uint64_t *)X.base_sz;
+        if (packed && fix_mask)
+            hipLaunchKernelGGL(k_fastq_text_packed_trimmed<true>, grid, dim3(256), 0, z->st, (const uint8_t *)k->names.p, lens, (const uint64_t *)k->text_sz.p,
+                               (const uint64_t *)out_off, base_off, d_keep, r->att_bases, r->att_nmask, r->att_offcase, d_qual, fix_mask, fix_bases, n, payload);
+        else if (packed)
+            hipLaunchKernelGGL(k_fastq_text_packed_trimmed<false>, grid, dim3(256), 0, z->st, (const uint8_t *)k->names.p, lens, (const uint64_t *)k->text_sz.p,
+                               (const uint64_t *)out_off, base_off, d_keep, r->att_bases, r->att_nmask, r->att_offcase, d_qual, fix_mask, fix_bases, n, payload);
+        else if (fix_mask)
+            hipLaunchKernelGGL(k_fastq_text_indexed_trimmed<true>, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)out_off, base_off, d_keep, d_qual,
+                               fix_mask, fix_bases, n, payload);
+        else
+            hipLaunchKernelGGL(k_fastq_text_indexed_trimmed<false>, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)out_off, base_off, d_keep, d_qual,
+                               fix_mask, fix_bases, n, payload);
+    });
+}
+
+int kbbq_fastq_reader_trim_ms(kbbq_fastq_reader *r, double *sizes_ms) {
+    if (!r || !sizes_ms) return fail(KBBQ_EINVAL, "null argument");
+    *sizes_ms = r->ms_trim_sizes;
+    return KBBQ_OK;
+}
+
+int kbbq_fastq_reader_trim_written(kbbq_fastq_reader *r, uint64_t *records, uint64_t *shortened) {
+    if (!r || !records || !shortened) return fail(KBBQ_EINVAL, "null argument");
+    *records = r->trim_written;
+    *shortened = r->trim_shortened;
+    return KBBQ_OK;
 }
 
 int kbbq_fastq_reader_attach(kbbq_fastq_reader *r, const kbbq_reads *batch) {

@@ -95,6 +95,7 @@
 using namespace kbbq;
 
 // (headers of this unit alone, in this order: each uses what the ones before it define)
+#include "trim_values.h"
 #include "cli_options.h"
 #include "cli_device_io.h"
 #include "cli_pairs.h"
@@ -781,6 +782,7 @@ static int tally_fixed_on_device(kbbq_engine *e, const CliOptions &o, ScanState 
     return 0;
 }
 
+#include "cli_trim.h"
 #include "cli_pass4.h"
 #include "cli_table.h"
 
@@ -823,9 +825,10 @@ static void report_io_timing(DeviceInput &in, const Sink &w, const FixedOnDevice
 }
 
 // Pass 4 by the one of cli_pass4.h's writers that fits what the scan left behind
-static int write_output(kbbq_engine *e, ScanState &scan, const CliOptions &opt, Sink &sink, DeviceInput &dev_in, Batch &batch) {
+static int write_output(kbbq_engine *e, ScanState &scan, const CliOptions &opt, Sink &sink, DeviceInput &dev_in, Batch &batch, TrimRun *trim = nullptr) {
     const Resident &resident = scan.resident;
-    if (dev_in.active && sink.dev) return write_from_device_reader(e, scan, opt, sink, dev_in);
+    if (dev_in.active && sink.dev) return write_from_device_reader(e, scan, opt, sink, dev_in, 0, true, trim);
+    if (trim) return give_up(std::string(" Error: ") + opt.trim_option + ": the output does not go through the GPU reader's writer, which cuts and drops the reads.");
     if (resident.on && resident.keep_recs && opt.format == Format::fastq && sink.dev) return write_resident_fastq(e, scan, opt, sink);
     if (resident.on && resident.keep_recs && opt.format == Format::bam && sink.dev) return write_resident_bam(e, scan, opt, sink);
     if (resident.on && resident.keep_recs) return write_resident_records(e, scan, opt, sink);
@@ -931,6 +934,9 @@ int main(int argc, char *argv[]) {
     if (opt.correct && fmt != Format::fastq)
         return give_up(std::string(" Error: --correct with ") + (fmt == Format::bam ? "BAM" : "SAM") +
                        " input: changing SEQ there would falsify CIGAR, MD and NM, and this tool does not re-align.  Corrected reads are written for FASTQ.");
+    if (opt.trim_on() && fmt != Format::fastq)
+        return give_up(std::string(" Error: ") + opt.trim_option + " with " + (fmt == Format::bam ? "BAM" : "SAM") +
+                       " input: clipping SEQ there would falsify CIGAR, MD and NM, and a record's mate is in its FLAG.  Reads are cut and dropped for FASTQ.");
     if (const char *option = opt.pairs_option())
         if (const char *why = opt.pairs_format_refusal(fmt, opt.paired_files() ? sniff(opt.in2_path) : Format::fastq))
             return give_up(std::string(" Error: ") + option + " with" + why + ".");
@@ -984,6 +990,9 @@ int main(int argc, char *argv[]) {
                        (dev_in.refusal.empty() ? "." : ":" + dev_in.refusal));
     if (!read_on_device && opt.correct)      // (no host parsers behind --correct, as behind a stream)
         return give_up(" Error: --correct: the GPU reader hands this input back to the host parsers (or the reads do not stay in GPU memory), and they write no corrected reads.");
+    if (!read_on_device && opt.trim_on())      // (no host parsers behind the trimming options either)
+        return give_up(std::string(" Error: ") + opt.trim_option + ": the GPU reader hands this input back to the host parsers (or the reads do not stay in GPU memory), and they cut and drop no reads" +
+                       (dev_in.refusal.empty() ? "." : ":" + dev_in.refusal));
     if (!read_on_device && stream) {
         // no host parsers behind a stream; without a reason the stream held no read at all, and nothing is left to read
         if (!scan.resident.on) return give_up(" Error: input from a pipe is read once, and the reads cannot stay in GPU memory: write the input to a file first.");
@@ -1069,16 +1078,32 @@ int main(int argc, char *argv[]) {
     Sink sink;
     int rc = sink.open(opt, scan);
     if (rc) return rc;
+    // --trim-tail, --min-length, --max-ee: the kept lengths of every file's records, allocated now that the filters exist; a
+    // paired run takes every verdict, and applies the mate rule, before its first record is written (cli_trim.h)
+    TrimRun trim_run;
+    TrimRun *trim = nullptr;
+    if (opt.trim_on()) {
+        uint64_t reads[2] = {0, 0};
+        for (size_t bi = 0; bi < resident.dev.size(); ++bi) reads[opt.paired_files() && bi >= scan.in2_first_batch ? 1 : 0] += resident.dev[bi].n_reads;
+        if ((rc = trim_run.open(e, opt, reads[0], reads[1]))) return rc;
+        trim = &trim_run;
+        if (trim_run.paired) {
+            if (!sink.dev) return give_up(std::string(" Error: ") + opt.trim_option + ": the output does not go through the GPU reader's writer, which cuts and drops the reads.");
+            QualSlots slots{e};
+            if ((rc = trim_run.verdicts(slots, *sink.dev, resident.dev, scan.in2_first_batch, opt.paired_files(), !opt.report.empty()))) return rc;
+            clock.mark("trim verdicts");
+        }
+    }
     if (!opt.paired_files()) {
-        if (write_output(e, scan, opt, sink, dev_in, batch) || !sink.close()) return 1;
+        if (write_output(e, scan, opt, sink, dev_in, batch, trim) || !sink.close()) return 1;
     } else {
         // the first file's records to stdout as ever, then the second file's -- the resident batches behind the first file's --
         // to --out2 through a writer of its own; a run that fails on the way leaves no --out2 file
-        if (write_from_device_reader(e, scan, opt, sink, dev_in, 0, false)) return 1;
+        if (write_from_device_reader(e, scan, opt, sink, dev_in, 0, false, trim, 0)) return 1;
         FILE *f2 = fopen(opt.out2.c_str(), "wb");
         if (!f2) return give_up(" Error: --out2: cannot open " + opt.out2 + " for writing: " + strerror(errno));
         Sink sink2;
-        const bool ok2 = sink2.open_file(f2, opt) == 0 && write_from_device_reader(e, scan, opt, sink2, dev_in2, scan.in2_first_batch, true) == 0;
+        const bool ok2 = sink2.open_file(f2, opt) == 0 && write_from_device_reader(e, scan, opt, sink2, dev_in2, scan.in2_first_batch, true, trim, 1) == 0;
         const bool closed2 = sink2.close();      // (the writer goes before its file)
         if ((fclose(f2) != 0) | !ok2 | !closed2) {
             unlink(opt.out2.c_str());
@@ -1093,6 +1118,9 @@ int main(int argc, char *argv[]) {
     }
     if (opt.interleaved && clock.on)
         std::cerr << "[timing] pairs: interleaved; key kernel " << dev_in.pair_keys_ms() << " ms, " << scan.pairs.checks << " checks " << scan.pairs.ms_check << " ms" << std::endl;
+    if (trim && clock.on)
+        std::cerr << "[timing] trim: sizes + scan of the trimmed records " << trim_run.ms_sizes << " ms (their text kernels are in the writer's format time)" << std::endl;
+    trim_run.release();      // (before the engine goes: end_run may not come back)
     if (!opt.report.empty())
         if (const int bad = write_quality_report(e, opt, scan.groups.names(), nullptr, p.seed, scan.seqlen)) return bad;
     return end_run(opt, clock, dev_in, sink, fixed_report, OnePass(), scan, engine);

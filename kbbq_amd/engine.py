@@ -274,6 +274,50 @@ class Engine:
         _lib.check(self.L.kbbq_correct_counts(self.h, ctypes.byref(c), 1 if reset else 0))
         return dict(flagged=int(c.flagged), fixed=int(c.fixed), ambiguous=int(c.ambiguous), unsupported=int(c.unsupported))
 
+    # ---- trimming and filtering by the qualities pass 4 wrote
+    def trim_reads(self, dreads, qual_ptr, tail_q=None, min_length=1, max_ee=None):
+        """kbbq_trim_batch on a device batch (DeviceReads) and the device array of its written qualities: the kept length of
+        every read, 0 for a dropped one, as a NumPy uint32 array.  tail_q: the 3' cut's threshold (None: no cut); max_ee:
+        the most expected errors a kept read may carry (None: no bound).  Waits for the kernel."""
+        import torch
+        p = _lib.TrimParams()
+        p.tail_q = 0 if tail_q is None else int(tail_q)
+        if tail_q is not None and not 1 <= int(tail_q) <= MAXQ:
+            raise _lib.KbbqError(-22, "tail_q must be in 1..%d" % MAXQ)
+        p.min_length = int(min_length)
+        p.has_ee = 0 if max_ee is None else 1
+        p.ee_bound = 0 if max_ee is None else ee_bound(max_ee)
+        dev = "cuda:%d" % self.params.device
+        d_keep = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_trim_batch(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), d_keep.data_ptr()))
+        self.sync()
+        return d_keep.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
+
+    def trim_mates(self, keep_a, keep_b=None, adjacent=False):
+        """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
+        (a, b), or a alone with adjacent=True, where the pairs are a[2i], a[2i+1].  Waits for the kernel."""
+        import torch
+        dev = "cuda:%d" % self.params.device
+        a = np.ascontiguousarray(keep_a, dtype=np.uint32)
+        d_a = torch.from_numpy(a.view(np.int32).copy()).to(dev)
+        d_b = None
+        if not adjacent:
+            b = np.ascontiguousarray(keep_b, dtype=np.uint32)
+            assert len(b) == len(a), "two files of a pair hold equally many reads"
+            d_b = torch.from_numpy(b.view(np.int32).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        _lib.check(self.L.kbbq_trim_mates(self.h, d_a.data_ptr(), d_b.data_ptr() if d_b is not None else None, len(a), 1 if adjacent else 0))
+        self.sync()
+        out_a = d_a.cpu().numpy().view(np.uint32)
+        return out_a if adjacent else (out_a, d_b.cpu().numpy().view(np.uint32))
+
+    def trim_counts(self, reset=False):
+        """What trim_reads and trim_mates did since the last reset (waits): the fields of kbbq_trim_counts."""
+        c = _lib.TrimCounts()
+        _lib.check(self.L.kbbq_trim_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
+        return {n: int(getattr(c, n)) for n, _ in _lib.TrimCounts._fields_}
+
     def covariates(self):
         R, C = self.n_rg, self.max_read_len
         out = dict(R=R, C=C, rg=np.zeros((R, 2), np.uint64), q=np.zeros((R, NQ, 2), np.uint64),
@@ -570,6 +614,20 @@ def host_train(cov):
     d.meanq, d.rgdq, d.qdq, d.cycledq, d.dinucdq = (out[k].ctypes.data for k in ("meanq", "rg", "q", "cycle", "dinuc"))
     _lib.check(_lib.lib().kbbq_host_train(ctypes.byref(c), ctypes.byref(d)))
     return out
+
+
+def ee_table():
+    """The expected-error table trimming sums (kbbq_trim_ee_table): EE[v] = round(10^(-v/10) * 2^32), uint64[256].  No GPU is touched."""
+    out = np.zeros(256, dtype=np.uint64)
+    _lib.check(_lib.lib().kbbq_trim_ee_table(out.ctypes.data_as(_lib.c_u64p)))
+    return out
+
+
+def ee_bound(max_ee):
+    """floor(max_ee * 2^32): the bound the sums of ee_table() entries are held against (kbbq_trim_ee_bound)."""
+    out = ctypes.c_uint64()
+    _lib.check(_lib.lib().kbbq_trim_ee_bound(float(max_ee), ctypes.byref(out)))
+    return out.value
 
 
 def rng_state_at(seed, ordinal):
