@@ -360,6 +360,55 @@ int kbbq_trim_counts_get(kbbq_engine *e, kbbq_trim_counts *out, int32_t reset);
 int kbbq_trim_ee_table(uint64_t out[256]);
 int kbbq_trim_ee_bound(double max_ee, uint64_t *bound);
 
+/* ---- 3' adapters: where a read runs on into the adapter, and the trimming rule from there ------------------
+ * The rule is this project's own, exact and all integers: cutadapt's 3' adapter without indels, leftmost
+ * match.  A read of the packed batch has n bases with 2-bit codes c[0..n) and N bits u[0..n); an adapter is a[0..m), ACGT only,
+ * 4 <= m <= 64; v = min_overlap, 1 <= v <= m; t = max_error_permille, 0..500.
+ *     limit = n
+ *     for p = 0 .. n-1:
+ *         o = min(m, n - p)                      the adapter may run off the read's end
+ *         if o < v: break
+ *         mm = #{ j < o : u[p+j] is set  or  c[p+j] != a[j] }
+ *         if mm * 1000 <= o * t: limit = p; break
+ * A base with its N bit set is one mismatch (an N, or whatever else the packer gives code 0 and the N bit); a lower-case letter
+ * has its folded code and matches.  The search reads the batch's bases as the sequencer read them: with corrections
+ * (kbbq_correct_batch) the fixes take no part.  Bit 0 of the read's flag picks the adapter: `first` for a first-in-pair read,
+ * `second` for a second-in-pair read when one is given (second.len != 0), else `first`.  The result depends on the read, its
+ * flag and the parameters alone: not on how the batches were cut, on uniform or ragged batches, on hints or on offcase.
+ * Then the trimming rule above runs on the prefix q[0..limit) in place of q[0..n) (kbbq_trim_batch_limited): the cut from the
+ * new end, the expected errors of the kept prefix, the verdict, the mates.  limit = 0 (an adapter dimer) makes the read too
+ * short; reads_in and bases_in still count the input's lengths, and "shortened" still means "kept shorter than it stands in
+ * the input", for whichever reason. */
+#define KBBQ_ADAPTER_MIN 4
+#define KBBQ_ADAPTER_MAX 64
+typedef struct kbbq_adapter {
+    uint64_t code[2];       /* the adapter in the layout of kbbq_reads.bases: base j in bits 2(j%32).. of word j/32, 0 behind it */
+    int32_t len;            /* 4..64; 0 in kbbq_adapter_params.second: none */
+    int32_t reserved;
+} kbbq_adapter;
+typedef struct kbbq_adapter_params {
+    kbbq_adapter first, second;
+    int32_t min_overlap;            /* 1..the length of the shorter adapter given */
+    int32_t max_error_permille;     /* 0..500 */
+} kbbq_adapter_params;
+/* Sums since the last reset.  found_second counts the matches of `second`, found_first every other match;
+ * full + partial = found_first + found_second (full: all m bases of the adapter lie on the read); bases_behind = the sum of
+ * n - limit. */
+typedef struct kbbq_adapter_counts { uint64_t reads, found_first, found_second, full, partial, bases_behind; } kbbq_adapter_counts;
+/* An adapter from its text: 4 to 64 letters of ACGTacgt, or one of three names in any case -- illumina = AGATCGGAAGAGC,
+ * nextera = CTGTCTCTTATACACATCT, smallrna = TGGAATTCTCGGGTGCCAAGG.  Anything else is KBBQ_EINVAL.  Host code; no GPU is touched. */
+int kbbq_adapter_parse(const char *text, kbbq_adapter *out);
+/* limit[r] (device, n_reads words) = the rule's limit for read r of the device batch.  Queued on the engine's stream.
+ * KBBQ_EINVAL for a host batch, for a length or parameter out of range, for an adapter with bits set behind its length or for
+ * first.len == 0. */
+int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *device_reads, const kbbq_adapter_params *p, uint32_t *limit);
+/* kbbq_trim_batch on the prefix of min(n, limit[r]) qualities of every read (limit: device, n_reads words; NULL: the whole
+ * read, which is kbbq_trim_batch).  The counters count as the rule above says. */
+int kbbq_trim_batch_limited(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p,
+                            const uint32_t *limit, uint32_t *keep);
+/* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
+int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset);
+
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]
  *   cycle [n_rg][256][2][max_read_len][2]   (third index: 0 first-in-pair, 1 second)

@@ -95,6 +95,18 @@ class TrimCounts(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("reads_in", "bases_in", "shortened", "too_short", "over_ee", "reads_kept", "bases_kept", "with_mate")]
 
 
+class Adapter(ctypes.Structure):
+    _fields_ = [("code", c_u64 * 2), ("len", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AdapterParams(ctypes.Structure):
+    _fields_ = [("first", Adapter), ("second", Adapter), ("min_overlap", ctypes.c_int32), ("max_error_permille", ctypes.c_int32)]
+
+
+class AdapterCounts(ctypes.Structure):
+    _fields_ = [(n, c_u64) for n in ("reads", "found_first", "found_second", "full", "partial", "bases_behind")]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -151,6 +163,10 @@ SYMBOLS = {
     "kbbq_trim_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(TrimCounts), ctypes.c_int32]),
     "kbbq_trim_ee_table": (ctypes.c_int, [c_u64p]),
     "kbbq_trim_ee_bound": (ctypes.c_int, [ctypes.c_double, c_u64p]),
+    "kbbq_adapter_parse": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(Adapter)]),
+    "kbbq_adapter_find_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.POINTER(AdapterParams), c_vp]),
+    "kbbq_trim_batch_limited": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp]),
+    "kbbq_adapter_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(AdapterCounts), ctypes.c_int32]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),

@@ -31,6 +31,9 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"in2", required_argument, 0, 1008}, {"out2", required_argument, 0, 1009}, {"interleaved", no_argument, 0, 1010},
     // the output's reads cut and dropped by the qualities that are written (cli_trim.h); any of the three turns it on
     {"trim-tail", required_argument, 0, 1011}, {"min-length", required_argument, 0, 1012}, {"max-ee", required_argument, 0, 1013},
+    // the 3' adapter the reads run on into, searched on the GPU before that cut (cli_trim.h); --adapter turns trimming on
+    {"adapter", required_argument, 0, 1014}, {"adapter2", required_argument, 0, 1015}, {"adapter-min-overlap", required_argument, 0, 1016},
+    {"adapter-error-rate", required_argument, 0, 1017},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -106,7 +109,14 @@ struct CliOptions {
     // expected errors, and -- a paired run -- the mate of a dropped read (include/kbbq_engine.h: kbbq_trim_batch).  FASTQ through
     // the device reader with the reads resident: whatever leads elsewhere is refused (trim_refusal)
     kbbq_trim_params trim = {0, 0, 0, 0};
-    const char *trim_option = nullptr;      // the first of the three that was given: trimming is on
+    const char *trim_option = nullptr;      // the first of the three, or --adapter, that was given: trimming is on
+    // --adapter SEQ|NAME: every read is searched for that 3' adapter first (include/kbbq_engine.h: kbbq_adapter_find_batch) and
+    // the rule above runs on what stands in front of it; alone it cuts with no --trim-tail and --min-length 1.  --adapter2: the
+    // adapter of the second-in-pair reads, by the mate flag the batch carries (--in2, --interleaved, or a "/2" name).
+    // --adapter-min-overlap N (default 5, or the shortest adapter's length if that is less), --adapter-error-rate R (default 0.1)
+    kbbq_adapter_params adapter = {{{0, 0}, 0, 0}, {{0, 0}, 0, 0}, 0, 100};
+    const char *adapter_tuning = nullptr;   // the first of --adapter2 and the two tuning options that was given
+    bool adapter_on() const { return adapter.first.len != 0; }
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -303,6 +313,27 @@ struct CliOptions {
                     if (!trim_option) trim_option = "--max-ee";
                     break;
                 }
+                case 1014:
+                case 1015:
+                    if (kbbq_adapter_parse(optarg, opt == 1014 ? &adapter.first : &adapter.second) < 0)
+                        return !give_up(std::string(" Error: ") + (opt == 1014 ? "--adapter" : "--adapter2") +
+                                        " takes 4 to 64 letters of ACGT, or illumina, nextera or smallrna, not \"" + optarg + "\".");
+                    if (opt == 1014 && !trim_option) trim_option = "--adapter";
+                    if (opt == 1015 && !adapter_tuning) adapter_tuning = "--adapter2";
+                    break;
+                case 1016: {
+                    uint64_t v = 0;
+                    if (!trim_parse_integer(optarg, 1, KBBQ_ADAPTER_MAX, &v))
+                        return !give_up(std::string(" Error: --adapter-min-overlap takes an integer in 1..") + std::to_string(KBBQ_ADAPTER_MAX) + ", not \"" + optarg + "\".");
+                    adapter.min_overlap = (int32_t)v;
+                    if (!adapter_tuning) adapter_tuning = "--adapter-min-overlap";
+                    break;
+                }
+                case 1017:
+                    if (!adapter_parse_error_rate(optarg, &adapter.max_error_permille))
+                        return !give_up(std::string(" Error: --adapter-error-rate takes a decimal of at most three places in 0..0.5, not \"") + optarg + "\".");
+                    if (!adapter_tuning) adapter_tuning = "--adapter-error-rate";
+                    break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -318,6 +349,15 @@ struct CliOptions {
             return !give_up(std::string(" Error: --load-table with ") + trains_with + ": a table run does not train, it applies the model of the table.");
         if (correct)
             if (const char *why = correct_refusal()) return !give_up(std::string(" Error: --correct with ") + why + ".");
+        if (adapter_tuning && !adapter_on())
+            return !give_up(std::string(" Error: ") + adapter_tuning + " without --adapter: it says how, or in which reads, the adapter that --adapter names is searched.");
+        if (adapter_on()) {
+            const int shortest = adapter.second.len ? std::min(adapter.first.len, adapter.second.len) : adapter.first.len;
+            if (!adapter.min_overlap) adapter.min_overlap = std::min(5, shortest);
+            if (adapter.min_overlap > shortest)
+                return !give_up(" Error: --adapter-min-overlap " + std::to_string(adapter.min_overlap) + " is more than the " + std::to_string(shortest) +
+                                " bases of the shortest adapter given.");
+        }
         if (trim_on()) {
             if (!trim.min_length) trim.min_length = 1;
             if (const char *why = trim_refusal()) return !give_up(std::string(" Error: ") + trim_option + " with " + why + ".");

@@ -163,7 +163,7 @@ struct FixSlots {
 // first_batch: the resident batch of the reader's first chunk with records -- 0, or, for the second file of --in2, the number of
 // batches the first file made; totals: the "Corrected bases" and "[digest]" lines, which count every batch written so far (the
 // last reader's call prints them: one line each, over both files).
-// trim (--trim-tail, --min-length, --max-ee: cli_trim.h; null: none): the records are written cut to their kept lengths or left
+// trim (--trim-tail, --min-length, --max-ee, --adapter: cli_trim.h; null: none): the records are written cut to their kept lengths or left
 // out -- the verdicts taken here, batch by batch behind pass 4, unless a paired run's pre-pass has taken them all; which: the
 // file whose array of kept lengths this reader's records stand in (1: --in2's).
 static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in, size_t first_batch = 0, bool totals = true,

@@ -1,4 +1,4 @@
-// cli_trim.h -- --trim-tail, --min-length, --max-ee on the command line: the kept lengths of every input file's records in
+// cli_trim.h -- --trim-tail, --min-length, --max-ee and --adapter on the command line: the kept lengths of every input file's records in
 // device memory (TrimRun), the verdict pre-pass of a paired run, and the stamped line the run ends with.  The rule is
 // include/kbbq_engine.h's (kbbq_trim_batch); the records are cut and left out by the device reader's writer
 // (kbbq_fastq_reader_write_trimmed).  Compiled into kbbq_cli.cc alone, in front of cli_pass4.h.
@@ -9,6 +9,11 @@
 // arrays, then the usual write loop, which recalibrates again.  The pre-pass counts into neither the quality report nor the
 // digest: both come out as in the run without the options, over every base pass 4 recalibrated, written or not.
 //
+// --adapter: the verdicts of a batch start with the search for the 3' adapter in its packed bases (kbbq_adapter_find_batch), into
+// a scratch array of one limit per read of the batch, and the rule then runs in front of those limits
+// (kbbq_trim_batch_limited).  The search is part of batch(), so a paired run's pre-pass makes it and pass 4 does not repeat it:
+// once per read either way.  The limits depend on the packed batch alone -- with --correct the fixes take no part.
+//
 // One array of kept lengths per input file, indexed by the record's ordinal in its file: 4 bytes a read.  The two files'
 // chunks are cut where their own bytes say, and the mate rule does not have to care where.
 #pragma once
@@ -16,6 +21,9 @@
 struct TrimRun {
     kbbq_engine *e = nullptr;
     kbbq_trim_params params = {0, 0, 0, 0};
+    kbbq_adapter_params adapter = {{{0, 0}, 0, 0}, {{0, 0}, 0, 0}, 0, 0};      // (first.len == 0: no --adapter)
+    uint32_t *limit = nullptr;                   // device scratch: the adapter limits of the batch in hand, grown to the largest batch
+    uint64_t limit_reads = 0;
     bool on = false, paired = false, have_verdicts = false;
     uint32_t *keep[2] = {nullptr, nullptr};      // device: the kept lengths of the first (or only) input's records and of --in2's
     uint64_t n[2] = {0, 0};
@@ -30,11 +38,15 @@ struct TrimRun {
             if (k) kbbq_device_free(e, k);
             k = nullptr;
         }
+        if (limit) kbbq_device_free(e, limit);
+        limit = nullptr;
+        limit_reads = 0;
     }
     // The arrays, once the filters exist: reads[f] records of file f.  0, or the exit status with its line on stderr
     int open(kbbq_engine *engine, const CliOptions &o, uint64_t reads0, uint64_t reads1) {
         e = engine;
         params = o.trim;
+        adapter = o.adapter;
         on = true;
         paired = o.paired_files() || o.interleaved;
         n[0] = reads0;
@@ -54,7 +66,20 @@ struct TrimRun {
     // the verdicts of batch d of file f, whose first record is the file's record `ordinal`, from its written qualities q
     int batch(int f, uint64_t ordinal, const kbbq_reads &d, const uint8_t *q) {
         if (ordinal + d.n_reads > n[f]) return give_up(" Error: the input changed between the passes.");
-        if (kbbq_trim_batch(e, &d, q, &params, keep[f] + ordinal) < 0) return fail_engine("trimming");
+        if (adapter.first.len) {
+            if (d.n_reads > limit_reads) {      // (the engine's stream runs in order: the earlier batch's kernels are done with the old array when it goes)
+                if (limit && (kbbq_engine_sync(e) < 0 || kbbq_device_free(e, limit) < 0)) return fail_engine("trimming");
+                limit = nullptr;
+                limit_reads = 0;
+                void *p = nullptr;
+                if (kbbq_device_alloc(e, d.n_reads * 4, &p) < 0)
+                    return give_up(" Error: --adapter: the limits of a batch of " + std::to_string(d.n_reads) + " reads (4 bytes each) do not fit in GPU memory.");
+                limit = (uint32_t *)p;
+                limit_reads = d.n_reads;
+            }
+            if (kbbq_adapter_find_batch(e, &d, &adapter, limit) < 0) return fail_engine("searching the adapters");
+        }
+        if (kbbq_trim_batch_limited(e, &d, q, &params, adapter.first.len ? limit : nullptr, keep[f] + ordinal) < 0) return fail_engine("trimming");
         return 0;
     }
     // A paired run's pre-pass: pass 4 of every resident batch for its verdicts alone, then the mate rule.  Slots: QualSlots
@@ -93,6 +118,13 @@ struct TrimRun {
         std::cerr << put_now << " Trimmed reads: " << c.reads_in << " in, " << written << " written, " << shortened << " shortened, " << c.too_short << " too short, "
                   << c.over_ee << " over the expected errors, " << c.with_mate << " dropped with their mate; bases: " << c.bases_in << " in, " << c.bases_kept
                   << " written." << std::endl;
+        if (adapter.first.len) {
+            kbbq_adapter_counts a;
+            if (kbbq_adapter_counts_get(e, &a, 0) < 0) return fail_engine("searching the adapters");
+            std::cerr << put_now << " Adapters: " << a.reads << " reads searched, " << a.found_first << " with the first adapter, " << a.found_second
+                      << " with the second, " << a.full << " whole, " << a.partial << " running off the end; bases: " << a.bases_behind << " from the adapter on."
+                      << std::endl;
+        }
         return 0;
     }
 };

@@ -50,6 +50,8 @@ using namespace kbbq;
 #include "engine_correct.h"
 #include "trim.h"      // (its two kernels are no templates: defined here, behind every kernel above)
 #include "engine_trim.h"
+#include "adapter.h"   // (k_adapter_find: behind the trim kernels, for the same reason)
+#include "engine_adapter.h"
 
 extern "C" {
 
@@ -163,6 +165,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->d_totals);
     hipFree(e->d_fix_counts);
     hipFree(e->trim.d_counts);
+    hipFree(e->adapter.d_counts);
     hipFree(e->p4.d_dq_qslot);
     hipFree(e->d_qpresent);
     hipFree(e->p3.d_rg_present[0]);
@@ -191,6 +194,7 @@ int kbbq_engine_reset(kbbq_engine *e) {
     e->p4.reset();
     if ((rc = e->rep.reset(e->stream))) return rc;
     if ((rc = e->trim.reset(e->stream))) return rc;
+    if ((rc = e->adapter.reset(e->stream))) return rc;
     e->profile.reset();
     return sync_engine(e);
 }

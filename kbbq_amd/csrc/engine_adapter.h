@@ -1,0 +1,74 @@
+// engine_adapter.h -- 3' adapter removal (include/kbbq_engine.h: kbbq_adapter_find_batch, kbbq_adapter_counts_get): the launch of
+// adapter.h's kernel and the counters.  Part of engine.hip; behind engine_trim.h, so that every kernel before it keeps its
+// place in the code object.  (kbbq_adapter_parse is host_adapter.cc's; the cut from the new end is kbbq_trim_batch_limited.)
+#pragma once
+
+namespace {
+
+// the first search of this engine: the counters (engine_state.h: AdapterState)
+int adapter_state(kbbq_engine *e) {
+    if (e->adapter.d_counts) return KBBQ_OK;
+    unsigned long long *d = nullptr;
+    HIP_TRY(hipMalloc(&d, ADAPTER_COUNTS * 8));
+    hipError_t he = hipMemsetAsync(d, 0, ADAPTER_COUNTS * 8, e->stream);
+    if (he != hipSuccess) { hipFree(d); HIP_TRY(he); }
+    e->adapter.d_counts = d;
+    return KBBQ_OK;
+}
+
+// an adapter as the caller gave it: a length in range, and no bit set behind it (the kernel compares whole words)
+bool adapter_ok(const kbbq_adapter &a) {
+    if (a.len < KBBQ_ADAPTER_MIN || a.len > KBBQ_ADAPTER_MAX) return false;
+    for (int w = 0; w < 2; ++w) {
+        const int bases = std::min(32, std::max(0, a.len - 32 * w));
+        if (bases < 32 && (a.code[w] >> (2 * bases))) return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *reads, const kbbq_adapter_params *p, uint32_t *limit) {
+    ENGINE_DEVICE(e);
+    if (!reads || !p || !limit) return fail(KBBQ_EINVAL, "null argument");
+    if (!reads->on_device) return fail(KBBQ_EINVAL, "not a device batch");
+    if (!adapter_ok(p->first)) return fail(KBBQ_EINVAL, "first: an adapter of %d to %d bases, no bit set behind them", KBBQ_ADAPTER_MIN, KBBQ_ADAPTER_MAX);
+    const bool has_second = p->second.len != 0;
+    if (has_second && !adapter_ok(p->second))
+        return fail(KBBQ_EINVAL, "second: an adapter of %d to %d bases, no bit set behind them, or len = 0 for none", KBBQ_ADAPTER_MIN, KBBQ_ADAPTER_MAX);
+    const int shortest = has_second ? std::min(p->first.len, p->second.len) : p->first.len;
+    if (p->min_overlap < 1 || p->min_overlap > shortest) return fail(KBBQ_EINVAL, "min_overlap must be in 1..%d, the (shorter) adapter's length", shortest);
+    if (p->max_error_permille < 0 || p->max_error_permille > 500) return fail(KBBQ_EINVAL, "max_error_permille must be in 0..500");
+    ReadsDev R; int max_len;
+    int rc = device_view(e, reads, &R, &max_len, false);
+    if (rc) return rc;
+    if ((rc = adapter_state(e))) return rc;
+    AdapterDev A;
+    const kbbq_adapter &second = has_second ? p->second : p->first;
+    A.code[0][0] = p->first.code[0]; A.code[0][1] = p->first.code[1]; A.len[0] = p->first.len;
+    A.code[1][0] = second.code[0]; A.code[1][1] = second.code[1]; A.len[1] = second.len;
+    A.has_second = has_second ? 1 : 0;
+    A.min_overlap = p->min_overlap;
+    A.permille = p->max_error_permille;
+    Timed t(e, "k_adapter_find");
+    hipLaunchKernelGGL(k_adapter_find, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, A, limit, e->adapter.d_counts);
+    HIP_TRY(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset) {
+    ENGINE_DEVICE(e);
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
+    int rc = sync_engine(e);
+    if (rc) return rc;
+    unsigned long long c[ADAPTER_COUNTS] = {};
+    if (e->adapter.d_counts) HIP_TRY(hipMemcpy(c, e->adapter.d_counts, sizeof c, hipMemcpyDeviceToHost));
+    out->reads = c[ADAPTER_READS]; out->found_first = c[ADAPTER_FOUND_FIRST]; out->found_second = c[ADAPTER_FOUND_SECOND];
+    out->full = c[ADAPTER_FULL]; out->partial = c[ADAPTER_PARTIAL]; out->bases_behind = c[ADAPTER_BASES_BEHIND];
+    if (reset && e->adapter.d_counts) HIP_TRY(hipMemset(e->adapter.d_counts, 0, sizeof c));
+    return KBBQ_OK;
+}
+
+}  // extern "C"

@@ -258,6 +258,16 @@ struct TrimState {
     }
 };
 
+// 3' adapter removal (include/kbbq_engine.h: kbbq_adapter_find_batch; engine_adapter.h): the kbbq_adapter_counts of
+// k_adapter_find.  Allocated by the first search, as the trim counters are by the first trimming call
+struct AdapterState {
+    unsigned long long *d_counts = nullptr;
+    int reset(hipStream_t stream) {
+        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 6 * 8, stream));      // (ADAPTER_COUNTS words: adapter.h)
+        return KBBQ_OK;
+    }
+};
+
 // Host batches: a ring of device staging slots owned by the engine and a copy stream.  A host batch is copied
 // into the next slot with hipMemcpyAsync on the copy stream (DMA straight from the caller's memory when that is
 // page-locked), the pass's kernels wait for the copy by event, and the entry point returns as soon as the COPY
@@ -347,6 +357,7 @@ struct kbbq_engine {
     Pass4State p4;
     ReportState rep;
     TrimState trim;
+    AdapterState adapter;
     Staging stage;
     Buckets bk;
     Profile profile;

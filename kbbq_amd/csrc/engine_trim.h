@@ -1,4 +1,4 @@
-// engine_trim.h -- trimming and filtering reads by the qualities pass 4 wrote (include/kbbq_engine.h: kbbq_trim_batch,
+// engine_trim.h -- trimming and filtering reads by the qualities pass 4 wrote (include/kbbq_engine.h: kbbq_trim_batch, kbbq_trim_batch_limited,
 // kbbq_trim_mates, kbbq_trim_counts_get): the launches of trim.h's two kernels and the counters.  Part of engine.hip; behind
 // engine_correct.h, so that every kernel before it keeps its place in the code object.
 #pragma once
@@ -27,6 +27,11 @@ int trim_state(kbbq_engine *e) {
 extern "C" {
 
 int kbbq_trim_batch(kbbq_engine *e, const kbbq_reads *reads, const uint8_t *device_qual, const kbbq_trim_params *p, uint32_t *keep) {
+    return kbbq_trim_batch_limited(e, reads, device_qual, p, nullptr, keep);
+}
+
+int kbbq_trim_batch_limited(kbbq_engine *e, const kbbq_reads *reads, const uint8_t *device_qual, const kbbq_trim_params *p, const uint32_t *limit,
+                            uint32_t *keep) {
     ENGINE_DEVICE(e);
     if (!reads || !device_qual || !p || !keep) return fail(KBBQ_EINVAL, "null argument");
     if (!reads->on_device) return fail(KBBQ_EINVAL, "not a device batch");
@@ -42,7 +47,7 @@ int kbbq_trim_batch(kbbq_engine *e, const kbbq_reads *reads, const uint8_t *devi
     P.min_len = (uint32_t)std::max<uint64_t>(1, p->min_length);
     P.ee_bound = p->ee_bound;
     Timed t(e, "k_trim_reads");
-    hipLaunchKernelGGL(k_trim_reads, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, device_qual, P, e->trim.d_ee, keep, e->trim.d_counts);
+    hipLaunchKernelGGL(k_trim_reads, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, device_qual, P, e->trim.d_ee, limit, keep, e->trim.d_counts);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }

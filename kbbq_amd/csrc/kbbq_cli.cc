@@ -53,6 +53,10 @@
 //     records written to a file of its own, or one input whose records alternate; second-in-pair is then the file's or the
 //     ordinal's word instead of the "/2" name suffix that the reference alone knows (readutils.cc:74-97, still the default), and
 //     the run checks on the GPU that the pairs are in step.  Through the device reader only; without them nothing changes;
+//   * --trim-tail Q, --min-length L and --max-ee E cut and drop the output's reads by the qualities that are written, and
+//     --adapter SEQ|NAME (--adapter2 for the second-in-pair reads, --adapter-min-overlap N, --adapter-error-rate R) finds the 3'
+//     adapter a read runs on into, on the GPU, and has that cut start in front of it (cli_trim.h).  FASTQ through the device
+//     reader only; without them nothing changes;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -96,6 +100,7 @@ using namespace kbbq;
 
 // (headers of this unit alone, in this order: each uses what the ones before it define)
 #include "trim_values.h"
+#include "adapter_values.h"
 #include "cli_options.h"
 #include "cli_device_io.h"
 #include "cli_pairs.h"
@@ -1030,6 +1035,7 @@ int main(int argc, char *argv[]) {
             }
         }
         if (!derive_sampling(opt, scan, estimated, p, alpha)) return 1;
+        if (opt.timing && opt.adapter_on()) p.flags |= KBBQ_F_PROFILE;      // (the search kernel's time beside pass 4's, for the timing line)
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
         scan.error_flags.e = e;
         const std::vector<int> devices = device_list(opt, scan);
@@ -1120,6 +1126,17 @@ int main(int argc, char *argv[]) {
         std::cerr << "[timing] pairs: interleaved; key kernel " << dev_in.pair_keys_ms() << " ms, " << scan.pairs.checks << " checks " << scan.pairs.ms_check << " ms" << std::endl;
     if (trim && clock.on)
         std::cerr << "[timing] trim: sizes + scan of the trimmed records " << trim_run.ms_sizes << " ms (their text kernels are in the writer's format time)" << std::endl;
+    if (trim && clock.on && opt.adapter_on()) {
+        kbbq_profile_entry prof[256];
+        int32_t n = 0;
+        double ms_find = 0, ms_recal = 0;
+        if (kbbq_engine_sync(e) == 0 && kbbq_profile_get(e, prof, 256, &n) == 0)
+            for (int32_t i = 0; i < n && i < 256; ++i) {
+                if (!strcmp(prof[i].name, "k_adapter_find")) ms_find = prof[i].total_ms;
+                if (!strcmp(prof[i].name, "k_recalibrate")) ms_recal = prof[i].total_ms;
+            }
+        std::cerr << "[timing] adapter: k_adapter_find " << ms_find << " ms beside k_recalibrate " << ms_recal << " ms, every launch of the run" << std::endl;
+    }
     trim_run.release();      // (before the engine goes: end_run may not come back)
     if (!opt.report.empty())
         if (const int bad = write_quality_report(e, opt, scan.groups.names(), nullptr, p.seed, scan.seqlen)) return bad;

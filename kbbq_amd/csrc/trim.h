@@ -55,8 +55,10 @@ __device__ __forceinline__ bool trim_round(int d, bool valid, int first_i, int l
 
 // One wavefront per read, four per workgroup.  Sums stay below 2^31: |Q - q| <= 255 and a read has fewer than 2^23 bases.
 // The counters are kept per wavefront, added up per workgroup in LDS and added to the engine's once per workgroup.
+// limit (optional): the rule runs on the read's first min(len, limit[r]) qualities (kbbq_trim_batch_limited: the end a 3'
+// adapter search found); the read still counts with its own length, and as shortened when less than that is kept.
 __global__ void __launch_bounds__(256) k_trim_reads(ReadsDev R, const uint8_t *qual, TrimDev P, const unsigned long long *ee_table,
-                                                    uint32_t *keep, unsigned long long *counts) {
+                                                    const uint32_t *limit, uint32_t *keep, unsigned long long *counts) {
     __shared__ unsigned long long ee[256];
     __shared__ unsigned long long tot[4][TRIM_WITH_MATE];
     ee[threadIdx.x] = ee_table[threadIdx.x];
@@ -71,8 +73,8 @@ __global__ void __launch_bounds__(256) k_trim_reads(ReadsDev R, const uint8_t *q
         uint32_t len;
         read_span(R, r, off, len);
         const uint8_t *q = qual + off;
-        const int n = (int)len;
-        uint32_t kept = len;
+        const int n = (int)(limit ? min(len, limit[r]) : len);
+        uint32_t kept = (uint32_t)n;
         uint64_t sum = 0;
         if (n <= kTrimRegRounds * 64) {
             uint32_t qv[kTrimRegRounds];

@@ -275,10 +275,11 @@ class Engine:
         return dict(flagged=int(c.flagged), fixed=int(c.fixed), ambiguous=int(c.ambiguous), unsupported=int(c.unsupported))
 
     # ---- trimming and filtering by the qualities pass 4 wrote
-    def trim_reads(self, dreads, qual_ptr, tail_q=None, min_length=1, max_ee=None):
+    def trim_reads(self, dreads, qual_ptr, tail_q=None, min_length=1, max_ee=None, limit=None):
         """kbbq_trim_batch on a device batch (DeviceReads) and the device array of its written qualities: the kept length of
         every read, 0 for a dropped one, as a NumPy uint32 array.  tail_q: the 3' cut's threshold (None: no cut); max_ee:
-        the most expected errors a kept read may carry (None: no bound).  Waits for the kernel."""
+        the most expected errors a kept read may carry (None: no bound); limit: one length per read (find_adapters'
+        result), the rule then runs on that prefix of the read (kbbq_trim_batch_limited).  Waits for the kernel."""
         import torch
         p = _lib.TrimParams()
         p.tail_q = 0 if tail_q is None else int(tail_q)
@@ -289,10 +290,43 @@ class Engine:
         p.ee_bound = 0 if max_ee is None else ee_bound(max_ee)
         dev = "cuda:%d" % self.params.device
         d_keep = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
+        d_limit = None
+        if limit is not None:
+            lim = np.ascontiguousarray(limit, dtype=np.uint32)
+            assert len(lim) == dreads.n_reads, "limit: one length per read"
+            d_limit = torch.from_numpy(lim.view(np.int32).copy()).to(dev)
         torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        _lib.check(self.L.kbbq_trim_batch(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), d_keep.data_ptr()))
+        if d_limit is None:
+            _lib.check(self.L.kbbq_trim_batch(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), d_keep.data_ptr()))
+        else:
+            _lib.check(self.L.kbbq_trim_batch_limited(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), d_limit.data_ptr(), d_keep.data_ptr()))
         self.sync()
         return d_keep.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
+
+    # ---- 3' adapters: where each read runs on into the adapter
+    def find_adapters(self, dreads, first, second=None, min_overlap=5, max_error_permille=100):
+        """kbbq_adapter_find_batch on a device batch (DeviceReads): the limit of every read -- the start of the leftmost
+        match of its adapter, or its length -- as a NumPy uint32 array.  first, second: text (parse_adapter) or an
+        _lib.Adapter; second-in-pair reads are searched for `second` when one is given.  Waits for the kernel."""
+        import torch
+        p = _lib.AdapterParams()
+        p.first = first if isinstance(first, _lib.Adapter) else parse_adapter(first)
+        if second is not None:
+            p.second = second if isinstance(second, _lib.Adapter) else parse_adapter(second)
+        p.min_overlap = int(min_overlap)
+        p.max_error_permille = int(max_error_permille)
+        dev = "cuda:%d" % self.params.device
+        d_limit = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_adapter_find_batch(self.h, self._c(dreads), ctypes.byref(p), d_limit.data_ptr()))
+        self.sync()
+        return d_limit.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
+
+    def adapter_counts(self, reset=False):
+        """What find_adapters did since the last reset (waits): the fields of kbbq_adapter_counts."""
+        c = _lib.AdapterCounts()
+        _lib.check(self.L.kbbq_adapter_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
+        return {n: int(getattr(c, n)) for n, _ in _lib.AdapterCounts._fields_}
 
     def trim_mates(self, keep_a, keep_b=None, adjacent=False):
         """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
@@ -613,6 +647,14 @@ def host_train(cov):
     d.n_rg, d.n_cycle = R, C
     d.meanq, d.rgdq, d.qdq, d.cycledq, d.dinucdq = (out[k].ctypes.data for k in ("meanq", "rg", "q", "cycle", "dinuc"))
     _lib.check(_lib.lib().kbbq_host_train(ctypes.byref(c), ctypes.byref(d)))
+    return out
+
+
+def parse_adapter(text):
+    """An adapter from its text (kbbq_adapter_parse): 4 to 64 letters of ACGT in either case, or illumina, nextera or smallrna;
+    an _lib.Adapter whose code is the sequence in the layout of a batch's bases.  No GPU is touched."""
+    out = _lib.Adapter()
+    _lib.check(_lib.lib().kbbq_adapter_parse(text.encode() if isinstance(text, str) else bytes(text), ctypes.byref(out)))
     return out
 
 
