@@ -409,6 +409,46 @@ int kbbq_trim_batch_limited(kbbq_engine *e, const kbbq_reads *device_reads, cons
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset);
 
+/* ---- adapters from the overlap of a read pair: where both mates run off the insert ---------------------------
+ * When the insert is shorter than a read, the two mates are reverse complements of each other over the insert, and whatever
+ * stands behind it is adapter, of whichever kit.  The rule is this project's own, exact and all
+ * integers, without indels.  A pair is two reads of the packed batch: read 1 has n1 bases with codes c1[0..n1) and N bits
+ * u1[0..n1), read 2 has n2, c2, u2; A C G T = 0 1 2 3, so the complement of c is 3 - c.  V = min_overlap, D = max_diff,
+ * t = max_error_permille.  For an insert length L:
+ *     lo(L) = max(0, L - n2)      hi(L) = min(n1, L)      o(L) = hi(L) - lo(L)
+ *     mm(L) = #{ i in [lo, hi) : u1[i] or u2[L-1-i] or c1[i] != 3 - c2[L-1-i] }
+ *     hit(L)  iff  o(L) >= V  and  mm(L) <= D  and  mm(L) * 1000 <= o(L) * t
+ * The candidates are L = V .. n1 + n2 - V (a pair with n1 + n2 < 2V has none).  Among the hits L* is the one with the largest
+ * overlap o(L); among hits of equal overlap the larger L wins, so a hit that cuts nothing beats an equally good one that cuts.
+ * With a hit limit1 = min(n1, L*) and limit2 = min(n2, L*); with none limit1 = n1 and limit2 = n2.  The rule is symmetric in
+ * the two reads: which one carries the second-in-pair flag does not matter.  A base with its N bit is a mismatch whatever its
+ * code says, a lower-case letter has its folded code, and the search reads the bases as the sequencer read them (with
+ * kbbq_correct_batch the fixes take no part): the conventions of the adapter rule above.  An insert shorter than V is not
+ * found (an adapter dimer, say): that is what kbbq_adapter_find_batch is for, and a read's limit may be the smaller of the two.
+ * A pair in which either read has more than KBBQ_OVERLAP_MAX_READ bases is not searched: its limits are its lengths, and it
+ * is counted in too_long and not in pairs. */
+#define KBBQ_OVERLAP_MAX_READ 512
+#define KBBQ_OVERLAP_MIN 8
+typedef struct kbbq_overlap_params {
+    int32_t min_overlap;            /* KBBQ_OVERLAP_MIN..KBBQ_OVERLAP_MAX_READ */
+    int32_t max_diff;               /* 0..KBBQ_OVERLAP_MAX_READ */
+    int32_t max_error_permille;     /* 0..500 */
+    int32_t merge;                  /* != 0: the arrays hold limits already, and each becomes the smaller of the two */
+} kbbq_overlap_params;
+/* Sums since the last reset, of the rule's own limits whatever merge says.  pairs: the pairs searched (pairs + too_long = the
+ * pairs given); overlapping: those with a hit; short_insert: those with L* < max(n1, n2); reads_cut: reads with limit < n;
+ * bases_behind: the sum of n - limit. */
+typedef struct kbbq_overlap_counts { uint64_t pairs, overlapping, short_insert, reads_cut, bases_behind, too_long; } kbbq_overlap_counts;
+/* Pair j, j < n_pairs, is read first_a + j * stride of device batch a and read first_b + j * stride of device batch b, which may
+ * be the same batch; its limits go to limit_a[j * stride] and limit_b[j * stride] (device).  stride is 1 (two files: a run of
+ * pairs that lies in one batch of each) or 2 (interleaved: a == b, first_b = first_a + 1; a pair that straddles two batches
+ * is n_pairs = 1).  Queued on the engine's stream.  KBBQ_EINVAL for a null argument, a host batch, another stride, a pair
+ * behind either batch's n_reads or a parameter out of range. */
+int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
+                            uint64_t stride, uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b);
+/* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
+int kbbq_overlap_counts_get(kbbq_engine *e, kbbq_overlap_counts *out, int32_t reset);
+
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]
  *   cycle [n_rg][256][2][max_read_len][2]   (third index: 0 first-in-pair, 1 second)

@@ -107,6 +107,14 @@ class AdapterCounts(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("reads", "found_first", "found_second", "full", "partial", "bases_behind")]
 
 
+class OverlapParams(ctypes.Structure):
+    _fields_ = [("min_overlap", ctypes.c_int32), ("max_diff", ctypes.c_int32), ("max_error_permille", ctypes.c_int32), ("merge", ctypes.c_int32)]
+
+
+class OverlapCounts(ctypes.Structure):
+    _fields_ = [(n, c_u64) for n in ("pairs", "overlapping", "short_insert", "reads_cut", "bases_behind", "too_long")]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -167,6 +175,9 @@ SYMBOLS = {
     "kbbq_adapter_find_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.POINTER(AdapterParams), c_vp]),
     "kbbq_trim_batch_limited": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp]),
     "kbbq_adapter_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(AdapterCounts), ctypes.c_int32]),
+    "kbbq_pair_overlap_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64,
+                                               ctypes.POINTER(OverlapParams), c_vp, c_vp]),
+    "kbbq_overlap_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(OverlapCounts), ctypes.c_int32]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),

@@ -34,6 +34,9 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     // the 3' adapter the reads run on into, searched on the GPU before that cut (cli_trim.h); --adapter turns trimming on
     {"adapter", required_argument, 0, 1014}, {"adapter2", required_argument, 0, 1015}, {"adapter-min-overlap", required_argument, 0, 1016},
     {"adapter-error-rate", required_argument, 0, 1017},
+    // the adapters both mates of a pair run on into behind a short insert, from the overlap of the two (cli_trim.h); turns trimming on
+    {"pair-overlap", no_argument, 0, 1018}, {"pair-overlap-min", required_argument, 0, 1019}, {"pair-overlap-diff", required_argument, 0, 1020},
+    {"pair-overlap-error-rate", required_argument, 0, 1021},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -117,6 +120,13 @@ struct CliOptions {
     kbbq_adapter_params adapter = {{{0, 0}, 0, 0}, {{0, 0}, 0, 0}, 0, 100};
     const char *adapter_tuning = nullptr;   // the first of --adapter2 and the two tuning options that was given
     bool adapter_on() const { return adapter.first.len != 0; }
+    // --pair-overlap: the mates of every pair are laid over each other (include/kbbq_engine.h: kbbq_pair_overlap_batch), and where
+    // the insert is shorter than a read both end at the insert's length: the rule above runs on what stands in front, the smaller
+    // of this and --adapter's limit; alone it cuts with no --trim-tail and --min-length 1.  Needs --in2/--out2 or --interleaved.
+    // --pair-overlap-min N (default 30), --pair-overlap-diff D (5), --pair-overlap-error-rate R (0.2): fastp's defaults
+    kbbq_overlap_params overlap = {30, 5, 200, 1};
+    bool pair_overlap = false;
+    const char *overlap_tuning = nullptr;   // the first of the three tuning options that was given
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -334,6 +344,25 @@ struct CliOptions {
                         return !give_up(std::string(" Error: --adapter-error-rate takes a decimal of at most three places in 0..0.5, not \"") + optarg + "\".");
                     if (!adapter_tuning) adapter_tuning = "--adapter-error-rate";
                     break;
+                case 1018:
+                    pair_overlap = true;
+                    if (!trim_option) trim_option = "--pair-overlap";
+                    break;
+                case 1019:
+                case 1020: {
+                    uint64_t v = 0;
+                    if (!trim_parse_integer(optarg, opt == 1019 ? KBBQ_OVERLAP_MIN : 0, KBBQ_OVERLAP_MAX_READ, &v))
+                        return !give_up(std::string(" Error: ") + (opt == 1019 ? "--pair-overlap-min" : "--pair-overlap-diff") + " takes an integer in " +
+                                        std::to_string(opt == 1019 ? KBBQ_OVERLAP_MIN : 0) + ".." + std::to_string(KBBQ_OVERLAP_MAX_READ) + ", not \"" + optarg + "\".");
+                    (opt == 1019 ? overlap.min_overlap : overlap.max_diff) = (int32_t)v;
+                    if (!overlap_tuning) overlap_tuning = opt == 1019 ? "--pair-overlap-min" : "--pair-overlap-diff";
+                    break;
+                }
+                case 1021:
+                    if (!adapter_parse_error_rate(optarg, &overlap.max_error_permille))
+                        return !give_up(std::string(" Error: --pair-overlap-error-rate takes a decimal of at most three places in 0..0.5, not \"") + optarg + "\".");
+                    if (!overlap_tuning) overlap_tuning = "--pair-overlap-error-rate";
+                    break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -358,6 +387,10 @@ struct CliOptions {
                 return !give_up(" Error: --adapter-min-overlap " + std::to_string(adapter.min_overlap) + " is more than the " + std::to_string(shortest) +
                                 " bases of the shortest adapter given.");
         }
+        if (overlap_tuning && !pair_overlap)
+            return !give_up(std::string(" Error: ") + overlap_tuning + " without --pair-overlap: it says how the overlap of a pair's mates is searched.");
+        if (pair_overlap && !paired_files() && !interleaved)
+            return !give_up(" Error: --pair-overlap without --in2/--out2 or --interleaved: it lays the mates of a pair over each other, and those say where the mates are.");
         if (trim_on()) {
             if (!trim.min_length) trim.min_length = 1;
             if (const char *why = trim_refusal()) return !give_up(std::string(" Error: ") + trim_option + " with " + why + ".");

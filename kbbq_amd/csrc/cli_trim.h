@@ -16,6 +16,13 @@
 //
 // One array of kept lengths per input file, indexed by the record's ordinal in its file: 4 bytes a read.  The two files'
 // chunks are cut where their own bytes say, and the mate rule does not have to care where.
+//
+// --pair-overlap (a paired run always): one array of limits per input file beside the kept lengths, indexed alike.  The
+// pre-pass first fills it -- --adapter's search of every batch writes there at the batch's ordinal in place of the scratch
+// array, then the overlap of every pair (kbbq_pair_overlap_batch) takes the smaller of that and its own (overlaps()) -- and then
+// recalibrates batch by batch and runs the rule in front of file_limit + ordinal.  The mates of a pair may lie in different
+// batches: two files are walked side by side, a run of pairs per call that lies in one batch of each, and an interleaved chunk
+// that ends between two mates gives one call for that pair.  Once per read, both searches, and the write loop repeats neither.
 #pragma once
 
 struct TrimRun {
@@ -24,6 +31,9 @@ struct TrimRun {
     kbbq_adapter_params adapter = {{{0, 0}, 0, 0}, {{0, 0}, 0, 0}, 0, 0};      // (first.len == 0: no --adapter)
     uint32_t *limit = nullptr;                   // device scratch: the adapter limits of the batch in hand, grown to the largest batch
     uint64_t limit_reads = 0;
+    kbbq_overlap_params overlap = {0, 0, 0, 0};
+    bool overlap_on = false;                     // --pair-overlap
+    uint32_t *file_limit[2] = {nullptr, nullptr};      // device, --pair-overlap: the limits of each input's records, by ordinal like keep[]
     bool on = false, paired = false, have_verdicts = false;
     uint32_t *keep[2] = {nullptr, nullptr};      // device: the kept lengths of the first (or only) input's records and of --in2's
     uint64_t n[2] = {0, 0};
@@ -35,6 +45,10 @@ struct TrimRun {
     ~TrimRun() { release(); }
     void release() {
         for (uint32_t *&k : keep) {
+            if (k) kbbq_device_free(e, k);
+            k = nullptr;
+        }
+        for (uint32_t *&k : file_limit) {
             if (k) kbbq_device_free(e, k);
             k = nullptr;
         }
@@ -60,6 +74,68 @@ struct TrimRun {
                                " reads (4 bytes each) do not fit in GPU memory beside the reads and the filters.");
             }
             keep[f] = (uint32_t *)p;
+        }
+        overlap = o.overlap;
+        overlap_on = o.pair_overlap;
+        for (int f = 0; f < 2 && overlap_on; ++f) {
+            if (!n[f]) continue;
+            void *p = nullptr;
+            if (kbbq_device_alloc(e, n[f] * 4, &p) < 0) {
+                release();
+                return give_up(" Error: --pair-overlap: the limits of " + std::to_string(n[0] + n[1]) +
+                               " reads (4 bytes each) do not fit in GPU memory beside the reads and the filters.");
+            }
+            file_limit[f] = (uint32_t *)p;
+        }
+        return 0;
+    }
+    // --pair-overlap: every read's limit into file_limit[], before any verdict -- --adapter's search of every batch, then the
+    // overlap of every pair, the smaller of the two where both ran
+    int overlaps(const std::vector<kbbq_reads> &batches, size_t in2_first_batch, bool two_files) {
+        uint64_t ordinal[2] = {0, 0};
+        std::vector<const kbbq_reads *> of[2];      // the batches of each file that hold reads
+        std::vector<uint64_t> at[2];                // ... and the ordinal of their first record
+        for (size_t bi = 0; bi < batches.size(); ++bi) {
+            const int f = two_files && bi >= in2_first_batch ? 1 : 0;
+            const kbbq_reads &d = batches[bi];
+            if (!d.n_reads) continue;
+            if (ordinal[f] + d.n_reads > n[f]) return give_up(" Error: the input changed between the passes.");
+            if (adapter.first.len && kbbq_adapter_find_batch(e, &d, &adapter, file_limit[f] + ordinal[f]) < 0) return fail_engine("searching the adapters");
+            of[f].push_back(&d);
+            at[f].push_back(ordinal[f]);
+            ordinal[f] += d.n_reads;
+        }
+        if (ordinal[0] != n[0] || ordinal[1] != n[1]) return give_up(" Error: the input changed between the passes.");
+        if (two_files && n[0] != n[1]) return give_up(" Error: --in2: the files are not in step.");      // (the scan has checked it)
+        if (!two_files && (n[0] & 1)) return give_up(" Error: --interleaved: an odd number of reads.");     // (the scan has checked it)
+        kbbq_overlap_params p = overlap;
+        p.merge = adapter.first.len ? 1 : 0;      // (without --adapter the arrays hold nothing yet)
+        if (two_files) {
+            // side by side: as many pairs a call as are left in the batch in hand of either file
+            size_t ia = 0, ib = 0;
+            uint64_t pa = 0, pb = 0, done = 0;
+            while (ia < of[0].size() && ib < of[1].size()) {
+                const uint64_t take = std::min(of[0][ia]->n_reads - pa, of[1][ib]->n_reads - pb);
+                if (kbbq_pair_overlap_batch(e, of[0][ia], pa, of[1][ib], pb, 1, take, &p, file_limit[0] + done, file_limit[1] + done) < 0)
+                    return fail_engine("searching the pairs' overlaps");
+                done += take;
+                if ((pa += take) == of[0][ia]->n_reads) { ++ia; pa = 0; }
+                if ((pb += take) == of[1][ib]->n_reads) { ++ib; pb = 0; }
+            }
+            return 0;
+        }
+        // interleaved: record 2k and record 2k + 1 are mates, and a batch may begin with a second mate or end with a first one
+        for (size_t i = 0; i < of[0].size(); ++i) {
+            const kbbq_reads &d = *of[0][i];
+            const uint64_t first = at[0][i] & 1;      // (1: read 0 is the mate of the batch before's last read, searched with that batch)
+            const uint64_t inside = (d.n_reads - first) / 2;
+            uint32_t *lim = file_limit[0] + at[0][i];
+            if (inside && kbbq_pair_overlap_batch(e, &d, first, &d, first + 1, 2, inside, &p, lim + first, lim + first + 1) < 0)
+                return fail_engine("searching the pairs' overlaps");
+            if ((d.n_reads - first) & 1) {      // the last read's mate is the next batch's read 0 (there is one: the reads are even in number)
+                if (kbbq_pair_overlap_batch(e, &d, d.n_reads - 1, of[0][i + 1], 0, 1, 1, &p, lim + d.n_reads - 1, lim + d.n_reads) < 0)
+                    return fail_engine("searching the pairs' overlaps");
+            }
         }
         return 0;
     }
@@ -87,12 +163,18 @@ struct TrimRun {
     template <class Slots>
     int verdicts(Slots &slots, DeviceBgzfWriter &out, const std::vector<kbbq_reads> &batches, size_t in2_first_batch, bool two_files, bool report_on) {
         if (report_on && kbbq_report_enable(e, 0) < 0) return fail_engine("trimming");
+        if (overlap_on)
+            if (const int rc = overlaps(batches, in2_first_batch, two_files)) return rc;
         uint64_t ordinal[2] = {0, 0};
         for (size_t bi = 0; bi < batches.size(); ++bi) {
             const int f = two_files && bi >= in2_first_batch ? 1 : 0;
             const uint8_t *q = nullptr;
             if (const int rc = slots.recalibrate(out, 0, batches[bi], &q)) return rc;      // (one slot: the kernels run in order on the engine's stream)
-            if (const int rc = batch(f, ordinal[f], batches[bi], q)) return rc;
+            if (!overlap_on) {
+                if (const int rc = batch(f, ordinal[f], batches[bi], q)) return rc;
+            } else if (batches[bi].n_reads) {      // (the limits are there already: overlaps() has checked the ordinals)
+                if (kbbq_trim_batch_limited(e, &batches[bi], q, &params, file_limit[f] + ordinal[f], keep[f] + ordinal[f]) < 0) return fail_engine("trimming");
+            }
             ordinal[f] += batches[bi].n_reads;
         }
         if (ordinal[0] != n[0] || ordinal[1] != n[1]) return give_up(" Error: the input changed between the passes.");
@@ -124,6 +206,13 @@ struct TrimRun {
             std::cerr << put_now << " Adapters: " << a.reads << " reads searched, " << a.found_first << " with the first adapter, " << a.found_second
                       << " with the second, " << a.full << " whole, " << a.partial << " running off the end; bases: " << a.bases_behind << " from the adapter on."
                       << std::endl;
+        }
+        if (overlap_on) {
+            kbbq_overlap_counts c2;
+            if (kbbq_overlap_counts_get(e, &c2, 0) < 0) return fail_engine("searching the pairs' overlaps");
+            std::cerr << put_now << " Pair overlaps: " << c2.pairs << " pairs searched, " << c2.overlapping << " overlapping, " << c2.short_insert
+                      << " with an insert shorter than a read, " << c2.reads_cut << " reads cut, " << c2.too_long << " too long to search; bases: "
+                      << c2.bases_behind << " behind the insert." << std::endl;
         }
         return 0;
     }

@@ -268,6 +268,16 @@ struct AdapterState {
     }
 };
 
+// Adapters from the overlap of a pair (include/kbbq_engine.h: kbbq_pair_overlap_batch; engine_overlap.h): the
+// kbbq_overlap_counts of k_pair_overlap.  Allocated by the first search
+struct OverlapState {
+    unsigned long long *d_counts = nullptr;
+    int reset(hipStream_t stream) {
+        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 6 * 8, stream));      // (OVERLAP_COUNTS words: overlap.h)
+        return KBBQ_OK;
+    }
+};
+
 // Host batches: a ring of device staging slots owned by the engine and a copy stream.  A host batch is copied
 // into the next slot with hipMemcpyAsync on the copy stream (DMA straight from the caller's memory when that is
 // page-locked), the pass's kernels wait for the copy by event, and the entry point returns as soon as the COPY
@@ -358,6 +368,7 @@ struct kbbq_engine {
     ReportState rep;
     TrimState trim;
     AdapterState adapter;
+    OverlapState overlap;
     Staging stage;
     Buckets bk;
     Profile profile;

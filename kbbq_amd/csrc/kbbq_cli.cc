@@ -55,8 +55,10 @@
 //     the run checks on the GPU that the pairs are in step.  Through the device reader only; without them nothing changes;
 //   * --trim-tail Q, --min-length L and --max-ee E cut and drop the output's reads by the qualities that are written, and
 //     --adapter SEQ|NAME (--adapter2 for the second-in-pair reads, --adapter-min-overlap N, --adapter-error-rate R) finds the 3'
-//     adapter a read runs on into, on the GPU, and has that cut start in front of it (cli_trim.h).  FASTQ through the device
-//     reader only; without them nothing changes;
+//     adapter a read runs on into, on the GPU, and has that cut start in front of it (cli_trim.h); --pair-overlap (--pair-overlap-min
+//     N, --pair-overlap-diff D, --pair-overlap-error-rate R) finds whatever adapter stands behind an insert shorter than the
+//     reads from the overlap of a pair's mates, with --in2 or --interleaved.  FASTQ through the device reader only; without them
+//     nothing changes;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -1035,7 +1037,7 @@ int main(int argc, char *argv[]) {
             }
         }
         if (!derive_sampling(opt, scan, estimated, p, alpha)) return 1;
-        if (opt.timing && opt.adapter_on()) p.flags |= KBBQ_F_PROFILE;      // (the search kernel's time beside pass 4's, for the timing line)
+        if (opt.timing && (opt.adapter_on() || opt.pair_overlap)) p.flags |= KBBQ_F_PROFILE;      // (the search kernels' time beside pass 4's, for the timing lines)
         if (kbbq_engine_create(&p, &e) < 0) return fail_engine("cannot create the engine");
         scan.error_flags.e = e;
         const std::vector<int> devices = device_list(opt, scan);
@@ -1136,6 +1138,16 @@ int main(int argc, char *argv[]) {
                 if (!strcmp(prof[i].name, "k_recalibrate")) ms_recal = prof[i].total_ms;
             }
         std::cerr << "[timing] adapter: k_adapter_find " << ms_find << " ms beside k_recalibrate " << ms_recal << " ms, every launch of the run" << std::endl;
+    }
+    if (trim && clock.on && opt.pair_overlap) {
+        kbbq_profile_entry prof[256];
+        int32_t n = 0;
+        double ms_find = 0;
+        uint64_t launches = 0;
+        if (kbbq_engine_sync(e) == 0 && kbbq_profile_get(e, prof, 256, &n) == 0)
+            for (int32_t i = 0; i < n && i < 256; ++i)
+                if (!strcmp(prof[i].name, "k_pair_overlap")) { ms_find = prof[i].total_ms; launches = prof[i].launches; }
+        std::cerr << "[timing] pair overlap: k_pair_overlap " << ms_find << " ms in " << launches << " launches" << std::endl;
     }
     trim_run.release();      // (before the engine goes: end_run may not come back)
     if (!opt.report.empty())

@@ -328,6 +328,45 @@ class Engine:
         _lib.check(self.L.kbbq_adapter_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
         return {n: int(getattr(c, n)) for n, _ in _lib.AdapterCounts._fields_}
 
+    # ---- adapters from the overlap of a pair: where both mates run off the insert
+    def find_pair_overlaps(self, dev_a, dev_b, first_a=0, first_b=0, stride=1, n_pairs=None, min_overlap=30, max_diff=5, max_error_permille=200,
+                           limit_a=None, limit_b=None):
+        """kbbq_pair_overlap_batch on two device batches (DeviceReads; the same one twice for an interleaved batch): pair j is
+        read first_a + j * stride of dev_a and read first_b + j * stride of dev_b; n_pairs: None for as many as both batches
+        hold from there.  The limits of every pair's two reads -- the insert's length where the mates overlap in a shorter
+        insert than the read, else the read's length -- as two NumPy uint32 arrays of n_pairs entries.  limit_a, limit_b:
+        limits the reads have already (one per pair, both or neither); each result is then the smaller of the two (merge).
+        Waits for the kernel."""
+        import torch
+        stride = int(stride)
+        if n_pairs is None:
+            step = stride if stride > 0 else 1
+            n_pairs = max(0, min((dev_a.n_reads - first_a + step - 1) // step, (dev_b.n_reads - first_b + step - 1) // step))
+        n_pairs = int(n_pairs)
+        assert (limit_a is None) == (limit_b is None), "limit_a and limit_b: both or neither"
+        p = _lib.OverlapParams(int(min_overlap), int(max_diff), int(max_error_permille), 0 if limit_a is None else 1)
+        dev = "cuda:%d" % self.params.device
+        words = max(1, (n_pairs - 1) * max(stride, 1) + 1) if n_pairs else 1
+        d_lim = []
+        for given in (limit_a, limit_b):
+            host = np.zeros(words, np.uint32)
+            if given is not None:
+                lim = np.ascontiguousarray(given, dtype=np.uint32)
+                assert len(lim) == n_pairs, "limit_a, limit_b: one length per pair"
+                host[::max(stride, 1)][:n_pairs] = lim
+            d_lim.append(torch.from_numpy(host.view(np.int32)).to(dev))
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_pair_overlap_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, ctypes.byref(p),
+                                                  d_lim[0].data_ptr(), d_lim[1].data_ptr()))
+        self.sync()
+        return tuple(d.cpu().numpy().view(np.uint32)[::max(stride, 1)][:n_pairs].copy() for d in d_lim)
+
+    def overlap_counts(self, reset=False):
+        """What find_pair_overlaps did since the last reset (waits): the fields of kbbq_overlap_counts."""
+        c = _lib.OverlapCounts()
+        _lib.check(self.L.kbbq_overlap_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
+        return {n: int(getattr(c, n)) for n, _ in _lib.OverlapCounts._fields_}
+
     def trim_mates(self, keep_a, keep_b=None, adjacent=False):
         """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
         (a, b), or a alone with adjacent=True, where the pairs are a[2i], a[2i+1].  Waits for the kernel."""
