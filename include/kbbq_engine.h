@@ -448,6 +448,52 @@ int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_
                             uint64_t stride, uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b);
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_overlap_counts_get(kbbq_engine *e, kbbq_overlap_counts *out, int32_t reset);
+/* kbbq_pair_overlap_batch -- the same limits, the same counts -- that also hands out the insert length: insert[j] (device,
+ * n_pairs words, one per pair whatever the stride) = L* of pair j, or 0 where the pair has no hit or was not searched (too
+ * long).  The limits lose L* once it is larger than a read; the rule below needs it. */
+int kbbq_pair_overlap_inserts(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
+                              uint64_t stride, uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b,
+                              uint32_t *insert);
+
+/* ---- bases corrected from the mate: inside the overlap every base was sequenced twice -------------------------
+ * The rule is this project's own (fastp's -c is its model), exact and all integers.  A pair has an insert
+ * length L (L* of the overlap rule above; 0: no hit, not searched or too long).  Read 1 has n1 bases, codes c1, N bits u1,
+ * written qualities q1 (what pass 4 is about to write, behind a quality map where one is set) and fix bits f1; read 2 has n2,
+ * c2, u2, q2, f2.  f is the read's fix_mask as it stands when the rule runs: zero everywhere, or kbbq_correct_batch's.
+ * G = good_q and B = bad_q, 1 <= B < G <= 93.  For L > 0 and every i in [max(0, L - n2), min(n1, L)), with k = L - 1 - i:
+ *     if f1[i] or f2[k]:  skipped -- a base the k-mers have fixed keeps its fix and its quality, and votes for nothing
+ *     agree  iff  !u1[i] and !u2[k] and c1[i] == 3 - c2[k]:  nothing changes
+ *     else if !u1[i] and q1[i] >= G and q2[k] <= B:  read 2's base k becomes 3 - c1[i] -- its fix_mask bit is set, its
+ *                                                    fix_bases code is written -- and q2[k] = q1[i]
+ *     else if !u2[k] and q2[k] >= G and q1[i] <= B:  the mirror image, on read 1
+ *     else:  the position stays as it is, and counts as "left"
+ * B < G makes the two corrections exclusive.  An N can lose but never win.  A lower-case letter has its folded code and comes
+ * out upper case when corrected, as with kbbq_correct_batch's fixes.  The bases compared are the bases as the sequencer read
+ * them.  The rule is symmetric in the two reads, and idempotent: behind it the position agrees and both qualities are equal.
+ * A position's outcome depends on that position's values alone, so the call is exact in place, the result does not depend on
+ * how the calls were cut, and a call that writes one side gives that side the bytes a call that writes both gives it. */
+typedef struct kbbq_consensus_params {
+    int32_t good_q;                 /* G: bad_q + 1..93 */
+    int32_t bad_q;                  /* B: 1..good_q - 1 */
+} kbbq_consensus_params;
+/* Sums since the last reset, per written read: reads_changed: reads with a corrected base; bases_corrected; from_n: those of
+ * them that had their N bit; bases_left: bases of a written read that disagree with the mate's and stay (skipped positions are
+ * not counted).  A run that writes every read once has the same sums however its calls were cut. */
+typedef struct kbbq_pair_consensus_counts { uint64_t reads_changed, bases_corrected, from_n, bases_left; } kbbq_pair_consensus_counts;
+/* The pairs are kbbq_pair_overlap_batch's (device batches, first_a, first_b, stride, n_pairs); insert: device, n_pairs words,
+ * what kbbq_pair_overlap_inserts wrote for these pairs (a value the search cannot have written, such as one of n1 + n2 or more,
+ * is taken as 0).  qual_a, qual_b: device, the batches' written qualities in the batches' base order (n_bases bytes; the
+ * array kbbq_recalibrate_batch filled), in and out.  fix_mask_*, fix_bases_*: device, kbbq_correct_batch's arrays for the two
+ * batches (zeroed, or as that call left them), in and out: bits are OR-ed in.  sides: bit 0: a is written, bit 1: b is
+ * written; a side that is not written is only read, and nothing of it is counted.  An interleaved batch: a == b, qual_a ==
+ * qual_b, the same fix arrays twice, stride 2.  Queued on the engine's stream.  KBBQ_EINVAL for a null argument, a host
+ * batch, another stride, a pair behind either batch's n_reads, qualities out of range or sides outside 1..3. */
+int kbbq_pair_consensus_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
+                              uint64_t stride, uint64_t n_pairs, const uint32_t *insert, const kbbq_consensus_params *params,
+                              uint8_t *qual_a, uint8_t *qual_b, uint64_t *fix_mask_a, uint64_t *fix_bases_a, uint64_t *fix_mask_b,
+                              uint64_t *fix_bases_b, int32_t sides);
+/* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
+int kbbq_pair_consensus_counts_get(kbbq_engine *e, kbbq_pair_consensus_counts *out, int32_t reset);
 
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]

@@ -115,6 +115,14 @@ class OverlapCounts(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("pairs", "overlapping", "short_insert", "reads_cut", "bases_behind", "too_long")]
 
 
+class ConsensusParams(ctypes.Structure):
+    _fields_ = [("good_q", ctypes.c_int32), ("bad_q", ctypes.c_int32)]
+
+
+class ConsensusCounts(ctypes.Structure):
+    _fields_ = [(n, c_u64) for n in ("reads_changed", "bases_corrected", "from_n", "bases_left")]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -178,6 +186,11 @@ SYMBOLS = {
     "kbbq_pair_overlap_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64,
                                                ctypes.POINTER(OverlapParams), c_vp, c_vp]),
     "kbbq_overlap_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(OverlapCounts), ctypes.c_int32]),
+    "kbbq_pair_overlap_inserts": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64,
+                                                 ctypes.POINTER(OverlapParams), c_vp, c_vp, c_vp]),
+    "kbbq_pair_consensus_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp,
+                                                 ctypes.POINTER(ConsensusParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
+    "kbbq_pair_consensus_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(ConsensusCounts), ctypes.c_int32]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),

@@ -37,6 +37,8 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     // the adapters both mates of a pair run on into behind a short insert, from the overlap of the two (cli_trim.h); turns trimming on
     {"pair-overlap", no_argument, 0, 1018}, {"pair-overlap-min", required_argument, 0, 1019}, {"pair-overlap-diff", required_argument, 0, 1020},
     {"pair-overlap-error-rate", required_argument, 0, 1021},
+    // inside the overlap that --pair-overlap finds, a base the mate is sure of replaces the one this read is unsure of (cli_trim.h)
+    {"pair-correct", no_argument, 0, 1022}, {"pair-correct-quals", required_argument, 0, 1023},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -127,6 +129,11 @@ struct CliOptions {
     kbbq_overlap_params overlap = {30, 5, 200, 1};
     bool pair_overlap = false;
     const char *overlap_tuning = nullptr;   // the first of the three tuning options that was given
+    // --pair-correct: where the mates disagree inside the overlap and one base has a quality of G or more and the other of B or
+    // less, the second becomes the complement of the first and takes its quality (include/kbbq_engine.h: kbbq_pair_consensus_batch).
+    // --pair-correct-quals G,B (default 30,15: fastp's values)
+    kbbq_consensus_params consensus = {30, 15};
+    bool pair_correct = false, pair_correct_quals = false;
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -363,6 +370,19 @@ struct CliOptions {
                         return !give_up(std::string(" Error: --pair-overlap-error-rate takes a decimal of at most three places in 0..0.5, not \"") + optarg + "\".");
                     if (!overlap_tuning) overlap_tuning = "--pair-overlap-error-rate";
                     break;
+                case 1022:
+                    pair_correct = true;
+                    break;
+                case 1023: {
+                    const char *comma = strchr(optarg, ',');
+                    uint64_t g = 0, b = 0;
+                    if (!comma || !trim_parse_integer(std::string(optarg, (size_t)(comma - optarg)).c_str(), 2, KBBQ_MAXQ, &g) || !trim_parse_integer(comma + 1, 1, KBBQ_MAXQ - 1, &b) || b >= g)
+                        return !give_up(std::string(" Error: --pair-correct-quals takes two integers G,B with 1 <= B < G <= ") + std::to_string(KBBQ_MAXQ) + ", not \"" + optarg + "\".");
+                    consensus.good_q = (int32_t)g;
+                    consensus.bad_q = (int32_t)b;
+                    pair_correct_quals = true;
+                    break;
+                }
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -391,6 +411,10 @@ struct CliOptions {
             return !give_up(std::string(" Error: ") + overlap_tuning + " without --pair-overlap: it says how the overlap of a pair's mates is searched.");
         if (pair_overlap && !paired_files() && !interleaved)
             return !give_up(" Error: --pair-overlap without --in2/--out2 or --interleaved: it lays the mates of a pair over each other, and those say where the mates are.");
+        if (pair_correct_quals && !pair_correct)
+            return !give_up(" Error: --pair-correct-quals without --pair-correct: it says which qualities let a mate's base replace a read's.");
+        if (pair_correct && !pair_overlap)
+            return !give_up(" Error: --pair-correct without --pair-overlap: it corrects inside the overlap that --pair-overlap finds.");
         if (trim_on()) {
             if (!trim.min_length) trim.min_length = 1;
             if (const char *why = trim_refusal()) return !give_up(std::string(" Error: ") + trim_option + " with " + why + ".");

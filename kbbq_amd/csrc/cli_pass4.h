@@ -139,7 +139,7 @@ struct FixSlots {
     void *p[2] = {nullptr, nullptr};
     size_t bytes[2] = {0, 0};
     ~FixSlots() { for (int i = 0; i < 2; ++i) if (p[i]) kbbq_device_free(e, p[i]); }
-    // The fixes of batch d, whose error flags pass 3 left in `errors`, into slot t; call behind QualSlots::recalibrate of the
+    // The fixes of batch d, whose error flags pass 3 left in `errors` (null: zeroed arrays, for --pair-correct without --correct), into slot t; call behind QualSlots::recalibrate of the
     // same batch, which has waited for the writer to be through with the slot.  0 and the two arrays, or the exit status.
     int correct(int t, const kbbq_reads &d, const uint64_t *errors, const uint64_t **mask, const uint64_t **bases) {
         const size_t mask_bytes = (d.n_bases / 64 + 2) * 8, need = mask_bytes + (d.n_bases / 32 + 2) * 8;
@@ -152,7 +152,7 @@ struct FixSlots {
         if (kbbq_device_zero(e, p[t], need) < 0) return fail_engine("correcting");
         *mask = (const uint64_t *)p[t];
         *bases = (const uint64_t *)((const char *)p[t] + mask_bytes);
-        if (kbbq_correct_batch(e, &d, errors, (uint64_t *)*mask, (uint64_t *)*bases) < 0) return fail_engine("correcting");
+        if (errors && kbbq_correct_batch(e, &d, errors, (uint64_t *)*mask, (uint64_t *)*bases) < 0) return fail_engine("correcting");
         return 0;
     }
 };
@@ -204,8 +204,11 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
             // (--correct: the fixes first, then the cut; the writer call returns when its text kernel has run, so the arrays of
             // slot t are free again whether or not this chunk made a submission)
             const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
-            if (correct)
+            if (correct || trim->consensus_on)
                 if (const int rc = fixes.correct(t, d, errors, &fix_mask, &fix_bases)) return rc;
+            // (--pair-correct: behind the fixes and in front of the write; the verdicts were taken from the same result)
+            if (trim->consensus_on)
+                if (const int rc = trim->consensus_batch(which, ordinal, d, (uint8_t *)q, (uint64_t *)fix_mask, (uint64_t *)fix_bases, o.paired_files(), !o.report.empty())) return rc;
             if (!trim->have_verdicts)
                 if (const int rc = trim->batch(which, ordinal, d, q)) return rc;
             if (ordinal + d.n_reads > trim->n[which]) return input_changed();
@@ -224,7 +227,8 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
         if (const int rc = trim->line()) return rc;
     if (correct) {
         kbbq_fix_counts c;
-        if (kbbq_correct_counts(e, &c, 0) < 0) return fail_engine("correcting");
+        if (trim && trim->consensus_on) c = trim->fix_counts;      // (taken where every read was met once: cli_trim.h)
+        else if (kbbq_correct_counts(e, &c, 0) < 0) return fail_engine("correcting");
         std::cerr << put_now << " Corrected bases: " << c.flagged << " flagged, " << c.fixed << " fixed, " << c.ambiguous << " ambiguous, " << c.unsupported
                   << " unsupported." << std::endl;
     }

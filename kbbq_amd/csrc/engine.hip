@@ -54,6 +54,8 @@ using namespace kbbq;
 #include "engine_adapter.h"
 #include "overlap.h"   // (k_pair_overlap: behind k_adapter_find, for the same reason)
 #include "engine_overlap.h"
+#include "consensus.h"   // (k_pair_consensus: behind k_pair_overlap, for the same reason)
+#include "engine_consensus.h"
 
 extern "C" {
 
@@ -169,6 +171,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->trim.d_counts);
     hipFree(e->adapter.d_counts);
     hipFree(e->overlap.d_counts);
+    hipFree(e->consensus.d_counts);
     hipFree(e->p4.d_dq_qslot);
     hipFree(e->d_qpresent);
     hipFree(e->p3.d_rg_present[0]);
@@ -199,6 +202,7 @@ int kbbq_engine_reset(kbbq_engine *e) {
     if ((rc = e->trim.reset(e->stream))) return rc;
     if ((rc = e->adapter.reset(e->stream))) return rc;
     if ((rc = e->overlap.reset(e->stream))) return rc;
+    if ((rc = e->consensus.reset(e->stream))) return rc;
     e->profile.reset();
     return sync_engine(e);
 }

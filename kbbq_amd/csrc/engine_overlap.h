@@ -16,12 +16,9 @@ int overlap_state(kbbq_engine *e) {
     return KBBQ_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b, uint64_t stride,
-                            uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b) {
+// the search of kbbq_pair_overlap_batch; insert: null, or one word per pair for L* or 0 (engine_consensus.h: kbbq_pair_overlap_inserts)
+int pair_overlap_launch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b, uint64_t stride,
+                        uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b, uint32_t *insert) {
     static_assert(kOverlapMaxRead == KBBQ_OVERLAP_MAX_READ, "the kernel's streams hold KBBQ_OVERLAP_MAX_READ bases");
     ENGINE_DEVICE(e);
     if (!a || !b || !p || !limit_a || !limit_b) return fail(KBBQ_EINVAL, "null argument");
@@ -45,9 +42,18 @@ int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_
     P.first_a = first_a; P.first_b = first_b; P.stride = stride; P.n_pairs = n_pairs;
     P.min_overlap = p->min_overlap; P.max_diff = p->max_diff; P.permille = p->max_error_permille; P.merge = p->merge ? 1 : 0;
     Timed t(e, "k_pair_overlap");
-    hipLaunchKernelGGL(k_pair_overlap, dim3(wave_grid(n_pairs)), dim3(256), 0, e->stream, RA, RB, P, limit_a, limit_b, e->overlap.d_counts);
+    hipLaunchKernelGGL(k_pair_overlap, dim3(wave_grid(n_pairs)), dim3(256), 0, e->stream, RA, RB, P, limit_a, limit_b, insert, e->overlap.d_counts);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b, uint64_t stride,
+                            uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b) {
+    return pair_overlap_launch(e, a, first_a, b, first_b, stride, n_pairs, p, limit_a, limit_b, nullptr);
 }
 
 int kbbq_overlap_counts_get(kbbq_engine *e, kbbq_overlap_counts *out, int32_t reset) {

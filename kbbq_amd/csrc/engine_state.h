@@ -278,6 +278,16 @@ struct OverlapState {
     }
 };
 
+// Bases corrected from the mate (include/kbbq_engine.h: kbbq_pair_consensus_batch; engine_consensus.h): the
+// kbbq_pair_consensus_counts of k_pair_consensus.  Allocated by the first call
+struct ConsensusState {
+    unsigned long long *d_counts = nullptr;
+    int reset(hipStream_t stream) {
+        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * 8, stream));      // (CONSENSUS_COUNTS words: consensus.h)
+        return KBBQ_OK;
+    }
+};
+
 // Host batches: a ring of device staging slots owned by the engine and a copy stream.  A host batch is copied
 // into the next slot with hipMemcpyAsync on the copy stream (DMA straight from the caller's memory when that is
 // page-locked), the pass's kernels wait for the copy by event, and the entry point returns as soon as the COPY
@@ -369,6 +379,7 @@ struct kbbq_engine {
     TrimState trim;
     AdapterState adapter;
     OverlapState overlap;
+    ConsensusState consensus;
     Staging stage;
     Buckets bk;
     Profile profile;

@@ -57,8 +57,9 @@
 //     --adapter SEQ|NAME (--adapter2 for the second-in-pair reads, --adapter-min-overlap N, --adapter-error-rate R) finds the 3'
 //     adapter a read runs on into, on the GPU, and has that cut start in front of it (cli_trim.h); --pair-overlap (--pair-overlap-min
 //     N, --pair-overlap-diff D, --pair-overlap-error-rate R) finds whatever adapter stands behind an insert shorter than the
-//     reads from the overlap of a pair's mates, with --in2 or --interleaved.  FASTQ through the device reader only; without them
-//     nothing changes;
+//     reads from the overlap of a pair's mates, with --in2 or --interleaved; --pair-correct (--pair-correct-quals G,B) with it
+//     lets a base of quality G or more replace, complemented, the mate's differing base of quality B or less inside that
+//     overlap.  FASTQ through the device reader only; without them nothing changes;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -1098,6 +1099,10 @@ int main(int argc, char *argv[]) {
         if (trim_run.paired) {
             if (!sink.dev) return give_up(std::string(" Error: ") + opt.trim_option + ": the output does not go through the GPU reader's writer, which cuts and drops the reads.");
             QualSlots slots{e};
+            if (opt.correct && opt.pair_correct) {
+                if (scan.error_flags.of.size() != resident.dev.size()) return give_up(" Error: --correct: pass 3 left no error flags for the resident batches.");
+                trim_run.errors = &scan.error_flags.of;
+            }
             if ((rc = trim_run.verdicts(slots, *sink.dev, resident.dev, scan.in2_first_batch, opt.paired_files(), !opt.report.empty()))) return rc;
             clock.mark("trim verdicts");
         }
@@ -1148,6 +1153,16 @@ int main(int argc, char *argv[]) {
             for (int32_t i = 0; i < n && i < 256; ++i)
                 if (!strcmp(prof[i].name, "k_pair_overlap")) { ms_find = prof[i].total_ms; launches = prof[i].launches; }
         std::cerr << "[timing] pair overlap: k_pair_overlap " << ms_find << " ms in " << launches << " launches" << std::endl;
+    }
+    if (trim && clock.on && opt.pair_correct) {
+        kbbq_profile_entry prof[256];
+        int32_t n = 0;
+        double ms = 0;
+        uint64_t launches = 0;
+        if (kbbq_engine_sync(e) == 0 && kbbq_profile_get(e, prof, 256, &n) == 0)
+            for (int32_t i = 0; i < n && i < 256; ++i)
+                if (!strcmp(prof[i].name, "k_pair_consensus")) { ms = prof[i].total_ms; launches = prof[i].launches; }
+        std::cerr << "[timing] pair correct: k_pair_consensus " << ms << " ms in " << launches << " launches" << std::endl;
     }
     trim_run.release();      // (before the engine goes: end_run may not come back)
     if (!opt.report.empty())

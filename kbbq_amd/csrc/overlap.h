@@ -43,15 +43,50 @@ __device__ __forceinline__ uint64_t overlap_reverse_groups(uint64_t x) {
     return ((x >> 1) & 0x5555555555555555ULL) | ((x & 0x5555555555555555ULL) << 1);
 }
 
-// One wavefront per pair, four per workgroup, on k_trim_reads' grid.  The wave fetches both reads' words once, one per lane
-// (overlap_stage), and shifts each read to bit 0 of a stream of its own: read 1's codes in lanes 0..15 of `a`, its N bits in
-// lanes 0..7 of `an`, zero behind the read and in every other lane.  Read 2 is reverse-complemented once: the groups of each
-// word reversed, the lanes reversed by __shfl, the 512 - n2 empty groups in front shifted out, the codes XORed with 3 (`b`,
-// `bn`).  Then lane l of round r tests insert length L = min_overlap + 64 r + l: the o(L) bases from base max(0, L - n2) of
+// A read's 1-bit stream (lanes 0..7, zero in every other lane, its n bits from bit 0 on) backwards: bit k becomes bit
+// n - 1 - k.  The words reversed, the lanes reversed by __shfl, the 512 - n empty bits in front shifted out.
+__device__ __forceinline__ uint64_t overlap_backwards(uint64_t s, int n, int lane) {
+    uint64_t rev = __brevll(__shfl(s, (7 - lane) & 63));
+    rev = lane < 8 ? rev : 0;
+    const uint64_t r = adapter_window(rev, 0, (kOverlapMaxRead - n) + 64 * (lane & 7));
+    return lane < 8 ? r & overlap_keep(n, lane) : 0;
+}
+
+// The two mates as streams from bit 0 on (every lane calls; both reads have at most kOverlapMaxRead bases): read 1's codes in
+// lanes 0..15 of `a`, its N bits in lanes 0..7 of `an`, zero behind the read and in every other lane; `b` and `bn` the same of
+// read 2's reverse complement, base m of which is base n2 - 1 - m of read 2.  The wave fetches both reads' words once, one per
+// lane (overlap_stage).  Read 2 is reversed once: the groups of each word reversed, the lanes reversed by __shfl, the 512 - n2
+// empty groups in front shifted out, the codes XORed with 3.
+struct OverlapStreams { uint64_t a, an, b, bn; };
+__device__ __forceinline__ OverlapStreams overlap_streams(const ReadsDev &RA, const ReadsDev &RB, uint64_t off1, uint64_t off2, int n1, int n2, int lane) {
+    uint64_t w = 0;
+    if (lane < OVERLAP_B2) w = overlap_stage(RA, off1, lane);
+    else if (lane < OVERLAP_STAGED) w = overlap_stage(RB, off2, lane - OVERLAP_B2);
+    // each read from bit 0 on, zero behind its end
+    uint64_t a = adapter_window(w, OVERLAP_B1, 2 * (int)(off1 & 31) + 64 * (lane & 15));
+    uint64_t an = adapter_window(w, OVERLAP_N1, (int)(off1 & 63) + 64 * (lane & 7));
+    uint64_t f = adapter_window(w, OVERLAP_B2, 2 * (int)(off2 & 31) + 64 * (lane & 15));
+    uint64_t fn = adapter_window(w, OVERLAP_N2, (int)(off2 & 63) + 64 * (lane & 7));
+    a = lane < 16 ? a & overlap_keep(2 * n1, lane) : 0;
+    an = lane < 8 ? an & overlap_keep(n1, lane) : 0;
+    f = lane < 16 ? f & overlap_keep(2 * n2, lane) : 0;
+    fn = lane < 8 ? fn & overlap_keep(n2, lane) : 0;
+    // read 2 backwards: base k of the reversed 512-base stream is base 511 - k of read 2
+    uint64_t rev = overlap_reverse_groups(__shfl(f, (15 - lane) & 63));
+    rev = lane < 16 ? rev : 0;
+    uint64_t b = adapter_window(rev, 0, 2 * (kOverlapMaxRead - n2) + 64 * (lane & 15));
+    b = lane < 16 ? ~b & overlap_keep(2 * n2, lane) : 0;
+    return {a, an, b, overlap_backwards(fn, n2, lane)};
+}
+
+// One wavefront per pair, four per workgroup, on k_trim_reads' grid.  The wave lays both reads out as streams from bit 0 on
+// (overlap_streams: `a`, `an`, and read 2 reverse-complemented, `b`, `bn`).  Then lane l of round r tests insert length L = min_overlap + 64 r + l: the o(L) bases from base max(0, L - n2) of
 // read 1 against those from base max(0, n2 - L) of rc2, 32 bases a step, by XOR and popcount over windows cut out of the two
 // streams by __shfl (adapter_window).  The winner is the wave-wide maximum of o * 2048 + L over the hits.  The counters are kept
 // per wavefront, added up per workgroup in LDS and added to the engine's once per workgroup.
-__global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, OverlapDev P, uint32_t *limit_a, uint32_t *limit_b, unsigned long long *counts) {
+// insert (may be null): one word per pair, L* of the winner or 0 (kbbq_pair_overlap_inserts).
+__global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, OverlapDev P, uint32_t *limit_a, uint32_t *limit_b, uint32_t *insert,
+                                                      unsigned long long *counts) {
     __shared__ unsigned long long tot[4][OVERLAP_COUNTS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
@@ -64,7 +99,7 @@ __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, 
         uint32_t len1, len2;
         read_span(RA, P.first_a + j * P.stride, off1, len1);
         read_span(RB, P.first_b + j * P.stride, off2, len2);
-        int lim1 = (int)len1, lim2 = (int)len2;
+        int lim1 = (int)len1, lim2 = (int)len2, found = 0;      // found: L* of the hit, 0 for none
         if (len1 > (uint32_t)kOverlapMaxRead || len2 > (uint32_t)kOverlapMaxRead) {
             cnt[OVERLAP_TOO_LONG] += 1;
         } else {
@@ -72,27 +107,8 @@ __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, 
             cnt[OVERLAP_PAIRS] += 1;
             int best = 0;      // o * 2048 + L of this lane's best hit
             if (n1 + n2 >= 2 * V) {
-                uint64_t w = 0;
-                if (lane < OVERLAP_B2) w = overlap_stage(RA, off1, lane);
-                else if (lane < OVERLAP_STAGED) w = overlap_stage(RB, off2, lane - OVERLAP_B2);
-                // each read from bit 0 on, zero behind its end
-                uint64_t a = adapter_window(w, OVERLAP_B1, 2 * (int)(off1 & 31) + 64 * (lane & 15));
-                uint64_t an = adapter_window(w, OVERLAP_N1, (int)(off1 & 63) + 64 * (lane & 7));
-                uint64_t f = adapter_window(w, OVERLAP_B2, 2 * (int)(off2 & 31) + 64 * (lane & 15));
-                uint64_t fn = adapter_window(w, OVERLAP_N2, (int)(off2 & 63) + 64 * (lane & 7));
-                a = lane < 16 ? a & overlap_keep(2 * n1, lane) : 0;
-                an = lane < 8 ? an & overlap_keep(n1, lane) : 0;
-                f = lane < 16 ? f & overlap_keep(2 * n2, lane) : 0;
-                fn = lane < 8 ? fn & overlap_keep(n2, lane) : 0;
-                // read 2 backwards: base k of the reversed 512-base stream is base 511 - k of read 2
-                uint64_t rev = overlap_reverse_groups(__shfl(f, (15 - lane) & 63));
-                uint64_t revn = __brevll(__shfl(fn, (7 - lane) & 63));
-                rev = lane < 16 ? rev : 0;
-                revn = lane < 8 ? revn : 0;
-                uint64_t b = adapter_window(rev, 0, 2 * (kOverlapMaxRead - n2) + 64 * (lane & 15));
-                uint64_t bn = adapter_window(revn, 0, (kOverlapMaxRead - n2) + 64 * (lane & 7));
-                b = lane < 16 ? ~b & overlap_keep(2 * n2, lane) : 0;
-                bn = lane < 8 ? bn & overlap_keep(n2, lane) : 0;
+                const OverlapStreams S = overlap_streams(RA, RB, off1, off2, n1, n2, lane);
+                const uint64_t a = S.a, an = S.an, b = S.b, bn = S.bn;
                 const bool has_n = __ballot((an | bn) != 0) != 0;      // (rare: a base with its N bit is one mismatch whatever its code says)
                 const int last = n1 + n2 - V;
                 for (int first_l = V; first_l <= last; first_l += 64) {
@@ -116,7 +132,7 @@ __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, 
                 for (int m = 32; m; m >>= 1) best = max(best, __shfl_xor(best, m));
             }
             if (best) {
-                const int L = best & 2047;
+                const int L = found = best & 2047;
                 lim1 = min(n1, L);
                 lim2 = min(n2, L);
                 cnt[OVERLAP_OVERLAPPING] += 1;
@@ -129,6 +145,7 @@ __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, 
             uint32_t *la = limit_a + j * P.stride, *lb = limit_b + j * P.stride;
             *la = P.merge ? min(*la, (uint32_t)lim1) : (uint32_t)lim1;
             *lb = P.merge ? min(*lb, (uint32_t)lim2) : (uint32_t)lim2;
+            if (insert) insert[j] = (uint32_t)found;
         }
     }
     if (lane == 0) {

@@ -337,11 +337,24 @@ class Engine:
         insert than the read, else the read's length -- as two NumPy uint32 arrays of n_pairs entries.  limit_a, limit_b:
         limits the reads have already (one per pair, both or neither); each result is then the smaller of the two (merge).
         Waits for the kernel."""
+        return self._pair_overlaps(False, dev_a, dev_b, first_a, first_b, stride, n_pairs, min_overlap, max_diff, max_error_permille, limit_a, limit_b)
+
+    def find_pair_inserts(self, dev_a, dev_b, first_a=0, first_b=0, stride=1, n_pairs=None, min_overlap=30, max_diff=5, max_error_permille=200,
+                          limit_a=None, limit_b=None):
+        """kbbq_pair_overlap_inserts: find_pair_overlaps' two arrays of limits and, third, the insert length of every pair as a
+        NumPy uint32 array of n_pairs entries -- 0 where the pair has no hit or was not searched.  Waits for the kernel."""
+        return self._pair_overlaps(True, dev_a, dev_b, first_a, first_b, stride, n_pairs, min_overlap, max_diff, max_error_permille, limit_a, limit_b)
+
+    @staticmethod
+    def _pairs_from(dev_a, dev_b, first_a, first_b, stride):
+        step = stride if stride > 0 else 1
+        return max(0, min((dev_a.n_reads - first_a + step - 1) // step, (dev_b.n_reads - first_b + step - 1) // step))
+
+    def _pair_overlaps(self, want_insert, dev_a, dev_b, first_a, first_b, stride, n_pairs, min_overlap, max_diff, max_error_permille, limit_a, limit_b):
         import torch
         stride = int(stride)
         if n_pairs is None:
-            step = stride if stride > 0 else 1
-            n_pairs = max(0, min((dev_a.n_reads - first_a + step - 1) // step, (dev_b.n_reads - first_b + step - 1) // step))
+            n_pairs = self._pairs_from(dev_a, dev_b, first_a, first_b, stride)
         n_pairs = int(n_pairs)
         assert (limit_a is None) == (limit_b is None), "limit_a and limit_b: both or neither"
         p = _lib.OverlapParams(int(min_overlap), int(max_diff), int(max_error_permille), 0 if limit_a is None else 1)
@@ -355,17 +368,81 @@ class Engine:
                 assert len(lim) == n_pairs, "limit_a, limit_b: one length per pair"
                 host[::max(stride, 1)][:n_pairs] = lim
             d_lim.append(torch.from_numpy(host.view(np.int32)).to(dev))
+        d_insert = torch.zeros(max(1, n_pairs), dtype=torch.int32, device=dev) if want_insert else None
         torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        _lib.check(self.L.kbbq_pair_overlap_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, ctypes.byref(p),
-                                                  d_lim[0].data_ptr(), d_lim[1].data_ptr()))
+        if want_insert:
+            _lib.check(self.L.kbbq_pair_overlap_inserts(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, ctypes.byref(p),
+                                                        d_lim[0].data_ptr(), d_lim[1].data_ptr(), d_insert.data_ptr()))
+        else:
+            _lib.check(self.L.kbbq_pair_overlap_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, ctypes.byref(p),
+                                                      d_lim[0].data_ptr(), d_lim[1].data_ptr()))
         self.sync()
-        return tuple(d.cpu().numpy().view(np.uint32)[::max(stride, 1)][:n_pairs].copy() for d in d_lim)
+        out = tuple(d.cpu().numpy().view(np.uint32)[::max(stride, 1)][:n_pairs].copy() for d in d_lim)
+        return out + (d_insert.cpu().numpy().view(np.uint32)[:n_pairs].copy(),) if want_insert else out
 
     def overlap_counts(self, reset=False):
         """What find_pair_overlaps did since the last reset (waits): the fields of kbbq_overlap_counts."""
         c = _lib.OverlapCounts()
         _lib.check(self.L.kbbq_overlap_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
         return {n: int(getattr(c, n)) for n, _ in _lib.OverlapCounts._fields_}
+
+    # ---- bases corrected from the mate inside the overlap
+    def pair_consensus(self, dev_a, dev_b, insert, qual_a, qual_b=None, first_a=0, first_b=0, stride=1, n_pairs=None, good_q=30, bad_q=15,
+                       fix_a=None, fix_b=None, sides=3):
+        """kbbq_pair_consensus_batch on two device batches (DeviceReads) and host arrays: insert, one length per pair
+        (find_pair_inserts'); qual_a, qual_b, the written qualities of the two batches in base order (uint8); fix_a, fix_b,
+        each None for "nothing fixed" or the (fix_mask, fix_bases) words of correct_bases.  An interleaved batch is the same
+        DeviceReads twice with stride 2; qual_b and fix_b are then not given, the batch has one of each.  Returns, after the call,
+        ((qual_a, fix_mask_a, fix_bases_a), (qual_b, fix_mask_b, fix_bases_b)) as NumPy arrays -- the same arrays twice for an
+        interleaved batch; a side that `sides` (bit 0: a, bit 1: b) does not name comes back as it went in.  Waits for the kernel."""
+        import torch
+        stride = int(stride)
+        if n_pairs is None:
+            n_pairs = self._pairs_from(dev_a, dev_b, first_a, first_b, stride)
+        n_pairs = int(n_pairs)
+        dev = "cuda:%d" % self.params.device
+        one = dev_a is dev_b
+        assert not one or (qual_b is None and fix_b is None), "one batch has one quality array and one pair of fix arrays"
+        ins = np.zeros(max(1, n_pairs), np.uint32)
+        given = np.ascontiguousarray(insert, dtype=np.uint32)
+        assert len(given) == n_pairs, "insert: one length per pair"
+        ins[:n_pairs] = given
+        d_insert = torch.from_numpy(ins.view(np.int32)).to(dev)
+
+        def side(dreads, qual, fix):
+            nb = dreads.n_bases
+            q = np.ascontiguousarray(qual, dtype=np.uint8)
+            assert len(q) == nb, "one quality per base of the batch"
+            words = []
+            for given, n in zip(fix if fix is not None else (None, None), (nb // 64 + 2, nb // 32 + 2)):
+                w = np.zeros(n, np.uint64)
+                if given is not None:
+                    g = np.ascontiguousarray(given, dtype=np.uint64)
+                    assert len(g) <= n, "fix arrays: at most n_bases/64+2 and n_bases/32+2 words"
+                    w[:len(g)] = g
+                words.append(torch.from_numpy(w.view(np.int64)).to(dev))
+            return [torch.from_numpy(np.concatenate([q, np.zeros(1, np.uint8)])).to(dev)] + words
+
+        da = side(dev_a, qual_a, fix_a)
+        db = da if one else side(dev_b, qual_b, fix_b)
+        p = _lib.ConsensusParams(int(good_q), int(bad_q))
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_pair_consensus_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs,
+                                                    d_insert.data_ptr(), ctypes.byref(p), da[0].data_ptr(), db[0].data_ptr(), da[1].data_ptr(),
+                                                    da[2].data_ptr(), db[1].data_ptr(), db[2].data_ptr(), int(sides)))
+        self.sync()
+
+        def back(d, dreads):
+            return (d[0].cpu().numpy()[:dreads.n_bases].copy(), d[1].cpu().numpy().view(np.uint64), d[2].cpu().numpy().view(np.uint64))
+
+        out_a = back(da, dev_a)
+        return out_a, (out_a if one else back(db, dev_b))
+
+    def pair_consensus_counts(self, reset=False):
+        """What pair_consensus did since the last reset (waits): the fields of kbbq_pair_consensus_counts."""
+        c = _lib.ConsensusCounts()
+        _lib.check(self.L.kbbq_pair_consensus_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
+        return {n: int(getattr(c, n)) for n, _ in _lib.ConsensusCounts._fields_}
 
     def trim_mates(self, keep_a, keep_b=None, adjacent=False):
         """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
