@@ -6,6 +6,7 @@
 // as one difference; starts whose overlap is below min_overlap are not tested.  No match: limit = n.
 #pragma once
 #include "device_common.h"
+#include "wave_helpers.h"
 
 namespace kbbq {
 
@@ -62,7 +63,6 @@ __device__ __forceinline__ uint64_t adapter_window(uint64_t w, int lane0, int po
 // first round with a match ends the read, at its lowest matching lane.  The counters are kept per wavefront, added up per
 // workgroup in LDS and added to the engine's once per workgroup.
 __global__ void __launch_bounds__(256) k_adapter_find(ReadsDev R, AdapterDev A, uint32_t *limit, unsigned long long *counts) {
-    __shared__ unsigned long long tot[4][ADAPTER_COUNTS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
     unsigned long long cnt[ADAPTER_COUNTS];
@@ -120,15 +120,7 @@ __global__ void __launch_bounds__(256) k_adapter_find(ReadsDev R, AdapterDev A, 
         }
         if (lane == 0) limit[r] = (uint32_t)(found >= 0 ? found : n);
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < ADAPTER_COUNTS; ++c) tot[wave][c] = cnt[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < ADAPTER_COUNTS) {
-        const unsigned long long v = tot[0][threadIdx.x] + tot[1][threadIdx.x] + tot[2][threadIdx.x] + tot[3][threadIdx.x];
-        if (v) atomicAdd(&counts[threadIdx.x], v);
-    }
+    add_wave_counts(cnt, counts);
 }
 
 }  // namespace kbbq

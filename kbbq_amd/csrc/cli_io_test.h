@@ -1,5 +1,5 @@
 // cli_io_test.h -- `kbbq --io-test ...`: hidden helpers for the CPU test-suite, which exercise the readers, the name rules, the
-// BAM and SAM codecs, the BGZF writer and the device reader's byte source without touching the GPU (the synth-* helpers, which
+// BAM and SAM codecs, the BGZF writer, the device reader's byte source and the pair walk without touching the GPU (the synth-* helpers, which
 // write the bench's reads as files, do use it).  Compiled into kbbq_cli.cc alone.
 #pragma once
 
@@ -50,6 +50,26 @@ template <class Reader, class Record> static int io_test_copy(const char *path, 
     while (in.next(r) >= 0)
         if (const int rc = io_test_copy_record(r, set_oq, w, out, scratch)) return rc;
     return out.close() ? 0 : 1;
+}
+
+// "pair-runs": the pair walk (cli_pair_walk.h) over the batches whose read counts the comma lists give -- s0 file 0's, s1 --in2's
+// or null for an interleaved input.  One line per run, then one per batch: the runs with a read of it.  0, or the refusal's status
+static int io_test_pair_runs(const char *s0, const char *s1) {
+    std::vector<uint64_t> sizes[2];
+    const char *lists[2] = {s0, s1};
+    for (int f = 0; f < 2 && lists[f]; ++f) {
+        std::stringstream list(lists[f]);
+        for (std::string item; std::getline(list, item, ',');)
+            if (const uint64_t n = strtoull(item.c_str(), nullptr, 10)) sizes[f].push_back(n);      // (the walk is over the batches that hold reads)
+    }
+    PairWalk walk;
+    if (const char *refusal = walk.build(sizes[0], s1 ? &sizes[1] : nullptr)) return give_up(refusal);
+    for (const PairRun &r : walk.runs)
+        printf("run %zu %zu %llu %llu %llu %llu %llu\n", r.ia, r.ib, (unsigned long long)r.first_a, (unsigned long long)r.first_b, (unsigned long long)r.stride,
+               (unsigned long long)r.n_pairs, (unsigned long long)r.pair);
+    for (int f = 0; f < 2; ++f)
+        for (size_t i = 0; i < walk.touch[f].size(); ++i) printf("batch %d %zu %zu %zu\n", f, i, walk.touch[f][i].begin, walk.touch[f][i].end);
+    return 0;
 }
 
 static int io_test(int argc, char *argv[], const CliOptions &o) {
@@ -182,6 +202,19 @@ static int io_test(int argc, char *argv[], const CliOptions &o) {
         while ((n = fread(buf.data(), 1, buf.size(), stdin)) > 0)
             if (!out.write(buf.data(), n)) return 1;
         return out.close() ? 0 : 1;
+    }
+    if (what == "pair-runs" && argc > 3) {
+        // --io-test pair-runs SIZES0 [SIZES1]; or --io-test pair-runs - for many cases in one run: a case per line of standard
+        // input, "SIZES0" or "SIZES0 SIZES1", each answered by its lines and "#end STATUS"
+        if (std::string(argv[3]) != "-") return io_test_pair_runs(argv[3], argc > 4 ? argv[4] : nullptr);
+        for (std::string line; std::getline(std::cin, line);) {
+            std::stringstream words(line);
+            std::string s0, s1;
+            words >> s0;
+            const bool two = (bool)(words >> s1);
+            printf("#end %d\n", io_test_pair_runs(s0.c_str(), two ? s1.c_str() : nullptr));
+        }
+        return 0;
     }
     if (what == "pieces" && argc > 3) {
         // Standard input through the device reader's byte source and I/O thread (piece_reader.h), no GPU call:

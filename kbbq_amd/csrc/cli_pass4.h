@@ -1,6 +1,7 @@
 // cli_pass4.h -- pass 4 of the command line (kbbq.cc:455-457: recalibrate_and_write): the output's BGZF layer and the record
-// writers of the three formats (Sink), the device quality arrays of the batches in flight (QualSlots; --correct: their fix arrays, FixSlots) and the six ways from
-// what the first scan left behind to the output, of which main() picks one.  Compiled into kbbq_cli.cc alone.
+// writers of the three formats (Sink) and the six ways from what the first scan left behind to the output, of which main() picks
+// one.  (The device quality and fix arrays of the batches in flight, QualSlots and FixSlots, are cli_slots.h's.)  Compiled into
+// kbbq_cli.cc alone.
 #pragma once
 
 // BamFile::recalibrate, htsiter.cc:11-33: the OQ tag takes the old qualities, the record the new ones (reversed for a
@@ -110,53 +111,6 @@ struct Sink {
     }
 };
 
-// Pass 4's pair of device quality arrays: batch n writes slot n & 1 while the writer still reads the other one.
-struct QualSlots {
-    kbbq_engine *e;
-    void *q[2] = {nullptr, nullptr};
-    size_t bytes[2] = {0, 0};
-    ~QualSlots() { for (int i = 0; i < 2; ++i) if (q[i]) kbbq_device_free(e, q[i]); }
-    // Pass 4 of batch d into slot t -- grown, with an eighth to spare, when the batch needs more room -- once the writer is
-    // through with what it read from there.  0 and the array in *to, or the exit status.
-    int recalibrate(DeviceBgzfWriter &out, int t, const kbbq_reads &d, const uint8_t **to) {
-        if (!out.drain_to(1)) return 1;      // (the array this batch writes was read by the submission two back)
-        if (bytes[t] < d.n_bases + 16) {
-            if (q[t] && kbbq_device_free(e, q[t]) < 0) return fail_engine("recalibrating");
-            q[t] = nullptr;
-            bytes[t] = d.n_bases + d.n_bases / 8 + 4096;
-            if (kbbq_device_alloc(e, bytes[t], &q[t]) < 0) return fail_engine("recalibrating");
-        }
-        if (kbbq_recalibrate_batch(e, &d, (uint8_t *)q[t]) < 0) return fail_engine("recalibrating");
-        *to = (const uint8_t *)q[t];
-        return 0;
-    }
-};
-
-// --correct: pass 4's pair of fix arrays (kbbq_correct_batch's fix_mask and fix_bases of one batch, one allocation), handled as
-// QualSlots handles the qualities: batch n fills slot n & 1 while the writer still reads the other one.
-struct FixSlots {
-    kbbq_engine *e;
-    void *p[2] = {nullptr, nullptr};
-    size_t bytes[2] = {0, 0};
-    ~FixSlots() { for (int i = 0; i < 2; ++i) if (p[i]) kbbq_device_free(e, p[i]); }
-    // The fixes of batch d, whose error flags pass 3 left in `errors` (null: zeroed arrays, for --pair-correct without --correct), into slot t; call behind QualSlots::recalibrate of the
-    // same batch, which has waited for the writer to be through with the slot.  0 and the two arrays, or the exit status.
-    int correct(int t, const kbbq_reads &d, const uint64_t *errors, const uint64_t **mask, const uint64_t **bases) {
-        const size_t mask_bytes = (d.n_bases / 64 + 2) * 8, need = mask_bytes + (d.n_bases / 32 + 2) * 8;
-        if (bytes[t] < need) {
-            if (p[t] && kbbq_device_free(e, p[t]) < 0) return fail_engine("correcting");
-            p[t] = nullptr;
-            bytes[t] = need + need / 8 + 4096;
-            if (kbbq_device_alloc(e, bytes[t], &p[t]) < 0) return fail_engine("correcting");
-        }
-        if (kbbq_device_zero(e, p[t], need) < 0) return fail_engine("correcting");
-        *mask = (const uint64_t *)p[t];
-        *bases = (const uint64_t *)((const char *)p[t] + mask_bytes);
-        if (errors && kbbq_correct_batch(e, &d, errors, (uint64_t *)*mask, (uint64_t *)*bases) < 0) return fail_engine("correcting");
-        return 0;
-    }
-};
-
 // Pass 4, the device path: the file's chunks again (inflate + record index, as in the first scan) or the chunks kept in HBM,
 // pass 4 into a device array, the text assembled from the device's own copy of the input, deflated, written.  Nothing but
 // compressed bytes crosses the host link in either direction.
@@ -208,11 +162,11 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
                 if (const int rc = fixes.correct(t, d, errors, &fix_mask, &fix_bases)) return rc;
             // (--pair-correct: behind the fixes and in front of the write; the verdicts were taken from the same result)
             if (trim->consensus_on)
-                if (const int rc = trim->consensus_batch(which, ordinal, d, (uint8_t *)q, (uint64_t *)fix_mask, (uint64_t *)fix_bases, o.paired_files(), !o.report.empty())) return rc;
+                if (const int rc = trim->consensus_batch(which, ordinal, d, (uint8_t *)q, (uint64_t *)fix_mask, (uint64_t *)fix_bases, !o.report.empty())) return rc;
             if (!trim->have_verdicts)
                 if (const int rc = trim->batch(which, ordinal, d, q)) return rc;
             if (ordinal + d.n_reads > trim->n[which]) return input_changed();
-            if (!in.write_chunk_trimmed(out, q, trim->keep[which] + ordinal, fix_mask, fix_bases, kbbq_engine_stream(e))) return 1;
+            if (!in.write_chunk_trimmed(out, q, trim->kept(which, ordinal), fix_mask, fix_bases, kbbq_engine_stream(e))) return 1;
             ordinal += d.n_reads;
         } else if (correct) {
             const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;

@@ -12,7 +12,7 @@
 namespace kbbq {
 
 struct ConsensusDev {
-    uint64_t first_a, first_b, stride, n_pairs;
+    PairsDev pairs;
     int good_q, bad_q, sides;
 };
 // the words of the counter array (kbbq_pair_consensus_counts, in its order)
@@ -49,13 +49,13 @@ __global__ void __launch_bounds__(256) k_pair_consensus(ReadsDev RA, ReadsDev RB
     unsigned long long cnt[CONSENSUS_COUNTS];
 #pragma unroll
     for (int c = 0; c < CONSENSUS_COUNTS; ++c) cnt[c] = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * 4 + wave; j < P.n_pairs; j += n_waves) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 4 + wave; j < P.pairs.n_pairs; j += n_waves) {
         const int L = (int)insert[j];
         if (!L) continue;
         uint64_t off1, off2;
         uint32_t len1, len2;
-        read_span(RA, P.first_a + j * P.stride, off1, len1);
-        read_span(RB, P.first_b + j * P.stride, off2, len2);
+        read_span(RA, P.pairs.a(j), off1, len1);
+        read_span(RB, P.pairs.b(j), off2, len2);
         // (an insert the search cannot have written: the streams hold kOverlapMaxRead bases, and the overlap must not be empty)
         if (len1 > (uint32_t)kOverlapMaxRead || len2 > (uint32_t)kOverlapMaxRead || !len1 || !len2 || (uint32_t)L >= len1 + len2) continue;
         const int n1 = (int)len1, n2 = (int)len2;
@@ -122,6 +122,8 @@ __global__ void __launch_bounds__(256) k_pair_consensus(ReadsDev RA, ReadsDev RB
         cnt[CONSENSUS_FROM_N] += (unsigned long long)from_n;
         cnt[CONSENSUS_BASES_LEFT] += (unsigned long long)left * ((write_a ? 1 : 0) + (write_b ? 1 : 0));
     }
+    // (spelled out where the three kernels before it call add_wave_counts: through the helper the compiler allocates this
+    // kernel's registers another way, and its time has not been shown to stay inside the run-to-run spread)
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < CONSENSUS_COUNTS; ++c) tot[wave][c] = cnt[c];

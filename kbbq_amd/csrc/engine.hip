@@ -168,10 +168,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->d_tickets);
     hipFree(e->d_totals);
     hipFree(e->d_fix_counts);
-    hipFree(e->trim.d_counts);
-    hipFree(e->adapter.d_counts);
-    hipFree(e->overlap.d_counts);
-    hipFree(e->consensus.d_counts);
+    for (CounterBlock *c : {&e->trim, &e->adapter, &e->overlap, &e->consensus}) c->free();
     hipFree(e->p4.d_dq_qslot);
     hipFree(e->d_qpresent);
     hipFree(e->p3.d_rg_present[0]);

@@ -5,17 +5,6 @@
 
 namespace {
 
-// the first search of this engine: the counters (engine_state.h: AdapterState)
-int adapter_state(kbbq_engine *e) {
-    if (e->adapter.d_counts) return KBBQ_OK;
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc(&d, ADAPTER_COUNTS * 8));
-    hipError_t he = hipMemsetAsync(d, 0, ADAPTER_COUNTS * 8, e->stream);
-    if (he != hipSuccess) { hipFree(d); HIP_TRY(he); }
-    e->adapter.d_counts = d;
-    return KBBQ_OK;
-}
-
 // an adapter as the caller gave it: a length in range, and no bit set behind it (the kernel compares whole words)
 bool adapter_ok(const kbbq_adapter &a) {
     if (a.len < KBBQ_ADAPTER_MIN || a.len > KBBQ_ADAPTER_MAX) return false;
@@ -44,7 +33,7 @@ int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *reads, const kbbq_
     ReadsDev R; int max_len;
     int rc = device_view(e, reads, &R, &max_len, false);
     if (rc) return rc;
-    if ((rc = adapter_state(e))) return rc;
+    if ((rc = e->adapter.ensure(e, ADAPTER_COUNTS))) return rc;
     AdapterDev A;
     const kbbq_adapter &second = has_second ? p->second : p->first;
     A.code[0][0] = p->first.code[0]; A.code[0][1] = p->first.code[1]; A.len[0] = p->first.len;
@@ -53,7 +42,7 @@ int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *reads, const kbbq_
     A.min_overlap = p->min_overlap;
     A.permille = p->max_error_permille;
     Timed t(e, "k_adapter_find");
-    hipLaunchKernelGGL(k_adapter_find, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, A, limit, e->adapter.d_counts);
+    hipLaunchKernelGGL(k_adapter_find, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, A, limit, e->adapter.d);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
@@ -61,13 +50,10 @@ int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *reads, const kbbq_
 int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset) {
     ENGINE_DEVICE(e);
     if (!out) return fail(KBBQ_EINVAL, "null argument");
-    int rc = sync_engine(e);
-    if (rc) return rc;
     unsigned long long c[ADAPTER_COUNTS] = {};
-    if (e->adapter.d_counts) HIP_TRY(hipMemcpy(c, e->adapter.d_counts, sizeof c, hipMemcpyDeviceToHost));
+    if (const int rc = e->adapter.read(e, c, reset)) return rc;
     out->reads = c[ADAPTER_READS]; out->found_first = c[ADAPTER_FOUND_FIRST]; out->found_second = c[ADAPTER_FOUND_SECOND];
     out->full = c[ADAPTER_FULL]; out->partial = c[ADAPTER_PARTIAL]; out->bases_behind = c[ADAPTER_BASES_BEHIND];
-    if (reset && e->adapter.d_counts) HIP_TRY(hipMemset(e->adapter.d_counts, 0, sizeof c));
     return KBBQ_OK;
 }
 

@@ -5,14 +5,25 @@
 
 namespace {
 
-// the first search of this engine: the counters (engine_state.h: OverlapState)
-int overlap_state(kbbq_engine *e) {
-    if (e->overlap.d_counts) return KBBQ_OK;
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc(&d, OVERLAP_COUNTS * 8));
-    hipError_t he = hipMemsetAsync(d, 0, OVERLAP_COUNTS * 8, e->stream);
-    if (he != hipSuccess) { hipFree(d); HIP_TRY(he); }
-    e->overlap.d_counts = d;
+// What a call on the pairs of two device batches brings, for k_pair_overlap and k_pair_consensus alike: pair j is read
+// first_a + j * stride of a and read first_b + j * stride of b.  The two batches' views and the pairs' addressing, and in *launch
+// whether there is a pair at all
+int pair_view(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b, uint64_t stride, uint64_t n_pairs, ReadsDev *RA,
+              ReadsDev *RB, PairsDev *pairs, bool *launch) {
+    *launch = false;
+    if (!a->on_device || !b->on_device) return fail(KBBQ_EINVAL, "not a device batch");
+    if (stride != 1 && stride != 2) return fail(KBBQ_EINVAL, "stride must be 1 or 2");
+    // (n_reads is below 2^32, and so is every index that passes: nothing wraps)
+    if (n_pairs > 0xFFFFFFFFULL || first_a > 0xFFFFFFFFULL || first_b > 0xFFFFFFFFULL) return fail(KBBQ_EINVAL, "a pair behind the batch's reads");
+    if (n_pairs && (first_a + (n_pairs - 1) * stride >= a->n_reads || first_b + (n_pairs - 1) * stride >= b->n_reads))
+        return fail(KBBQ_EINVAL, "a pair behind the batch's reads");
+    if (!n_pairs) return KBBQ_OK;
+    int max_len;
+    int rc = device_view(e, a, RA, &max_len, false);
+    if (rc) return rc;
+    if ((rc = device_view(e, b, RB, &max_len, false))) return rc;
+    *pairs = PairsDev{first_a, first_b, stride, n_pairs};
+    *launch = true;
     return KBBQ_OK;
 }
 
@@ -22,27 +33,19 @@ int pair_overlap_launch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, c
     static_assert(kOverlapMaxRead == KBBQ_OVERLAP_MAX_READ, "the kernel's streams hold KBBQ_OVERLAP_MAX_READ bases");
     ENGINE_DEVICE(e);
     if (!a || !b || !p || !limit_a || !limit_b) return fail(KBBQ_EINVAL, "null argument");
-    if (!a->on_device || !b->on_device) return fail(KBBQ_EINVAL, "not a device batch");
-    if (stride != 1 && stride != 2) return fail(KBBQ_EINVAL, "stride must be 1 or 2");
     if (p->min_overlap < KBBQ_OVERLAP_MIN || p->min_overlap > KBBQ_OVERLAP_MAX_READ)
         return fail(KBBQ_EINVAL, "min_overlap must be in %d..%d", KBBQ_OVERLAP_MIN, KBBQ_OVERLAP_MAX_READ);
     if (p->max_diff < 0 || p->max_diff > KBBQ_OVERLAP_MAX_READ) return fail(KBBQ_EINVAL, "max_diff must be in 0..%d", KBBQ_OVERLAP_MAX_READ);
     if (p->max_error_permille < 0 || p->max_error_permille > 500) return fail(KBBQ_EINVAL, "max_error_permille must be in 0..500");
-    // (n_reads is below 2^32, and so is every index that passes: nothing wraps)
-    if (n_pairs > 0xFFFFFFFFULL || first_a > 0xFFFFFFFFULL || first_b > 0xFFFFFFFFULL) return fail(KBBQ_EINVAL, "a pair behind the batch's reads");
-    if (n_pairs && (first_a + (n_pairs - 1) * stride >= a->n_reads || first_b + (n_pairs - 1) * stride >= b->n_reads))
-        return fail(KBBQ_EINVAL, "a pair behind the batch's reads");
-    if (!n_pairs) return KBBQ_OK;
-    ReadsDev RA, RB; int max_len;
-    int rc = device_view(e, a, &RA, &max_len, false);
-    if (rc) return rc;
-    if ((rc = device_view(e, b, &RB, &max_len, false))) return rc;
-    if ((rc = overlap_state(e))) return rc;
+    ReadsDev RA, RB;
     OverlapDev P;
-    P.first_a = first_a; P.first_b = first_b; P.stride = stride; P.n_pairs = n_pairs;
+    bool launch;
+    int rc = pair_view(e, a, first_a, b, first_b, stride, n_pairs, &RA, &RB, &P.pairs, &launch);
+    if (rc || !launch) return rc;
+    if ((rc = e->overlap.ensure(e, OVERLAP_COUNTS))) return rc;
     P.min_overlap = p->min_overlap; P.max_diff = p->max_diff; P.permille = p->max_error_permille; P.merge = p->merge ? 1 : 0;
     Timed t(e, "k_pair_overlap");
-    hipLaunchKernelGGL(k_pair_overlap, dim3(wave_grid(n_pairs)), dim3(256), 0, e->stream, RA, RB, P, limit_a, limit_b, insert, e->overlap.d_counts);
+    hipLaunchKernelGGL(k_pair_overlap, dim3(wave_grid(n_pairs)), dim3(256), 0, e->stream, RA, RB, P, limit_a, limit_b, insert, e->overlap.d);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
@@ -59,13 +62,10 @@ int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_
 int kbbq_overlap_counts_get(kbbq_engine *e, kbbq_overlap_counts *out, int32_t reset) {
     ENGINE_DEVICE(e);
     if (!out) return fail(KBBQ_EINVAL, "null argument");
-    int rc = sync_engine(e);
-    if (rc) return rc;
     unsigned long long c[OVERLAP_COUNTS] = {};
-    if (e->overlap.d_counts) HIP_TRY(hipMemcpy(c, e->overlap.d_counts, sizeof c, hipMemcpyDeviceToHost));
+    if (const int rc = e->overlap.read(e, c, reset)) return rc;
     out->pairs = c[OVERLAP_PAIRS]; out->overlapping = c[OVERLAP_OVERLAPPING]; out->short_insert = c[OVERLAP_SHORT_INSERT];
     out->reads_cut = c[OVERLAP_READS_CUT]; out->bases_behind = c[OVERLAP_BASES_BEHIND]; out->too_long = c[OVERLAP_TOO_LONG];
-    if (reset && e->overlap.d_counts) HIP_TRY(hipMemset(e->overlap.d_counts, 0, sizeof c));
     return KBBQ_OK;
 }
 

@@ -246,45 +246,25 @@ struct ReportState {
     }
 };
 
-// trimming and filtering (include/kbbq_engine.h: kbbq_trim_batch; engine_trim.h): the kbbq_trim_counts of k_trim_reads and
-// k_trim_mates and, behind them in the same allocation, the expected-error table.  Allocated by the first trimming call, as
-// d_fix_counts is: an engine that never trims makes exactly the allocations it made before there was such a call
-struct TrimState {
-    unsigned long long *d_counts = nullptr;
-    const unsigned long long *d_ee = nullptr;
+// A block of 8-byte device counters that a feature's kernels add to and its *_counts_get call reads: those of trimming and
+// filtering (kbbq_trim_counts; k_trim_reads, k_trim_mates: engine_trim.h, which keeps the expected-error table behind them in the
+// same allocation), of 3' adapter removal (kbbq_adapter_counts; engine_adapter.h), of the adapters from a pair's overlap
+// (kbbq_overlap_counts; engine_overlap.h) and of the bases corrected from the mate (kbbq_pair_consensus_counts; engine_consensus.h).
+// Allocated by the feature's first call, as d_fix_counts is: an engine that never makes one makes exactly the allocations it made
+// before there was such a call.  (The members that need the engine are defined behind it.)
+struct CounterBlock {
+    unsigned long long *d = nullptr;
+    int words = 0;      // the counters: what a reset clears and read() copies
+    int ensure(kbbq_engine *e, int n_words, int extra_words = 0);      // the block, zeroed, and extra_words behind it left as they are
+    int read(kbbq_engine *e, unsigned long long *host, int32_t reset);      // waits; host keeps what it holds while there is no block
     int reset(hipStream_t stream) {
-        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 8 * 8, stream));      // (TRIM_COUNTS words: trim.h)
+        if (d) HIP_TRY(hipMemsetAsync(d, 0, (size_t)words * 8, stream));
         return KBBQ_OK;
     }
-};
-
-// 3' adapter removal (include/kbbq_engine.h: kbbq_adapter_find_batch; engine_adapter.h): the kbbq_adapter_counts of
-// k_adapter_find.  Allocated by the first search, as the trim counters are by the first trimming call
-struct AdapterState {
-    unsigned long long *d_counts = nullptr;
-    int reset(hipStream_t stream) {
-        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 6 * 8, stream));      // (ADAPTER_COUNTS words: adapter.h)
-        return KBBQ_OK;
-    }
-};
-
-// Adapters from the overlap of a pair (include/kbbq_engine.h: kbbq_pair_overlap_batch; engine_overlap.h): the
-// kbbq_overlap_counts of k_pair_overlap.  Allocated by the first search
-struct OverlapState {
-    unsigned long long *d_counts = nullptr;
-    int reset(hipStream_t stream) {
-        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 6 * 8, stream));      // (OVERLAP_COUNTS words: overlap.h)
-        return KBBQ_OK;
-    }
-};
-
-// Bases corrected from the mate (include/kbbq_engine.h: kbbq_pair_consensus_batch; engine_consensus.h): the
-// kbbq_pair_consensus_counts of k_pair_consensus.  Allocated by the first call
-struct ConsensusState {
-    unsigned long long *d_counts = nullptr;
-    int reset(hipStream_t stream) {
-        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * 8, stream));      // (CONSENSUS_COUNTS words: consensus.h)
-        return KBBQ_OK;
+    void free() {
+        hipFree(d);
+        d = nullptr;
+        words = 0;
     }
 };
 
@@ -376,10 +356,7 @@ struct kbbq_engine {
     Pass3State p3;
     Pass4State p4;
     ReportState rep;
-    TrimState trim;
-    AdapterState adapter;
-    OverlapState overlap;
-    ConsensusState consensus;
+    CounterBlock trim, adapter, overlap, consensus;
     Staging stage;
     Buckets bk;
     Profile profile;
@@ -517,6 +494,24 @@ int sync_engine(kbbq_engine *e) {
         if (rc) return rc;
     }
     drain_profile(e);
+    return KBBQ_OK;
+}
+
+int CounterBlock::ensure(kbbq_engine *e, int n_words, int extra_words) {
+    if (d) return KBBQ_OK;
+    unsigned long long *p = nullptr;
+    HIP_TRY(hipMalloc(&p, (size_t)(n_words + extra_words) * 8));
+    hipError_t he = hipMemsetAsync(p, 0, (size_t)n_words * 8, e->stream);
+    if (he != hipSuccess) { hipFree(p); HIP_TRY(he); }
+    d = p;
+    words = n_words;
+    return KBBQ_OK;
+}
+int CounterBlock::read(kbbq_engine *e, unsigned long long *host, int32_t reset) {
+    int rc = sync_engine(e);
+    if (rc || !d) return rc;
+    HIP_TRY(hipMemcpy(host, d, (size_t)words * 8, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(d, 0, (size_t)words * 8));
     return KBBQ_OK;
 }
 

@@ -5,20 +5,16 @@
 
 namespace {
 
-// the first trimming call of this engine: the counters and the expected-error table (engine_state.h: TrimState)
+// the first trimming call of this engine: the counters and, behind them in the same allocation, the expected-error table
 int trim_state(kbbq_engine *e) {
-    if (e->trim.d_counts) return KBBQ_OK;
+    if (e->trim.d) return KBBQ_OK;
     uint64_t table[256];
     int rc = kbbq_trim_ee_table(table);
     if (rc) return rc;
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc(&d, (TRIM_COUNTS + 256) * 8));
-    hipError_t he = hipMemsetAsync(d, 0, TRIM_COUNTS * 8, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(d + TRIM_COUNTS, table, sizeof table, hipMemcpyHostToDevice, e->stream);
+    if ((rc = e->trim.ensure(e, TRIM_COUNTS, 256))) return rc;
+    hipError_t he = hipMemcpyAsync(e->trim.d + TRIM_COUNTS, table, sizeof table, hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);      // (the table is on this call's stack)
-    if (he != hipSuccess) { hipFree(d); HIP_TRY(he); }
-    e->trim.d_counts = d;
-    e->trim.d_ee = d + TRIM_COUNTS;
+    if (he != hipSuccess) { e->trim.free(); HIP_TRY(he); }
     return KBBQ_OK;
 }
 
@@ -47,7 +43,7 @@ int kbbq_trim_batch_limited(kbbq_engine *e, const kbbq_reads *reads, const uint8
     P.min_len = (uint32_t)std::max<uint64_t>(1, p->min_length);
     P.ee_bound = p->ee_bound;
     Timed t(e, "k_trim_reads");
-    hipLaunchKernelGGL(k_trim_reads, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, device_qual, P, e->trim.d_ee, limit, keep, e->trim.d_counts);
+    hipLaunchKernelGGL(k_trim_reads, dim3(wave_grid(R.n_reads)), dim3(256), 0, e->stream, R, device_qual, P, e->trim.d + TRIM_COUNTS, limit, keep, e->trim.d);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
@@ -62,7 +58,7 @@ int kbbq_trim_mates(kbbq_engine *e, uint32_t *keep_a, uint32_t *keep_b, uint64_t
     if (!n_pairs) return KBBQ_OK;
     Timed t(e, "k_trim_mates");
     hipLaunchKernelGGL(k_trim_mates, dim3((unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 4096)), dim3(256), 0, e->stream, keep_a, keep_b, n_pairs,
-                       adjacent ? 1 : 0, e->trim.d_counts);
+                       adjacent ? 1 : 0, e->trim.d);
     HIP_TRY(hipGetLastError());
     return KBBQ_OK;
 }
@@ -70,14 +66,11 @@ int kbbq_trim_mates(kbbq_engine *e, uint32_t *keep_a, uint32_t *keep_b, uint64_t
 int kbbq_trim_counts_get(kbbq_engine *e, kbbq_trim_counts *out, int32_t reset) {
     ENGINE_DEVICE(e);
     if (!out) return fail(KBBQ_EINVAL, "null argument");
-    int rc = sync_engine(e);
-    if (rc) return rc;
     unsigned long long c[TRIM_COUNTS] = {};
-    if (e->trim.d_counts) HIP_TRY(hipMemcpy(c, e->trim.d_counts, sizeof c, hipMemcpyDeviceToHost));
+    if (const int rc = e->trim.read(e, c, reset)) return rc;
     out->reads_in = c[TRIM_READS_IN]; out->bases_in = c[TRIM_BASES_IN]; out->shortened = c[TRIM_SHORTENED];
     out->too_short = c[TRIM_TOO_SHORT]; out->over_ee = c[TRIM_OVER_EE]; out->reads_kept = c[TRIM_READS_KEPT];
     out->bases_kept = c[TRIM_BASES_KEPT]; out->with_mate = c[TRIM_WITH_MATE];
-    if (reset && e->trim.d_counts) HIP_TRY(hipMemset(e->trim.d_counts, 0, sizeof c));
     return KBBQ_OK;
 }
 

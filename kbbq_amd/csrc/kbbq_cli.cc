@@ -108,6 +108,7 @@ using namespace kbbq;
 #include "cli_device_io.h"
 #include "cli_pairs.h"
 #include "cli_host_batch.h"
+#include "cli_pair_walk.h"
 
 // minion::create_seed_seq().GenerateOne() (minion.hpp:320-345, 377-408; the chrono/random_device branch
 // is disabled there by the __cpluscplus typo, so the inputs are time(nullptr), getpid() and two constants)
@@ -790,6 +791,7 @@ static int tally_fixed_on_device(kbbq_engine *e, const CliOptions &o, ScanState 
     return 0;
 }
 
+#include "cli_slots.h"
 #include "cli_trim.h"
 #include "cli_pass4.h"
 #include "cli_table.h"

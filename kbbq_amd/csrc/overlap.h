@@ -11,8 +11,14 @@
 
 namespace kbbq {
 
-struct OverlapDev {
+// The pairs of a call on two batches (engine_overlap.h: pair_view): pair j is read a(j) of the one and read b(j) of the other
+struct PairsDev {
     uint64_t first_a, first_b, stride, n_pairs;
+    __device__ __forceinline__ uint64_t a(uint64_t j) const { return first_a + j * stride; }
+    __device__ __forceinline__ uint64_t b(uint64_t j) const { return first_b + j * stride; }
+};
+struct OverlapDev {
+    PairsDev pairs;
     int min_overlap, max_diff, permille, merge;
 };
 // the words of the counter array (kbbq_overlap_counts, in its order)
@@ -87,18 +93,17 @@ __device__ __forceinline__ OverlapStreams overlap_streams(const ReadsDev &RA, co
 // insert (may be null): one word per pair, L* of the winner or 0 (kbbq_pair_overlap_inserts).
 __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, OverlapDev P, uint32_t *limit_a, uint32_t *limit_b, uint32_t *insert,
                                                       unsigned long long *counts) {
-    __shared__ unsigned long long tot[4][OVERLAP_COUNTS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
     const int V = P.min_overlap;
     unsigned long long cnt[OVERLAP_COUNTS];
 #pragma unroll
     for (int c = 0; c < OVERLAP_COUNTS; ++c) cnt[c] = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * 4 + wave; j < P.n_pairs; j += n_waves) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 4 + wave; j < P.pairs.n_pairs; j += n_waves) {
         uint64_t off1, off2;
         uint32_t len1, len2;
-        read_span(RA, P.first_a + j * P.stride, off1, len1);
-        read_span(RB, P.first_b + j * P.stride, off2, len2);
+        read_span(RA, P.pairs.a(j), off1, len1);
+        read_span(RB, P.pairs.b(j), off2, len2);
         int lim1 = (int)len1, lim2 = (int)len2, found = 0;      // found: L* of the hit, 0 for none
         if (len1 > (uint32_t)kOverlapMaxRead || len2 > (uint32_t)kOverlapMaxRead) {
             cnt[OVERLAP_TOO_LONG] += 1;
@@ -142,21 +147,13 @@ __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, 
             }
         }
         if (lane == 0) {
-            uint32_t *la = limit_a + j * P.stride, *lb = limit_b + j * P.stride;
+            uint32_t *la = limit_a + j * P.pairs.stride, *lb = limit_b + j * P.pairs.stride;
             *la = P.merge ? min(*la, (uint32_t)lim1) : (uint32_t)lim1;
             *lb = P.merge ? min(*lb, (uint32_t)lim2) : (uint32_t)lim2;
             if (insert) insert[j] = (uint32_t)found;
         }
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < OVERLAP_COUNTS; ++c) tot[wave][c] = cnt[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < OVERLAP_COUNTS) {
-        const unsigned long long v = tot[0][threadIdx.x] + tot[1][threadIdx.x] + tot[2][threadIdx.x] + tot[3][threadIdx.x];
-        if (v) atomicAdd(&counts[threadIdx.x], v);
-    }
+    add_wave_counts(cnt, counts);
 }
 
 }  // namespace kbbq

@@ -6,6 +6,7 @@
 // prefix, summed from a table of 2^32-scaled integers, and one verdict per read.
 #pragma once
 #include "device_common.h"
+#include "wave_helpers.h"
 
 namespace kbbq {
 
@@ -60,7 +61,6 @@ __device__ __forceinline__ bool trim_round(int d, bool valid, int first_i, int l
 __global__ void __launch_bounds__(256) k_trim_reads(ReadsDev R, const uint8_t *qual, TrimDev P, const unsigned long long *ee_table,
                                                     const uint32_t *limit, uint32_t *keep, unsigned long long *counts) {
     __shared__ unsigned long long ee[256];
-    __shared__ unsigned long long tot[4][TRIM_WITH_MATE];
     ee[threadIdx.x] = ee_table[threadIdx.x];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -127,15 +127,7 @@ __global__ void __launch_bounds__(256) k_trim_reads(ReadsDev R, const uint8_t *q
         }
         if (lane == 0) keep[r] = out;
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < TRIM_WITH_MATE; ++c) tot[wave][c] = cnt[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < TRIM_WITH_MATE) {
-        const unsigned long long v = tot[0][threadIdx.x] + tot[1][threadIdx.x] + tot[2][threadIdx.x] + tot[3][threadIdx.x];
-        if (v) atomicAdd(&counts[threadIdx.x], v);
-    }
+    add_wave_counts(cnt, counts);
 }
 
 // The mate rule: pair i is (a[i], b[i]), or (a[2i], a[2i+1]) with `adjacent` (b is not read).  Where exactly one of the two

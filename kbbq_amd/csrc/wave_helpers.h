@@ -1,5 +1,6 @@
 // wave_helpers.h -- __device__ helpers that kernels of more than one translation unit use (gfx950): unaligned 8-byte
-// loads, the CRC-32 of a byte range by one wavefront, and the text of one FASTQ record written by one wavefront.
+// loads, the CRC-32 of a byte range by one wavefront, the text of one FASTQ record written by one wavefront, and the
+// per-workgroup add-up of per-wavefront counters (add_wave_counts: the engine's trim, adapter and pair-overlap kernels).
 // No kernels here: every __global__ function of the I/O side is defined in a header that exactly one unit includes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -129,4 +130,21 @@ __device__ __forceinline__ void emit_fastq_record(int lane, const uint8_t *name,
 }
 
 }  // namespace dfl
+
+// The end of a kernel of four wavefronts a workgroup that counts per wavefront (every thread calls, cnt wave-uniform): the four
+// waves' cnt[] are added up in LDS and the sums, where not zero, added to the engine's counts[] once per workgroup.
+template <int N> __device__ __forceinline__ void add_wave_counts(const unsigned long long (&cnt)[N], unsigned long long *counts) {
+    __shared__ unsigned long long tot[4][N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) tot[wave][c] = cnt[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const unsigned long long v = tot[0][threadIdx.x] + tot[1][threadIdx.x] + tot[2][threadIdx.x] + tot[3][threadIdx.x];
+        if (v) atomicAdd(&counts[threadIdx.x], v);
+    }
+}
+
 }  // namespace kbbq

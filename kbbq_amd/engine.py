@@ -270,9 +270,13 @@ class Engine:
 
     def fix_counts(self, reset=False):
         """What correct_bases did since the last reset (waits): flagged, fixed, ambiguous, unsupported."""
-        c = _lib.FixCounts()
-        _lib.check(self.L.kbbq_correct_counts(self.h, ctypes.byref(c), 1 if reset else 0))
-        return dict(flagged=int(c.flagged), fixed=int(c.fixed), ambiguous=int(c.ambiguous), unsupported=int(c.unsupported))
+        return self._counts(self.L.kbbq_correct_counts, _lib.FixCounts, reset)
+
+    def _counts(self, fn, Struct, reset):
+        """One of the engine's counter blocks through its *_counts call (waits): the struct's fields by name."""
+        c = Struct()
+        _lib.check(fn(self.h, ctypes.byref(c), 1 if reset else 0))
+        return {n: int(getattr(c, n)) for n, _ in Struct._fields_}
 
     # ---- trimming and filtering by the qualities pass 4 wrote
     def trim_reads(self, dreads, qual_ptr, tail_q=None, min_length=1, max_ee=None, limit=None):
@@ -324,9 +328,7 @@ class Engine:
 
     def adapter_counts(self, reset=False):
         """What find_adapters did since the last reset (waits): the fields of kbbq_adapter_counts."""
-        c = _lib.AdapterCounts()
-        _lib.check(self.L.kbbq_adapter_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
-        return {n: int(getattr(c, n)) for n, _ in _lib.AdapterCounts._fields_}
+        return self._counts(self.L.kbbq_adapter_counts_get, _lib.AdapterCounts, reset)
 
     # ---- adapters from the overlap of a pair: where both mates run off the insert
     def find_pair_overlaps(self, dev_a, dev_b, first_a=0, first_b=0, stride=1, n_pairs=None, min_overlap=30, max_diff=5, max_error_permille=200,
@@ -382,9 +384,7 @@ class Engine:
 
     def overlap_counts(self, reset=False):
         """What find_pair_overlaps did since the last reset (waits): the fields of kbbq_overlap_counts."""
-        c = _lib.OverlapCounts()
-        _lib.check(self.L.kbbq_overlap_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
-        return {n: int(getattr(c, n)) for n, _ in _lib.OverlapCounts._fields_}
+        return self._counts(self.L.kbbq_overlap_counts_get, _lib.OverlapCounts, reset)
 
     # ---- bases corrected from the mate inside the overlap
     def pair_consensus(self, dev_a, dev_b, insert, qual_a, qual_b=None, first_a=0, first_b=0, stride=1, n_pairs=None, good_q=30, bad_q=15,
@@ -440,9 +440,7 @@ class Engine:
 
     def pair_consensus_counts(self, reset=False):
         """What pair_consensus did since the last reset (waits): the fields of kbbq_pair_consensus_counts."""
-        c = _lib.ConsensusCounts()
-        _lib.check(self.L.kbbq_pair_consensus_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
-        return {n: int(getattr(c, n)) for n, _ in _lib.ConsensusCounts._fields_}
+        return self._counts(self.L.kbbq_pair_consensus_counts_get, _lib.ConsensusCounts, reset)
 
     def trim_mates(self, keep_a, keep_b=None, adjacent=False):
         """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
@@ -464,9 +462,7 @@ class Engine:
 
     def trim_counts(self, reset=False):
         """What trim_reads and trim_mates did since the last reset (waits): the fields of kbbq_trim_counts."""
-        c = _lib.TrimCounts()
-        _lib.check(self.L.kbbq_trim_counts_get(self.h, ctypes.byref(c), 1 if reset else 0))
-        return {n: int(getattr(c, n)) for n, _ in _lib.TrimCounts._fields_}
+        return self._counts(self.L.kbbq_trim_counts_get, _lib.TrimCounts, reset)
 
     def covariates(self):
         R, C = self.n_rg, self.max_read_len
