@@ -16,7 +16,6 @@
 //   end <rows>                             the number of transfer / cycle / observed lines: a file cut short has none
 //
 // The reader indexes with nothing it has not checked, and every refusal names the line.  No GPU is touched.
-#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -24,179 +23,107 @@
 #include <unordered_set>
 #include <vector>
 
-#include "../../include/kbbq_engine.h"
-
-// (abi_internal.h, which a unit without the HIP headers cannot include: the text of kbbq_last_error())
-int kbbq_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+#include "host_text.h"
 
 namespace {
 
-constexpr uint64_t kMaxGroups = 65534;      // as in the table file
+using namespace host_text;
+
 constexpr uint64_t kNOut = KBBQ_MAXQ + 1;   // columns of the transfer table
-
-bool clean_field(const char *s) {
-    for (; *s; ++s) if (*s == '\t' || *s == '\n' || *s == '\r') return false;
-    return true;
-}
-
-// one line of the text, cut at its TABs
-struct Fields {
-    std::vector<std::pair<const char *, size_t>> f;
-    void cut(const char *line, size_t n) {
-        f.clear();
-        size_t a = 0;
-        for (size_t i = 0; i <= n; ++i)
-            if (i == n || line[i] == '\t') { f.emplace_back(line + a, i - a); a = i + 1; }
-    }
-    bool is(size_t i, const char *word) const { return f[i].second == strlen(word) && !memcmp(f[i].first, word, f[i].second); }
-};
-
-// decimal digits and nothing else, a value that fits u64
-bool parse_u64(const std::pair<const char *, size_t> &s, uint64_t *out) {
-    if (!s.second) return false;
-    uint64_t v = 0;
-    for (size_t i = 0; i < s.second; ++i) {
-        const char c = s.first[i];
-        if (c < '0' || c > '9') return false;
-        const uint64_t d = (uint64_t)(c - '0');
-        if (v > (UINT64_MAX - d) / 10) return false;
-        v = v * 10 + d;
-    }
-    *out = v;
-    return true;
-}
 
 // value > bases * per (per > 0); a product that overflows 64 bits is above every value
 bool product_exceeds(uint64_t bases, uint64_t per, uint64_t value) { return bases <= UINT64_MAX / per && value > bases * per; }
 
-struct Parsed {
-    uint64_t n_rg = 0, n_cycle = 0, id_bytes = 0, above = 0;
-    std::vector<std::string> ids;
+struct Parsed : Head {
+    uint64_t above = 0;
 };
 
 // The whole file, checked line by line.  rep / observed_q: null (the dimensions alone) or zeroed arrays of the file's dimensions.
 int parse_report(const char *path, const std::string &text, Parsed &t, const kbbq_quality_report *rep, uint64_t *observed_q) {
     enum { kTransfer, kCycle, kObserved };
     std::unordered_set<uint64_t> seen;      // the cells given so far: a row given twice is refused
-    std::unordered_set<std::string> seen_ids;
     std::vector<uint64_t> transfer_total, cycle_total;      // per read group
     Fields fl;
-    uint64_t line_no = 0, rows = 0;
-    bool have_cycle = false, in_rows = false, have_above = false, ended = false;
-    size_t at = 0;
-    auto bad = [&](const char *what) { return kbbq_fail(KBBQ_EINVAL, "report %s: line %llu: %s", path, (unsigned long long)line_no, what); };
-    while (at < text.size()) {
-        ++line_no;
-        const char *line = text.data() + at;
-        const char *nl = (const char *)memchr(line, '\n', text.size() - at);
-        if (!nl) return bad("the file ends inside a line (truncated)");
-        const size_t n = (size_t)(nl - line);
-        at += n + 1;
-        if (line_no == 1) {
-            if (n < 13 || memcmp(line, "#kbbq-report ", 13)) return bad("not a kbbq quality report (the first line must be \"#kbbq-report 1\")");
-            if (n != 14 || line[13] != '1') return bad("unknown report version (this build reads version 1)");
+    Lines ln("report", path, text);
+    uint64_t rows = 0;
+    bool in_rows = false, have_above = false, ended = false;
+    for (int got; (got = ln.next()) != 0;) {
+        if (got < 0) return got;
+        if (ln.line_no == 1) {
+            if ((got = ln.magic("not a kbbq quality report (the first line must be \"#kbbq-report 1\")", "unknown report version (this build reads version 1)"))) return got;
             continue;
         }
-        if (ended) return bad("text after the end line");
-        if (n && line[0] == '#') continue;
-        fl.cut(line, n);
+        if (ended) return ln.bad("text after the end line");
+        if (ln.n && ln.line[0] == '#') continue;
+        fl.cut(ln.line, ln.n);
         const size_t nf = fl.f.size();
         uint64_t v[6] = {0, 0, 0, 0, 0, 0};
-        if (fl.is(0, "n_cycle")) {
-            if (have_cycle) return bad("n_cycle given twice");
-            if (nf != 2 || !parse_u64(fl.f[1], &v[0])) return bad("n_cycle needs one number");
-            if (v[0] < 1 || v[0] > KBBQ_MAX_READ_LEN) return bad("n_cycle out of range");
-            t.n_cycle = v[0];
-            have_cycle = true;
-        } else if (fl.is(0, "read_group")) {
-            if (!have_cycle) return bad("read_group before n_cycle");
-            if (in_rows) return bad("read_group after the first row");
-            if (nf != 3 || !parse_u64(fl.f[1], &v[0])) return bad("read_group needs an index and an id");
-            if (v[0] != t.ids.size()) return bad("read groups must come in index order 0, 1, ...");
-            if (t.ids.size() >= kMaxGroups) return bad("more than 65534 read groups");
-            std::string id(fl.f[2].first, fl.f[2].second);
-            if (id.find('\0') != std::string::npos || id.find('\r') != std::string::npos) return bad("a read group id with a control character");
-            if (!seen_ids.insert(id).second) return bad("a read group id given twice");
-            t.id_bytes += id.size() + 1;
-            t.ids.push_back(std::move(id));
+        if ((got = t.take(ln, fl, in_rows, "read_group after the first row"))) {
+            if (got < 0) return got;
         } else if (fl.is(0, "above_maxq")) {
-            if (!have_cycle || t.ids.empty()) return bad("above_maxq before n_cycle and the read groups");
-            if (have_above) return bad("above_maxq given twice");
-            if (nf != 2 || !parse_u64(fl.f[1], &v[0])) return bad("above_maxq needs one number");
+            if (!t.complete()) return ln.bad("above_maxq before n_cycle and the read groups");
+            if (have_above) return ln.bad("above_maxq given twice");
+            if (nf != 2 || !fl.number(1, &v[0])) return ln.bad("above_maxq needs one number");
             t.above = v[0];
             have_above = in_rows = true;
         } else if (fl.is(0, "end")) {
-            if (!have_cycle || t.ids.empty()) return bad("end before n_cycle and the read groups");
-            if (!have_above) return bad("end before above_maxq");
-            if (nf != 2 || !parse_u64(fl.f[1], &v[0])) return bad("end needs the number of rows");
-            if (v[0] != rows) return bad("the end line's row count is not the number of rows read (truncated or edited)");
-            transfer_total.resize(t.ids.size(), 0);
-            cycle_total.resize(t.ids.size(), 0);
-            for (size_t g = 0; g < t.ids.size(); ++g)
-                if (transfer_total[g] != cycle_total[g]) return bad("a read group's transfer rows and cycle rows count different numbers of bases");
+            if (!t.complete()) return ln.bad("end before n_cycle and the read groups");
+            if (!have_above) return ln.bad("end before above_maxq");
+            if (nf != 2 || !fl.number(1, &v[0])) return ln.bad("end needs the number of rows");
+            if (v[0] != rows) return ln.bad("the end line's row count is not the number of rows read (truncated or edited)");
+            transfer_total.resize(t.n_rg(), 0);
+            cycle_total.resize(t.n_rg(), 0);
+            for (size_t g = 0; g < t.n_rg(); ++g)
+                if (transfer_total[g] != cycle_total[g]) return ln.bad("a read group's transfer rows and cycle rows count different numbers of bases");
             ended = true;
         } else {
             int kind, n_index, n_values;
             if (fl.is(0, "transfer")) { kind = kTransfer; n_index = 3; n_values = 1; }
             else if (fl.is(0, "cycle")) { kind = kCycle; n_index = 3; n_values = 3; }
             else if (fl.is(0, "observed")) { kind = kObserved; n_index = 2; n_values = 2; }
-            else return bad("unknown record");
-            if (!have_cycle || t.ids.empty()) return bad("a row before n_cycle and the read groups");
-            if (have_above) return bad("a row after above_maxq");
+            else return ln.bad("unknown record");
+            if (!t.complete()) return ln.bad("a row before n_cycle and the read groups");
+            if (have_above) return ln.bad("a row after above_maxq");
             in_rows = true;
-            t.n_rg = t.ids.size();
-            transfer_total.resize(t.n_rg, 0);
-            cycle_total.resize(t.n_rg, 0);
-            if (nf != (size_t)(1 + n_index + n_values)) return bad("wrong number of fields");
+            transfer_total.resize(t.n_rg(), 0);
+            cycle_total.resize(t.n_rg(), 0);
+            if (nf != (size_t)(1 + n_index + n_values)) return ln.bad("wrong number of fields");
             for (int i = 0; i < n_index + n_values; ++i)
-                if (!parse_u64(fl.f[(size_t)i + 1], &v[i])) return bad("a number does not parse or overflows 64 bits");
-            if (v[0] >= t.n_rg) return bad("an index is out of range");
+                if (!fl.number((size_t)i + 1, &v[i])) return ln.bad("a number does not parse or overflows 64 bits");
+            if (v[0] >= t.n_rg()) return ln.bad("an index is out of range");
             if (kind == kTransfer) {
-                if (v[1] >= KBBQ_NQ) return bad("an index is out of range");
-                if (v[2] > KBBQ_MAXQ) return bad("q_out > 93");
+                if (v[1] >= KBBQ_NQ) return ln.bad("an index is out of range");
+                if (v[2] > KBBQ_MAXQ) return ln.bad("q_out > 93");
             } else if (kind == kCycle) {
-                if (v[1] >= 2 || v[2] >= t.n_cycle) return bad("an index is out of range");
+                if (v[1] >= 2 || v[2] >= t.n_cycle) return ln.bad("an index is out of range");
             } else {
-                if (v[1] >= KBBQ_NQ) return bad("an index is out of range");
+                if (v[1] >= KBBQ_NQ) return ln.bad("an index is out of range");
             }
             const uint64_t *val = v + n_index;
             if (kind == kObserved) {
-                if (val[0] > val[1]) return bad("errors > total");
-                if (!val[1]) return bad("a row whose total is zero");
+                if (val[0] > val[1]) return ln.bad("errors > total");
+                if (!val[1]) return ln.bad("a row whose total is zero");
             } else {
-                if (!val[0]) return bad("a row that counts no bases");
+                if (!val[0]) return ln.bad("a row that counts no bases");
                 uint64_t &sum = (kind == kTransfer ? transfer_total : cycle_total)[v[0]];
-                if (sum > UINT64_MAX - val[0]) return bad("a read group's bases overflow 64 bits");
+                if (sum > UINT64_MAX - val[0]) return ln.bad("a read group's bases overflow 64 bits");
                 sum += val[0];
                 if (kind == kCycle) {
-                    if (product_exceeds(val[0], 255, val[1])) return bad("sum_in > 255 * bases");
-                    if (product_exceeds(val[0], KBBQ_MAXQ, val[2])) return bad("sum_out > 93 * bases");
+                    if (product_exceeds(val[0], 255, val[1])) return ln.bad("sum_in > 255 * bases");
+                    if (product_exceeds(val[0], KBBQ_MAXQ, val[2])) return ln.bad("sum_out > 93 * bases");
                 }
             }
             // (2 bits of kind, 16 of rg, 8 of q_in / q / pair, 23 of q_out / cycle)
             const uint64_t key = (uint64_t)kind | v[0] << 2 | v[1] << 18 | (n_index > 2 ? v[2] : 0) << 26;
-            if (!seen.insert(key).second) return bad("a row given twice");
+            if (!seen.insert(key).second) return ln.bad("a row given twice");
             ++rows;
             if (kind == kTransfer && rep) rep->transfer[(v[0] * KBBQ_NQ + v[1]) * kNOut + v[2]] = val[0];
             if (kind == kCycle && rep) memcpy(rep->cycle + ((v[0] * 2 + v[1]) * t.n_cycle + v[2]) * 3, val, 24);
             if (kind == kObserved && observed_q) memcpy(observed_q + (v[0] * KBBQ_NQ + v[1]) * 2, val, 16);
         }
     }
-    if (line_no == 0) { line_no = 1; return bad("the file is empty"); }
-    if (!ended) { ++line_no; return bad("the file ends without its end line (truncated)"); }
-    t.n_rg = t.ids.size();
-    return KBBQ_OK;
-}
-
-int slurp(const char *path, std::string &text) {
-    FILE *f = fopen(path, "rb");
-    if (!f) return kbbq_fail(KBBQ_EINVAL, "report %s: %s", path, strerror(errno));
-    char buf[1 << 16];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
-    const bool err = ferror(f) != 0;
-    fclose(f);
-    if (err) return kbbq_fail(KBBQ_EIO, "report %s: read error", path);
+    if (!ln.line_no) return ln.bad_after("the file is empty");
+    if (!ended) return ln.bad_after("the file ends without its end line (truncated)");
     return KBBQ_OK;
 }
 
@@ -210,23 +137,11 @@ int kbbq_host_report_write(const char *path, const kbbq_quality_report *rep, con
     if (rep->n_rg < 1 || rep->n_rg > kMaxGroups) return kbbq_fail(KBBQ_EINVAL, "a report holds 1 to 65534 read groups");
     if (rep->n_cycle < 1 || rep->n_cycle > KBBQ_MAX_READ_LEN) return kbbq_fail(KBBQ_EINVAL, "n_cycle out of range");
     if (observed && (!observed->q || observed->n_rg != rep->n_rg)) return kbbq_fail(KBBQ_EINVAL, "the observed histograms are not of the report's read groups");
-    std::unordered_set<std::string> ids;
-    for (uint64_t g = 0; g < rep->n_rg; ++g) {
-        if (!rg_ids[g] || !clean_field(rg_ids[g])) return kbbq_fail(KBBQ_EINVAL, "read group %llu has no id, or one with a TAB or a line break", (unsigned long long)g);
-        if (!ids.insert(rg_ids[g]).second) return kbbq_fail(KBBQ_EINVAL, "read group id \"%s\" is given twice", rg_ids[g]);
-    }
+    if (const int rc = check_ids(rg_ids, rep->n_rg)) return rc;
     const uint64_t C = rep->n_cycle;
     std::string head = "#kbbq-report 1\n", body;
     char line[320];
-    if (info) {
-        snprintf(line, sizeof line, "#k\t%d\n#seed\t%u\n#bases\t%llu\n", (int)info->k, (unsigned)info->seed, (unsigned long long)info->total_bases);
-        head += line;
-        if (info->command) {
-            head += "#command\t";
-            for (const char *c = info->command; *c; ++c) head += *c == '\n' || *c == '\r' ? ' ' : *c;
-            head += '\n';
-        }
-    }
+    put_info(head, info);
     uint64_t rows = 0;
     // rows of the body, and per read group the summary line for people and the checks a reader would make
     for (uint64_t g = 0; g < rep->n_rg; ++g) {
@@ -278,50 +193,35 @@ int kbbq_host_report_write(const char *path, const kbbq_quality_report *rep, con
                  mean_in, mean_out, (unsigned long long)changed);
         head += line;
     }
-    snprintf(line, sizeof line, "n_cycle\t%llu\n", (unsigned long long)C);
-    head += line;
-    for (uint64_t g = 0; g < rep->n_rg; ++g) {
-        snprintf(line, sizeof line, "read_group\t%llu\t", (unsigned long long)g);
-        head += line;
-        head += rg_ids[g];
-        head += '\n';
-    }
+    put_head(head, C, rg_ids, rep->n_rg);
     snprintf(line, sizeof line, "above_maxq\t%llu\nend\t%llu\n", (unsigned long long)rep->above_maxq, (unsigned long long)rows);
     body += line;
-    FILE *f = fopen(path, "wb");
-    if (!f) return kbbq_fail(KBBQ_EIO, "report %s: %s", path, strerror(errno));
-    const bool ok = fwrite(head.data(), 1, head.size(), f) == head.size() && fwrite(body.data(), 1, body.size(), f) == body.size();
-    if (fclose(f) != 0 || !ok) return kbbq_fail(KBBQ_EIO, "report %s: write error", path);
-    return KBBQ_OK;
+    return write_file("report", path, head, body);
 }
 
 int kbbq_host_report_read(const char *path, kbbq_quality_report *rep, uint64_t *observed_q, char *rg_ids, uint64_t *rg_ids_bytes) {
     if (!path || !rep || !rg_ids_bytes) return kbbq_fail(KBBQ_EINVAL, "null argument");
     std::string text;
-    int rc = slurp(path, text);
+    int rc = slurp("report", path, text);
     if (rc) return rc;
     Parsed dims;
     if ((rc = parse_report(path, text, dims, nullptr, nullptr))) return rc;
     if (!rep->transfer && !rep->cycle && !observed_q && !rg_ids) {      // step one: the dimensions
-        rep->n_rg = dims.n_rg;
+        rep->n_rg = dims.n_rg();
         rep->n_cycle = dims.n_cycle;
         rep->above_maxq = dims.above;
         *rg_ids_bytes = dims.id_bytes;
         return KBBQ_OK;
     }
     if (!rep->transfer || !rep->cycle || !rg_ids) return kbbq_fail(KBBQ_EINVAL, "null argument");
-    if (rep->n_rg != dims.n_rg || rep->n_cycle != dims.n_cycle || *rg_ids_bytes < dims.id_bytes)
-        return kbbq_fail(KBBQ_EINVAL, "report %s is [%llu rg][%llu cycles] with %llu bytes of ids: the arrays given are for another", path,
-                         (unsigned long long)dims.n_rg, (unsigned long long)dims.n_cycle, (unsigned long long)dims.id_bytes);
-    memset(rep->transfer, 0, dims.n_rg * KBBQ_NQ * kNOut * 8);
-    memset(rep->cycle, 0, dims.n_rg * 2 * dims.n_cycle * 3 * 8);
-    if (observed_q) memset(observed_q, 0, dims.n_rg * KBBQ_NQ * 2 * 8);
+    if ((rc = dims.check_dims("report", path, rep->n_rg, rep->n_cycle, *rg_ids_bytes))) return rc;
+    memset(rep->transfer, 0, dims.n_rg() * KBBQ_NQ * kNOut * 8);
+    memset(rep->cycle, 0, dims.n_rg() * 2 * dims.n_cycle * 3 * 8);
+    if (observed_q) memset(observed_q, 0, dims.n_rg() * KBBQ_NQ * 2 * 8);
     Parsed t;
     if ((rc = parse_report(path, text, t, rep, observed_q))) return rc;
     rep->above_maxq = t.above;
-    char *to = rg_ids;
-    for (const std::string &id : t.ids) { memcpy(to, id.c_str(), id.size() + 1); to += id.size() + 1; }
-    *rg_ids_bytes = dims.id_bytes;
+    t.copy_ids(rg_ids, rg_ids_bytes);
     return KBBQ_OK;
 }
 

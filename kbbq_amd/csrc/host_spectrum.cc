@@ -23,18 +23,16 @@
 // whatever the writer cannot have written -- and the writer refuses the same results: sums that disagree with the bins
 // (distinct, counted against the bins and the tail mass, a tail mass below what the last bin implies, more counted than
 // valid positions), an estimate that is not the estimator's for these bins.
-#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
 
-#include "../../include/kbbq_engine.h"
-
-// (abi_internal.h, which a unit without the HIP headers cannot include: the text of kbbq_last_error())
-int kbbq_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+#include "host_text.h"
 
 namespace {
+
+using namespace host_text;
 
 typedef unsigned __int128 u128;
 constexpr int B = KBBQ_SPECTRUM_BINS;
@@ -79,20 +77,6 @@ const char *inconsistent(const kbbq_spectrum_result *r) {
 bool same(const kbbq_spectrum_estimate &a, const kbbq_spectrum_estimate &b) {
     return a.genome_length == b.genome_length && a.valley == b.valley && a.peak == b.peak && a.window_kmers == b.window_kmers &&
            a.kmer_coverage_milli == b.kmer_coverage_milli;
-}
-
-// decimal digits and nothing else, a value that fits u64
-bool parse_u64(const char *s, size_t n, uint64_t *out) {
-    if (!n) return false;
-    uint64_t v = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (s[i] < '0' || s[i] > '9') return false;
-        const uint64_t d = (uint64_t)(s[i] - '0');
-        if (v > (UINT64_MAX - d) / 10) return false;
-        v = v * 10 + d;
-    }
-    *out = v;
-    return true;
 }
 
 }  // namespace
@@ -158,76 +142,56 @@ int kbbq_host_spectrum_write(const char *path, const kbbq_spectrum_result *r, co
         snprintf(line, sizeof line, "%d\t%llu\n", m, (unsigned long long)r->hist[m]);
         out += line;
     }
-    FILE *f = fopen(path, "wb");
-    if (!f) return kbbq_fail(KBBQ_EIO, "spectrum %s: %s", path, strerror(errno));
-    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
-    if (fclose(f) != 0 || !ok) return kbbq_fail(KBBQ_EIO, "spectrum %s: write error", path);
-    return KBBQ_OK;
+    return write_file("spectrum", path, out);
 }
 
 int kbbq_host_spectrum_read(const char *path, kbbq_spectrum_result *r, kbbq_spectrum_estimate *est) {
     if (!path || !r) return kbbq_fail(KBBQ_EINVAL, "null argument");
     std::string text;
-    {
-        FILE *f = fopen(path, "rb");
-        if (!f) return kbbq_fail(KBBQ_EINVAL, "spectrum %s: %s", path, strerror(errno));
-        char buf[1 << 16];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
-        const bool err = ferror(f) != 0;
-        fclose(f);
-        if (err) return kbbq_fail(KBBQ_EIO, "spectrum %s: read error", path);
-    }
+    if (const int rc = slurp("spectrum", path, text)) return rc;
     static const char *const kNames[9] = {"#k", "#sample_shift", "#valid_kmers", "#distinct", "#counted", "#tail_mass", "#valley", "#peak", "#genome_length"};
     uint64_t head[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     kbbq_spectrum_result t;
     memset(&t, 0, sizeof t);
-    uint64_t line_no = 0, next_m = 1;
-    auto bad = [&](const char *what) { return kbbq_fail(KBBQ_EINVAL, "spectrum %s: line %llu: %s", path, (unsigned long long)line_no, what); };
-    size_t at = 0;
-    while (at < text.size()) {
-        ++line_no;
-        const char *line = text.data() + at;
-        const char *nl = (const char *)memchr(line, '\n', text.size() - at);
-        if (!nl) return bad("the file ends inside a line (truncated)");
-        const size_t n = (size_t)(nl - line);
-        at += n + 1;
-        if (line_no == 1) {
-            if (n < 15 || memcmp(line, "#kbbq-spectrum ", 15)) return bad("not a kbbq spectrum (the first line must be \"#kbbq-spectrum 1\")");
-            if (n != 16 || line[15] != '1') return bad("unknown spectrum version (this build reads version 1)");
+    uint64_t next_m = 1;
+    Lines ln("spectrum", path, text);
+    for (int got; (got = ln.next()) != 0;) {
+        if (got < 0) return got;
+        if (ln.line_no == 1) {
+            if ((got = ln.magic("not a kbbq spectrum (the first line must be \"#kbbq-spectrum 1\")", "unknown spectrum version (this build reads version 1)"))) return got;
             continue;
         }
-        const char *tab = (const char *)memchr(line, '\t', n);
-        if (!tab) return bad("a line without a TAB");
-        const size_t a = (size_t)(tab - line), b = n - a - 1;
-        if (line_no <= 10) {
-            const char *name = kNames[line_no - 2];
-            if (a != strlen(name) || memcmp(line, name, a)) return bad("the header lines are not the ten of a spectrum, in their order");
-            if (!parse_u64(tab + 1, b, &head[line_no - 2])) return bad("a number does not parse or overflows 64 bits");
+        const char *tab = (const char *)memchr(ln.line, '\t', ln.n);
+        if (!tab) return ln.bad("a line without a TAB");
+        const size_t a = (size_t)(tab - ln.line), b = ln.n - a - 1;
+        if (ln.line_no <= 10) {
+            const char *name = kNames[ln.line_no - 2];
+            if (a != strlen(name) || memcmp(ln.line, name, a)) return ln.bad("the header lines are not the ten of a spectrum, in their order");
+            if (!parse_u64(tab + 1, b, &head[ln.line_no - 2])) return ln.bad("a number does not parse or overflows 64 bits");
             continue;
         }
         uint64_t m = 0, c = 0;
-        if (!parse_u64(line, a, &m) || !parse_u64(tab + 1, b, &c)) return bad("a number does not parse or overflows 64 bits");
-        if (m != next_m || m >= (uint64_t)B) return bad("the bins must come in the order 1, 2, ... and end below 1024");
+        if (!parse_u64(ln.line, a, &m) || !parse_u64(tab + 1, b, &c)) return ln.bad("a number does not parse or overflows 64 bits");
+        if (m != next_m || m >= (uint64_t)B) return ln.bad("the bins must come in the order 1, 2, ... and end below 1024");
         t.hist[m] = c;
         ++next_m;
     }
-    if (line_no < 10) { ++line_no; return bad("the file ends inside its header (truncated)"); }
-    if (next_m > 1 && !t.hist[next_m - 1]) return bad("the last bin is zero (truncated or edited)");
-    if (head[0] > KBBQ_MAX_KMER || head[1] > 32) return bad("k or sample_shift out of range");
+    if (ln.line_no < 10) return ln.bad_after("the file ends inside its header (truncated)");
+    if (next_m > 1 && !t.hist[next_m - 1]) return ln.bad("the last bin is zero (truncated or edited)");
+    if (head[0] > KBBQ_MAX_KMER || head[1] > 32) return ln.bad("k or sample_shift out of range");
     t.k = (uint32_t)head[0];
     t.sample_shift = (uint32_t)head[1];
     t.valid_positions = head[2];
     t.distinct = head[3];
     t.counted = head[4];
     t.tail_mass = head[5];
-    if (const char *why = inconsistent(&t)) return bad(why);
+    if (const char *why = inconsistent(&t)) return ln.bad(why);
     kbbq_spectrum_estimate own, given;
     memset(&given, 0, sizeof given);
     const int rc = kbbq_host_spectrum_estimate(&t, &own);
     if (rc < 0) return rc;
     if (head[6] || head[7] || head[8]) {
-        if (head[6] != own.valley || head[7] != own.peak || head[8] != own.genome_length || rc) return bad("the estimate is not the one these bins give (edited)");
+        if (head[6] != own.valley || head[7] != own.peak || head[8] != own.genome_length || rc) return ln.bad("the estimate is not the one these bins give (edited)");
         given = own;
     }
     *r = t;

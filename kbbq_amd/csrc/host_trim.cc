@@ -7,10 +7,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/kbbq_engine.h"
-
-// (abi_internal.h, which a unit without the HIP headers cannot include: the text of kbbq_last_error())
-int kbbq_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+#include "host_text.h"      // (for kbbq_fail alone)
 
 extern "C" {
 

@@ -465,11 +465,7 @@ class Engine:
         return self._counts(self.L.kbbq_trim_counts_get, _lib.TrimCounts, reset)
 
     def covariates(self):
-        R, C = self.n_rg, self.max_read_len
-        out = dict(R=R, C=C, rg=np.zeros((R, 2), np.uint64), q=np.zeros((R, NQ, 2), np.uint64),
-                   cycle=np.zeros((R, NQ, 2, C, 2), np.uint64), dinuc=np.zeros((R, NQ, 16, 2), np.uint64))
-        c = _lib.Covariates()
-        c.rg, c.q, c.cycle, c.dinuc = (out[k].ctypes.data for k in ("rg", "q", "cycle", "dinuc"))
+        out, c = _covariates_arrays(self.n_rg, self.max_read_len)
         _lib.check(self.L.kbbq_covariates_get(self.h, ctypes.byref(c)))
         return out
 
@@ -479,19 +475,12 @@ class Engine:
         return self.dq()
 
     def dq(self):
-        R, C = self.n_rg, self.max_read_len
-        out = dict(R=R, C=C, meanq=np.zeros(R, np.int32), rg=np.zeros(R, np.int32), q=np.zeros((R, NQ), np.int32),
-                   cycle=np.zeros((R, NQ, 2, C), np.int32), dinuc=np.zeros((R, NQ, 16), np.int32))
-        d = _lib.Dq()
-        d.meanq, d.rgdq, d.qdq, d.cycledq, d.dinucdq = (out[k].ctypes.data for k in ("meanq", "rg", "q", "cycle", "dinuc"))
+        out, d = _dq_arrays(self.n_rg, self.max_read_len)
         _lib.check(self.L.kbbq_dq_get(self.h, ctypes.byref(d)))
         return out
 
     def set_dq(self, dq):
-        a = {k: np.ascontiguousarray(dq[k], dtype=np.int32) for k in ("meanq", "rg", "q", "cycle", "dinuc")}
-        d = _lib.Dq()
-        d.n_rg, d.n_cycle = self.n_rg, self.max_read_len
-        d.meanq, d.rgdq, d.qdq, d.cycledq, d.dinucdq = (a[k].ctypes.data for k in ("meanq", "rg", "q", "cycle", "dinuc"))
+        _keep, d = _dq_arrays(self.n_rg, self.max_read_len, dq)
         _lib.check(self.L.kbbq_set_dq(self.h, ctypes.byref(d)))
 
     # ---- pass 4
@@ -529,10 +518,7 @@ class Engine:
 
     def report(self, reset=False):
         """The report so far (waits): transfer [R][256][94], cycle [R][2][C][3] = bases, sum in, sum out; above_maxq."""
-        R, C = self.n_rg, self.max_read_len
-        out = dict(R=R, C=C, transfer=np.zeros((R, NQ, MAXQ + 1), np.uint64), cycle=np.zeros((R, 2, C, 3), np.uint64))
-        q = _lib.QualityReport()
-        q.transfer, q.cycle = out["transfer"].ctypes.data, out["cycle"].ctypes.data
+        out, q = _report_arrays(self.n_rg, self.max_read_len)
         _lib.check(self.L.kbbq_report_get(self.h, ctypes.byref(q), 1 if reset else 0))
         out["above_maxq"] = int(q.above_maxq)
         return out
@@ -585,25 +571,47 @@ def device_tensor(ptr, nbytes, dtype, device=0):
     return t.view(dtype)
 
 
-def _covariates_struct(cov):
-    """A kbbq_covariates over the arrays of a covariates dict (Engine.covariates()); the arrays it points into."""
-    R, C = int(cov["R"]), int(cov["C"])
-    a = {k: np.ascontiguousarray(cov[k], dtype=np.uint64) for k in ("rg", "q", "cycle", "dinuc")}
-    assert a["rg"].size == R * 2 and a["q"].size == R * NQ * 2 and a["cycle"].size == R * NQ * 2 * C * 2 and a["dinuc"].size == R * NQ * 32
-    c = _lib.Covariates()
-    c.n_rg, c.n_cycle = R, C
-    c.rg, c.q, c.cycle, c.dinuc = (a[k].ctypes.data for k in ("rg", "q", "cycle", "dinuc"))
-    return c, a
+def _arrays(Struct, dtype, R, C, shapes, src=None):
+    """A dict of R read groups and C cycles with the arrays `shapes` names -- zeroed, or those of the dict src as dtype, their
+    sizes checked -- and the ABI struct over them (keep the dict for as long as the struct is in use)."""
+    out = dict(R=R, C=C, **{k: np.zeros(s, dtype) if src is None else np.ascontiguousarray(src[k], dtype=dtype) for k, s in shapes.items()})
+    assert all(out[k].size == int(np.prod(s, dtype=np.int64)) for k, s in shapes.items())
+    return out, Struct(R, C, *(out[k].ctypes.data for k in shapes))
+
+
+# the three such dicts: what Engine.covariates(), Engine.dq() and Engine.report() return, with kbbq_covariates, kbbq_dq, kbbq_quality_report
+def _covariates_arrays(R, C, cov=None):
+    return _arrays(_lib.Covariates, np.uint64, R, C, dict(rg=(R, 2), q=(R, NQ, 2), cycle=(R, NQ, 2, C, 2), dinuc=(R, NQ, 16, 2)), cov)
+
+
+def _dq_arrays(R, C, dq=None):
+    return _arrays(_lib.Dq, np.int32, R, C, dict(meanq=(R,), rg=(R,), q=(R, NQ), cycle=(R, NQ, 2, C), dinuc=(R, NQ, 16)), dq)
+
+
+def _report_arrays(R, C, report=None):
+    return _arrays(_lib.QualityReport, np.uint64, R, C, dict(transfer=(R, NQ, MAXQ + 1), cycle=(R, 2, C, 3)), report)
+
+
+# the read-group ids of the table and report files: R of them (str or bytes) for a writer, a reader's buffer (a NUL behind each) cut up
+def _id_array(rg_ids, R):
+    ids = [i.encode() if isinstance(i, str) else bytes(i) for i in rg_ids]
+    assert len(ids) == R
+    return (ctypes.c_char_p * R)(*ids)
+
+
+def _table_info(k, seed, total_bases, command):
+    return _lib.TableInfo(k, seed & 0xFFFFFFFF, total_bases, command.encode() if isinstance(command, str) else command)
+
+
+def _split_ids(buf, id_bytes, R):
+    return [b.decode(errors="surrogateescape") for b in buf.raw[:id_bytes.value].split(b"\0")[:R]]
 
 
 def write_table(path, cov, rg_ids, k=0, seed=0, total_bases=0, command=None):
     """The recalibration table file of a covariates dict (kbbq_host_table_write); rg_ids: one id per read group, in
     dense-index order ("" is a value).  No GPU is touched."""
-    c, _keep = _covariates_struct(cov)
-    ids = [i.encode() if isinstance(i, str) else bytes(i) for i in rg_ids]
-    assert len(ids) == int(cov["R"])
-    arr = (ctypes.c_char_p * len(ids))(*ids)
-    info = _lib.TableInfo(k, seed & 0xFFFFFFFF, total_bases, command.encode() if isinstance(command, str) else command)
+    _keep, c = _covariates_arrays(int(cov["R"]), int(cov["C"]), cov)
+    arr, info = _id_array(rg_ids, int(cov["R"])), _table_info(k, seed, total_bases, command)
     _lib.check(_lib.lib().kbbq_host_table_write(str(path).encode(), ctypes.byref(c), arr, ctypes.byref(info)))
 
 
@@ -614,28 +622,21 @@ def read_table(path):
     c = _lib.Covariates()
     id_bytes = ctypes.c_uint64()
     _lib.check(L.kbbq_host_table_read(str(path).encode(), ctypes.byref(c), None, ctypes.byref(id_bytes)))
-    R, C = int(c.n_rg), int(c.n_cycle)
-    out = dict(R=R, C=C, rg=np.zeros((R, 2), np.uint64), q=np.zeros((R, NQ, 2), np.uint64),
-               cycle=np.zeros((R, NQ, 2, C, 2), np.uint64), dinuc=np.zeros((R, NQ, 16, 2), np.uint64))
-    c.rg, c.q, c.cycle, c.dinuc = (out[k].ctypes.data for k in ("rg", "q", "cycle", "dinuc"))
+    R = int(c.n_rg)
+    out, c = _covariates_arrays(R, int(c.n_cycle))
     ids = ctypes.create_string_buffer(max(1, id_bytes.value))
     _lib.check(L.kbbq_host_table_read(str(path).encode(), ctypes.byref(c), ctypes.cast(ids, _lib.c_vp), ctypes.byref(id_bytes)))
-    out["rg_ids"] = [b.decode(errors="surrogateescape") for b in ids.raw[:id_bytes.value].split(b"\0")[:R]]
+    out["rg_ids"] = _split_ids(ids, id_bytes, R)
     return out
 
 
 def write_report(path, report, rg_ids, observed=None, k=0, seed=0, total_bases=0, command=None):
     """The quality report file of a report dict (Engine.report(); kbbq_host_report_write); observed: a covariates dict
     whose q histogram goes into `observed` rows, or None.  No GPU is touched."""
-    R, C = int(report["R"]), int(report["C"])
-    a = {k_: np.ascontiguousarray(report[k_], dtype=np.uint64) for k_ in ("transfer", "cycle")}
-    assert a["transfer"].size == R * NQ * (MAXQ + 1) and a["cycle"].size == R * 2 * C * 3
-    q = _lib.QualityReport(R, C, a["transfer"].ctypes.data, a["cycle"].ctypes.data, int(report.get("above_maxq", 0)))
-    ids = [i.encode() if isinstance(i, str) else bytes(i) for i in rg_ids]
-    assert len(ids) == R
-    arr = (ctypes.c_char_p * len(ids))(*ids)
-    c, _keep = _covariates_struct(observed) if observed is not None else (None, None)
-    info = _lib.TableInfo(k, seed & 0xFFFFFFFF, total_bases, command.encode() if isinstance(command, str) else command)
+    _keep_q, q = _report_arrays(int(report["R"]), int(report["C"]), report)
+    q.above_maxq = int(report.get("above_maxq", 0))
+    arr, info = _id_array(rg_ids, int(report["R"])), _table_info(k, seed, total_bases, command)
+    _keep, c = _covariates_arrays(int(observed["R"]), int(observed["C"]), observed) if observed is not None else (None, None)
     _lib.check(_lib.lib().kbbq_host_report_write(str(path).encode(), ctypes.byref(q), arr, ctypes.byref(c) if c is not None else None,
                                                  ctypes.byref(info)))
 
@@ -647,15 +648,14 @@ def read_report(path):
     q = _lib.QualityReport()
     id_bytes = ctypes.c_uint64()
     _lib.check(L.kbbq_host_report_read(str(path).encode(), ctypes.byref(q), None, None, ctypes.byref(id_bytes)))
-    R, C = int(q.n_rg), int(q.n_cycle)
-    out = dict(R=R, C=C, transfer=np.zeros((R, NQ, MAXQ + 1), np.uint64), cycle=np.zeros((R, 2, C, 3), np.uint64),
-               observed=np.zeros((R, NQ, 2), np.uint64))
-    q.transfer, q.cycle = out["transfer"].ctypes.data, out["cycle"].ctypes.data
+    R = int(q.n_rg)
+    out, q = _report_arrays(R, int(q.n_cycle))
+    out["observed"] = np.zeros((R, NQ, 2), np.uint64)
     ids = ctypes.create_string_buffer(max(1, id_bytes.value))
     _lib.check(L.kbbq_host_report_read(str(path).encode(), ctypes.byref(q), out["observed"].ctypes.data, ctypes.cast(ids, _lib.c_vp),
                                        ctypes.byref(id_bytes)))
     out["above_maxq"] = int(q.above_maxq)
-    out["rg_ids"] = [b.decode(errors="surrogateescape") for b in ids.raw[:id_bytes.value].split(b"\0")[:R]]
+    out["rg_ids"] = _split_ids(ids, id_bytes, R)
     return out
 
 
@@ -751,13 +751,8 @@ def read_spectrum(path):
 
 def host_train(cov):
     """kbbq_host_train on a covariates dict (a loaded table): the delta-Q tables as Engine.dq() returns them."""
-    R, C = int(cov["R"]), int(cov["C"])
-    c, _keep = _covariates_struct(cov)
-    out = dict(R=R, C=C, meanq=np.zeros(R, np.int32), rg=np.zeros(R, np.int32), q=np.zeros((R, NQ), np.int32),
-               cycle=np.zeros((R, NQ, 2, C), np.int32), dinuc=np.zeros((R, NQ, 16), np.int32))
-    d = _lib.Dq()
-    d.n_rg, d.n_cycle = R, C
-    d.meanq, d.rgdq, d.qdq, d.cycledq, d.dinucdq = (out[k].ctypes.data for k in ("meanq", "rg", "q", "cycle", "dinuc"))
+    _keep, c = _covariates_arrays(int(cov["R"]), int(cov["C"]), cov)
+    out, d = _dq_arrays(int(c.n_rg), int(c.n_cycle))
     _lib.check(_lib.lib().kbbq_host_train(ctypes.byref(c), ctypes.byref(d)))
     return out
 
