@@ -171,6 +171,20 @@ int kbbq_fastq_reader_write_corrected(kbbq_fastq_reader *r, kbbq_bgzf *z, const 
  * nothing to collect).  The call returns when the text kernel has run. */
 int kbbq_fastq_reader_write_trimmed(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint8_t *d_qual, const uint32_t *d_keep, const uint64_t *d_fix_mask,
                                     const uint64_t *d_fix_bases, void *after_stream, uint64_t *out_bytes);
+/* Records whose sequence and quality lines come from neither input record: the merged reads of overlapping pairs
+ * (kbbq_engine.h: kbbq_pair_merge_batch).  d_len[rec] (device, one word per record of the current chunk) is the merged length,
+ * 0: nothing is written for the record -- nonzero at first mates only, where a pair is merged; d_at[rec] (device, uint64 per
+ * record, read where d_len is not 0) is where its text starts in d_seq (the characters) and d_qual (the raw qualities), device
+ * arrays of no particular alignment.  Record rec is written as "@name\n" + d_seq[at .. at+len) + "\n+comment\n" +
+ * (d_qual[at .. at+len) + 33) + "\n", with the record's own name line and '+' line byte for byte, in the chunk's record order.
+ * All three forms of a chunk: live, kept whole, kept without its text (whose batch need not be attached: nothing of the
+ * record's own sequence is read).  after_stream and *out_bytes as for kbbq_fastq_reader_write_trimmed: a chunk with nothing
+ * merged submits nothing.  The call returns when the text kernel has run. */
+int kbbq_fastq_reader_write_merged(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint32_t *d_len, const uint64_t *d_at, const uint8_t *d_seq,
+                                   const uint8_t *d_qual, void *after_stream, uint64_t *out_bytes);
+/* The records kbbq_fastq_reader_write_merged has written since creation, and the milliseconds the device spent on its size
+ * pass and scan. */
+int kbbq_fastq_reader_merged_written(kbbq_fastq_reader *r, uint64_t *records, double *sizes_ms);
 /* Milliseconds the device spent on the size pass and scan of kbbq_fastq_reader_write_trimmed since creation (its text kernels
  * are in the writer's format time: kbbq_bgzf_kernel_ms). */
 int kbbq_fastq_reader_trim_ms(kbbq_fastq_reader *r, double *sizes_ms);

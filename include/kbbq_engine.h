@@ -495,6 +495,82 @@ int kbbq_pair_consensus_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t firs
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_pair_consensus_counts_get(kbbq_engine *e, kbbq_pair_consensus_counts *out, int32_t reset);
 
+/* ---- overlapping pairs merged into single reads: the insert read once, from both ends -------------------------
+ * The rule is this project's own (fastp -m, PEAR, FLASH and bbmerge are its models), exact and all
+ * integers, without indels.  A pair has read 1 (n1 bases, codes c1, N bits u1, written qualities q1), read 2 (n2, c2, u2, q2),
+ * an insert length L (L* of the overlap rule above; 0: none) and the two limits the adapter and overlap searches left.  Bases
+ * are as written: where a read's fix_mask bit is set, the code is fix_bases' and the N bit is clear, whether the bit is
+ * kbbq_correct_batch's or kbbq_pair_consensus_batch's.  Qualities are those pass 4 is about to write: behind the quality map,
+ * behind kbbq_pair_consensus_batch.
+ *     mergeable  iff  L > 0  and  limit1 >= min(n1, L)  and  limit2 >= min(n2, L)
+ * A pair whose adapter search cut a read in front of the insert is held back: it stays a pair and is trimmed as without this
+ * rule, and so does a pair without a hit.  The merged read M of a mergeable pair has L bases, in read 1's orientation.  With
+ * lo = max(0, L - n2), hi = min(n1, L) and k = L - 1 - i:
+ *     i < lo:         (c1[i], u1[i], q1[i])
+ *     i >= hi:        (3 - c2[k], u2[k], q2[k])
+ *     lo <= i < hi:   x = (c1[i], u1[i], q1[i]), y = (3 - c2[k], u2[k], q2[k]):
+ *         both N:                 N, quality min(qx, qy)
+ *         exactly one N:          the other's base and quality
+ *         codes equal:            that base, quality max(qx, qy) -- not the sum: behind kbbq_pair_consensus_batch a corrected
+ *                                 position agrees and carries the winner's quality twice, one observation, not two
+ *         codes differ, qx != qy: the base of the higher quality, quality d = max(2, |qx - qy|); while a quality map is set
+ *                                 (kbbq_set_quality_map) map[d] -- only this computed value goes through the map, every other
+ *                                 merged quality is one pass 4 wrote
+ *         codes differ, qx == qy: N, quality 2 (undecided)
+ * An N bit means N whatever the code says; a lower-case letter has its folded code; the merged text is upper-case ACGTN.
+ * The rule is symmetric: merging (read 2, read 1) gives the reverse complement of M with its qualities reversed.  The result
+ * depends on the pair and the parameters alone: not on how the batches were cut, on uniform or ragged batches, on hints or on
+ * offcase.
+ * The verdict of a merged read is steps 2 and 3 of the trimming rule with kept = L -- there is no cut, both ends of a merged
+ * read are 5' ends, and tail_q is not read: L < max(1, min_length): too short; else has_ee and the sum of EE[Mq[i]] over
+ * i < L above ee_bound: over the expected errors; else merged.  Either drop verdict drops the pair from every output.
+ * A read of a mergeable pair counts in kbbq_trim_counts.reads_in and bases_in and in no other field of it
+ * (kbbq_trim_batch_unmerged): it has no verdict of its own and its mate is not "dropped with its mate".  With this rule
+ *     reads_in = reads_kept + too_short + over_ee + with_mate + 2 * (merged + merge.too_short + merge.over_ee). */
+/* Sums since the last reset.  pairs: pairs with L > 0 that were seen; held_back: those of them that are not mergeable; merged,
+ * too_short, over_ee: the verdicts of the mergeable ones (pairs = held_back + merged + too_short + over_ee); bases_written: the
+ * sum of L over the merged; overlap_bases (the sum of hi - lo), disagreeing (positions where neither is N and the codes
+ * differ) and undecided (those of them with equal qualities): over the mergeable pairs, whatever their verdict. */
+typedef struct kbbq_merge_counts {
+    uint64_t pairs, held_back, merged, too_short, over_ee, bases_written, overlap_bases, disagreeing, undecided;
+} kbbq_merge_counts;
+/* merged_len[j] of a pair that is mergeable and dropped as a merged read; a merged length is below 2 * KBBQ_OVERLAP_MAX_READ */
+#define KBBQ_MERGE_DROPPED 0x80000000u
+/* The pairs are kbbq_pair_overlap_batch's (device batches, first_a, first_b, stride, n_pairs), but stride 2 only for an
+ * interleaved batch with read 1 in front: a and b the same batch and first_b = first_a + 1.  insert: device, n_pairs words, what kbbq_pair_overlap_inserts wrote for these pairs (a value the search cannot
+ * have written is taken as 0); limit_a, limit_b: device, the limits at [j * stride] as that call left them; qual_a, qual_b: the
+ * batches' written qualities in base order; fix_mask_*, fix_bases_*: the batches' fix arrays, all four set or all four NULL
+ * (nothing fixed).  Nothing of these is written.  params: min_length, has_ee and ee_bound are read.
+ * merged_len[j] (device, n_pairs words, one per pair whatever the stride) = L for a merged pair, 0 for a pair that is not
+ * mergeable (it stays a pair), KBBQ_MERGE_DROPPED for one dropped as a merged read (both mates leave every output).
+ * seq_out, qual_out (device, of no particular alignment): pair j's text stands from byte S(j) on, the number of bases of the
+ * pairs 0..j-1 of the call -- (off1(j) - off1(0)) + (off2(j) - off2(0)) for two batches, off1(j) - off1(0) inside an
+ * interleaved batch (stride 2), so both hold as many bytes as the call's pairs have bases: seq_out the characters ACGTN,
+ * qual_out the raw qualities.  The L bytes of a merged pair are written; those of a pair dropped as a merged read hold the
+ * text it would have had, and no other byte is touched.  Both NULL: the verdicts alone, with the same merged_len and the same
+ * counts.  Queued on the engine's stream.  KBBQ_EINVAL as kbbq_pair_consensus_batch gives it, for another use of stride 2, for
+ * fix arrays or outputs half set, or for trimming parameters out of range. */
+int kbbq_pair_merge_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
+                          uint64_t stride, uint64_t n_pairs, const uint32_t *insert, const uint32_t *limit_a, const uint32_t *limit_b,
+                          const uint8_t *qual_a, const uint8_t *qual_b, const uint64_t *fix_mask_a, const uint64_t *fix_bases_a,
+                          const uint64_t *fix_mask_b, const uint64_t *fix_bases_b, const kbbq_trim_params *params,
+                          uint32_t *merged_len, uint8_t *seq_out, uint8_t *qual_out);
+/* Where that call put its text, for kbbq_fastq_reader_write_merged (kbbq_bgzf.h), whose arrays go by the record: for the same
+ * pairs and the merged_len the call wrote, rec_len[first_a + j * stride] = the merged length of pair j, 0 where it is not
+ * merged, and rec_at[first_a + j * stride] = at0 + S(j) -- at0: where the call's seq_out and qual_out start in the arrays the
+ * writer is given.  rec_len (n_reads of a words) and rec_at (as many uint64) are device arrays by the records of a's batch;
+ * no other entry is written.  Queued on the engine's stream. */
+int kbbq_pair_merge_places(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
+                           uint64_t stride, uint64_t n_pairs, const uint32_t *merged_len, uint64_t at0, uint32_t *rec_len, uint64_t *rec_at);
+/* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
+int kbbq_merge_counts_get(kbbq_engine *e, kbbq_merge_counts *out, int32_t reset);
+/* kbbq_trim_batch_limited (limit may be NULL) that leaves the reads of mergeable pairs out: read r of the batch belongs to
+ * pair (first + r) / 2 with adjacent != 0 (interleaved: first is the ordinal of the batch's first record) and to pair
+ * first + r with adjacent == 0, and where merged_len[that pair] (device, kbbq_pair_merge_batch's words by the pair's ordinal)
+ * is not 0 the read counts in reads_in and bases_in alone and keep[r] = 0.  Every other read: as kbbq_trim_batch_limited. */
+int kbbq_trim_batch_unmerged(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p,
+                             const uint32_t *limit, const uint32_t *merged_len, uint64_t first, int32_t adjacent, uint32_t *keep);
+
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]
  *   cycle [n_rg][256][2][max_read_len][2]   (third index: 0 first-in-pair, 1 second)

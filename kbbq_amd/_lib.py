@@ -123,6 +123,10 @@ class ConsensusCounts(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("reads_changed", "bases_corrected", "from_n", "bases_left")]
 
 
+class MergeCounts(ctypes.Structure):
+    _fields_ = [(n, c_u64) for n in ("pairs", "held_back", "merged", "too_short", "over_ee", "bases_written", "overlap_bases", "disagreeing", "undecided")]
+
+
 class SynthParams(ctypes.Structure):
     _fields_ = [("seed", c_u64), ("genome_len", c_u64), ("n_reads", c_u64), ("read_len", ctypes.c_uint32),
                 ("n_rg", ctypes.c_uint32), ("paired", ctypes.c_uint32), ("n_per_million", ctypes.c_uint32)]
@@ -191,6 +195,11 @@ SYMBOLS = {
     "kbbq_pair_consensus_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp,
                                                  ctypes.POINTER(ConsensusParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
     "kbbq_pair_consensus_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(ConsensusCounts), ctypes.c_int32]),
+    "kbbq_pair_merge_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp, c_vp]),
+    "kbbq_pair_merge_places": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "kbbq_merge_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(MergeCounts), ctypes.c_int32]),
+    "kbbq_trim_batch_unmerged": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp, c_u64, ctypes.c_int32, c_vp]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),
@@ -262,6 +271,8 @@ SYMBOLS = {
     "kbbq_fastq_reader_write_trimmed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u64p]),
     "kbbq_fastq_reader_trim_ms": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double)]),
     "kbbq_fastq_reader_trim_written": (ctypes.c_int, [c_vp, c_u64p, c_u64p]),
+    "kbbq_fastq_reader_write_merged": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u64p]),
+    "kbbq_fastq_reader_merged_written": (ctypes.c_int, [c_vp, c_u64p, ctypes.POINTER(ctypes.c_double)]),
     "kbbq_reads_upload_text": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.c_void_p, ctypes.POINTER(Reads)]),
     "kbbq_fastq_reader_inflate": (ctypes.c_int, [c_vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),

@@ -163,6 +163,20 @@ class FastqReader(_RecordReader):
         self._call("trim_written", ctypes.byref(n), ctypes.byref(m))
         return n.value, m.value
 
+    def write_merged(self, writer, d_len, d_at, d_seq, d_qual, after_stream=None):
+        """For every record of the current chunk with d_len[r] != 0 (device uint32 per record) a record under its name and '+'
+        lines whose d_len[r] characters and raw qualities stand at d_seq + d_at[r] and d_qual + d_at[r] (d_at: device uint64 per
+        record).  Returns the bytes of text submitted: 0 means nothing was, so nothing is to collect."""
+        n = ctypes.c_uint64()
+        self._call("write_merged", writer.h, d_len, d_at, d_seq, d_qual, after_stream, ctypes.byref(n))
+        return n.value
+
+    def merged_written(self):
+        """(records written by write_merged since the reader was made, milliseconds of its size pass and scan)."""
+        n, ms = ctypes.c_uint64(), ctypes.c_double()
+        self._call("merged_written", ctypes.byref(n), ctypes.byref(ms))
+        return n.value, ms.value
+
     def trim_ms(self):
         ms = ctypes.c_double()
         self._call("trim_ms", ctypes.byref(ms))

@@ -38,6 +38,10 @@ struct ReaderCalls {
                          void *after_stream, uint64_t *out_bytes);
     int (*trim_written)(void *h, uint64_t *records, uint64_t *shortened);
     int (*trim_ms)(void *h, double *sizes_ms);
+    // --merged-out (cli_trim.h): records whose sequence and quality lines are a merged pair's, and what was written that way (FASTQ's)
+    int (*write_merged)(void *h, kbbq_bgzf *z, const uint32_t *d_len, const uint64_t *d_at, const uint8_t *d_seq, const uint8_t *d_qual, void *after_stream,
+                        uint64_t *out_bytes);
+    int (*merged_written)(void *h, uint64_t *records, double *sizes_ms);
 };
 // f, whose first argument is a reader of type R, as a call on the opaque handle
 template <auto f> struct Thunk;
@@ -50,7 +54,8 @@ static const ReaderCalls kFastqReaderCalls = {
     Thunk<kbbq_fastq_reader_attach>::call, nullptr, nullptr, Thunk<kbbq_fastq_reader_take_text>::call, 0,
     Thunk<kbbq_fastq_reader_write_corrected>::call,
     Thunk<kbbq_fastq_reader_set_mates>::call, Thunk<kbbq_fastq_reader_pair_keys>::call, Thunk<kbbq_fastq_reader_pair_keys_ms>::call, Thunk<kbbq_fastq_reader_record_name>::call,
-    Thunk<kbbq_fastq_reader_write_trimmed>::call, Thunk<kbbq_fastq_reader_trim_written>::call, Thunk<kbbq_fastq_reader_trim_ms>::call};
+    Thunk<kbbq_fastq_reader_write_trimmed>::call, Thunk<kbbq_fastq_reader_trim_written>::call, Thunk<kbbq_fastq_reader_trim_ms>::call,
+    Thunk<kbbq_fastq_reader_write_merged>::call, Thunk<kbbq_fastq_reader_merged_written>::call};
 // (sam_read1, the BAM constructor of CReadData, BamFile::recalibrate / write are kernels: htsiter.cc:5-45, readutils.cc:13-61)
 static const ReaderCalls kBamReaderCalls = {
     [](bool use_oq, int32_t n_ref, uint64_t header_bytes, const char *const *ids, uint32_t n_ids, void **out) {
@@ -591,6 +596,16 @@ public:
             return rc < 0 ? rc : bytes ? 1 : 0;
         });
     }
+    // ... and the merged reads of its pairs: for every record with d_len != 0 one under its name whose text stands at d_at in
+    // d_seq and d_qual (--merged-out: FASTQ).  A chunk with nothing merged submits nothing
+    bool write_chunk_merged(DeviceBgzfWriter &out, const uint32_t *d_len, const uint64_t *d_at, const uint8_t *d_seq, const uint8_t *d_qual, void *after_stream) {
+        return out.submit_if_any([&](kbbq_bgzf *z) {
+            uint64_t bytes = 0;
+            const int rc = r_->write_merged(h_, z, d_len, d_at, d_seq, d_qual, after_stream, &bytes);
+            return rc < 0 ? rc : bytes ? 1 : 0;
+        });
+    }
+    void merged_written(uint64_t &records, double &ms) { records = 0; ms = 0; if (h_ && r_->merged_written) r_->merged_written(h_, &records, &ms); }
     bool can_trim() const { return r_ && r_->write_trimmed; }
     void trim_written(uint64_t &records, uint64_t &shortened) { records = shortened = 0; if (h_ && r_->trim_written) r_->trim_written(h_, &records, &shortened); }
     double trim_ms() { double ms = 0; if (h_ && r_->trim_ms) r_->trim_ms(h_, &ms); return ms; }

@@ -39,6 +39,8 @@ static struct option long_options[] = {   // kbbq.cc:66-79
     {"pair-overlap-error-rate", required_argument, 0, 1021},
     // inside the overlap that --pair-overlap finds, a base the mate is sure of replaces the one this read is unsure of (cli_trim.h)
     {"pair-correct", no_argument, 0, 1022}, {"pair-correct-quals", required_argument, 0, 1023},
+    // the pairs whose overlap --pair-overlap finds, merged into one read each and written to a file of their own (cli_trim.h); turns trimming on
+    {"merged-out", required_argument, 0, 1024},
     {0, 0, 0, 0}};
 
 enum class Format { fastq, bam, sam, cram, unknown };
@@ -134,6 +136,11 @@ struct CliOptions {
     // --pair-correct-quals G,B (default 30,15: fastp's values)
     kbbq_consensus_params consensus = {30, 15};
     bool pair_correct = false, pair_correct_quals = false;
+    // --merged-out FILE: a pair whose mates overlap and whose reads no adapter cut in front of the insert becomes one read over
+    // the whole insert (include/kbbq_engine.h: kbbq_pair_merge_batch), written to FILE as BGZF FASTQ under read 1's name; neither
+    // mate goes to stdout or --out2.  Needs --pair-overlap; FILE is handled like --out2
+    std::string merged_out;
+    bool merge_on() const { return !merged_out.empty(); }
     bool quantize = false;
     uint8_t quality_map[256];
     const char *trains_with = nullptr;      // the first option given that only a training run uses (--load-table refuses it)
@@ -253,6 +260,12 @@ struct CliOptions {
         if (serial_parse) return "KBBQ_SERIAL_PARSE=1 leaves it to the host parsers, which read it again for the output";
         if (host_deflate) return "KBBQ_HOST_DEFLATE=1 leaves it to the host parsers, which read it again for the output";
         return nullptr;
+    }
+    // two names of one file: the same text, or both there with one device and inode
+    static bool same_file(const std::string &a, const std::string &b) {
+        if (a == b) return true;
+        struct stat sa, sb;
+        return stat(a.c_str(), &sa) == 0 && stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
     }
     // The name to open for a file argument, and whether it is a stream
     static std::string resolve(const std::string &name, bool &is_stream) {
@@ -383,6 +396,11 @@ struct CliOptions {
                     pair_correct_quals = true;
                     break;
                 }
+                case 1024:
+                    merged_out = std::string(optarg);
+                    if (merged_out.empty()) return !give_up(" Error: --merged-out takes the name of a file.");
+                    if (!trim_option) trim_option = "--merged-out";
+                    break;
                 case 't':
                     nthreads = std::stoi(std::string(optarg));
                     if (nthreads < 0) std::cerr << put_now << " Error: threads must be >= 0." << std::endl;
@@ -415,6 +433,8 @@ struct CliOptions {
             return !give_up(" Error: --pair-correct-quals without --pair-correct: it says which qualities let a mate's base replace a read's.");
         if (pair_correct && !pair_overlap)
             return !give_up(" Error: --pair-correct without --pair-overlap: it corrects inside the overlap that --pair-overlap finds.");
+        if (merge_on() && !pair_overlap)
+            return !give_up(" Error: --merged-out without --pair-overlap: it merges the pairs whose overlap --pair-overlap finds.");
         if (trim_on()) {
             if (!trim.min_length) trim.min_length = 1;
             if (const char *why = trim_refusal()) return !give_up(std::string(" Error: ") + trim_option + " with " + why + ".");
@@ -437,6 +457,10 @@ struct CliOptions {
         if (paired_files()) in2_path = resolve(in2, in2_stream);
         if (const char *option = pairs_option())
             if (const char *why = pairs_refusal()) return !give_up(std::string(" Error: ") + option + " with" + why + ".");
+        if (merge_on())      // (the merged reads would overwrite what the run still reads, or what it writes beside them)
+            for (const auto &other : {std::make_pair("the input", &filename), std::make_pair("--in2's file", &in2), std::make_pair("--out2's file", &out2)})
+                if (!other.second->empty() && same_file(merged_out, *other.second))
+                    return !give_up(std::string(" Error: --merged-out names ") + other.first + ", " + *other.second + ": the merged reads go to a file of their own.");
         return true;
     }
 };

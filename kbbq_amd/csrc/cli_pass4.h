@@ -119,7 +119,8 @@ struct Sink {
 // last reader's call prints them: one line each, over both files).
 // trim (--trim-tail, --min-length, --max-ee, --adapter: cli_trim.h; null: none): the records are written cut to their kept lengths or left
 // out -- the verdicts taken here, batch by batch behind pass 4, unless a paired run's pre-pass has taken them all; which: the
-// file whose array of kept lengths this reader's records stand in (1: --in2's).
+// file whose array of kept lengths this reader's records stand in (1: --in2's).  --merged-out: the merged reads of the first file's
+// (or the interleaved file's) chunks go to trim->merged_writer beside them.
 static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptions &o, Sink &sink, DeviceInput &in, size_t first_batch = 0, bool totals = true,
                                     TrimRun *trim = nullptr, int which = 0) {
     DeviceBgzfWriter &out = *sink.dev;
@@ -158,15 +159,17 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
             // (--correct: the fixes first, then the cut; the writer call returns when its text kernel has run, so the arrays of
             // slot t are free again whether or not this chunk made a submission)
             const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
-            if (correct || trim->consensus_on)
+            if (correct || trim->consensus_on || trim->merge_on)      // (--merged-out: zeroed arrays where nothing fixes, the merge takes all four or none)
                 if (const int rc = fixes.correct(t, d, errors, &fix_mask, &fix_bases)) return rc;
-            // (--pair-correct: behind the fixes and in front of the write; the verdicts were taken from the same result)
-            if (trim->consensus_on)
+            // (--pair-correct, --merged-out: behind the fixes and in front of the write; the verdicts were taken from the same result)
+            if (trim->consensus_on || trim->merge_on)
                 if (const int rc = trim->consensus_batch(which, ordinal, d, (uint8_t *)q, (uint64_t *)fix_mask, (uint64_t *)fix_bases, !o.report.empty())) return rc;
             if (!trim->have_verdicts)
                 if (const int rc = trim->batch(which, ordinal, d, q)) return rc;
             if (ordinal + d.n_reads > trim->n[which]) return input_changed();
             if (!in.write_chunk_trimmed(out, q, trim->kept(which, ordinal), fix_mask, fix_bases, kbbq_engine_stream(e))) return 1;
+            if (trim->merge_on && which == 0)
+                if (const int rc = trim->write_merged(in)) return rc;
             ordinal += d.n_reads;
         } else if (correct) {
             const uint64_t *fix_mask = nullptr, *fix_bases = nullptr;
@@ -175,13 +178,14 @@ static int write_from_device_reader(kbbq_engine *e, ScanState &s, const CliOptio
         } else if (!in.write_chunk(out, q, o.set_oq, kbbq_engine_stream(e))) return 1;
     }
     if (!out.drain()) return 1;
+    if (trim && trim->merge_on && which == 0 && !trim->merged_writer->drain()) return 1;
     if (trim) trim->wrote(in);
     if (!totals) return 0;
     if (trim)
         if (const int rc = trim->line()) return rc;
     if (correct) {
         kbbq_fix_counts c;
-        if (trim && trim->consensus_on) c = trim->fix_counts;      // (taken where every read was met once: cli_trim.h)
+        if (trim && trim->errors) c = trim->fix_counts;      // (taken where every read was met once: cli_trim.h)
         else if (kbbq_correct_counts(e, &c, 0) < 0) return fail_engine("correcting");
         std::cerr << put_now << " Corrected bases: " << c.flagged << " flagged, " << c.fixed << " fixed, " << c.ambiguous << " ambiguous, " << c.unsupported
                   << " unsupported." << std::endl;

@@ -33,6 +33,15 @@
 // write loop (consensus_batch()) is one loop over the runs with a read of the batch it writes: in place where the run lies inside
 // the batch, else one-sided against the mates' batch recalibrated (and fixed) into a MateSlot.
 //
+// --merged-out (with --pair-overlap): a pair whose mates overlap and whose reads no search cut in front of the insert becomes one
+// read (kbbq_pair_merge_batch).  A merging run always takes the run loop, with or without --pair-correct: per run the consensus if
+// on, then the verdict-only merge call into an array of 4 bytes a pair by the pair's ordinal, and a batch's own verdicts -- which
+// leave the reads of mergeable pairs out (kbbq_trim_batch_unmerged) -- when its last run is done.  While the first file's batches (or
+// the interleaved ones) are written, each run with a first mate in the batch in hand gets the full call: its mates' batch stands
+// recalibrated, fixed and -- two-sided here: the rule is exact in place -- corrected in slot 0, the merged text goes to an array of
+// two bytes per base of the run's pairs, and one writer call per chunk hands it to a third BGZF writer under the first mates'
+// names (kbbq_fastq_reader_write_merged), the pair that crosses into the next batch in its pair-order place.
+//
 // Every device array here is a DeviceArray (cli_slots.h), freed with the run.
 #pragma once
 
@@ -44,10 +53,10 @@ struct MateSlot {
     uint8_t *qual() const { return q.as<uint8_t>(); }
     // Pass 4 of batch d, and with errors (--correct: pass 3's flags of the batch) its fixes, on the engine's stream, which runs
     // in order: the kernels that read what stood here before are queued in front.  0, or the exit status
-    int fill(kbbq_engine *e, const kbbq_reads &d, const uint64_t *errors) {
+    int fill(kbbq_engine *e, const kbbq_reads &d, const uint64_t *errors, const char *option = "--pair-correct") {
         holds = nullptr;
         if (!q.ensure(e, d.n_bases + 16) || !fix.ensure(e, fix_bytes(d)))
-            return give_up(" Error: --pair-correct: the qualities of one more batch of " + std::to_string(d.n_bases) + " bases do not fit in GPU memory.");
+            return give_up(std::string(" Error: ") + option + ": the qualities of one more batch of " + std::to_string(d.n_bases) + " bases do not fit in GPU memory.");
         if (kbbq_recalibrate_batch(e, &d, qual()) < 0) return fail_engine("recalibrating");
         if (const int rc = fix_arrays(e, fix, d, errors, "correcting from the mates", &mask, &bases)) return rc;
         holds = &d;
@@ -73,6 +82,16 @@ struct TrimRun {
     PairWalk walk;                               // which reads of those batches are mates, run by run (overlaps())
     const std::vector<uint64_t *> *errors = nullptr;      // --correct: pass 3's error flags by resident batch
     MateSlot slot[2];
+    // --merged-out
+    bool merge_on = false;
+    DeviceArray merged;                          // device: kbbq_pair_merge_batch's word of every pair, by the pair's ordinal
+    DeviceArray rec_len, rec_at, text;           // device, the batch in hand: the writer's two arrays by the record, and the merged characters and qualities
+    std::vector<uint64_t> run_bases;             // by run: the bases of its pairs (overlaps())
+    DeviceBgzfWriter *merged_writer = nullptr;   // --merged-out's file (main() owns it)
+    uint8_t *merged_seq = nullptr, *merged_qual = nullptr;      // the two halves of `text`
+    kbbq_merge_counts merge_counts = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // taken in the pre-pass
+    uint64_t merged_written = 0;
+    double ms_merged_sizes = 0;
     kbbq_pair_consensus_counts consensus_counts = {0, 0, 0, 0};      // taken in the pre-pass, which meets every read once
     kbbq_fix_counts fix_counts = {0, 0, 0, 0};                       // ... and so are --correct's, which the mates' batches would count again
     bool on = false, paired = false, have_verdicts = false;
@@ -83,7 +102,9 @@ struct TrimRun {
 
     // every device array now (the members' destructors would free them with the run)
     void release() {
-        for (DeviceArray *a : {&keep[0], &keep[1], &file_limit[0], &file_limit[1], &limit, &insert, &slot[0].q, &slot[0].fix, &slot[1].q, &slot[1].fix}) a->release();
+        for (DeviceArray *a : {&keep[0], &keep[1], &file_limit[0], &file_limit[1], &limit, &insert, &slot[0].q, &slot[0].fix, &slot[1].q, &slot[1].fix, &merged, &rec_len, &rec_at,
+                               &text})
+            a->release();
     }
     // where record `ordinal` of file f stands in the kept lengths and in --pair-overlap's limits
     uint32_t *kept(int f, uint64_t ordinal) const { return keep[f].as<uint32_t>() + ordinal; }
@@ -101,6 +122,7 @@ struct TrimRun {
         overlap_on = o.pair_overlap;
         consensus = o.consensus;
         consensus_on = o.pair_correct;
+        merge_on = o.merge_on();
         // one array of `words` entries for the whole run
         auto whole = [&](DeviceArray &a, uint64_t words, const std::string &what) {
             if (!words || a.alloc(e, words * 4)) return 0;
@@ -111,8 +133,11 @@ struct TrimRun {
             if (const int rc = whole(keep[f], n[f], std::string(o.trim_option) + ": the kept lengths of " + reads)) return rc;
         for (int f = 0; f < 2 && overlap_on; ++f)
             if (const int rc = whole(file_limit[f], n[f], "--pair-overlap: the limits of " + reads)) return rc;
-        const uint64_t pairs = !consensus_on ? 0 : o.paired_files() ? n[0] : (n[0] + 1) / 2;
-        return whole(insert, pairs, "--pair-correct: the insert lengths of " + std::to_string(pairs) + " pairs");
+        const uint64_t pairs = !(consensus_on || merge_on) ? 0 : o.paired_files() ? n[0] : (n[0] + 1) / 2;
+        if (const int rc = whole(insert, pairs, std::string(consensus_on ? "--pair-correct" : "--merged-out") + ": the insert lengths of " + std::to_string(pairs) + " pairs")) return rc;
+        if (const int rc = whole(merged, merge_on ? pairs : 0, "--merged-out: the merged lengths of " + std::to_string(pairs) + " pairs")) return rc;
+        if (merged.p && kbbq_device_zero(e, merged.p, pairs * 4) < 0) return fail_engine("merging the pairs");
+        return 0;
     }
     // --pair-overlap: every read's limit into file_limit[], before any verdict -- --adapter's search of every batch, then the
     // overlap of every pair, the smaller of the two where both ran; with --pair-correct the pairs' insert lengths as well
@@ -139,10 +164,22 @@ struct TrimRun {
         const int fb = walk.fb;
         for (const PairRun &r : walk.runs) {
             uint32_t *limit_a = limits(0, at[0][r.ia] + r.first_a), *limit_b = limits(fb, at[fb][r.ib] + r.first_b);
-            const int rc = consensus_on ? kbbq_pair_overlap_inserts(e, of[0][r.ia], r.first_a, of[fb][r.ib], r.first_b, r.stride, r.n_pairs, &p, limit_a, limit_b,
+            const int rc = insert.p ? kbbq_pair_overlap_inserts(e, of[0][r.ia], r.first_a, of[fb][r.ib], r.first_b, r.stride, r.n_pairs, &p, limit_a, limit_b,
                                                                     insert.as<uint32_t>() + r.pair)
                                         : kbbq_pair_overlap_batch(e, of[0][r.ia], r.first_a, of[fb][r.ib], r.first_b, r.stride, r.n_pairs, &p, limit_a, limit_b);
             if (rc < 0) return fail_engine("searching the pairs' overlaps");
+        }
+        // --merged-out: how many bases the pairs of every run have, which is where the next run's merged text starts (the batches'
+        // offsets are in device memory: four words a run)
+        run_bases.assign(merge_on ? walk.runs.size() : 0, 0);
+        for (size_t k = 0; k < run_bases.size(); ++k) {
+            const PairRun &r = walk.runs[k];
+            const uint64_t last = (r.n_pairs - 1) * r.stride;
+            uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+            if (kbbq_reads_offset(e, of[0][r.ia], r.first_a, &a0) < 0 || kbbq_reads_offset(e, of[0][r.ia], r.first_a + last + 1, &a1) < 0 ||
+                kbbq_reads_offset(e, of[fb][r.ib], r.first_b, &b0) < 0 || kbbq_reads_offset(e, of[fb][r.ib], r.first_b + last + 1, &b1) < 0)
+                return fail_engine("merging the pairs");
+            run_bases[k] = r.stride == 2 ? b1 - a0 : (a1 - a0) + (b1 - b0);
         }
         return 0;
     }
@@ -172,12 +209,22 @@ struct TrimRun {
             return fail_engine("correcting from the mates");
         return 0;
     }
+    // --merged-out: the merge of the pairs of run r between sides a and b, into `merged` at the pairs' ordinals; seq, qual: where the
+    // run's text goes, or both null for the verdicts alone
+    int merge_pairs(const PairRun &r, const Side &a, const Side &b, uint8_t *seq, uint8_t *qual) {
+        const int fb = walk.fb;
+        if (kbbq_pair_merge_batch(e, a.d, a.first, b.d, b.first, r.stride, r.n_pairs, insert.as<uint32_t>() + r.pair, limits(0, at[0][r.ia] + r.first_a),
+                                  limits(fb, at[fb][r.ib] + r.first_b), a.q, b.q, a.mask, a.bases, b.mask, b.bases, &params, merged.as<uint32_t>() + r.pair, seq,
+                                  qual) < 0)
+            return fail_engine("merging the pairs");
+        return 0;
+    }
     // batch i of file f into slot s, unless it stands there
     int hold(MateSlot &s, int f, size_t i) {
         if (s.holds == of[f][i]) return 0;
-        return s.fill(e, *of[f][i], errors ? (*errors)[index[f][i]] : nullptr);
+        return s.fill(e, *of[f][i], errors ? (*errors)[index[f][i]] : nullptr, consensus_on ? "--pair-correct" : "--merged-out");
     }
-    // --pair-correct's pre-pass, behind overlaps(): run by run the rule two-sided on the qualities (and fix arrays) of the run's two
+    // --pair-correct's and --merged-out's pre-pass, behind overlaps(): run by run the rule two-sided on the qualities (and fix arrays) of the run's two
     // batches, each held in a slot -- slot[0] and slot[1] by file, or by the batch's parity when interleaved, where a batch may
     // stand there already because the run before crossed into it -- and a batch's verdicts when the last run with a read of it is done
     int consensus_verdicts() {
@@ -185,7 +232,11 @@ struct TrimRun {
         // the verdicts of batch i of file f from slot s, if run k is the last with a read of it
         auto verdicts_after = [&](size_t k, int f, size_t i, const MateSlot &s) {
             if (walk.touch[f][i].end != k + 1) return 0;
-            if (kbbq_trim_batch_limited(e, of[f][i], s.qual(), &params, limits(f, at[f][i]), kept(f, at[f][i])) < 0) return fail_engine("trimming");
+            // (--merged-out: the reads of mergeable pairs are left out; every run with a read of the batch has written its pairs' words)
+            const int rc = merge_on ? kbbq_trim_batch_unmerged(e, of[f][i], s.qual(), &params, limits(f, at[f][i]), merged.as<uint32_t>(), at[f][i], fb ? 0 : 1,
+                                                               kept(f, at[f][i]))
+                                    : kbbq_trim_batch_limited(e, of[f][i], s.qual(), &params, limits(f, at[f][i]), kept(f, at[f][i]));
+            if (rc < 0) return fail_engine("trimming");
             return 0;
         };
         for (size_t k = 0; k < walk.runs.size(); ++k) {
@@ -193,13 +244,18 @@ struct TrimRun {
             MateSlot &sa = slot[fb ? 0 : r.ia & 1], &sb = slot[fb ? 1 : r.ib & 1];      // (one slot twice for a run inside an interleaved batch)
             if (const int rc = hold(sa, 0, r.ia)) return rc;
             if (const int rc = hold(sb, fb, r.ib)) return rc;
-            if (const int rc = correct_pairs(r, side(of[0][r.ia], r.first_a, sa), side(of[fb][r.ib], r.first_b, sb), 3)) return rc;
+            const Side a = side(of[0][r.ia], r.first_a, sa), b = side(of[fb][r.ib], r.first_b, sb);
+            if (consensus_on)
+                if (const int rc = correct_pairs(r, a, b, 3)) return rc;
+            if (merge_on)
+                if (const int rc = merge_pairs(r, a, b, nullptr, nullptr)) return rc;
             if (const int rc = verdicts_after(k, 0, r.ia, sa)) return rc;
             if (&sb != &sa)
                 if (const int rc = verdicts_after(k, fb, r.ib, sb)) return rc;
         }
         // every read has been met once: the counts of the stamped lines (the write loop's calls count some reads again)
-        if (kbbq_pair_consensus_counts_get(e, &consensus_counts, 1) < 0) return fail_engine("correcting from the mates");
+        if (consensus_on && kbbq_pair_consensus_counts_get(e, &consensus_counts, 1) < 0) return fail_engine("correcting from the mates");
+        if (merge_on && kbbq_merge_counts_get(e, &merge_counts, 1) < 0) return fail_engine("merging the pairs");
         if (errors && kbbq_correct_counts(e, &fix_counts, 1) < 0) return fail_engine("correcting");
         slot[0].holds = slot[1].holds = nullptr;      // (what stands there is behind the rule: the write loop starts afresh)
         return 0;
@@ -209,6 +265,9 @@ struct TrimRun {
     // in place, both sides written.  Any other: against the mates' batch, recalibrated (and fixed) into slot 0 and only read; the
     // written batch is side a of the call whichever mates it holds.  The run inside goes first, then the others in pair order.
     // report_on: the quality report is switched off while a mates' batch is recalibrated.
+    // --merged-out, while the first file's batches (or the interleaved ones) are written: a run whose first mates are the batch's
+    // gets the full merge call behind its correction -- the mates' batch is then corrected too, the call writes both sides -- and
+    // the writer's arrays get its pairs' places; the text of the batch's runs stands side by side in `text`.
     int consensus_batch(int which, uint64_t ordinal, const kbbq_reads &d, uint8_t *q, uint64_t *mask, uint64_t *bases, bool report_on) {
         if (!d.n_reads) return 0;
         const size_t i = (size_t)(std::lower_bound(at[which].begin(), at[which].end(), ordinal) - at[which].begin());
@@ -216,24 +275,55 @@ struct TrimRun {
         MateSlot &s = slot[0];
         const int fb = walk.fb;
         const PairWalk::Range t = walk.touch[which][i];
+        const bool merging = merge_on && which == 0;
+        uint64_t at0 = 0;      // where the next run's text starts
+        if (merging) {
+            uint64_t room = 0;
+            for (size_t k = t.begin; k < t.end; ++k)
+                if (walk.runs[k].ia == i) room += run_bases[k];
+            if (!rec_len.ensure(e, d.n_reads * 4) || !rec_at.ensure(e, d.n_reads * 8) || !text.ensure(e, 2 * room + 16))
+                return give_up(" Error: --merged-out: the merged text of a batch (" + std::to_string(2 * room) + " bytes) does not fit in GPU memory.");
+            if (kbbq_device_zero(e, rec_len.p, d.n_reads * 4) < 0) return fail_engine("merging the pairs");
+            merged_seq = text.as<uint8_t>();
+            merged_qual = merged_seq + room;
+        }
+        // the full merge call of run k, whose first mates are the batch's, and its pairs' places for the writer
+        auto merge_run = [&](size_t k, const Side &a, const Side &b) {
+            const PairRun &r = walk.runs[k];
+            if (const int rc = merge_pairs(r, a, b, merged_seq + at0, merged_qual + at0)) return rc;
+            if (kbbq_pair_merge_places(e, a.d, a.first, b.d, b.first, r.stride, r.n_pairs, merged.as<uint32_t>() + r.pair, at0, rec_len.as<uint32_t>(),
+                                       rec_at.as<uint64_t>()) < 0)
+                return fail_engine("merging the pairs");
+            at0 += run_bases[k];
+            return 0;
+        };
         for (int in_place = 1; in_place >= 0; --in_place) {
             for (size_t k = t.begin; k < t.end; ++k) {
                 const PairRun &r = walk.runs[k];
                 if ((!fb && r.ia == r.ib) != (in_place != 0)) continue;
                 if (in_place) {
-                    if (const int rc = correct_pairs(r, Side{&d, r.first_a, q, mask, bases}, Side{&d, r.first_b, q, mask, bases}, 3)) return rc;
+                    const Side a{&d, r.first_a, q, mask, bases}, b{&d, r.first_b, q, mask, bases};
+                    if (consensus_on)
+                        if (const int rc = correct_pairs(r, a, b, 3)) return rc;
+                    if (merging)
+                        if (const int rc = merge_run(k, a, b)) return rc;
                     continue;
                 }
                 const bool mine_a = fb ? which == 0 : r.ia == i;      // (which side of the run the written batch is)
                 const int f = mine_a ? fb : 0;
                 const size_t m = mine_a ? r.ib : r.ia;
+                if (!consensus_on && !(merging && mine_a)) continue;      // (a merging run without --pair-correct needs the mates of its first mates alone)
                 if (s.holds != of[f][m]) {
                     if (report_on && kbbq_report_enable(e, 0) < 0) return fail_engine("correcting from the mates");
                     if (const int rc = hold(s, f, m)) return rc;
                     if (report_on && kbbq_report_enable(e, 1) < 0) return fail_engine("correcting from the mates");
                 }
-                const Side mine{&d, mine_a ? r.first_a : r.first_b, q, mask, bases};
-                if (const int rc = correct_pairs(r, mine, side(of[f][m], mine_a ? r.first_b : r.first_a, s), 1)) return rc;
+                const Side mine{&d, mine_a ? r.first_a : r.first_b, q, mask, bases}, theirs = side(of[f][m], mine_a ? r.first_b : r.first_a, s);
+                // (a merging run corrects the slot too: the merge reads both sides as they are written)
+                if (consensus_on)
+                    if (const int rc = correct_pairs(r, mine, theirs, merging && mine_a ? 3 : 1)) return rc;
+                if (merging && mine_a)
+                    if (const int rc = merge_run(k, mine, theirs)) return rc;
             }
         }
         return 0;
@@ -244,7 +334,7 @@ struct TrimRun {
         if (report_on && kbbq_report_enable(e, 0) < 0) return fail_engine("trimming");
         if (overlap_on)      // (which checks every ordinal, and that the files are in step)
             if (const int rc = overlaps(batches, in2_first_batch, two_files)) return rc;
-        if (consensus_on) {
+        if (consensus_on || merge_on) {
             if (const int rc = consensus_verdicts()) return rc;
         } else {
             uint64_t ordinal[2] = {0, 0};
@@ -276,12 +366,32 @@ struct TrimRun {
         written += records;
         shortened += cut;
         ms_sizes += in.trim_ms();
+        if (merge_on) {
+            uint64_t merged_records = 0;
+            double ms = 0;
+            in.merged_written(merged_records, ms);
+            merged_written += merged_records;
+            ms_merged_sizes += ms;
+        }
+    }
+    // the ordinals of the pairs whose mates lie in two interleaved batches, " none" if there is none (the timing line)
+    std::string crossing_pairs() const {
+        std::string out;
+        for (const PairRun &r : walk.runs)
+            if (!walk.fb && r.ia != r.ib) out += " " + std::to_string(r.pair);
+        return out.empty() ? " none" : out;
+    }
+    // --merged-out: the merged reads of the batch consensus_batch() has just been through, to the third writer
+    int write_merged(DeviceInput &in) {
+        return in.write_chunk_merged(*merged_writer, rec_len.as<uint32_t>(), rec_at.as<uint64_t>(), merged_seq, merged_qual, kbbq_engine_stream(e)) ? 0 : 1;
     }
     // the stamped line, printed by the last writer call over both files
     int line() {
         kbbq_trim_counts c;
         if (kbbq_trim_counts_get(e, &c, 0) < 0) return fail_engine("trimming");
         if (written != c.reads_kept) return give_up(" Error: trimming: the writer wrote " + std::to_string(written) + " reads where the verdicts kept " + std::to_string(c.reads_kept) + ".");
+        if (merge_on && merged_written != merge_counts.merged)
+            return give_up(" Error: merging: the writer wrote " + std::to_string(merged_written) + " merged reads where the verdicts merged " + std::to_string(merge_counts.merged) + ".");
         std::cerr << put_now << " Trimmed reads: " << c.reads_in << " in, " << written << " written, " << shortened << " shortened, " << c.too_short << " too short, "
                   << c.over_ee << " over the expected errors, " << c.with_mate << " dropped with their mate; bases: " << c.bases_in << " in, " << c.bases_kept
                   << " written." << std::endl;
@@ -301,6 +411,11 @@ struct TrimRun {
             if (consensus_on)
                 std::cerr << put_now << " Pair corrections: " << consensus_counts.reads_changed << " reads changed, " << consensus_counts.bases_corrected
                           << " bases corrected, " << consensus_counts.from_n << " of them were N, " << consensus_counts.bases_left << " differing bases left."
+                          << std::endl;
+            if (merge_on)
+                std::cerr << put_now << " Merged pairs: " << merge_counts.merged << " merged, " << merge_counts.bases_written << " bases written, " << merge_counts.too_short
+                          << " too short, " << merge_counts.over_ee << " over the expected errors, " << merge_counts.held_back << " held back by an adapter; overlap: "
+                          << merge_counts.overlap_bases << " bases, " << merge_counts.disagreeing << " disagreeing, " << merge_counts.undecided << " undecided."
                           << std::endl;
         }
         return 0;

@@ -56,6 +56,8 @@ using namespace kbbq;
 #include "engine_overlap.h"
 #include "consensus.h"   // (k_pair_consensus: behind k_pair_overlap, for the same reason)
 #include "engine_consensus.h"
+#include "merge.h"   // (k_pair_merge, k_trim_unmerged: behind k_pair_consensus, for the same reason)
+#include "engine_merge.h"
 
 extern "C" {
 
@@ -168,7 +170,7 @@ void kbbq_engine_destroy(kbbq_engine *e) {
     hipFree(e->d_tickets);
     hipFree(e->d_totals);
     hipFree(e->d_fix_counts);
-    for (CounterBlock *c : {&e->trim, &e->adapter, &e->overlap, &e->consensus}) c->free();
+    for (CounterBlock *c : {&e->trim, &e->adapter, &e->overlap, &e->consensus, &e->merge}) c->free();
     hipFree(e->p4.d_dq_qslot);
     hipFree(e->d_qpresent);
     hipFree(e->p3.d_rg_present[0]);
@@ -200,6 +202,7 @@ int kbbq_engine_reset(kbbq_engine *e) {
     if ((rc = e->adapter.reset(e->stream))) return rc;
     if ((rc = e->overlap.reset(e->stream))) return rc;
     if ((rc = e->consensus.reset(e->stream))) return rc;
+    if ((rc = e->merge.reset(e->stream))) return rc;
     e->profile.reset();
     return sync_engine(e);
 }

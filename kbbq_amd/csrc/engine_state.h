@@ -356,7 +356,7 @@ struct kbbq_engine {
     Pass3State p3;
     Pass4State p4;
     ReportState rep;
-    CounterBlock trim, adapter, overlap, consensus;
+    CounterBlock trim, adapter, overlap, consensus, merge;
     Staging stage;
     Buckets bk;
     Profile profile;

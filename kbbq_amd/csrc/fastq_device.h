@@ -12,6 +12,8 @@
 //                        the same two with corrected sequence lines (kbbq_fastq_reader_write_corrected): kernels of their own, so
 //                        that the two above stay what they are
 //   k_fastq_trim_sizes / k_fastq_text_indexed_trimmed / k_fastq_text_packed_trimmed
+//   k_fastq_merged_sizes / k_fastq_text_indexed_merged / k_fastq_text_packed_merged
+//                        records whose sequence and quality lines come from arrays of the caller's (kbbq_fastq_reader_write_merged)
 //                        records whose output is shorter than their input, or absent (kbbq_fastq_reader_write_trimmed): the sizes
 //                        of what is kept, and the two text kernels again around offsets of their own -- behind the seven above
 #pragma once
@@ -221,6 +223,51 @@ __global__ void __launch_bounds__(256) k_fastq_text_packed_trimmed(const uint8_t
         const uint8_t *name = names + (text_off[r] - 2 * b0 - 6 * r);      // (the chunk's own text offsets: where the names were put)
         const SeqSource from = {nullptr, bases, nmask, offcase, b0, fix_mask, fix_bases, b0};
         emit_fastq_record<FIX>(lane, name, nl, name + nl, cl, from, kl, new_qual + b0, out + out_off[r]);
+    }
+}
+
+// ---- merged records (kbbq_fastq_reader_write_merged) --------------------------------------------------------------------
+// A record whose sequence and quality lines come from neither input record: len[r] bases (0: nothing is written for record r)
+// whose characters and raw qualities stand at seq[at[r]] and qual[at[r]], under record r's own name and '+' lines.  Its output
+// is name + comment + 2 x len + 6 bytes; the offsets are the scanned sizes, as for the trimmed records.  written[0] += the
+// records that are written, once per wavefront.
+__global__ void __launch_bounds__(256) k_fastq_merged_sizes(const uint32_t *name_len, const uint32_t *com_len, uint32_t stride, const uint32_t *len,
+                                                             uint64_t n_records, uint64_t *out_sz, unsigned long long *written) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t ml = 0;
+    if (r < n_records) {
+        ml = len[r];
+        out_sz[r] = ml ? (uint64_t)name_len[r * stride] + com_len[r * stride] + 2 * ml + 6 : 0;
+    }
+    const int n_written = __popcll(__ballot(ml != 0));
+    if ((threadIdx.x & 63) == 0 && n_written) atomicAdd(&written[0], (unsigned long long)n_written);
+}
+
+__global__ void __launch_bounds__(256) k_fastq_text_indexed_merged(const uint8_t *text, FastqIndex X, const uint64_t *out_off, const uint32_t *len,
+                                                                    const uint64_t *at, const uint8_t *seq, const uint8_t *qual, uint64_t n_records,
+                                                                    uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t r = wave; r < n_records; r += n_waves) {
+        const uint32_t ml = len[r];
+        if (!ml) continue;
+        const SeqSource from = {seq + at[r], nullptr, nullptr, nullptr, 0};
+        emit_fastq_record(lane, text + X.name_off[r], X.name_len[r], text + X.com_off[r], X.com_len[r], from, ml, qual + at[r], out + out_off[r]);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_fastq_text_packed_merged(const uint8_t *names, const uint32_t *lens, const uint64_t *text_off, const uint64_t *base_off,
+                                                                   const uint64_t *out_off, const uint32_t *len, const uint64_t *at, const uint8_t *seq,
+                                                                   const uint8_t *qual, uint64_t n_records, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t r = wave; r < n_records; r += n_waves) {
+        const uint32_t ml = len[r];
+        if (!ml) continue;
+        const uint32_t nl = lens[2 * r], cl = lens[2 * r + 1];
+        const uint8_t *name = names + (text_off[r] - 2 * base_off[r] - 6 * r);      // (the chunk's own offsets: where the names were put)
+        const SeqSource from = {seq + at[r], nullptr, nullptr, nullptr, 0};
+        emit_fastq_record(lane, name, nl, name + nl, cl, from, ml, qual + at[r], out + out_off[r]);
     }
 }
 

@@ -55,6 +55,9 @@ struct kbbq_fastq_reader : FastqCounts, TextChunks, ChunkState {
     Buf trim_off;
     double ms_trim_sizes = 0;
     uint64_t trim_written = 0, trim_shortened = 0;      // records written by such calls, and those of them that were cut
+    // merged output (kbbq_fastq_reader_write_merged): the records written, the time of the size pass and scan (the offsets are trim_off's)
+    uint64_t merged_written = 0;
+    double ms_merged_sizes = 0;
 };
 
 namespace {
@@ -514,6 +517,65 @@ int kbbq_fastq_reader_write_trimmed(kbbq_fastq_reader *r, kbbq_bgzf *z, const ui
             hipLaunchKernelGGL(k_fastq_text_indexed_trimmed<false>, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)out_off, base_off, d_keep, d_qual,
                                fix_mask, fix_bases, n, payload);
     });
+}
+
+int kbbq_fastq_reader_write_merged(kbbq_fastq_reader *r, kbbq_bgzf *z, const uint32_t *d_len, const uint64_t *d_at, const uint8_t *d_seq, const uint8_t *d_qual,
+                                   void *after_stream, uint64_t *out_bytes) {
+    if (!r || !z || !d_len || !d_at || !d_seq || !d_qual || !out_bytes) return fail(KBBQ_EINVAL, "null argument");
+    if (!r->have_chunk || !r->n_records) return fail(KBBQ_ESTATE, "no records in the current chunk");
+    if (r->device != z->device) return fail(KBBQ_EINVAL, "reader and writer are on different devices");
+    KbbqDeviceGuard guard(z->device);
+    HIP_TRY(guard.err);
+    *out_bytes = 0;
+    const uint64_t n = r->n_records;
+    const bool from_kept = r->selected >= 0;
+    const kbbq_fastq_reader::Kept *k = from_kept ? &r->kept[(size_t)r->selected] : nullptr;
+    const bool packed = from_kept && k->short_form;      // (the names and comments are all a merged record takes from the chunk: no batch need be attached)
+    const FastqIndex X = from_kept ? index_from(k->idx_u32.p, nullptr, k->base_sz.p, k->text_sz.p, nullptr, n) : index_of(r, n);
+    const uint8_t *text = (const uint8_t *)(from_kept ? k->text.p : r->text.p);
+    // ---- the sizes of what is written, scanned into offsets of their own, and their total: on the reader's stream, behind the
+    // caller's (which fills d_len, d_at, d_seq and d_qual).  The offsets share kbbq_fastq_reader_write_trimmed's array: each
+    // call waits for its text kernel before it returns.
+    int rc;
+    if ((rc = r->trim_off.reserve((n + 4) * 8))) return rc;
+    if ((rc = r->h_small.reserve(4096))) return rc;
+    uint64_t *out_off = (uint64_t *)r->trim_off.p;
+    if (after_stream) {
+        HIP_TRY(hipEventRecord(r->t2, (hipStream_t)after_stream));
+        HIP_TRY(hipStreamWaitEvent(r->st, r->t2, 0));
+    }
+    HIP_TRY(hipEventRecord(r->t0, r->st));
+    HIP_TRY(hipMemsetAsync(out_off + n + 1, 0, 16, r->st));
+    const uint32_t *lens = packed ? (const uint32_t *)k->lens.p : nullptr;
+    hipLaunchKernelGGL(k_fastq_merged_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->st, packed ? lens : X.name_len, packed ? lens + 1 : X.com_len,
+                       packed ? 2u : 1u, d_len, n, out_off, (unsigned long long *)(out_off + n + 1));
+    HIP_TRY(hipGetLastError());
+    if ((rc = device_scan_on(r->tile_sums, r->st, out_off, n, out_off + n))) return rc;
+    HIP_TRY(hipEventRecord(r->t1, r->st));
+    uint64_t *hs = (uint64_t *)r->h_small.p;
+    HIP_TRY(hipMemcpyAsync(hs, out_off + n, 16, hipMemcpyDeviceToHost, r->st));
+    HIP_TRY(hipStreamSynchronize(r->st));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, r->t0, r->t1) == hipSuccess) r->ms_merged_sizes += ms;
+    const uint64_t total = hs[0];
+    r->merged_written += hs[1];
+    *out_bytes = total;
+    if (!total) return KBBQ_OK;      // nothing of this chunk was merged: nothing is submitted
+    const dim3 grid((unsigned)std::min<uint64_t>((n + 3) / 4, 256 * 32));
+    return submit_rewrite(z, after_stream, total, true, [&](uint8_t *payload) {
+        if (packed)
+            hipLaunchKernelGGL(k_fastq_text_packed_merged, grid, dim3(256), 0, z->st, (const uint8_t *)k->names.p, lens, (const uint64_t *)k->text_sz.p,
+                               (const uint64_t *)k->base_sz.p, (const uint64_t *)out_off, d_len, d_at, d_seq, d_qual, n, payload);
+        else
+            hipLaunchKernelGGL(k_fastq_text_indexed_merged, grid, dim3(256), 0, z->st, text, X, (const uint64_t *)out_off, d_len, d_at, d_seq, d_qual, n, payload);
+    });
+}
+
+int kbbq_fastq_reader_merged_written(kbbq_fastq_reader *r, uint64_t *records, double *sizes_ms) {
+    if (!r || !records || !sizes_ms) return fail(KBBQ_EINVAL, "null argument");
+    *records = r->merged_written;
+    *sizes_ms = r->ms_merged_sizes;
+    return KBBQ_OK;
 }
 
 int kbbq_fastq_reader_trim_ms(kbbq_fastq_reader *r, double *sizes_ms) {

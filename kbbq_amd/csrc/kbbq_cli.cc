@@ -59,7 +59,8 @@
 //     N, --pair-overlap-diff D, --pair-overlap-error-rate R) finds whatever adapter stands behind an insert shorter than the
 //     reads from the overlap of a pair's mates, with --in2 or --interleaved; --pair-correct (--pair-correct-quals G,B) with it
 //     lets a base of quality G or more replace, complemented, the mate's differing base of quality B or less inside that
-//     overlap.  FASTQ through the device reader only; without them nothing changes;
+//     overlap, and --merged-out FILE with it writes every pair whose mates overlap as one read over the whole insert to FILE
+//     and neither mate to the pair outputs.  FASTQ through the device reader only; without them nothing changes;
 //   * where the reference prints an error and then crashes or throws (missing --genomelen on FASTQ,
 //     kbbq.cc:218; missing RG / OQ tags, readutils.cc:20-30,42-53) this prints the same text and exits 1.
 #include <fcntl.h>
@@ -975,6 +976,13 @@ int main(int argc, char *argv[]) {
         fclose(f);
         if (!was_there) unlink(opt.out2.c_str());
     }
+    if (opt.merge_on()) {      // --merged-out: likewise
+        const bool was_there = access(opt.merged_out.c_str(), F_OK) == 0;
+        FILE *f = fopen(opt.merged_out.c_str(), "ab");
+        if (!f) return give_up(" Error: --merged-out: cannot open " + opt.merged_out + " for writing: " + strerror(errno));
+        fclose(f);
+        if (!was_there) unlink(opt.merged_out.c_str());
+    }
     if (opt.inflate_on_device()) set_bgzf_source_factory(&DeviceBgzfSource::open);
     if (opt.table_run()) return run_table(opt, stream.get());
 
@@ -1093,6 +1101,22 @@ int main(int argc, char *argv[]) {
     // paired run takes every verdict, and applies the mate rule, before its first record is written (cli_trim.h)
     TrimRun trim_run;
     TrimRun *trim = nullptr;
+    // --merged-out: the merged reads' file and its writer, open while the first (or the interleaved) file's records are written;
+    // a run that fails on the way leaves no such file
+    struct MergedFile {
+        std::string path;
+        FILE *f = nullptr;
+        Sink sink;
+        bool keep = false;
+        ~MergedFile() { if (f) { if (sink.dev) (void)sink.close(); fclose(f); } if (!path.empty() && !keep) unlink(path.c_str()); }
+        // the writer's last blocks and the file's end; false: something of it failed
+        bool finish() {
+            const bool closed = sink.close();
+            const bool ok = (fclose(f) == 0) & closed;
+            f = nullptr;
+            return ok;
+        }
+    } merged_file;
     if (opt.trim_on()) {
         uint64_t reads[2] = {0, 0};
         for (size_t bi = 0; bi < resident.dev.size(); ++bi) reads[opt.paired_files() && bi >= scan.in2_first_batch ? 1 : 0] += resident.dev[bi].n_reads;
@@ -1101,20 +1125,32 @@ int main(int argc, char *argv[]) {
         if (trim_run.paired) {
             if (!sink.dev) return give_up(std::string(" Error: ") + opt.trim_option + ": the output does not go through the GPU reader's writer, which cuts and drops the reads.");
             QualSlots slots{e};
-            if (opt.correct && opt.pair_correct) {
+            if (opt.correct && (opt.pair_correct || opt.merge_on())) {
                 if (scan.error_flags.of.size() != resident.dev.size()) return give_up(" Error: --correct: pass 3 left no error flags for the resident batches.");
                 trim_run.errors = &scan.error_flags.of;
             }
             if ((rc = trim_run.verdicts(slots, *sink.dev, resident.dev, scan.in2_first_batch, opt.paired_files(), !opt.report.empty()))) return rc;
             clock.mark("trim verdicts");
         }
+        if (opt.merge_on()) {
+            if (!(merged_file.f = fopen(opt.merged_out.c_str(), "wb")))
+                return give_up(" Error: --merged-out: cannot open " + opt.merged_out + " for writing: " + strerror(errno));
+            merged_file.path = opt.merged_out;
+            if ((rc = merged_file.sink.open_file(merged_file.f, opt))) return rc;
+            trim_run.merged_writer = merged_file.sink.dev.get();
+        }
     }
+    // (--merged-out's file is whole once the first reader's records are written)
+    auto finish_merged = [&] {
+        if (!merged_file.f || merged_file.finish()) return 0;
+        return give_up(" Error: --merged-out: writing " + opt.merged_out + " failed.");
+    };
     if (!opt.paired_files()) {
-        if (write_output(e, scan, opt, sink, dev_in, batch, trim) || !sink.close()) return 1;
+        if (write_output(e, scan, opt, sink, dev_in, batch, trim) || finish_merged() || !sink.close()) return 1;
     } else {
         // the first file's records to stdout as ever, then the second file's -- the resident batches behind the first file's --
         // to --out2 through a writer of its own; a run that fails on the way leaves no --out2 file
-        if (write_from_device_reader(e, scan, opt, sink, dev_in, 0, false, trim, 0)) return 1;
+        if (write_from_device_reader(e, scan, opt, sink, dev_in, 0, false, trim, 0) || finish_merged()) return 1;
         FILE *f2 = fopen(opt.out2.c_str(), "wb");
         if (!f2) return give_up(" Error: --out2: cannot open " + opt.out2 + " for writing: " + strerror(errno));
         Sink sink2;
@@ -1166,6 +1202,19 @@ int main(int argc, char *argv[]) {
                 if (!strcmp(prof[i].name, "k_pair_consensus")) { ms = prof[i].total_ms; launches = prof[i].launches; }
         std::cerr << "[timing] pair correct: k_pair_consensus " << ms << " ms in " << launches << " launches" << std::endl;
     }
+    if (trim && clock.on && opt.merge_on()) {
+        kbbq_profile_entry prof[256];
+        int32_t n = 0;
+        double ms = 0;
+        uint64_t launches = 0;
+        if (kbbq_engine_sync(e) == 0 && kbbq_profile_get(e, prof, 256, &n) == 0)
+            for (int32_t i = 0; i < n && i < 256; ++i)
+                if (!strcmp(prof[i].name, "k_pair_merge")) { ms = prof[i].total_ms; launches = prof[i].launches; }
+        std::cerr << "[timing] merge: k_pair_merge " << ms << " ms in " << launches << " launches; sizes + scan of the merged records " << trim_run.ms_merged_sizes
+                  << " ms (their text kernels are in the merged writer's format time); " << trim_run.walk.runs.size()
+                  << " runs, pairs that cross from one interleaved batch into the next:" << trim_run.crossing_pairs() << std::endl;
+    }
+    merged_file.keep = true;      // (the run has written everything it writes)
     trim_run.release();      // (before the engine goes: end_run may not come back)
     if (!opt.report.empty())
         if (const int bad = write_quality_report(e, opt, scan.groups.names(), nullptr, p.seed, scan.seqlen)) return bad;

@@ -442,6 +442,110 @@ class Engine:
         """What pair_consensus did since the last reset (waits): the fields of kbbq_pair_consensus_counts."""
         return self._counts(self.L.kbbq_pair_consensus_counts_get, _lib.ConsensusCounts, reset)
 
+    # ---- overlapping pairs merged into single reads
+    @staticmethod
+    def _trim_params(tail_q, min_length, max_ee):
+        p = _lib.TrimParams()
+        p.tail_q = 0 if tail_q is None else int(tail_q)
+        p.min_length = int(min_length)
+        p.has_ee = 0 if max_ee is None else 1
+        p.ee_bound = 0 if max_ee is None else ee_bound(max_ee)
+        return p
+
+    def pair_merge(self, dev_a, dev_b, insert, qual_a, qual_b=None, first_a=0, first_b=0, stride=1, n_pairs=None, limit_a=None, limit_b=None,
+                   fix_a=None, fix_b=None, min_length=1, max_ee=None, text=True, shift=0):
+        """kbbq_pair_merge_batch on two device batches (DeviceReads; the same one twice with stride 2 for an interleaved batch,
+        which has one quality array and one pair of fix arrays) and host arrays: insert, one length per pair (find_pair_inserts');
+        limit_a, limit_b, one limit per pair (None: the reads' lengths); qual_a, qual_b, the written qualities of the two batches
+        in base order; fix_a, fix_b, each the (fix_mask, fix_bases) words of correct_bases or pair_consensus -- both None: the
+        call gets no fix arrays.  Returns (merged_len, seq, qual): merged_len as the call wrote it (uint32 per pair) and, with
+        text, the two output arrays as NumPy uint8 arrays of as many bytes as the batches have bases (pair j's text stands at S(j);
+        bytes the call did not write are 0xFF); text=False is the verdict-only call and gives None for both.  shift: the
+        output arrays start that many bytes behind an aligned address.  Waits for the kernel."""
+        import torch
+        stride = int(stride)
+        if n_pairs is None:
+            n_pairs = self._pairs_from(dev_a, dev_b, first_a, first_b, stride)
+        n_pairs = int(n_pairs)
+        dev = "cuda:%d" % self.params.device
+        one = dev_a is dev_b
+        assert not one or (qual_b is None and fix_b is None), "one batch has one quality array and one pair of fix arrays"
+        step = max(stride, 1)
+        words = max(1, (n_pairs - 1) * step + 1) if n_pairs else 1
+
+        def per_pair(given, spread):
+            host = np.zeros(words if spread else max(1, n_pairs), np.uint32)
+            g = np.ascontiguousarray(given, dtype=np.uint32)
+            assert len(g) == n_pairs, "one value per pair"
+            if spread:
+                host[::step][:n_pairs] = g
+            else:
+                host[:n_pairs] = g
+            return torch.from_numpy(host.view(np.int32)).to(dev)
+
+        full = np.full(n_pairs, 0xFFFFFFFF, np.uint32)
+        d_insert = per_pair(insert, False)
+        d_lim = [per_pair(full if given is None else given, True) for given in (limit_a, limit_b)]
+        with_fix = fix_a is not None or fix_b is not None
+
+        def side(dreads, qual, fix):
+            nb = dreads.n_bases
+            q = np.ascontiguousarray(qual, dtype=np.uint8)
+            assert len(q) == nb, "one quality per base of the batch"
+            out = [torch.from_numpy(np.concatenate([q, np.zeros(1, np.uint8)])).to(dev)]
+            for given, n in zip(fix if fix is not None else (None, None), (nb // 64 + 2, nb // 32 + 2)):
+                w = np.zeros(n, np.uint64)
+                if given is not None:
+                    g = np.ascontiguousarray(given, dtype=np.uint64)
+                    assert len(g) <= n, "fix arrays: at most n_bases/64+2 and n_bases/32+2 words"
+                    w[:len(g)] = g
+                out.append(torch.from_numpy(w.view(np.int64)).to(dev) if with_fix else None)
+            return out
+
+        da = side(dev_a, qual_a, fix_a)
+        db = da if one else side(dev_b, qual_b, fix_b)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        d_len = torch.full((max(1, n_pairs),), -1, dtype=torch.int32, device=dev)
+        n_out = 0
+        if text and n_pairs:      # (room for every base of the batches: the call's pairs have no more)
+            n_out = dev_a.n_bases if one else dev_a.n_bases + dev_b.n_bases
+        d_seq = torch.full((n_out + int(shift) + 1,), 0xFF, dtype=torch.uint8, device=dev) if text else None
+        d_qual = torch.full((n_out + int(shift) + 1,), 0xFF, dtype=torch.uint8, device=dev) if text else None
+        p = self._trim_params(None, min_length, max_ee)
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_pair_merge_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, d_insert.data_ptr(),
+                                                d_lim[0].data_ptr(), d_lim[1].data_ptr(), da[0].data_ptr(), db[0].data_ptr(), ptr(da[1]), ptr(da[2]),
+                                                ptr(db[1]), ptr(db[2]), ctypes.byref(p), d_len.data_ptr(),
+                                                d_seq.data_ptr() + int(shift) if text else None, d_qual.data_ptr() + int(shift) if text else None))
+        self.sync()
+        lens = d_len.cpu().numpy().view(np.uint32)[:n_pairs].copy()
+        if not text:
+            return lens, None, None
+        return lens, d_seq.cpu().numpy()[int(shift):int(shift) + n_out].copy(), d_qual.cpu().numpy()[int(shift):int(shift) + n_out].copy()
+
+    def merge_counts(self, reset=False):
+        """What pair_merge did since the last reset (waits): the fields of kbbq_merge_counts."""
+        return self._counts(self.L.kbbq_merge_counts_get, _lib.MergeCounts, reset)
+
+    def trim_unmerged(self, dreads, qual_ptr, merged_len, first=0, adjacent=False, tail_q=None, min_length=1, max_ee=None, limit=None):
+        """kbbq_trim_batch_unmerged: trim_reads that leaves out the reads of the pairs whose merged_len word (pair_merge's, by the
+        pair's ordinal; read r is of pair first + r, or (first + r) // 2 with adjacent) is not 0.  Waits for the kernel."""
+        import torch
+        p = self._trim_params(tail_q, min_length, max_ee)
+        dev = "cuda:%d" % self.params.device
+        d_keep = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
+        d_merged = torch.from_numpy(np.concatenate([np.ascontiguousarray(merged_len, dtype=np.uint32), np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
+        d_limit = None
+        if limit is not None:
+            lim = np.ascontiguousarray(limit, dtype=np.uint32)
+            assert len(lim) == dreads.n_reads, "limit: one length per read"
+            d_limit = torch.from_numpy(lim.view(np.int32).copy()).to(dev)
+        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
+        _lib.check(self.L.kbbq_trim_batch_unmerged(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), None if d_limit is None else d_limit.data_ptr(),
+                                                   d_merged.data_ptr(), int(first), 1 if adjacent else 0, d_keep.data_ptr()))
+        self.sync()
+        return d_keep.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
+
     def trim_mates(self, keep_a, keep_b=None, adjacent=False):
         """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
         (a, b), or a alone with adjacent=True, where the pairs are a[2i], a[2i+1].  Waits for the kernel."""
