@@ -247,13 +247,15 @@ class Oracle:
                               _p(second, u8p), _p(out, u8p))
         return out
 
-    def run_all(self, seq, qual, off, rg=None, second=None):
-        """All four passes; returns a dict of every intermediate."""
+    def run_all(self, seq, qual, off, rg=None, second=None, thresholds=None):
+        """All four passes; returns a dict of every intermediate.  thresholds: used from pass 2 on in place of the computed ones."""
         out = {}
         self.sample(seq, off)
         out["sampled_inserted"] = self.filter_info(0)["inserted"]
         thr, p_text, too_high = self.compute_thresholds()
         out.update(thresholds=thr, p_text=p_text, fpr_too_high=too_high, fpr=self.sampled_fpr())
+        if thresholds is not None:
+            self.set_thresholds(thresholds)
         out["infer_errors"] = self.trusted(seq, qual, off, want_errors=True)
         out["trusted_inserted"] = self.filter_info(1)["inserted"]
         out["errors"] = self.errors(seq, qual, off, rg, second, tally=True)

@@ -222,12 +222,13 @@ PARITY_CASES = {
 }
 
 
-def run_oracle(d, k=32, seed=777, alpha=None, n_rg=1):
+def run_oracle(d, k=32, seed=777, alpha=None, n_rg=1, thresholds=None):
+    """thresholds: a vector of k+1 entries that replaces the computed one (which is still returned) from pass 2 on."""
     alpha_ld, cov, approx = plan_parameters(d["genome_len"], d["coverage"], alpha)
     o = pyoracle.Oracle(k, alpha_ld, seed, approx)
     rg = np.ascontiguousarray(d["rg"], dtype=np.int32)
     second = np.ascontiguousarray(d["second"], dtype=np.uint8)
-    out = o.run_all(d["seq"], d["qual"], d["off"], rg, second)
+    out = o.run_all(d["seq"], d["qual"], d["off"], rg, second, thresholds=thresholds)
     out["sampled_table"] = o.filter_table(0).copy()
     out["trusted_table"] = o.filter_table(1).copy()
     out["filter_info"] = [o.filter_info(0), o.filter_info(1)]
@@ -235,12 +236,14 @@ def run_oracle(d, k=32, seed=777, alpha=None, n_rg=1):
     return out
 
 
-def run_engine(d, k=32, seed=777, alpha=None, n_rg=1, uniform=False, n_batches=1, max_read_len=None, tune=None):
+def run_engine(d, k=32, seed=777, alpha=None, n_rg=1, uniform=False, n_batches=1, max_read_len=None, tune=None, thresholds=None,
+               flags=0):
+    """thresholds: as run_oracle's; flags: KBBQ_F_* switches for the engine."""
     alpha_ld, cov, approx = plan_parameters(d["genome_len"], d["coverage"], alpha)
     lens = np.diff(d["off"].astype(np.int64))
     if max_read_len is None:
         max_read_len = int(lens.max())
-    e = Engine(k, alpha_ld, seed, approx, n_rg=n_rg, max_read_len=max_read_len, tune=tune)
+    e = Engine(k, alpha_ld, seed, approx, n_rg=n_rg, max_read_len=max_read_len, tune=tune, flags=flags)
     full = ReadBatch(d["seq"], d["qual"], d["off"], d["rg"], d["second"], uniform=uniform)
     n = full.n_reads
     cuts = [n * i // n_batches for i in range(n_batches + 1)]
@@ -254,6 +257,8 @@ def run_engine(d, k=32, seed=777, alpha=None, n_rg=1, uniform=False, n_batches=1
     out["sampled_table"] = e.filter_table(0)
     thr, fpr, p_text, too_high = e.compute_thresholds()
     out.update(thresholds=thr, fpr=fpr, p_text=p_text, fpr_too_high=too_high)
+    if thresholds is not None:
+        e.set_thresholds(thresholds)
     out["infer_errors"] = np.concatenate([e.find_trusted_kmers(b, want_errors=True) for b in batches])
     out["trusted_inserted"] = e.trusted_finish()
     out["trusted_table"] = e.filter_table(1)
@@ -299,3 +304,97 @@ def assert_same_run(eng, ora, C=None):
     assert np.array_equal(ed["dinuc"][:R], od["dinuc"])
     bad = np.nonzero(eng["recal"] != ora["recal"])[0]
     assert len(bad) == 0, "recalibrated qualities differ at %d bases" % len(bad)
+
+
+def run_planted(side, k, plant_reads, test_reads, thresholds=None, pass2_test=True, pass3=True, alpha=None, seed=777, flags=0, tune=None,
+                n_batches=1, uniform=False, resident=False, max_read_len=None):
+    """A run whose trusted filter is planted (tests/planted_data.py), for the oracle (side = "oracle") or the engine
+    ("engine"): pass 1 on plant_reads; all thresholds -1 and pass 2 on plant_reads, which puts every valid k-mer of theirs
+    into the trusted filter; with pass2_test the thresholds `thresholds` (None: the computed ones) and pass 2 on
+    test_reads; with pass3 pass 3 on test_reads and the covariates.  Engine only: test_reads go in as n_batches batches, host batches
+    or -- resident -- uploaded ones, whose pass 3 alternates its two sides and returns no flags ("errors" is None).
+    "test_lookups" is what k_infer fetched for the test reads alone."""
+    assert side in ("oracle", "engine")
+    p, t = plant_reads, test_reads
+    alpha_ld, cov, approx = plan_parameters(p["genome_len"], p["coverage"], alpha)
+    minus1 = np.full(k + 1, -1, dtype=np.int32)
+    out = {}
+    if side == "oracle":
+        o = pyoracle.Oracle(k, alpha_ld, seed, approx)
+        rg = np.ascontiguousarray(t["rg"], dtype=np.int32)
+        second = np.ascontiguousarray(t["second"], dtype=np.uint8)
+        o.sample(p["seq"], p["off"])
+        out["sampled_inserted"] = o.filter_info(0)["inserted"]
+        out["sampled_table"] = o.filter_table(0).copy()
+        thr, p_text, too_high = o.compute_thresholds()
+        out.update(thresholds=thr, p_text=p_text, fpr_too_high=too_high)
+        o.set_thresholds(minus1)
+        out["plant_errors"] = o.trusted(p["seq"], p["qual"], p["off"], want_errors=True)
+        out["planted_inserted"] = o.filter_info(1)["inserted"]
+        out["planted_table"] = o.filter_table(1).copy()
+        if pass2_test:
+            o.set_thresholds(thr if thresholds is None else thresholds)
+            out["infer_errors"] = o.trusted(t["seq"], t["qual"], t["off"], want_errors=True)
+        out["trusted_inserted"] = o.filter_info(1)["inserted"]
+        out["trusted_table"] = o.filter_table(1).copy()
+        if pass3:
+            out["errors"] = o.errors(t["seq"], t["qual"], t["off"], rg, second, tally=True)
+            out["cov"] = o.covariates()
+        out["filter_info"] = [o.filter_info(0), o.filter_info(1)]
+        out["oracle"] = o      # (for ko_filter_contains_key and the like)
+        return out
+    lens = np.diff(t["off"].astype(np.int64))
+    plant_len = int(np.diff(p["off"].astype(np.int64)).max())
+    if max_read_len is None:
+        max_read_len = max(int(lens.max()), plant_len)
+    e = Engine(k, alpha_ld, seed, approx, n_rg=1, max_read_len=max_read_len, tune=tune, flags=flags)
+    try:
+        plant = ReadBatch(p["seq"], p["qual"], p["off"], p["rg"], p["second"], uniform=True)
+        full = ReadBatch(t["seq"], t["qual"], t["off"], t["rg"], t["second"], uniform=uniform)
+        n = full.n_reads
+        cuts = [n * i // n_batches for i in range(n_batches + 1)]
+        host = [full] if n_batches == 1 else [full.slice(cuts[i], cuts[i + 1]) for i in range(n_batches)]
+        e.subsample_kmers(plant, 0)
+        out["sampled_inserted"] = e.sample_finish()
+        out["sampled_table"] = e.filter_table(0)
+        thr, fpr, p_text, too_high = e.compute_thresholds()
+        out.update(thresholds=thr, p_text=p_text, fpr_too_high=too_high)
+        e.set_thresholds(minus1)
+        out["plant_errors"] = e.find_trusted_kmers(plant, want_errors=True)
+        out["planted_inserted"] = e.trusted_finish()
+        out["planted_table"] = e.filter_table(1)
+        before = e.stats()["infer_lookups"]
+        if pass2_test:
+            e.set_thresholds(thr if thresholds is None else thresholds)
+            out["infer_errors"] = np.concatenate([e.find_trusted_kmers(b, want_errors=True) for b in host])
+        out["trusted_inserted"] = e.trusted_finish()
+        out["trusted_table"] = e.filter_table(1)
+        out["test_lookups"] = e.stats()["infer_lookups"] - before
+        if not pass3:
+            pass
+        elif resident:
+            devs = [e.upload(b) for b in host]
+            for db in devs:
+                e.get_covariatedata(db)
+            out["errors"] = None
+            out["cov"] = e.covariates()
+            for db in devs:
+                db.free()
+        else:
+            out["errors"] = np.concatenate([e.get_covariatedata(b, want_errors=True) for b in host])
+            out["cov"] = e.covariates()
+        out["filter_info"] = [e.filter_info(0), e.filter_info(1)]
+        out["stats"] = e.stats()
+    finally:
+        e.close()
+    return out
+
+
+def assert_same_covariates(eng_cov, ora_cov):
+    """Every covariate table of the oracle, bit for bit, in the engine's (which may have more read groups and cycles)."""
+    R, Co = ora_cov["R"], ora_cov["C"]
+    assert eng_cov["R"] >= R and eng_cov["C"] >= Co
+    for key in ("rg", "q", "dinuc"):
+        assert np.array_equal(eng_cov[key][:R], ora_cov[key]), "covariate table %s differs" % key
+    assert np.array_equal(eng_cov["cycle"][:R, :, :, :Co], ora_cov["cycle"]), "covariate table cycle differs"
+    assert eng_cov["cycle"][:R, :, :, Co:].sum() == 0
