@@ -344,11 +344,23 @@ typedef struct kbbq_trim_params {
 /* Sums since the last reset.  reads_in = reads_kept + too_short + over_ee + with_mate.  `shortened` counts the reads whose own
  * verdict was "kept" with kept < n; kbbq_trim_mates does not know a read's length and leaves it alone. */
 typedef struct kbbq_trim_counts { uint64_t reads_in, bases_in, shortened, too_short, over_ee, reads_kept, bases_kept, with_mate; } kbbq_trim_counts;
+/* Which reads of a batch belong to merged pairs (the merge rule below): read r of the batch belongs to pair (first + r) / 2 with
+ * adjacent != 0 (interleaved: first is the ordinal of the batch's first record) and to pair first + r with adjacent == 0;
+ * merged_len: device, kbbq_pair_merge_batch's words by the pair's ordinal. */
+typedef struct kbbq_trim_merged {
+    const uint32_t *merged_len;
+    uint64_t first;
+    int32_t adjacent;
+} kbbq_trim_merged;
 /* keep[r] (device, n_reads words) = the kept length of read r of the device batch, or 0 for a dropped read; device_qual: the
- * batch's written qualities (the array kbbq_recalibrate_batch filled; the batch's own qual is not read).  Uniform or ragged
- * batches, reads of any length the engine takes.  Queued on the engine's stream.  KBBQ_EINVAL for a host batch or
- * parameters out of range. */
-int kbbq_trim_batch(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p, uint32_t *keep);
+ * batch's written qualities (the array kbbq_recalibrate_batch filled; the batch's own qual is not read).  limit (device,
+ * n_reads words; NULL: the whole read): the rule runs on the prefix of min(n, limit[r]) qualities of every read, and the
+ * counters count as the adapter rule below says.  merged (NULL: no read is left out): where merged_len[the read's pair] is not 0
+ * the read counts in reads_in and bases_in alone and keep[r] = 0; every other read as without it.  Uniform or ragged batches,
+ * reads of any length the engine takes.  Queued on the engine's stream.  KBBQ_EINVAL for a null argument (limit and merged
+ * may be NULL, merged->merged_len may not), a host batch or parameters out of range. */
+int kbbq_trim_batch(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p,
+                    const uint32_t *limit /* may be NULL */, const kbbq_trim_merged *merged /* may be NULL */, uint32_t *keep);
 /* Step 4 on device arrays of kept lengths: where exactly one of a[i], b[i] (i < n) is 0 both become 0; with adjacent != 0 the
  * pair is a[2i], a[2i+1] (i < n/2), b is not read and an odd n is KBBQ_EINVAL.  Each read dropped here is counted as
  * with_mate and taken out of reads_kept and bases_kept.  Queued on the engine's stream. */
@@ -375,7 +387,7 @@ int kbbq_trim_ee_bound(double max_ee, uint64_t *bound);
  * (kbbq_correct_batch) the fixes take no part.  Bit 0 of the read's flag picks the adapter: `first` for a first-in-pair read,
  * `second` for a second-in-pair read when one is given (second.len != 0), else `first`.  The result depends on the read, its
  * flag and the parameters alone: not on how the batches were cut, on uniform or ragged batches, on hints or on offcase.
- * Then the trimming rule above runs on the prefix q[0..limit) in place of q[0..n) (kbbq_trim_batch_limited): the cut from the
+ * Then the trimming rule above runs on the prefix q[0..limit) in place of q[0..n) (kbbq_trim_batch's limit): the cut from the
  * new end, the expected errors of the kept prefix, the verdict, the mates.  limit = 0 (an adapter dimer) makes the read too
  * short; reads_in and bases_in still count the input's lengths, and "shortened" still means "kept shorter than it stands in
  * the input", for whichever reason. */
@@ -402,10 +414,6 @@ int kbbq_adapter_parse(const char *text, kbbq_adapter *out);
  * KBBQ_EINVAL for a host batch, for a length or parameter out of range, for an adapter with bits set behind its length or for
  * first.len == 0. */
 int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *device_reads, const kbbq_adapter_params *p, uint32_t *limit);
-/* kbbq_trim_batch on the prefix of min(n, limit[r]) qualities of every read (limit: device, n_reads words; NULL: the whole
- * read, which is kbbq_trim_batch).  The counters count as the rule above says. */
-int kbbq_trim_batch_limited(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p,
-                            const uint32_t *limit, uint32_t *keep);
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset);
 
@@ -439,21 +447,32 @@ typedef struct kbbq_overlap_params {
  * pairs given); overlapping: those with a hit; short_insert: those with L* < max(n1, n2); reads_cut: reads with limit < n;
  * bases_behind: the sum of n - limit. */
 typedef struct kbbq_overlap_counts { uint64_t pairs, overlapping, short_insert, reads_cut, bases_behind, too_long; } kbbq_overlap_counts;
-/* Pair j, j < n_pairs, is read first_a + j * stride of device batch a and read first_b + j * stride of device batch b, which may
- * be the same batch; its limits go to limit_a[j * stride] and limit_b[j * stride] (device).  stride is 1 (two files: a run of
- * pairs that lies in one batch of each) or 2 (interleaved: a == b, first_b = first_a + 1; a pair that straddles two batches
- * is n_pairs = 1).  Queued on the engine's stream.  KBBQ_EINVAL for a null argument, a host batch, another stride, a pair
- * behind either batch's n_reads or a parameter out of range. */
-int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
-                            uint64_t stride, uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b);
+/* One side of a run of pairs, for every kbbq_pair_* call: pair j, j < n_pairs, is read a.first + j * stride of device batch
+ * a.reads and read b.first + j * stride of device batch b.reads, which may be the same batch.  stride is 1 (two files: a run of
+ * pairs that lies in one batch of each) or 2 (interleaved: the same batch on both sides, b.first = a.first + 1; a pair that
+ * straddles two batches is n_pairs = 1).  The other fields are device arrays of the side's batch, and each call says which of
+ * them it reads, which it writes and which it ignores:
+ *   qual                  the batch's written qualities in the batch's base order (n_bases bytes; the array
+ *                         kbbq_recalibrate_batch filled)
+ *   fix_mask, fix_bases   kbbq_correct_batch's arrays for the batch (zeroed, or as that call left them); both NULL: nothing fixed
+ *   limit                 the limit of pair j's read of this side at limit[j * stride]; NULL where the call reads none
+ * An interleaved batch gives both sides the same qual and the same fix arrays.  Every kbbq_pair_* call is KBBQ_EINVAL for a
+ * null side or batch, a host batch, another stride or a pair behind either batch's n_reads. */
+typedef struct kbbq_pair_side {
+    const kbbq_reads *reads;
+    uint64_t first;
+    uint8_t *qual;
+    uint64_t *fix_mask, *fix_bases;
+    uint32_t *limit;
+} kbbq_pair_side;
+/* Writes a->limit and b->limit (both must be set); qual and the fix arrays are ignored.  insert (may be NULL): the call also
+ * hands out the insert length, insert[j] (device, n_pairs words, one per pair whatever the stride) = L* of pair j, or 0 where
+ * the pair has no hit or was not searched (too long) -- the same limits, the same counts.  The limits lose L* once it is larger
+ * than a read; the rule below needs it.  Queued on the engine's stream.  KBBQ_EINVAL also for a parameter out of range. */
+int kbbq_pair_overlap_batch(kbbq_engine *e, const kbbq_pair_side *a, const kbbq_pair_side *b, uint64_t stride, uint64_t n_pairs,
+                            const kbbq_overlap_params *p, uint32_t *insert /* may be NULL */);
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_overlap_counts_get(kbbq_engine *e, kbbq_overlap_counts *out, int32_t reset);
-/* kbbq_pair_overlap_batch -- the same limits, the same counts -- that also hands out the insert length: insert[j] (device,
- * n_pairs words, one per pair whatever the stride) = L* of pair j, or 0 where the pair has no hit or was not searched (too
- * long).  The limits lose L* once it is larger than a read; the rule below needs it. */
-int kbbq_pair_overlap_inserts(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
-                              uint64_t stride, uint64_t n_pairs, const kbbq_overlap_params *p, uint32_t *limit_a, uint32_t *limit_b,
-                              uint32_t *insert);
 
 /* ---- bases corrected from the mate: inside the overlap every base was sequenced twice -------------------------
  * The rule is this project's own (fastp's -c is its model), exact and all integers.  A pair has an insert
@@ -480,18 +499,13 @@ typedef struct kbbq_consensus_params {
  * them that had their N bit; bases_left: bases of a written read that disagree with the mate's and stay (skipped positions are
  * not counted).  A run that writes every read once has the same sums however its calls were cut. */
 typedef struct kbbq_pair_consensus_counts { uint64_t reads_changed, bases_corrected, from_n, bases_left; } kbbq_pair_consensus_counts;
-/* The pairs are kbbq_pair_overlap_batch's (device batches, first_a, first_b, stride, n_pairs); insert: device, n_pairs words,
- * what kbbq_pair_overlap_inserts wrote for these pairs (a value the search cannot have written, such as one of n1 + n2 or more,
- * is taken as 0).  qual_a, qual_b: device, the batches' written qualities in the batches' base order (n_bases bytes; the
- * array kbbq_recalibrate_batch filled), in and out.  fix_mask_*, fix_bases_*: device, kbbq_correct_batch's arrays for the two
- * batches (zeroed, or as that call left them), in and out: bits are OR-ed in.  sides: bit 0: a is written, bit 1: b is
- * written; a side that is not written is only read, and nothing of it is counted.  An interleaved batch: a == b, qual_a ==
- * qual_b, the same fix arrays twice, stride 2.  Queued on the engine's stream.  KBBQ_EINVAL for a null argument, a host
- * batch, another stride, a pair behind either batch's n_reads, qualities out of range or sides outside 1..3. */
-int kbbq_pair_consensus_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
-                              uint64_t stride, uint64_t n_pairs, const uint32_t *insert, const kbbq_consensus_params *params,
-                              uint8_t *qual_a, uint8_t *qual_b, uint64_t *fix_mask_a, uint64_t *fix_bases_a, uint64_t *fix_mask_b,
-                              uint64_t *fix_bases_b, int32_t sides);
+/* The two sides of kbbq_pair_overlap_batch's pairs; insert: device, n_pairs words, what that call wrote for these pairs (a value
+ * the search cannot have written, such as one of n1 + n2 or more, is taken as 0).  Of each side qual, fix_mask and fix_bases
+ * (all must be set) are read and written: bits are OR-ed into the fix arrays; limit is ignored.  sides: bit 0: a is written,
+ * bit 1: b is written; a side that is not written is only read, and nothing of it is counted.  Queued on the engine's stream.
+ * KBBQ_EINVAL also for qualities out of range or sides outside 1..3. */
+int kbbq_pair_consensus_batch(kbbq_engine *e, const kbbq_pair_side *a, const kbbq_pair_side *b, uint64_t stride, uint64_t n_pairs,
+                              const uint32_t *insert, const kbbq_consensus_params *params, int32_t sides);
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_pair_consensus_counts_get(kbbq_engine *e, kbbq_pair_consensus_counts *out, int32_t reset);
 
@@ -525,7 +539,7 @@ int kbbq_pair_consensus_counts_get(kbbq_engine *e, kbbq_pair_consensus_counts *o
  * read are 5' ends, and tail_q is not read: L < max(1, min_length): too short; else has_ee and the sum of EE[Mq[i]] over
  * i < L above ee_bound: over the expected errors; else merged.  Either drop verdict drops the pair from every output.
  * A read of a mergeable pair counts in kbbq_trim_counts.reads_in and bases_in and in no other field of it
- * (kbbq_trim_batch_unmerged): it has no verdict of its own and its mate is not "dropped with its mate".  With this rule
+ * (kbbq_trim_batch's merged): it has no verdict of its own and its mate is not "dropped with its mate".  With this rule
  *     reads_in = reads_kept + too_short + over_ee + with_mate + 2 * (merged + merge.too_short + merge.over_ee). */
 /* Sums since the last reset.  pairs: pairs with L > 0 that were seen; held_back: those of them that are not mergeable; merged,
  * too_short, over_ee: the verdicts of the mergeable ones (pairs = held_back + merged + too_short + over_ee); bases_written: the
@@ -536,11 +550,11 @@ typedef struct kbbq_merge_counts {
 } kbbq_merge_counts;
 /* merged_len[j] of a pair that is mergeable and dropped as a merged read; a merged length is below 2 * KBBQ_OVERLAP_MAX_READ */
 #define KBBQ_MERGE_DROPPED 0x80000000u
-/* The pairs are kbbq_pair_overlap_batch's (device batches, first_a, first_b, stride, n_pairs), but stride 2 only for an
- * interleaved batch with read 1 in front: a and b the same batch and first_b = first_a + 1.  insert: device, n_pairs words, what kbbq_pair_overlap_inserts wrote for these pairs (a value the search cannot
- * have written is taken as 0); limit_a, limit_b: device, the limits at [j * stride] as that call left them; qual_a, qual_b: the
- * batches' written qualities in base order; fix_mask_*, fix_bases_*: the batches' fix arrays, all four set or all four NULL
- * (nothing fixed).  Nothing of these is written.  params: min_length, has_ee and ee_bound are read.
+/* The two sides of kbbq_pair_overlap_batch's pairs, but stride 2 only for an interleaved batch with read 1 in front: the same
+ * batch on both sides and b.first = a.first + 1.  insert: device, n_pairs words, what that call wrote for these pairs (a value
+ * the search cannot have written is taken as 0).  Of each side limit (the limits as that call left them) and qual are read and
+ * must be set; fix_mask and fix_bases are read, all four set or all four NULL (nothing fixed).  Nothing of a side is written.
+ * params: min_length, has_ee and ee_bound are read.
  * merged_len[j] (device, n_pairs words, one per pair whatever the stride) = L for a merged pair, 0 for a pair that is not
  * mergeable (it stays a pair), KBBQ_MERGE_DROPPED for one dropped as a merged read (both mates leave every output).
  * seq_out, qual_out (device, of no particular alignment): pair j's text stands from byte S(j) on, the number of bases of the
@@ -550,26 +564,19 @@ typedef struct kbbq_merge_counts {
  * text it would have had, and no other byte is touched.  Both NULL: the verdicts alone, with the same merged_len and the same
  * counts.  Queued on the engine's stream.  KBBQ_EINVAL as kbbq_pair_consensus_batch gives it, for another use of stride 2, for
  * fix arrays or outputs half set, or for trimming parameters out of range. */
-int kbbq_pair_merge_batch(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
-                          uint64_t stride, uint64_t n_pairs, const uint32_t *insert, const uint32_t *limit_a, const uint32_t *limit_b,
-                          const uint8_t *qual_a, const uint8_t *qual_b, const uint64_t *fix_mask_a, const uint64_t *fix_bases_a,
-                          const uint64_t *fix_mask_b, const uint64_t *fix_bases_b, const kbbq_trim_params *params,
-                          uint32_t *merged_len, uint8_t *seq_out, uint8_t *qual_out);
+int kbbq_pair_merge_batch(kbbq_engine *e, const kbbq_pair_side *a, const kbbq_pair_side *b, uint64_t stride, uint64_t n_pairs,
+                          const uint32_t *insert, const kbbq_trim_params *params, uint32_t *merged_len, uint8_t *seq_out,
+                          uint8_t *qual_out);
 /* Where that call put its text, for kbbq_fastq_reader_write_merged (kbbq_bgzf.h), whose arrays go by the record: for the same
- * pairs and the merged_len the call wrote, rec_len[first_a + j * stride] = the merged length of pair j, 0 where it is not
- * merged, and rec_at[first_a + j * stride] = at0 + S(j) -- at0: where the call's seq_out and qual_out start in the arrays the
- * writer is given.  rec_len (n_reads of a words) and rec_at (as many uint64) are device arrays by the records of a's batch;
- * no other entry is written.  Queued on the engine's stream. */
-int kbbq_pair_merge_places(kbbq_engine *e, const kbbq_reads *a, uint64_t first_a, const kbbq_reads *b, uint64_t first_b,
-                           uint64_t stride, uint64_t n_pairs, const uint32_t *merged_len, uint64_t at0, uint32_t *rec_len, uint64_t *rec_at);
+ * pairs (of the sides the batches and the first reads alone are read; every array of theirs is ignored) and the merged_len the
+ * call wrote, rec_len[a.first + j * stride] = the merged length of pair j, 0 where it is not merged, and
+ * rec_at[a.first + j * stride] = at0 + S(j) -- at0: where the call's seq_out and qual_out start in the arrays the writer is
+ * given.  rec_len (n_reads of a words) and rec_at (as many uint64) are device arrays by the records of a's batch; no other
+ * entry is written.  Queued on the engine's stream. */
+int kbbq_pair_merge_places(kbbq_engine *e, const kbbq_pair_side *a, const kbbq_pair_side *b, uint64_t stride, uint64_t n_pairs,
+                           const uint32_t *merged_len, uint64_t at0, uint32_t *rec_len, uint64_t *rec_at);
 /* Waits; sums since the last reset (kbbq_engine_reset zeroes them too). */
 int kbbq_merge_counts_get(kbbq_engine *e, kbbq_merge_counts *out, int32_t reset);
-/* kbbq_trim_batch_limited (limit may be NULL) that leaves the reads of mergeable pairs out: read r of the batch belongs to
- * pair (first + r) / 2 with adjacent != 0 (interleaved: first is the ordinal of the batch's first record) and to pair
- * first + r with adjacent == 0, and where merged_len[that pair] (device, kbbq_pair_merge_batch's words by the pair's ordinal)
- * is not 0 the read counts in reads_in and bases_in alone and keep[r] = 0.  Every other read: as kbbq_trim_batch_limited. */
-int kbbq_trim_batch_unmerged(kbbq_engine *e, const kbbq_reads *device_reads, const uint8_t *device_qual, const kbbq_trim_params *p,
-                             const uint32_t *limit, const uint32_t *merged_len, uint64_t first, int32_t adjacent, uint32_t *keep);
 
 /* Dense covariate histograms, {errors,total} pairs of u64 (KBBQ_NQ = 256 quality rows):
  *   rg    [n_rg][2]                 q     [n_rg][256][2]

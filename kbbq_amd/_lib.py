@@ -91,6 +91,14 @@ class TrimParams(ctypes.Structure):
     _fields_ = [("tail_q", ctypes.c_int32), ("has_ee", ctypes.c_int32), ("min_length", c_u64), ("ee_bound", c_u64)]
 
 
+class TrimMerged(ctypes.Structure):
+    _fields_ = [("merged_len", c_vp), ("first", c_u64), ("adjacent", ctypes.c_int32)]
+
+
+class PairSide(ctypes.Structure):
+    _fields_ = [("reads", ctypes.POINTER(Reads)), ("first", c_u64), ("qual", c_vp), ("fix_mask", c_vp), ("fix_bases", c_vp), ("limit", c_vp)]
+
+
 class TrimCounts(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("reads_in", "bases_in", "shortened", "too_short", "over_ee", "reads_kept", "bases_kept", "with_mate")]
 
@@ -142,6 +150,8 @@ class ProfileEntry(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("launches", c_u64), ("total_ms", ctypes.c_double)]
 
 
+# what every kbbq_pair_* call starts with: the engine, the two sides, stride, n_pairs
+_PAIRS = [c_vp, ctypes.POINTER(PairSide), ctypes.POINTER(PairSide), c_u64, c_u64]
 # every symbol include/kbbq_engine.h declares: (restype, argtypes)
 SYMBOLS = {
     "kbbq_engine_create": (ctypes.c_int, [ctypes.POINTER(Params), ctypes.POINTER(c_vp)]),
@@ -178,28 +188,21 @@ SYMBOLS = {
     "kbbq_fixed_errors_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_vp]),
     "kbbq_correct_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, c_vp, c_vp]),
     "kbbq_correct_counts": (ctypes.c_int, [c_vp, ctypes.POINTER(FixCounts), ctypes.c_int32]),
-    "kbbq_trim_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp]),
+    "kbbq_trim_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp, ctypes.POINTER(TrimMerged), c_vp]),
     "kbbq_trim_mates": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u64, ctypes.c_int32]),
     "kbbq_trim_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(TrimCounts), ctypes.c_int32]),
     "kbbq_trim_ee_table": (ctypes.c_int, [c_u64p]),
     "kbbq_trim_ee_bound": (ctypes.c_int, [ctypes.c_double, c_u64p]),
     "kbbq_adapter_parse": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(Adapter)]),
     "kbbq_adapter_find_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), ctypes.POINTER(AdapterParams), c_vp]),
-    "kbbq_trim_batch_limited": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp]),
     "kbbq_adapter_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(AdapterCounts), ctypes.c_int32]),
-    "kbbq_pair_overlap_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64,
-                                               ctypes.POINTER(OverlapParams), c_vp, c_vp]),
+    "kbbq_pair_overlap_batch": (ctypes.c_int, _PAIRS + [ctypes.POINTER(OverlapParams), c_vp]),
     "kbbq_overlap_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(OverlapCounts), ctypes.c_int32]),
-    "kbbq_pair_overlap_inserts": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64,
-                                                 ctypes.POINTER(OverlapParams), c_vp, c_vp, c_vp]),
-    "kbbq_pair_consensus_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp,
-                                                 ctypes.POINTER(ConsensusParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int32]),
+    "kbbq_pair_consensus_batch": (ctypes.c_int, _PAIRS + [c_vp, ctypes.POINTER(ConsensusParams), ctypes.c_int32]),
     "kbbq_pair_consensus_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(ConsensusCounts), ctypes.c_int32]),
-    "kbbq_pair_merge_batch": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                             c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp, c_vp]),
-    "kbbq_pair_merge_places": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_u64, ctypes.POINTER(Reads), c_u64, c_u64, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "kbbq_pair_merge_batch": (ctypes.c_int, _PAIRS + [c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp, c_vp]),
+    "kbbq_pair_merge_places": (ctypes.c_int, _PAIRS + [c_vp, c_u64, c_vp, c_vp]),
     "kbbq_merge_counts_get": (ctypes.c_int, [c_vp, ctypes.POINTER(MergeCounts), ctypes.c_int32]),
-    "kbbq_trim_batch_unmerged": (ctypes.c_int, [c_vp, ctypes.POINTER(Reads), c_vp, ctypes.POINTER(TrimParams), c_vp, c_vp, c_u64, ctypes.c_int32, c_vp]),
     "kbbq_covariates_get": (ctypes.c_int, [c_vp, ctypes.POINTER(Covariates)]),
     "kbbq_covariates_device": (c_vp, [c_vp, c_u64p]),
     "kbbq_train": (ctypes.c_int, [c_vp]),

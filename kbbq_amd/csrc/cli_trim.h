@@ -11,7 +11,7 @@
 //
 // --adapter: the verdicts of a batch start with the search for the 3' adapter in its packed bases (kbbq_adapter_find_batch), into
 // a scratch array of one limit per read of the batch, and the rule then runs in front of those limits
-// (kbbq_trim_batch_limited).  The search is part of batch(), so a paired run's pre-pass makes it and pass 4 does not repeat it:
+// (kbbq_trim_batch's limit).  The search is part of batch(), so a paired run's pre-pass makes it and pass 4 does not repeat it:
 // once per read either way.  The limits depend on the packed batch alone -- with --correct the fixes take no part.
 //
 // One array of kept lengths per input file, indexed by the record's ordinal in its file: 4 bytes a read.  The two files'
@@ -36,7 +36,7 @@
 // --merged-out (with --pair-overlap): a pair whose mates overlap and whose reads no search cut in front of the insert becomes one
 // read (kbbq_pair_merge_batch).  A merging run always takes the run loop, with or without --pair-correct: per run the consensus if
 // on, then the verdict-only merge call into an array of 4 bytes a pair by the pair's ordinal, and a batch's own verdicts -- which
-// leave the reads of mergeable pairs out (kbbq_trim_batch_unmerged) -- when its last run is done.  While the first file's batches (or
+// leave the reads of mergeable pairs out (kbbq_trim_batch's merged) -- when its last run is done.  While the first file's batches (or
 // the interleaved ones) are written, each run with a first mate in the batch in hand gets the full call: its mates' batch stands
 // recalibrated, fixed and -- two-sided here: the rule is exact in place -- corrected in slot 0, the merged text goes to an array of
 // two bytes per base of the run's pairs, and one writer call per chunk hands it to a third BGZF writer under the first mates'
@@ -163,11 +163,9 @@ struct TrimRun {
         p.merge = adapter.first.len ? 1 : 0;      // (without --adapter the arrays hold nothing yet)
         const int fb = walk.fb;
         for (const PairRun &r : walk.runs) {
-            uint32_t *limit_a = limits(0, at[0][r.ia] + r.first_a), *limit_b = limits(fb, at[fb][r.ib] + r.first_b);
-            const int rc = insert.p ? kbbq_pair_overlap_inserts(e, of[0][r.ia], r.first_a, of[fb][r.ib], r.first_b, r.stride, r.n_pairs, &p, limit_a, limit_b,
-                                                                    insert.as<uint32_t>() + r.pair)
-                                        : kbbq_pair_overlap_batch(e, of[0][r.ia], r.first_a, of[fb][r.ib], r.first_b, r.stride, r.n_pairs, &p, limit_a, limit_b);
-            if (rc < 0) return fail_engine("searching the pairs' overlaps");
+            const Side a = side(r, 0, nullptr, nullptr, nullptr), b = side(r, 1, nullptr, nullptr, nullptr);
+            if (kbbq_pair_overlap_batch(e, &a, &b, r.stride, r.n_pairs, &p, insert.p ? insert.as<uint32_t>() + r.pair : nullptr) < 0)
+                return fail_engine("searching the pairs' overlaps");
         }
         // --merged-out: how many bases the pairs of every run have, which is where the next run's merged text starts (the batches'
         // offsets are in device memory: four words a run)
@@ -191,31 +189,30 @@ struct TrimRun {
                 return give_up(" Error: --adapter: the limits of a batch of " + std::to_string(d.n_reads) + " reads (4 bytes each) do not fit in GPU memory.");
             if (kbbq_adapter_find_batch(e, &d, &adapter, limit.as<uint32_t>()) < 0) return fail_engine("searching the adapters");
         }
-        if (kbbq_trim_batch_limited(e, &d, q, &params, adapter.first.len ? limit.as<uint32_t>() : nullptr, kept(f, ordinal)) < 0) return fail_engine("trimming");
+        if (kbbq_trim_batch(e, &d, q, &params, adapter.first.len ? limit.as<uint32_t>() : nullptr, nullptr, kept(f, ordinal)) < 0) return fail_engine("trimming");
         return 0;
     }
-    // One side of a run as --pair-correct's rule takes it: a batch, where the run starts in it, and its written qualities and fix arrays
-    struct Side {
-        const kbbq_reads *d;
-        uint64_t first;
-        uint8_t *q;
-        uint64_t *mask, *bases;
-    };
-    Side side(const kbbq_reads *d, uint64_t first, const MateSlot &s) const { return Side{d, first, s.qual(), s.mask, s.bases}; }
+    // One side of a run as the kbbq_pair_* calls take it: the batch, where the run starts in it, the batch's written qualities and
+    // fix arrays wherever they stand, and the limits of the run's reads in file_limit[]
+    typedef kbbq_pair_side Side;
+    // the run's side a (b == 0) or b (b == 1)
+    Side side(const PairRun &r, int b, uint8_t *q, uint64_t *mask, uint64_t *bases) const {
+        const int f = b ? walk.fb : 0;
+        const size_t i = b ? r.ib : r.ia;
+        const uint64_t first = b ? r.first_b : r.first_a;
+        return Side{of[f][i], first, q, mask, bases, limits(f, at[f][i] + first)};
+    }
+    Side side(const PairRun &r, int b, const MateSlot &s) const { return side(r, b, s.qual(), s.mask, s.bases); }
     // --pair-correct: the rule on the pairs of run r between sides a and b; sides as kbbq_pair_consensus_batch's
     int correct_pairs(const PairRun &r, const Side &a, const Side &b, int sides) {
-        if (kbbq_pair_consensus_batch(e, a.d, a.first, b.d, b.first, r.stride, r.n_pairs, insert.as<uint32_t>() + r.pair, &consensus, a.q, b.q, a.mask, a.bases,
-                                      b.mask, b.bases, sides) < 0)
+        if (kbbq_pair_consensus_batch(e, &a, &b, r.stride, r.n_pairs, insert.as<uint32_t>() + r.pair, &consensus, sides) < 0)
             return fail_engine("correcting from the mates");
         return 0;
     }
-    // --merged-out: the merge of the pairs of run r between sides a and b, into `merged` at the pairs' ordinals; seq, qual: where the
-    // run's text goes, or both null for the verdicts alone
+    // --merged-out: the merge of the pairs of run r between its sides a and b, into `merged` at the pairs' ordinals; seq, qual: where
+    // the run's text goes, or both null for the verdicts alone
     int merge_pairs(const PairRun &r, const Side &a, const Side &b, uint8_t *seq, uint8_t *qual) {
-        const int fb = walk.fb;
-        if (kbbq_pair_merge_batch(e, a.d, a.first, b.d, b.first, r.stride, r.n_pairs, insert.as<uint32_t>() + r.pair, limits(0, at[0][r.ia] + r.first_a),
-                                  limits(fb, at[fb][r.ib] + r.first_b), a.q, b.q, a.mask, a.bases, b.mask, b.bases, &params, merged.as<uint32_t>() + r.pair, seq,
-                                  qual) < 0)
+        if (kbbq_pair_merge_batch(e, &a, &b, r.stride, r.n_pairs, insert.as<uint32_t>() + r.pair, &params, merged.as<uint32_t>() + r.pair, seq, qual) < 0)
             return fail_engine("merging the pairs");
         return 0;
     }
@@ -233,10 +230,8 @@ struct TrimRun {
         auto verdicts_after = [&](size_t k, int f, size_t i, const MateSlot &s) {
             if (walk.touch[f][i].end != k + 1) return 0;
             // (--merged-out: the reads of mergeable pairs are left out; every run with a read of the batch has written its pairs' words)
-            const int rc = merge_on ? kbbq_trim_batch_unmerged(e, of[f][i], s.qual(), &params, limits(f, at[f][i]), merged.as<uint32_t>(), at[f][i], fb ? 0 : 1,
-                                                               kept(f, at[f][i]))
-                                    : kbbq_trim_batch_limited(e, of[f][i], s.qual(), &params, limits(f, at[f][i]), kept(f, at[f][i]));
-            if (rc < 0) return fail_engine("trimming");
+            const kbbq_trim_merged m = {merged.as<uint32_t>(), at[f][i], fb ? 0 : 1};
+            if (kbbq_trim_batch(e, of[f][i], s.qual(), &params, limits(f, at[f][i]), merge_on ? &m : nullptr, kept(f, at[f][i])) < 0) return fail_engine("trimming");
             return 0;
         };
         for (size_t k = 0; k < walk.runs.size(); ++k) {
@@ -244,7 +239,7 @@ struct TrimRun {
             MateSlot &sa = slot[fb ? 0 : r.ia & 1], &sb = slot[fb ? 1 : r.ib & 1];      // (one slot twice for a run inside an interleaved batch)
             if (const int rc = hold(sa, 0, r.ia)) return rc;
             if (const int rc = hold(sb, fb, r.ib)) return rc;
-            const Side a = side(of[0][r.ia], r.first_a, sa), b = side(of[fb][r.ib], r.first_b, sb);
+            const Side a = side(r, 0, sa), b = side(r, 1, sb);
             if (consensus_on)
                 if (const int rc = correct_pairs(r, a, b, 3)) return rc;
             if (merge_on)
@@ -291,8 +286,7 @@ struct TrimRun {
         auto merge_run = [&](size_t k, const Side &a, const Side &b) {
             const PairRun &r = walk.runs[k];
             if (const int rc = merge_pairs(r, a, b, merged_seq + at0, merged_qual + at0)) return rc;
-            if (kbbq_pair_merge_places(e, a.d, a.first, b.d, b.first, r.stride, r.n_pairs, merged.as<uint32_t>() + r.pair, at0, rec_len.as<uint32_t>(),
-                                       rec_at.as<uint64_t>()) < 0)
+            if (kbbq_pair_merge_places(e, &a, &b, r.stride, r.n_pairs, merged.as<uint32_t>() + r.pair, at0, rec_len.as<uint32_t>(), rec_at.as<uint64_t>()) < 0)
                 return fail_engine("merging the pairs");
             at0 += run_bases[k];
             return 0;
@@ -302,7 +296,7 @@ struct TrimRun {
                 const PairRun &r = walk.runs[k];
                 if ((!fb && r.ia == r.ib) != (in_place != 0)) continue;
                 if (in_place) {
-                    const Side a{&d, r.first_a, q, mask, bases}, b{&d, r.first_b, q, mask, bases};
+                    const Side a = side(r, 0, q, mask, bases), b = side(r, 1, q, mask, bases);
                     if (consensus_on)
                         if (const int rc = correct_pairs(r, a, b, 3)) return rc;
                     if (merging)
@@ -318,7 +312,7 @@ struct TrimRun {
                     if (const int rc = hold(s, f, m)) return rc;
                     if (report_on && kbbq_report_enable(e, 1) < 0) return fail_engine("correcting from the mates");
                 }
-                const Side mine{&d, mine_a ? r.first_a : r.first_b, q, mask, bases}, theirs = side(of[f][m], mine_a ? r.first_b : r.first_a, s);
+                const Side mine = side(r, mine_a ? 0 : 1, q, mask, bases), theirs = side(r, mine_a ? 1 : 0, s);      // (mine: batch d's)
                 // (a merging run corrects the slot too: the merge reads both sides as they are written)
                 if (consensus_on)
                     if (const int rc = correct_pairs(r, mine, theirs, merging && mine_a ? 3 : 1)) return rc;
@@ -345,7 +339,7 @@ struct TrimRun {
                 if (!overlap_on) {
                     if (const int rc = batch(f, ordinal[f], batches[bi], q)) return rc;
                 } else if (batches[bi].n_reads) {      // (the limits are there already)
-                    if (kbbq_trim_batch_limited(e, &batches[bi], q, &params, limits(f, ordinal[f]), kept(f, ordinal[f])) < 0) return fail_engine("trimming");
+                    if (kbbq_trim_batch(e, &batches[bi], q, &params, limits(f, ordinal[f]), nullptr, kept(f, ordinal[f])) < 0) return fail_engine("trimming");
                 }
                 ordinal[f] += batches[bi].n_reads;
             }

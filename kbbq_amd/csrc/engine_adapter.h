@@ -1,6 +1,6 @@
 // engine_adapter.h -- 3' adapter removal (include/kbbq_engine.h: kbbq_adapter_find_batch, kbbq_adapter_counts_get): the launch of
 // adapter.h's kernel and the counters.  Part of engine.hip; behind engine_trim.h, so that every kernel before it keeps its
-// place in the code object.  (kbbq_adapter_parse is host_adapter.cc's; the cut from the new end is kbbq_trim_batch_limited.)
+// place in the code object.  (kbbq_adapter_parse is host_adapter.cc's; the cut from the new end is kbbq_trim_batch with a limit.)
 #pragma once
 
 namespace {
@@ -47,14 +47,6 @@ int kbbq_adapter_find_batch(kbbq_engine *e, const kbbq_reads *reads, const kbbq_
     return KBBQ_OK;
 }
 
-int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset) {
-    ENGINE_DEVICE(e);
-    if (!out) return fail(KBBQ_EINVAL, "null argument");
-    unsigned long long c[ADAPTER_COUNTS] = {};
-    if (const int rc = e->adapter.read(e, c, reset)) return rc;
-    out->reads = c[ADAPTER_READS]; out->found_first = c[ADAPTER_FOUND_FIRST]; out->found_second = c[ADAPTER_FOUND_SECOND];
-    out->full = c[ADAPTER_FULL]; out->partial = c[ADAPTER_PARTIAL]; out->bases_behind = c[ADAPTER_BASES_BEHIND];
-    return KBBQ_OK;
-}
+int kbbq_adapter_counts_get(kbbq_engine *e, kbbq_adapter_counts *out, int32_t reset) { return counts_get<ADAPTER_COUNTS>(e, &kbbq_engine::adapter, out, reset); }
 
 }  // extern "C"

@@ -523,6 +523,19 @@ typedef KbbqDeviceGuard DeviceGuard;
     if (engine_device_guard.err != hipSuccess)                                                        \
         return fail(KBBQ_EIO, "hipSetDevice(%d): %s", (e)->p.device, hipGetErrorString(engine_device_guard.err))
 
+// A *_counts_get call: the N words of one of the engine's blocks into the caller's struct, whose uint64_t fields are the words
+// of the block's enum in its order
+template <int N, typename Counts>
+int counts_get(kbbq_engine *e, CounterBlock kbbq_engine::*block, Counts *out, int32_t reset) {
+    static_assert(sizeof(Counts) == N * 8, "the struct has one uint64_t field per word of the enum");
+    ENGINE_DEVICE(e);
+    if (!out) return fail(KBBQ_EINVAL, "null argument");
+    unsigned long long c[N] = {};
+    if (const int rc = (e->*block).read(e, c, reset)) return rc;
+    memcpy(out, c, sizeof c);
+    return KBBQ_OK;
+}
+
 }  // namespace
 
 extern "C" {

@@ -1,5 +1,5 @@
 // merge.h -- the kernels of merging an overlapping pair into one read (include/kbbq_engine.h: kbbq_pair_merge_batch,
-// kbbq_trim_batch_unmerged): from the two mates as pass 4 is about to write them to the one read over the whole insert, its
+// kbbq_trim_batch's merged): from the two mates as pass 4 is about to write them to the one read over the whole insert, its
 // verdict, and the trimming verdicts of a batch that leave the reads of such pairs out.
 //
 // The rule (include/kbbq_engine.h): with the pair's insert length L > 0 and neither limit in front of the

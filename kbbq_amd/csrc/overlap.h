@@ -90,7 +90,7 @@ __device__ __forceinline__ OverlapStreams overlap_streams(const ReadsDev &RA, co
 // read 1 against those from base max(0, n2 - L) of rc2, 32 bases a step, by XOR and popcount over windows cut out of the two
 // streams by __shfl (adapter_window).  The winner is the wave-wide maximum of o * 2048 + L over the hits.  The counters are kept
 // per wavefront, added up per workgroup in LDS and added to the engine's once per workgroup.
-// insert (may be null): one word per pair, L* of the winner or 0 (kbbq_pair_overlap_inserts).
+// insert (may be null): one word per pair, L* of the winner or 0 (kbbq_pair_overlap_batch's insert).
 __global__ void __launch_bounds__(256) k_pair_overlap(ReadsDev RA, ReadsDev RB, OverlapDev P, uint32_t *limit_a, uint32_t *limit_b, uint32_t *insert,
                                                       unsigned long long *counts) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

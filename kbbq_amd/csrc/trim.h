@@ -56,7 +56,7 @@ __device__ __forceinline__ bool trim_round(int d, bool valid, int first_i, int l
 
 // One wavefront per read, four per workgroup.  Sums stay below 2^31: |Q - q| <= 255 and a read has fewer than 2^23 bases.
 // The counters are kept per wavefront, added up per workgroup in LDS and added to the engine's once per workgroup.
-// limit (optional): the rule runs on the read's first min(len, limit[r]) qualities (kbbq_trim_batch_limited: the end a 3'
+// limit (optional): the rule runs on the read's first min(len, limit[r]) qualities (kbbq_trim_batch's limit: the end a 3'
 // adapter search found); the read still counts with its own length, and as shortened when less than that is kept.
 __global__ void __launch_bounds__(256) k_trim_reads(ReadsDev R, const uint8_t *qual, TrimDev P, const unsigned long long *ee_table,
                                                     const uint32_t *limit, uint32_t *keep, unsigned long long *counts) {
@@ -129,6 +129,11 @@ __global__ void __launch_bounds__(256) k_trim_reads(ReadsDev R, const uint8_t *q
     }
     add_wave_counts(cnt, counts);
 }
+
+// k_trim_reads that leaves the reads of merged pairs out (kbbq_trim_batch's merged).  Declared here for the one launch site,
+// engine_trim.h; defined in merge.h, behind k_pair_merge, where it keeps its place in the code object.
+__global__ void k_trim_unmerged(ReadsDev R, const uint8_t *qual, TrimDev P, const unsigned long long *ee_table, const uint32_t *limit, const uint32_t *merged,
+                                uint64_t first, int shift, uint32_t *keep, unsigned long long *counts);
 
 // The mate rule: pair i is (a[i], b[i]), or (a[2i], a[2i+1]) with `adjacent` (b is not read).  Where exactly one of the two
 // is 0 the other becomes 0: that read is counted as dropped with its mate and leaves the kept counters, once per workgroup.

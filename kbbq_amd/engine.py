@@ -278,57 +278,130 @@ class Engine:
         _lib.check(fn(self.h, ctypes.byref(c), 1 if reset else 0))
         return {n: int(getattr(c, n)) for n, _ in Struct._fields_}
 
+    # ---- what the calls below share: host arrays to device tensors and back, the call between them
+    def _words(self, given, n, step=1, fill=0, what="one value each"):
+        """n uint32 values -- `given`, or `fill` n times for None -- as a device tensor with value j at [j * step]; never empty."""
+        import torch
+        host = np.full((n - 1) * step + 1 if n else 1, fill, np.uint32)
+        if given is not None:
+            g = np.ascontiguousarray(given, dtype=np.uint32)
+            assert len(g) == n, what
+            host[::step][:n] = g
+        return torch.from_numpy(host.view(np.int32)).to("cuda:%d" % self.params.device)
+
+    @staticmethod
+    def _back(d, n, step=1):
+        """_words' tensor as the call left it: the n values as a NumPy uint32 array."""
+        return d.cpu().numpy().view(np.uint32)[::step][:n].copy()
+
+    def _run(self, fn, *args):
+        """fn(engine, *args) on tensors torch has made -- the engine's stream does not wait for torch's, so torch finishes
+        first -- and the wait for the kernel."""
+        import torch
+        torch.cuda.synchronize("cuda:%d" % self.params.device)
+        _lib.check(fn(self.h, *args))
+        self.sync()
+
+    @staticmethod
+    def _ptr(t, shift=0):
+        return None if t is None else t.data_ptr() + int(shift)
+
+    @staticmethod
+    def _trim_params(tail_q, min_length, max_ee):
+        p = _lib.TrimParams()
+        p.tail_q = 0 if tail_q is None else int(tail_q)
+        p.min_length = int(min_length)
+        p.has_ee = 0 if max_ee is None else 1
+        p.ee_bound = 0 if max_ee is None else ee_bound(max_ee)
+        return p
+
+    def _trim(self, dreads, qual_ptr, p, limit, merged=None):
+        d_keep = self._words(None, dreads.n_reads)
+        d_limit = None if limit is None else self._words(limit, dreads.n_reads, what="limit: one length per read")
+        self._run(self.L.kbbq_trim_batch, self._c(dreads), qual_ptr, ctypes.byref(p), self._ptr(d_limit), merged, d_keep.data_ptr())
+        return self._back(d_keep, dreads.n_reads)
+
     # ---- trimming and filtering by the qualities pass 4 wrote
     def trim_reads(self, dreads, qual_ptr, tail_q=None, min_length=1, max_ee=None, limit=None):
         """kbbq_trim_batch on a device batch (DeviceReads) and the device array of its written qualities: the kept length of
         every read, 0 for a dropped one, as a NumPy uint32 array.  tail_q: the 3' cut's threshold (None: no cut); max_ee:
         the most expected errors a kept read may carry (None: no bound); limit: one length per read (find_adapters'
-        result), the rule then runs on that prefix of the read (kbbq_trim_batch_limited).  Waits for the kernel."""
-        import torch
-        p = _lib.TrimParams()
-        p.tail_q = 0 if tail_q is None else int(tail_q)
+        result), the rule then runs on that prefix of the read.  Waits for the kernel."""
         if tail_q is not None and not 1 <= int(tail_q) <= MAXQ:
             raise _lib.KbbqError(-22, "tail_q must be in 1..%d" % MAXQ)
-        p.min_length = int(min_length)
-        p.has_ee = 0 if max_ee is None else 1
-        p.ee_bound = 0 if max_ee is None else ee_bound(max_ee)
-        dev = "cuda:%d" % self.params.device
-        d_keep = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
-        d_limit = None
-        if limit is not None:
-            lim = np.ascontiguousarray(limit, dtype=np.uint32)
-            assert len(lim) == dreads.n_reads, "limit: one length per read"
-            d_limit = torch.from_numpy(lim.view(np.int32).copy()).to(dev)
-        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        if d_limit is None:
-            _lib.check(self.L.kbbq_trim_batch(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), d_keep.data_ptr()))
-        else:
-            _lib.check(self.L.kbbq_trim_batch_limited(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), d_limit.data_ptr(), d_keep.data_ptr()))
-        self.sync()
-        return d_keep.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
+        return self._trim(dreads, qual_ptr, self._trim_params(tail_q, min_length, max_ee), limit)
+
+    def trim_unmerged(self, dreads, qual_ptr, merged_len, first=0, adjacent=False, tail_q=None, min_length=1, max_ee=None, limit=None):
+        """kbbq_trim_batch with `merged`: trim_reads that leaves out the reads of the pairs whose merged_len word (pair_merge's,
+        by the pair's ordinal; read r is of pair first + r, or (first + r) // 2 with adjacent) is not 0.  Waits for the kernel."""
+        d_merged = self._words(merged_len, len(merged_len))
+        merged = _lib.TrimMerged(d_merged.data_ptr(), int(first), 1 if adjacent else 0)
+        return self._trim(dreads, qual_ptr, self._trim_params(tail_q, min_length, max_ee), limit, merged)
+
+    def trim_mates(self, keep_a, keep_b=None, adjacent=False):
+        """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
+        (a, b), or a alone with adjacent=True, where the pairs are a[2i], a[2i+1].  Waits for the kernel."""
+        n = len(keep_a)
+        assert adjacent or len(keep_b) == n, "two files of a pair hold equally many reads"
+        d_a = self._words(keep_a, n)
+        d_b = None if adjacent else self._words(keep_b, n)
+        self._run(self.L.kbbq_trim_mates, d_a.data_ptr(), self._ptr(d_b), n, 1 if adjacent else 0)
+        return self._back(d_a, n) if adjacent else (self._back(d_a, n), self._back(d_b, n))
+
+    def trim_counts(self, reset=False):
+        """What trim_reads and trim_mates did since the last reset (waits): the fields of kbbq_trim_counts."""
+        return self._counts(self.L.kbbq_trim_counts_get, _lib.TrimCounts, reset)
 
     # ---- 3' adapters: where each read runs on into the adapter
     def find_adapters(self, dreads, first, second=None, min_overlap=5, max_error_permille=100):
         """kbbq_adapter_find_batch on a device batch (DeviceReads): the limit of every read -- the start of the leftmost
         match of its adapter, or its length -- as a NumPy uint32 array.  first, second: text (parse_adapter) or an
         _lib.Adapter; second-in-pair reads are searched for `second` when one is given.  Waits for the kernel."""
-        import torch
         p = _lib.AdapterParams()
         p.first = first if isinstance(first, _lib.Adapter) else parse_adapter(first)
         if second is not None:
             p.second = second if isinstance(second, _lib.Adapter) else parse_adapter(second)
         p.min_overlap = int(min_overlap)
         p.max_error_permille = int(max_error_permille)
-        dev = "cuda:%d" % self.params.device
-        d_limit = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        _lib.check(self.L.kbbq_adapter_find_batch(self.h, self._c(dreads), ctypes.byref(p), d_limit.data_ptr()))
-        self.sync()
-        return d_limit.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
+        d_limit = self._words(None, dreads.n_reads)
+        self._run(self.L.kbbq_adapter_find_batch, self._c(dreads), ctypes.byref(p), d_limit.data_ptr())
+        return self._back(d_limit, dreads.n_reads)
 
     def adapter_counts(self, reset=False):
         """What find_adapters did since the last reset (waits): the fields of kbbq_adapter_counts."""
         return self._counts(self.L.kbbq_adapter_counts_get, _lib.AdapterCounts, reset)
+
+    # ---- the pair calls: pair j is read first_a + j * stride of dev_a and read first_b + j * stride of dev_b
+    @staticmethod
+    def _pairs(dev_a, dev_b, first_a, first_b, stride, n_pairs):
+        """(stride, n_pairs, step): n_pairs None for as many as both batches hold from the first reads on; step: how far pair
+        j + 1's word stands behind pair j's in an array by the read (a limit)."""
+        stride = int(stride)
+        step = max(stride, 1)
+        if n_pairs is None:
+            n_pairs = max(0, min((dev_a.n_reads - first_a + step - 1) // step, (dev_b.n_reads - first_b + step - 1) // step))
+        return stride, int(n_pairs), step
+
+    def _side(self, dreads, qual, fix, with_fix=True):
+        """The arrays of one side's batch on the device: [qual, fix_mask, fix_bases] -- host qualities in base order, and `fix`
+        None for zeroed fix arrays or the (fix_mask, fix_bases) words of correct_bases; with_fix False: no fix arrays, None twice."""
+        import torch
+        dev = "cuda:%d" % self.params.device
+        nb = dreads.n_bases
+        q = np.ascontiguousarray(qual, dtype=np.uint8)
+        assert len(q) == nb, "one quality per base of the batch"
+        out = [torch.from_numpy(np.concatenate([q, np.zeros(1, np.uint8)])).to(dev)]
+        for given, n in zip(fix if fix is not None else (None, None), (nb // 64 + 2, nb // 32 + 2)):
+            w = np.zeros(n, np.uint64)
+            if given is not None:
+                g = np.ascontiguousarray(given, dtype=np.uint64)
+                assert len(g) <= n, "fix arrays: at most n_bases/64+2 and n_bases/32+2 words"
+                w[:len(g)] = g
+            out.append(torch.from_numpy(w.view(np.int64)).to(dev) if with_fix else None)
+        return out
+
+    def _pair_side(self, dreads, first, arrays=(None, None, None), limit=None):
+        return _lib.PairSide(ctypes.pointer(dreads.c), int(first), *[self._ptr(t) for t in tuple(arrays) + (limit,)])
 
     # ---- adapters from the overlap of a pair: where both mates run off the insert
     def find_pair_overlaps(self, dev_a, dev_b, first_a=0, first_b=0, stride=1, n_pairs=None, min_overlap=30, max_diff=5, max_error_permille=200,
@@ -343,44 +416,20 @@ class Engine:
 
     def find_pair_inserts(self, dev_a, dev_b, first_a=0, first_b=0, stride=1, n_pairs=None, min_overlap=30, max_diff=5, max_error_permille=200,
                           limit_a=None, limit_b=None):
-        """kbbq_pair_overlap_inserts: find_pair_overlaps' two arrays of limits and, third, the insert length of every pair as a
-        NumPy uint32 array of n_pairs entries -- 0 where the pair has no hit or was not searched.  Waits for the kernel."""
+        """kbbq_pair_overlap_batch with `insert`: find_pair_overlaps' two arrays of limits and, third, the insert length of every
+        pair as a NumPy uint32 array of n_pairs entries -- 0 where the pair has no hit or was not searched.  Waits for the kernel."""
         return self._pair_overlaps(True, dev_a, dev_b, first_a, first_b, stride, n_pairs, min_overlap, max_diff, max_error_permille, limit_a, limit_b)
 
-    @staticmethod
-    def _pairs_from(dev_a, dev_b, first_a, first_b, stride):
-        step = stride if stride > 0 else 1
-        return max(0, min((dev_a.n_reads - first_a + step - 1) // step, (dev_b.n_reads - first_b + step - 1) // step))
-
     def _pair_overlaps(self, want_insert, dev_a, dev_b, first_a, first_b, stride, n_pairs, min_overlap, max_diff, max_error_permille, limit_a, limit_b):
-        import torch
-        stride = int(stride)
-        if n_pairs is None:
-            n_pairs = self._pairs_from(dev_a, dev_b, first_a, first_b, stride)
-        n_pairs = int(n_pairs)
+        stride, n_pairs, step = self._pairs(dev_a, dev_b, first_a, first_b, stride, n_pairs)
         assert (limit_a is None) == (limit_b is None), "limit_a and limit_b: both or neither"
         p = _lib.OverlapParams(int(min_overlap), int(max_diff), int(max_error_permille), 0 if limit_a is None else 1)
-        dev = "cuda:%d" % self.params.device
-        words = max(1, (n_pairs - 1) * max(stride, 1) + 1) if n_pairs else 1
-        d_lim = []
-        for given in (limit_a, limit_b):
-            host = np.zeros(words, np.uint32)
-            if given is not None:
-                lim = np.ascontiguousarray(given, dtype=np.uint32)
-                assert len(lim) == n_pairs, "limit_a, limit_b: one length per pair"
-                host[::max(stride, 1)][:n_pairs] = lim
-            d_lim.append(torch.from_numpy(host.view(np.int32)).to(dev))
-        d_insert = torch.zeros(max(1, n_pairs), dtype=torch.int32, device=dev) if want_insert else None
-        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        if want_insert:
-            _lib.check(self.L.kbbq_pair_overlap_inserts(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, ctypes.byref(p),
-                                                        d_lim[0].data_ptr(), d_lim[1].data_ptr(), d_insert.data_ptr()))
-        else:
-            _lib.check(self.L.kbbq_pair_overlap_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, ctypes.byref(p),
-                                                      d_lim[0].data_ptr(), d_lim[1].data_ptr()))
-        self.sync()
-        out = tuple(d.cpu().numpy().view(np.uint32)[::max(stride, 1)][:n_pairs].copy() for d in d_lim)
-        return out + (d_insert.cpu().numpy().view(np.uint32)[:n_pairs].copy(),) if want_insert else out
+        d_lim = [self._words(given, n_pairs, step, what="limit_a, limit_b: one length per pair") for given in (limit_a, limit_b)]
+        d_insert = self._words(None, n_pairs) if want_insert else None
+        a, b = self._pair_side(dev_a, first_a, limit=d_lim[0]), self._pair_side(dev_b, first_b, limit=d_lim[1])
+        self._run(self.L.kbbq_pair_overlap_batch, a, b, stride, n_pairs, ctypes.byref(p), self._ptr(d_insert))
+        out = tuple(self._back(d, n_pairs, step) for d in d_lim)
+        return out + (self._back(d_insert, n_pairs),) if want_insert else out
 
     def overlap_counts(self, reset=False):
         """What find_pair_overlaps did since the last reset (waits): the fields of kbbq_overlap_counts."""
@@ -395,42 +444,15 @@ class Engine:
         DeviceReads twice with stride 2; qual_b and fix_b are then not given, the batch has one of each.  Returns, after the call,
         ((qual_a, fix_mask_a, fix_bases_a), (qual_b, fix_mask_b, fix_bases_b)) as NumPy arrays -- the same arrays twice for an
         interleaved batch; a side that `sides` (bit 0: a, bit 1: b) does not name comes back as it went in.  Waits for the kernel."""
-        import torch
-        stride = int(stride)
-        if n_pairs is None:
-            n_pairs = self._pairs_from(dev_a, dev_b, first_a, first_b, stride)
-        n_pairs = int(n_pairs)
-        dev = "cuda:%d" % self.params.device
+        stride, n_pairs, _ = self._pairs(dev_a, dev_b, first_a, first_b, stride, n_pairs)
         one = dev_a is dev_b
         assert not one or (qual_b is None and fix_b is None), "one batch has one quality array and one pair of fix arrays"
-        ins = np.zeros(max(1, n_pairs), np.uint32)
-        given = np.ascontiguousarray(insert, dtype=np.uint32)
-        assert len(given) == n_pairs, "insert: one length per pair"
-        ins[:n_pairs] = given
-        d_insert = torch.from_numpy(ins.view(np.int32)).to(dev)
-
-        def side(dreads, qual, fix):
-            nb = dreads.n_bases
-            q = np.ascontiguousarray(qual, dtype=np.uint8)
-            assert len(q) == nb, "one quality per base of the batch"
-            words = []
-            for given, n in zip(fix if fix is not None else (None, None), (nb // 64 + 2, nb // 32 + 2)):
-                w = np.zeros(n, np.uint64)
-                if given is not None:
-                    g = np.ascontiguousarray(given, dtype=np.uint64)
-                    assert len(g) <= n, "fix arrays: at most n_bases/64+2 and n_bases/32+2 words"
-                    w[:len(g)] = g
-                words.append(torch.from_numpy(w.view(np.int64)).to(dev))
-            return [torch.from_numpy(np.concatenate([q, np.zeros(1, np.uint8)])).to(dev)] + words
-
-        da = side(dev_a, qual_a, fix_a)
-        db = da if one else side(dev_b, qual_b, fix_b)
+        d_insert = self._words(insert, n_pairs, what="insert: one length per pair")
+        da = self._side(dev_a, qual_a, fix_a)
+        db = da if one else self._side(dev_b, qual_b, fix_b)
         p = _lib.ConsensusParams(int(good_q), int(bad_q))
-        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        _lib.check(self.L.kbbq_pair_consensus_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs,
-                                                    d_insert.data_ptr(), ctypes.byref(p), da[0].data_ptr(), db[0].data_ptr(), da[1].data_ptr(),
-                                                    da[2].data_ptr(), db[1].data_ptr(), db[2].data_ptr(), int(sides)))
-        self.sync()
+        self._run(self.L.kbbq_pair_consensus_batch, self._pair_side(dev_a, first_a, da), self._pair_side(dev_b, first_b, db), stride, n_pairs,
+                  d_insert.data_ptr(), ctypes.byref(p), int(sides))
 
         def back(d, dreads):
             return (d[0].cpu().numpy()[:dreads.n_bases].copy(), d[1].cpu().numpy().view(np.uint64), d[2].cpu().numpy().view(np.uint64))
@@ -443,15 +465,6 @@ class Engine:
         return self._counts(self.L.kbbq_pair_consensus_counts_get, _lib.ConsensusCounts, reset)
 
     # ---- overlapping pairs merged into single reads
-    @staticmethod
-    def _trim_params(tail_q, min_length, max_ee):
-        p = _lib.TrimParams()
-        p.tail_q = 0 if tail_q is None else int(tail_q)
-        p.min_length = int(min_length)
-        p.has_ee = 0 if max_ee is None else 1
-        p.ee_bound = 0 if max_ee is None else ee_bound(max_ee)
-        return p
-
     def pair_merge(self, dev_a, dev_b, insert, qual_a, qual_b=None, first_a=0, first_b=0, stride=1, n_pairs=None, limit_a=None, limit_b=None,
                    fix_a=None, fix_b=None, min_length=1, max_ee=None, text=True, shift=0):
         """kbbq_pair_merge_batch on two device batches (DeviceReads; the same one twice with stride 2 for an interleaved batch,
@@ -463,62 +476,25 @@ class Engine:
         bytes the call did not write are 0xFF); text=False is the verdict-only call and gives None for both.  shift: the
         output arrays start that many bytes behind an aligned address.  Waits for the kernel."""
         import torch
-        stride = int(stride)
-        if n_pairs is None:
-            n_pairs = self._pairs_from(dev_a, dev_b, first_a, first_b, stride)
-        n_pairs = int(n_pairs)
+        stride, n_pairs, step = self._pairs(dev_a, dev_b, first_a, first_b, stride, n_pairs)
         dev = "cuda:%d" % self.params.device
         one = dev_a is dev_b
         assert not one or (qual_b is None and fix_b is None), "one batch has one quality array and one pair of fix arrays"
-        step = max(stride, 1)
-        words = max(1, (n_pairs - 1) * step + 1) if n_pairs else 1
-
-        def per_pair(given, spread):
-            host = np.zeros(words if spread else max(1, n_pairs), np.uint32)
-            g = np.ascontiguousarray(given, dtype=np.uint32)
-            assert len(g) == n_pairs, "one value per pair"
-            if spread:
-                host[::step][:n_pairs] = g
-            else:
-                host[:n_pairs] = g
-            return torch.from_numpy(host.view(np.int32)).to(dev)
-
-        full = np.full(n_pairs, 0xFFFFFFFF, np.uint32)
-        d_insert = per_pair(insert, False)
-        d_lim = [per_pair(full if given is None else given, True) for given in (limit_a, limit_b)]
+        d_insert = self._words(insert, n_pairs, what="one value per pair")
+        d_lim = [self._words(given, n_pairs, step, fill=0xFFFFFFFF, what="one value per pair") for given in (limit_a, limit_b)]
         with_fix = fix_a is not None or fix_b is not None
-
-        def side(dreads, qual, fix):
-            nb = dreads.n_bases
-            q = np.ascontiguousarray(qual, dtype=np.uint8)
-            assert len(q) == nb, "one quality per base of the batch"
-            out = [torch.from_numpy(np.concatenate([q, np.zeros(1, np.uint8)])).to(dev)]
-            for given, n in zip(fix if fix is not None else (None, None), (nb // 64 + 2, nb // 32 + 2)):
-                w = np.zeros(n, np.uint64)
-                if given is not None:
-                    g = np.ascontiguousarray(given, dtype=np.uint64)
-                    assert len(g) <= n, "fix arrays: at most n_bases/64+2 and n_bases/32+2 words"
-                    w[:len(g)] = g
-                out.append(torch.from_numpy(w.view(np.int64)).to(dev) if with_fix else None)
-            return out
-
-        da = side(dev_a, qual_a, fix_a)
-        db = da if one else side(dev_b, qual_b, fix_b)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        d_len = torch.full((max(1, n_pairs),), -1, dtype=torch.int32, device=dev)
+        da = self._side(dev_a, qual_a, fix_a, with_fix)
+        db = da if one else self._side(dev_b, qual_b, fix_b, with_fix)
+        d_len = self._words(None, n_pairs, fill=0xFFFFFFFF)
         n_out = 0
         if text and n_pairs:      # (room for every base of the batches: the call's pairs have no more)
             n_out = dev_a.n_bases if one else dev_a.n_bases + dev_b.n_bases
         d_seq = torch.full((n_out + int(shift) + 1,), 0xFF, dtype=torch.uint8, device=dev) if text else None
         d_qual = torch.full((n_out + int(shift) + 1,), 0xFF, dtype=torch.uint8, device=dev) if text else None
         p = self._trim_params(None, min_length, max_ee)
-        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        _lib.check(self.L.kbbq_pair_merge_batch(self.h, self._c(dev_a), int(first_a), self._c(dev_b), int(first_b), stride, n_pairs, d_insert.data_ptr(),
-                                                d_lim[0].data_ptr(), d_lim[1].data_ptr(), da[0].data_ptr(), db[0].data_ptr(), ptr(da[1]), ptr(da[2]),
-                                                ptr(db[1]), ptr(db[2]), ctypes.byref(p), d_len.data_ptr(),
-                                                d_seq.data_ptr() + int(shift) if text else None, d_qual.data_ptr() + int(shift) if text else None))
-        self.sync()
-        lens = d_len.cpu().numpy().view(np.uint32)[:n_pairs].copy()
+        self._run(self.L.kbbq_pair_merge_batch, self._pair_side(dev_a, first_a, da, d_lim[0]), self._pair_side(dev_b, first_b, db, d_lim[1]), stride, n_pairs,
+                  d_insert.data_ptr(), ctypes.byref(p), d_len.data_ptr(), self._ptr(d_seq, shift), self._ptr(d_qual, shift))
+        lens = self._back(d_len, n_pairs)
         if not text:
             return lens, None, None
         return lens, d_seq.cpu().numpy()[int(shift):int(shift) + n_out].copy(), d_qual.cpu().numpy()[int(shift):int(shift) + n_out].copy()
@@ -526,47 +502,6 @@ class Engine:
     def merge_counts(self, reset=False):
         """What pair_merge did since the last reset (waits): the fields of kbbq_merge_counts."""
         return self._counts(self.L.kbbq_merge_counts_get, _lib.MergeCounts, reset)
-
-    def trim_unmerged(self, dreads, qual_ptr, merged_len, first=0, adjacent=False, tail_q=None, min_length=1, max_ee=None, limit=None):
-        """kbbq_trim_batch_unmerged: trim_reads that leaves out the reads of the pairs whose merged_len word (pair_merge's, by the
-        pair's ordinal; read r is of pair first + r, or (first + r) // 2 with adjacent) is not 0.  Waits for the kernel."""
-        import torch
-        p = self._trim_params(tail_q, min_length, max_ee)
-        dev = "cuda:%d" % self.params.device
-        d_keep = torch.zeros(max(1, dreads.n_reads), dtype=torch.int32, device=dev)
-        d_merged = torch.from_numpy(np.concatenate([np.ascontiguousarray(merged_len, dtype=np.uint32), np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
-        d_limit = None
-        if limit is not None:
-            lim = np.ascontiguousarray(limit, dtype=np.uint32)
-            assert len(lim) == dreads.n_reads, "limit: one length per read"
-            d_limit = torch.from_numpy(lim.view(np.int32).copy()).to(dev)
-        torch.cuda.synchronize(dev)      # the engine's stream does not wait for torch's
-        _lib.check(self.L.kbbq_trim_batch_unmerged(self.h, self._c(dreads), qual_ptr, ctypes.byref(p), None if d_limit is None else d_limit.data_ptr(),
-                                                   d_merged.data_ptr(), int(first), 1 if adjacent else 0, d_keep.data_ptr()))
-        self.sync()
-        return d_keep.cpu().numpy().view(np.uint32)[:dreads.n_reads].copy()
-
-    def trim_mates(self, keep_a, keep_b=None, adjacent=False):
-        """kbbq_trim_mates on host arrays of kept lengths (copied to the device and back): the arrays after the mate rule --
-        (a, b), or a alone with adjacent=True, where the pairs are a[2i], a[2i+1].  Waits for the kernel."""
-        import torch
-        dev = "cuda:%d" % self.params.device
-        a = np.ascontiguousarray(keep_a, dtype=np.uint32)
-        d_a = torch.from_numpy(a.view(np.int32).copy()).to(dev)
-        d_b = None
-        if not adjacent:
-            b = np.ascontiguousarray(keep_b, dtype=np.uint32)
-            assert len(b) == len(a), "two files of a pair hold equally many reads"
-            d_b = torch.from_numpy(b.view(np.int32).copy()).to(dev)
-        torch.cuda.synchronize(dev)
-        _lib.check(self.L.kbbq_trim_mates(self.h, d_a.data_ptr(), d_b.data_ptr() if d_b is not None else None, len(a), 1 if adjacent else 0))
-        self.sync()
-        out_a = d_a.cpu().numpy().view(np.uint32)
-        return out_a if adjacent else (out_a, d_b.cpu().numpy().view(np.uint32))
-
-    def trim_counts(self, reset=False):
-        """What trim_reads and trim_mates did since the last reset (waits): the fields of kbbq_trim_counts."""
-        return self._counts(self.L.kbbq_trim_counts_get, _lib.TrimCounts, reset)
 
     def covariates(self):
         out, c = _covariates_arrays(self.n_rg, self.max_read_len)

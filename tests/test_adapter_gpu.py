@@ -1,4 +1,4 @@
-"""kbbq_adapter_find_batch and kbbq_trim_batch_limited (include/kbbq_engine.h; the kernel k_adapter_find:
+"""kbbq_adapter_find_batch and kbbq_trim_batch with a limit (include/kbbq_engine.h; the kernel k_adapter_find:
 kbbq_amd/csrc/adapter.h) through Engine.find_adapters / trim_reads(limit=...), against tests/plain_adapter_ref.py.  Every
 comparison is exact: the limit of every read and the six counts, the kept length of every read and the eight trim counts.
 
@@ -391,7 +391,7 @@ def test_refusals(cases):
             case.e.find_adapters(dev, "ACGTN")
         assert err.value.code == -22
         p = _lib.TrimParams(Q, 0, 1, 0)
-        assert case.e.L.kbbq_trim_batch_limited(case.e.h, host.c, dev.c.qual, p, limit.data_ptr(), limit.data_ptr()) == -22
-        assert case.e.L.kbbq_trim_batch_limited(case.e.h, dev.c, dev.c.qual, _lib.TrimParams(94, 0, 1, 0), limit.data_ptr(), limit.data_ptr()) == -22
+        assert case.e.L.kbbq_trim_batch(case.e.h, host.c, dev.c.qual, p, limit.data_ptr(), None, limit.data_ptr()) == -22
+        assert case.e.L.kbbq_trim_batch(case.e.h, dev.c, dev.c.qual, _lib.TrimParams(94, 0, 1, 0), limit.data_ptr(), None, limit.data_ptr()) == -22
     finally:
         dev.free()

@@ -1,4 +1,4 @@
-"""kbbq_pair_consensus_batch and kbbq_pair_overlap_inserts (include/kbbq_engine.h; the kernel k_pair_consensus:
+"""kbbq_pair_consensus_batch and kbbq_pair_overlap_batch with `insert` (include/kbbq_engine.h; the kernel k_pair_consensus:
 kbbq_amd/csrc/consensus.h) through Engine.pair_consensus and Engine.find_pair_inserts, against tests/plain_consensus_ref.py.
 Every comparison is exact: both quality arrays, both pairs of fix arrays word for word, and the four counts.
 
@@ -7,6 +7,8 @@ the candidate range and around the reads' lengths, disagreements at the overlap'
 at the last base of one read and the first of the next (the fix words those two share), and at the batch's last read.  The
 qualities of a disagreement are drawn so that about a third fall in each outcome, many sitting at the thresholds themselves, and
 about 2 % of all positions carry a fix bit before the call.  The insert lengths handed to the rule are the reference's."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -515,14 +517,15 @@ def test_refusals(case):
     ins, qa, qb, ma, ba, mb, bb = base, base + 1024, base + 9216, base + 17408, base + 19456, base + 22528, base + 24576
     lim = base + 28672
     run = case.e.L.kbbq_pair_consensus_batch
-    find = case.e.L.kbbq_pair_overlap_inserts
+    find = case.e.L.kbbq_pair_overlap_batch
+    side = lambda reads, first, *arrays: _lib.PairSide(None if reads is None else ctypes.pointer(reads), first, *arrays)
     h = case.e.h
 
     def params(g=G, b_=B):
         return _lib.ConsensusParams(g, b_)
 
     def call(e=h, a_=a.c, fa=0, b_=b.c, fb=0, stride=1, n=10, insert=ins, p=params(), q1=qa, q2=qb, m1=ma, c1=ba, m2=mb, c2=bb, sides=3):
-        return run(e, a_, fa, b_, fb, stride, n, insert, p, q1, q2, m1, c1, m2, c2, sides)
+        return run(e, side(a_, fa, q1, m1, c1), side(b_, fb, q2, m2, c2), stride, n, insert, p, sides)
 
     try:
         assert call() == 0 and call(sides=1) == 0 and call(sides=2) == 0
@@ -545,10 +548,11 @@ def test_refusals(case):
         for name in ("e", "a_", "b_", "insert", "p", "q1", "q2", "m1", "c1", "m2", "c2"):
             assert call(**{name: None}) == -22, name
         op = _lib.OverlapParams(V, D, T, 0)
-        assert find(h, a.c, 0, b.c, 0, 1, 10, op, lim, lim + 256, ins) == 0
-        assert find(h, a.c, 0, b.c, 0, 1, 10, op, lim, lim + 256, None) == -22
-        assert find(h, a.c, 0, b.c, 0, 1, 11, op, lim, lim + 256, ins) == -22
-        assert find(h, a.c, 0, b.c, 0, 1, 10, _lib.OverlapParams(7, D, T, 0), lim, lim + 256, ins) == -22
+        sa, sb = side(a.c, 0, None, None, None, lim), side(b.c, 0, None, None, None, lim + 256)
+        assert find(h, sa, sb, 1, 10, op, ins) == 0
+        assert find(h, sa, sb, 1, 10, op, None) == 0      # (the insert lengths are optional: the limits alone)
+        assert find(h, sa, sb, 1, 11, op, ins) == -22
+        assert find(h, sa, sb, 1, 10, _lib.OverlapParams(7, D, T, 0), ins) == -22
         case.e.sync()
         with pytest.raises(_lib.KbbqError) as err:
             case.e.pair_consensus(a, b, np.zeros(10, np.uint32), f.qual[:a.n_bases], case.files[1].qual[:b.n_bases], n_pairs=10, good_q=15, bad_q=30)

@@ -1,4 +1,4 @@
-"""kbbq_pair_merge_batch, kbbq_merge_counts_get and kbbq_trim_batch_unmerged (include/kbbq_engine.h; the kernels k_pair_merge and
+"""kbbq_pair_merge_batch, kbbq_merge_counts_get and kbbq_trim_batch with `merged` (include/kbbq_engine.h; the kernels k_pair_merge and
 k_trim_unmerged: kbbq_amd/csrc/merge.h) through Engine.pair_merge, Engine.merge_counts and Engine.trim_unmerged, against
 tests/plain_merge_ref.py.  Every comparison is exact: the merged lengths, every byte of both output arrays -- the bytes the call
 must not touch included -- and the nine counts.
@@ -7,6 +7,8 @@ One ragged batch pair of about 700 planted pairs: the read lengths at which the 
 inserts below, between and above the two lengths and such that the overlap ends on and beside multiples of 32 and 64, the
 longest merged reads there are, N's on either side and on both, disagreements with unequal and with equal qualities, lower case,
 about 2 % of all positions with a fix bit and a code of its own, pairs held back by a limit and pairs without an insert."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -464,7 +466,8 @@ def test_refusals(case):
         return p
 
     def call(e=h, a_=a.c, fa=0, b_=b.c, fb=0, stride=1, n=10, insert=ins, l1=la, l2=lb, q1=qa, q2=qb, m1=ma, c1=ba, m2=mb, c2=bb, p=params(), out=out_len, s=seq, q=qual):
-        return run(e, a_, fa, b_, fb, stride, n, insert, l1, l2, q1, q2, m1, c1, m2, c2, p, out, s, q)
+        side = lambda reads, first, *arrays: _lib.PairSide(None if reads is None else ctypes.pointer(reads), first, *arrays)
+        return run(e, side(a_, fa, q1, m1, c1, l1), side(b_, fb, q2, m2, c2, l2), stride, n, insert, p, out, s, q)
 
     try:
         assert call() == 0 and call(s=None, q=None) == 0 and call(m1=None, c1=None, m2=None, c2=None) == 0
@@ -489,11 +492,12 @@ def test_refusals(case):
             assert call(**{name: None}) == -22, name
         assert case.e.L.kbbq_merge_counts_get(h, None, 0) == -22
         keep = base + 50 * 1024
-        trim = case.e.L.kbbq_trim_batch_unmerged
-        assert trim(h, a.c, qa, params(), None, out_len, 0, 0, keep) == 0
-        assert trim(h, host.c, qa, params(), None, out_len, 0, 0, keep) == -22
-        assert trim(h, a.c, qa, params(), None, None, 0, 0, keep) == -22 and trim(h, a.c, None, params(), None, out_len, 0, 0, keep) == -22
-        assert trim(h, a.c, qa, params(tail_q=94), None, out_len, 0, 0, keep) == -22 and trim(h, a.c, qa, params(), None, out_len, 0, 0, None) == -22
+        trim = case.e.L.kbbq_trim_batch
+        of = lambda words: _lib.TrimMerged(words, 0, 0)
+        assert trim(h, a.c, qa, params(), None, of(out_len), keep) == 0
+        assert trim(h, host.c, qa, params(), None, of(out_len), keep) == -22
+        assert trim(h, a.c, qa, params(), None, of(None), keep) == -22 and trim(h, a.c, None, params(), None, of(out_len), keep) == -22
+        assert trim(h, a.c, qa, params(tail_q=94), None, of(out_len), keep) == -22 and trim(h, a.c, qa, params(), None, of(out_len), None) == -22
         case.e.sync()
     finally:
         a.free()

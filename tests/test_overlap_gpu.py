@@ -5,6 +5,8 @@ counts.
 One ragged batch pair of about 3 000 planted pairs: the read lengths at which the kernel's words and rounds change, inserts at
 the ends of the candidate range and around the reads' lengths, mismatches at the bounds and at the word boundaries.  Every
 planted pair carries the name of its class, and the reference says how many of each class came out as planted."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -413,8 +415,11 @@ def test_refusals(case):
     a, b = case.upload(0, 0, 10), case.upload(1, 0, 12)
     limit = torch.zeros(64, dtype=torch.int32, device="cuda:0")
     la, lb = limit.data_ptr(), limit.data_ptr() + 128
-    find = case.e.L.kbbq_pair_overlap_batch
     h = case.e.h
+
+    def find(e, x, fa, y, fb, stride, n, p, l1, l2):
+        side = lambda reads, first, limit: _lib.PairSide(None if reads is None else ctypes.pointer(reads), first, None, None, None, limit)
+        return case.e.L.kbbq_pair_overlap_batch(e, side(x, fa, l1), side(y, fb, l2), stride, n, p, None)
 
     def params(v=V, d=D, t=T, merge=0):
         return _lib.OverlapParams(v, d, t, merge)

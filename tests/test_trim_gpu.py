@@ -1,5 +1,6 @@
 """kbbq_trim_batch and kbbq_trim_mates (include/kbbq_engine.h; the kernels k_trim_reads and k_trim_mates:
-kbbq_amd/csrc/trim.h) through Engine.trim_reads / trim_mates, against tests/plain_trim_ref.py.  Every comparison is exact:
+kbbq_amd/csrc/trim.h, and k_trim_unmerged: kbbq_amd/csrc/merge.h) through Engine.trim_reads / trim_unmerged / trim_mates, against
+tests/plain_trim_ref.py.  Every comparison is exact:
 the kept length of every read and the eight counts.
 
 One ragged batch of about 2 000 reads: the lengths at which the kernel changes its path (a round is 64 bases, a read of up
@@ -219,17 +220,75 @@ def test_mates_two_arrays_and_adjacent(case):
     assert err.value.code == -22
 
 
+def both_rules(case, merged_len, first, adjacent, limit=None, **opts):
+    """the whole case through trim_reads and through trim_unmerged: (keep, counts) of each"""
+    batch = ReadBatch(case.seq, case.flat, case.off)
+    dev = case.e.upload(batch)
+    try:
+        case.e.trim_counts(reset=True)
+        plain = case.e.trim_reads(dev, dev.c.qual, limit=limit, **opts)
+        plain_counts = case.e.trim_counts(reset=True)
+        got = case.e.trim_unmerged(dev, dev.c.qual, merged_len, first=first, adjacent=adjacent, limit=limit, **opts)
+        return (plain, plain_counts), (got, case.e.trim_counts(reset=True))
+    finally:
+        dev.free()
+
+
+@pytest.mark.parametrize("adjacent,first", [(False, 0), (False, 7), (True, 0), (True, 3)])
+@pytest.mark.parametrize("limited", [False, True])
+def test_unmerged_with_nothing_merged_is_the_plain_rule(case, adjacent, first, limited):
+    n = len(case.quals)
+    # limits on both sides of the reads' lengths and of the 256 bases a read keeps in registers, and some of 0
+    limit = np.random.default_rng(5).choice([0, 1, 64, 200, 255, 256, 257, 300, 699, 700, 5000], n).astype(np.uint32) if limited else None
+    (plain, plain_counts), (got, got_counts) = both_rules(case, np.zeros(first + n + 1, np.uint32), first, adjacent, limit, **case.opts("all"))
+    assert np.array_equal(got, plain) and got_counts == plain_counts
+    if limited:
+        assert (limit < case.lens).sum() > 100 and (plain != case.reference("all")[2]).sum() > 100      # (the limits decide something)
+    else:
+        assert np.array_equal(plain, case.reference("all")[2]) and plain_counts == case.reference("all")[3]
+
+
+@pytest.mark.parametrize("adjacent,first", [(False, 0), (False, 7), (True, 3)])
+def test_unmerged_leaves_every_third_pair_out(case, adjacent, first):
+    n = len(case.quals)
+    of_pair = (first + np.arange(n)) // 2 if adjacent else first + np.arange(n)
+    merged_len = np.zeros(int(of_pair.max()) + 2, np.uint32)
+    merged_len[0::3] = 100      # (any value but 0 marks the pair)
+    gone = merged_len[of_pair] != 0
+    # both paths of the rule, on both sides of the skip: reads around the 256 bases that stay in registers, and long ones
+    for length in (255, 256, 257, 700):
+        assert (gone & (case.lens == length)).sum() >= 5 and (~gone & (case.lens == length)).sum() >= 5, length
+    (plain, _), (got, got_counts) = both_rules(case, merged_len, first, adjacent, **case.opts("all"))
+    assert (got[gone] == 0).all() and np.array_equal(got[~gone], plain[~gone]) and (plain[gone] > 0).sum() >= 100
+    kept, v = ref.verdicts([q for q, g in zip(case.quals, gone) if not g], **case.opts("all"))
+    want = ref.counts(case.lens[~gone], kept, v)
+    want["reads_in"], want["bases_in"] = n, int(case.lens.sum())
+    assert got_counts == want
+
+
 def test_refusals(case):
     host = ReadBatch(case.seq[:10], case.flat[:10], np.array([0, 10], np.uint64))
     p = _lib.TrimParams(Q, 0, 1, 0)
     dev = case.e.upload(host)
     keep = torch.zeros(4, dtype=torch.int32, device="cuda:0")
+    words = torch.zeros(16, dtype=torch.int32, device="cuda:0")
+    trim, h = case.e.L.kbbq_trim_batch, case.e.h
     try:
-        assert case.e.L.kbbq_trim_batch(case.e.h, host.c, dev.c.qual, p, keep.data_ptr()) == -22      # a host batch
-        for bad in (94, -1):
-            assert case.e.L.kbbq_trim_batch(case.e.h, dev.c, dev.c.qual, _lib.TrimParams(bad, 0, 1, 0), keep.data_ptr()) == -22
+        # without and with `merged`: the same refusals, the same words
+        for merged in (None, _lib.TrimMerged(words.data_ptr(), 0, 0)):
+            said = []
+            assert trim(h, host.c, dev.c.qual, p, None, merged, keep.data_ptr()) == -22      # a host batch
+            for bad in (_lib.TrimParams(94, 0, 1, 0), _lib.TrimParams(-1, 0, 1, 0), _lib.TrimParams(Q, 0, 1 << 32, 0)):      # tail_q, tail_q, min_length
+                assert trim(h, dev.c, dev.c.qual, bad, None, merged, keep.data_ptr()) == -22
+                said.append(case.e.L.kbbq_last_error())
+            if merged is None:
+                plain_said = said
+            assert said == plain_said and said[0] and said[0] != said[2]
+        assert trim(h, dev.c, dev.c.qual, p, None, _lib.TrimMerged(None, 0, 0), keep.data_ptr()) == -22      # merged without its words
         with pytest.raises(_lib.KbbqError):
             case.e.trim_reads(dev, dev.c.qual, tail_q=0)
+        with pytest.raises(_lib.KbbqError):
+            case.e.trim_unmerged(dev, dev.c.qual, np.zeros(2, np.uint32), tail_q=94)
     finally:
         dev.free()
 
