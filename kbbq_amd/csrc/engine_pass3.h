@@ -147,16 +147,17 @@ static int run_tally(kbbq_engine *e, const Pass3 &c, const ReadsDev &R, const ui
     // histograms, only the dinucleotide counters in LDS (TallyPlan::direct_cycles).
     const int n_windows = (max_len + ccap - 1) / ccap;
     const bool direct_cycles = n_windows > kTallyMaxWindows;
-    // per quality slot: totals and errors of 2 x ccap cycles as 16-bit counters + 2 x 16 dinucleotide words
-    const size_t per_slot = (direct_cycles ? 0 : (size_t)8 * ccap) + 128;
+    // the tables' sizes are tally.h's: bytes per quality slot, then per read group with the plan's slots, then per launch
+    const size_t per_slot = (size_t)tally_rg_words(1, ccap, direct_cycles) * 4;
     TallyPlan P;
     plan_tally_slots(P, e->qpresent, (int)((152 * 1024 - 512) / per_slot), n_rg);
     P.direct_cycles = direct_cycles ? 1 : 0;
-    const size_t per_rg = (size_t)P.n_slots * per_slot;
+    const int rg_words = tally_rg_words(P.n_slots, ccap, direct_cycles);
+    const size_t per_rg = (size_t)rg_words * 4;
     // (half of the LDS if everything fits in it: two blocks per CU)
     const size_t budget = (size_t)n_rg * per_rg <= 70 * 1024 ? 70 * 1024 : 140 * 1024;
     const int per_launch = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_rg, budget / per_rg));
-    const size_t lds = (size_t)per_launch * per_rg + 4 + 256 + 4;
+    const size_t lds = tally_lds_bytes(per_launch, rg_words);
     for (const void *fn : {(const void *)k_tally, (const void *)k_tally_uniform<true>, (const void *)k_tally_uniform<false>}) {
         const int lrc = raise_dynamic_lds(e, fn, lds);      // (all three at once: whichever serves the next batch is ready)
         if (lrc) return lrc;

@@ -94,13 +94,13 @@ static int recalibrate_impl(kbbq_engine *e, const kbbq_reads *reads, uint8_t *qu
     D.n_rg = e->p.n_rg; D.n_cycle = e->p.max_read_len; D.n_slots = e->p4.dq_slots;
     const uint32_t *read_index;
     if ((rc = build_read_index(e, R, 0, e->stream, &read_index))) return rc;      // (the engine's stream's index: pass 3's in-order tallies use the same one)
-    const int per_rg = (D.n_slots * (4 * D.n_cycle + 16) + KBBQ_NQ * 2 + 3) & ~3;
-    // tables of as many read groups as fit (kernels.h: compacted over the quality axis): two 1024-lane blocks
+    const int per_rg = recal_rg_bytes(D.n_slots, D.n_cycle);
+    // tables of as many read groups as fit (recalibrate.h: compacted over the quality axis): two 1024-lane blocks
     // per CU share the 160 KB of LDS when one group takes at most 64 KB; otherwise one block per CU and up to 152 KB.
     // (More than 255 quality values with a delta of their own -- no real data -- leave the slot map: global tables.)
     const int budget = per_rg + 256 <= 64 * 1024 ? 64 * 1024 - 256 : 152 * 1024 - 256;
     const int lds_rgs = D.n_slots > 255 ? 0 : std::max(0, std::min(D.n_rg, budget / per_rg));
-    const size_t lds = 256 + (size_t)lds_rgs * per_rg;
+    const size_t lds = recal_lds_bytes(lds_rgs, D.n_slots, D.n_cycle);
     if ((rc = raise_dynamic_lds(e, (const void *)k_recalibrate, lds))) return rc;
     const int vec_ok = (((uintptr_t)R.qual | (uintptr_t)d_out) & 15) == 0;
     auto launch = [&](uint64_t base0, uint64_t base1) -> int {      // the bases [base0, base1), base0 a multiple of 16

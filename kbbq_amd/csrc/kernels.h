@@ -1,4 +1,6 @@
-// kernels.h -- every __global__ kernel of the engine (gfx950), included once by engine.hip.
+// kernels.h -- every __global__ kernel of the engine (gfx950), included once by engine.hip.  Pass 3c and pass 4 stand in
+// headers of their own (tally.h, recalibrate.h), included below where their kernels belong in the code object; what they and
+// quality_report.h share is base_groups.h.
 //
 //   pass 1  k_draw_mask        one xoshiro256** draw per k-mer position (htsiter.cc:113-129)
 //           k_insert_marked    sampled & valid k-mers -> sampled filter   (recalibrateutils.cc:7-13)
@@ -8,10 +10,10 @@
 //                              errors in its fast path (fast_path)
 //           k_compact          work list of reads that need more
 //           k_correct_wave     get_errors, one read per wavefront (correct_wave.h); k_correct: one read per lane (correct.h)
-//           k_tally            covariate histograms                      (covariateutils.cc:30-164,193-202)
-//   pass 4  k_recalibrate      delta-Q apply                             (readutils.cc:572-595)
-//   helpers k_kmer_counts, k_scan_tiles / k_scan_tile_sums / k_scan_add, k_read_index, k_rg_presence, k_or_words,
-//           k_or_pieces, k_synth
+//           k_tally            covariate histograms: tally.h             (covariateutils.cc:30-164,193-202)
+//   pass 4  k_recalibrate      delta-Q apply: recalibrate.h              (readutils.cc:572-595)
+//   helpers k_kmer_counts, k_scan_tiles / k_scan_tile_sums / k_scan_add, k_read_index, k_rg_presence and k_qpresence
+//           (tally.h), k_or_words, k_or_pieces, k_synth
 // Integer / hash / bit work throughout: no MFMA.  What bounds passes 1-3 is HBM bandwidth at the L2's line
 // granularity: every Bloom lookup fetches one random 128-byte line for its 16-byte block.
 #pragma once
@@ -161,6 +163,7 @@ __device__ __forceinline__ void find_read(const ReadsDev &R, const uint32_t *ind
     end = R.offsets[r + 1];
     while (end <= g0) { ++r; start = end; end = R.offsets[r + 1]; }
 }
+#include "base_groups.h"      // what the kernels that take 16 bases per lane share (no kernel)
 
 __device__ __forceinline__ uint64_t kmer_base(const uint64_t *kofs, uint64_t r, uint32_t read_len, int k) {
     if (kofs) return kofs[r];
@@ -854,588 +857,8 @@ __global__ void __launch_bounds__(256, 5) k_correct_wave(ReadsDev R, KParams K, 
     if (lane == 0 && q_total) atomicAdd(&stats[1], q_total);
 }
 
-// ---- pass 3c: covariate tally ---------------------------------------------------
-// CCovariateData::consume_read (covariateutils.cc:193-202).  Only the cycle and
-// dinucleotide tables are tallied: qcov[rg][q] and rgcov[rg] are exact sums of
-// the cycle table (every base is counted in all three, :30-42, :65-76, :102-116)
-// and are formed once at the end.  Totals go through an LDS-private table
-// (16-bit counters, packed two per word, flushed before they can wrap) for the
-// read group of the block's first read; error counts and anything outside the
-// LDS table go straight to 64-bit global atomics (rare).
-struct HistDev {
-    unsigned long long *cycle;   // [n_rg][256][2][n_cycle][2]
-    unsigned long long *dinuc;   // [n_rg][256][16][2]
-    int n_rg, n_cycle;
-};
-
-// A read's patch word (k_correct / k_correct_wave): bit 31 = the walk returned early with one base replaced
-// (readutils.cc:263-265), bits 8-30 = its position in the read (KBBQ_MAX_READ_LEN is what 23 bits hold), bits 0-1 = the base.
-__device__ __forceinline__ int patch_at(uint32_t pt) { return (int)((pt >> 8) & 0x7FFFFFu); }
-
-__device__ __forceinline__ uint64_t cyc_index(const HistDev &H, int rg, int q, int s, int c) {
-    return ((((uint64_t)rg * KBBQ_NQ + q) * 2 + s) * H.n_cycle + c) * 2;
-}
-
-// One lane per 16 consecutive bases of the batch (16-byte quality load, 4-byte base load), a block of
-// 1024 lanes per 16 Ki bases; the block's LDS table is flushed before any 16-bit counter could wrap
-// (a read adds at most 1 to a counter, so the block counts the reads it has touched).
-// One launch tallies the cycles [cbase, cbase + ccap) (reads longer than the LDS tables' 192 cycles take several
-// launches; cycles beyond the tables used to go through global atomics: 100 ms per launch for 250-base reads) of
-// the reads of ONE read group (lds_rg; its tables are the ones in LDS) and ignores the rest: a
-// batch with several read groups gets one launch per group that occurs in it (`present`, a bit per group from
-// k_rg_presence; a launch for an absent group returns at once).  Counting the other groups through global atomics
-// in the same launch serialises on a few hundred hot addresses -- 400 ms instead of 1 ms for four groups.
-__global__ void k_rg_presence(const uint16_t *rg, uint64_t n_reads, uint32_t n_rg, uint32_t *present) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_reads) {
-        const uint32_t g = rg[i] < n_rg ? rg[i] : 0;      // reads of an undeclared group are not tallied anyway
-        // a few bits, millions of reads: look before the atomic (the words sit in cache), or every read of the
-        // batch queues up on the same address
-        const uint32_t bit = 1u << (g & 31);
-        if (!(present[g >> 5] & bit)) atomicOr(&present[g >> 5], bit);
-    }
-}
-
-struct TallyPlan {
-    uint8_t qslot[256];    // slot of a quality value in the LDS tables, 255 = none (counted through global atomics)
-    uint8_t qof[256];      // quality value of a slot
-    int n_slots;           // slots in use (at most 255)
-    int identity;          // slot == quality for every quality below n_slots (few, small values: no lookup needed)
-    int rg_base, n_rgs;    // this launch tallies the read groups [rg_base, rg_base + n_rgs)
-    int cbase;             // ... and the cycles [cbase, cbase + ccap)
-    int direct_cycles;     // k_tally only: the cycle counters have no LDS table (reads of many thousand bases: a window of ccap
-                           // cycles per launch would re-read the batch once per window) -- every cycle in one launch, straight to
-                           // the histograms, where a long read's counters are as many addresses as it has bases; the few, hot
-                           // dinucleotide counters stay in LDS
-};
-
-// The quality axis of the LDS tables is compacted to the values the batches hold (TallyPlan; a quality is any uint8_t,
-// as in the reference, whose tables grow with the largest one seen).
-__global__ void __launch_bounds__(1024) k_tally(ReadsDev R, HistDev H, const uint32_t *err_bits, const uint32_t *patch,
-                                                 int ccap, int minscore, int vec_ok, TallyPlan P, const uint32_t *present,
-                                                 const uint32_t *read_index) {
-    extern __shared__ uint32_t lds[];
-    const int ns = P.n_slots, cbase = P.cbase;
-    if (present) {      // none of this launch's read groups occurs in the batch
-        bool any = false;
-        for (int g = P.rg_base; g < P.rg_base + P.n_rgs; ++g) any = any || ((present[g >> 5] >> (g & 31)) & 1);
-        if (!any) return;
-    }
-    // layout per read group: cycle totals [2][ns][ccap] u16 (packed, cycle slots permuted), cycle errors likewise,
-    // dinuc totals [ns][16] u32, dinuc errors [ns][16] u32 (few, hot addresses: global atomics on them serialise
-    // at the memory side); then the quality -> slot map and the reads-touched counter
-    const bool direct = P.direct_cycles != 0;
-    const int cyc_words = direct ? 0 : (2 * ccap * ns + 1) / 2;
-    const int per_rg = 2 * cyc_words + 2 * ns * 16;
-    uint32_t *l_reads = lds + P.n_rgs * per_rg;
-    uint8_t *l_qslot = reinterpret_cast<uint8_t *>(l_reads + 1);
-    const int lds_words = P.n_rgs * per_rg + 1;
-    for (int i = threadIdx.x; i < lds_words; i += blockDim.x) lds[i] = 0;
-    if (threadIdx.x < 256) l_qslot[threadIdx.x] = P.qslot[threadIdx.x];
-    __syncthreads();
-    // one base: cycle and dinucleotide counters of (read group slot lr, quality q, second, cycle cyc)
-    auto count = [&](int lr, int rg, int q, int second, int cyc, int er, bool dinuc_ok, int d) {
-        const int cr = cyc - cbase;      // inside this launch's cycle window?
-        if (!direct && (unsigned)cr >= (unsigned)ccap) return;
-        const int sl = (int)l_qslot[q];
-        if (direct) {
-            atomicAdd(&H.cycle[cyc_index(H, rg, q, second, cyc) + 1], 1ULL);
-            if (er) atomicAdd(&H.cycle[cyc_index(H, rg, q, second, cyc)], 1ULL);
-            if (dinuc_ok) {
-                if (sl != 255) {
-                    uint32_t *t = lds + lr * per_rg;
-                    atomicAdd(&t[sl * 16 + d], 1u);
-                    if (er) atomicAdd(&t[ns * 16 + sl * 16 + d], 1u);
-                } else {
-                    atomicAdd(&H.dinuc[(((uint64_t)rg * KBBQ_NQ + q) * 16 + d) * 2 + 1], 1ULL);
-                    if (er) atomicAdd(&H.dinuc[(((uint64_t)rg * KBBQ_NQ + q) * 16 + d) * 2], 1ULL);
-                }
-            }
-        } else if (sl != 255) {
-            uint32_t *t = lds + lr * per_rg;
-            // lanes of one instruction are 16 cycles apart: store cycle c at slot (c%16)*(ccap/16) + c/16 so that
-            // they land in neighbouring words, not in two banks
-            const int idx = (second * ns + sl) * ccap + (cr & 15) * (ccap >> 4) + (cr >> 4);
-            const uint32_t one = 1u << (16 * (idx & 1));
-            atomicAdd(&t[idx >> 1], one);
-            if (er) atomicAdd(&t[cyc_words + (idx >> 1)], one);
-            if (dinuc_ok) {
-                atomicAdd(&t[2 * cyc_words + sl * 16 + d], 1u);
-                if (er) atomicAdd(&t[2 * cyc_words + ns * 16 + sl * 16 + d], 1u);
-            }
-        } else {      // a quality value without a slot (not announced, or more distinct values than fit): straight to the histograms
-            atomicAdd(&H.cycle[cyc_index(H, rg, q, second, cyc) + 1], 1ULL);
-            if (er) atomicAdd(&H.cycle[cyc_index(H, rg, q, second, cyc)], 1ULL);
-            if (dinuc_ok) {
-                atomicAdd(&H.dinuc[(((uint64_t)rg * KBBQ_NQ + q) * 16 + d) * 2 + 1], 1ULL);
-                if (er) atomicAdd(&H.dinuc[(((uint64_t)rg * KBBQ_NQ + q) * 16 + d) * 2], 1ULL);
-            }
-        }
-    };
-    const uint64_t n_groups = (R.n_bases + 15) / 16;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t iters = (n_groups + stride - 1) / stride;
-    for (uint64_t it = 0; it < iters; ++it) {
-        const uint64_t grp = it * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-        const uint64_t g0 = grp * 16;
-        int starts = 0;
-        if (g0 < R.n_bases) {
-            uint64_t r, start, end;
-            if (R.offsets) {
-                find_read(R, read_index, g0, r, start, end);
-            } else {
-                r = g0 / R.read_len;
-                start = r * R.read_len;
-                end = start + R.read_len;
-            }
-            const int n = (int)min((uint64_t)16, R.n_bases - g0);
-            uint8_t qv[16];
-            if (n == 16 && vec_ok) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(R.qual + g0);
-                memcpy(qv, &v, 16);
-            } else {
-                for (int i = 0; i < 16; ++i) qv[i] = i < n ? R.qual[g0 + i] : 0;
-            }
-            const uint32_t bw = (uint32_t)(R.bases[g0 >> 5] >> ((g0 & 31) * 2));
-            const uint32_t nw = (uint32_t)(R.nmask[g0 >> 6] >> (g0 & 63)) & 0xFFFFu;
-            const uint32_t ew = (err_bits[g0 >> 5] >> (g0 & 31)) & 0xFFFFu;
-            int prev_b = 0, prev_n = 1;
-            if (g0 > 0) {
-                const uint64_t gp = g0 - 1;
-                prev_b = (int)((R.bases[gp >> 5] >> ((gp & 31) * 2)) & 3);
-                prev_n = (int)((R.nmask[gp >> 6] >> (gp & 63)) & 1);
-            }
-            int rg = R.rg ? (int)R.rg[r] : 0;
-            int second = R.flags ? (R.flags[r] & 1) : 0;
-            uint32_t pt = patch ? patch[r] : 0u;
-            starts = g0 == start ? 1 : 0;
-            // Same shape as the apply kernel: a group lies in one read or straddles one boundary, and which read a
-            // base belongs to is a select on its index (also for the read's patch, if it has one).  Anything else
-            // -- a second boundary inside the group, the batch's last group -- takes the general loop.
-            const int bpos = end - g0 < 16 ? (int)(end - g0) : 16;
-            int rg2 = rg, second2 = second;
-            uint32_t pt2 = 0;
-            uint64_t end2 = end;
-            if (bpos < 16 && r + 1 < R.n_reads) {
-                rg2 = R.rg ? (int)R.rg[r + 1] : 0;
-                second2 = R.flags ? (R.flags[r + 1] & 1) : 0;
-                pt2 = patch ? patch[r + 1] : 0u;
-                end2 = R.offsets ? R.offsets[r + 2] : end + R.read_len;
-            }
-            const int c0 = (int)(g0 - start);
-            // read groups of this launch are [rg_base, rg_base + n_rgs); everything else belongs to another launch
-            const int lr1 = rg - P.rg_base, lr2 = rg2 - P.rg_base;
-            const bool mine1 = (unsigned)lr1 < (unsigned)P.n_rgs && rg < H.n_rg;
-            const bool mine2 = (unsigned)lr2 < (unsigned)P.n_rgs && rg2 < H.n_rg;
-            const bool one_boundary = bpos == 16 || (r + 1 < R.n_reads && end2 >= g0 + 16);
-            if (n == 16 && one_boundary && !mine1 && (bpos == 16 || !mine2)) {
-                starts += bpos < 16 ? 1 : 0;       // a group of other launches' read groups
-            } else if (n == 16 && one_boundary && c0 + bpos <= H.n_cycle && 16 - bpos <= H.n_cycle) {
-                const int pp1 = (pt >> 31) ? patch_at(pt) : -2, pp2 = (pt2 >> 31) ? patch_at(pt2) : -2;
-                if (pp1 >= 0 && pp1 == c0 - 1) { prev_b = (int)(pt & 3); prev_n = 0; }
-                starts += bpos < 16 ? 1 : 0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const bool in2 = i >= bpos;
-                    const int cyc = in2 ? i - bpos : c0 + i;
-                    int b = (int)((bw >> (2 * i)) & 3), nn = (int)((nw >> i) & 1);
-                    if (cyc == (in2 ? pp2 : pp1)) { b = (int)((in2 ? pt2 : pt) & 3); nn = 0; }
-                    const int q = qv[i];
-                    if (in2 ? mine2 : mine1)
-                        count(in2 ? lr2 : lr1, in2 ? rg2 : rg, q, in2 ? second2 : second, cyc, (int)((ew >> i) & 1u),
-                              cyc >= 1 && q >= minscore && !(nn | prev_n), (prev_b << 2) | b);
-                    prev_b = b;
-                    prev_n = nn;
-                }
-            } else {
-            // the read this group starts in may carry a patch on the base just before the group
-            if ((pt >> 31) && g0 > start && patch_at(pt) == (int)(g0 - 1 - start)) { prev_b = (int)(pt & 3); prev_n = 0; }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const uint64_t g = g0 + i;
-                if (i < n) {
-                    while (g >= end) {
-                        ++r; start = end;
-                        end = R.offsets ? R.offsets[r + 1] : end + R.read_len;
-                        rg = R.rg ? (int)R.rg[r] : 0;
-                        second = R.flags ? (R.flags[r] & 1) : 0;
-                        pt = patch ? patch[r] : 0u;
-                        if (end > start) ++starts;
-                    }
-                    const int cyc = (int)(g - start);
-                    int b = (int)((bw >> (2 * i)) & 3), nn = (int)((nw >> i) & 1);
-                    if ((pt >> 31) && patch_at(pt) == cyc) { b = (int)(pt & 3); nn = 0; }
-                    const int q = qv[i];
-                    const int lr = rg - P.rg_base;
-                    if ((unsigned)lr < (unsigned)P.n_rgs && rg < H.n_rg && cyc < H.n_cycle)
-                        count(lr, rg, q, second, cyc, (int)((ew >> i) & 1), cyc >= 1 && q >= minscore && !nn && !prev_n, (prev_b << 2) | b);
-                    prev_b = b;
-                    prev_n = nn;
-                }
-            }
-            }
-            // a read that began before this group and continues into it also counts once for this block
-            starts += g0 != start ? 1 : 0;
-        }
-        {
-            // reads touched by this wavefront (a lane touches at most 17): bit-sliced ballot sum, one LDS add per wave
-            const int s = g0 < R.n_bases ? starts : 0;
-            unsigned int tot = 0;
-#pragma unroll
-            for (int b = 0; b < 5; ++b) tot += (unsigned int)__popcll(__ballot((s >> b) & 1)) << b;
-            if ((threadIdx.x & 63) == 0 && tot) atomicAdd(l_reads, tot);
-        }
-        __syncthreads();
-        // a block-uniform decision: everyone reads the counter before anyone may add to it again (next iteration)
-        // (direct_cycles: only the 32-bit dinucleotide counters are in LDS, and a block adds at most 2^14 per iteration to one)
-        const bool flush = (direct ? (it & 0xFFFF) == 0xFFFF : *l_reads >= 40000u) || it + 1 == iters;
-        __syncthreads();
-        if (flush) {
-            for (int lr = 0; lr < P.n_rgs; ++lr) {
-                uint32_t *t = lds + lr * per_rg;
-                const int rg = P.rg_base + lr;
-                for (int w = threadIdx.x; w < cyc_words; w += blockDim.x) {
-                    const uint32_t v = t[w], ve = t[cyc_words + w];
-                    if (!v) continue;      // no total, no error
-                    t[w] = 0;
-                    t[cyc_words + w] = 0;
-                    for (int h = 0; h < 2; ++h) {
-                        const uint32_t cnt = (v >> (16 * h)) & 0xFFFFu, cne = (ve >> (16 * h)) & 0xFFFFu;
-                        if (!cnt) continue;
-                        const int idx = 2 * w + h;
-                        const int slot = idx % ccap, rest = idx / ccap;
-                        const int q = P.qof[rest % ns], s = rest / ns;
-                        const int c = cbase + (slot % (ccap >> 4)) * 16 + slot / (ccap >> 4);
-                        if (c < H.n_cycle) {
-                            atomicAdd(&H.cycle[cyc_index(H, rg, q, s, c) + 1], (unsigned long long)cnt);
-                            if (cne) atomicAdd(&H.cycle[cyc_index(H, rg, q, s, c)], (unsigned long long)cne);
-                        }
-                    }
-                }
-                for (int w = threadIdx.x; w < ns * 16; w += blockDim.x) {
-                    const uint32_t v = t[2 * cyc_words + w], ve = t[2 * cyc_words + ns * 16 + w];
-                    const uint64_t cell = ((uint64_t)rg * KBBQ_NQ + P.qof[w >> 4]) * 16 + (w & 15);
-                    if (v) { t[2 * cyc_words + w] = 0; atomicAdd(&H.dinuc[cell * 2 + 1], (unsigned long long)v); }
-                    if (ve) { t[2 * cyc_words + ns * 16 + w] = 0; atomicAdd(&H.dinuc[cell * 2], (unsigned long long)ve); }
-                }
-            }
-            if (threadIdx.x == 0) *l_reads = 0;
-            __syncthreads();
-        }
-    }
-}
-
-// ---- pass 3c, the common shape: uniform read length, one read group, one cycle window ------------------------
-// k_tally's general loop spends 1 700 VALU + 1 700 SALU instructions per 16 bases on bookkeeping that a batch of
-// equally long reads of one read group does not need (read boundaries from an offsets array, read-group slots,
-// cycle windows).  Here: the read of a 16-base group is one 64-bit multiply-high (inv_len = ceil(2^64 / read_len),
-// exact for the 32-bit base offsets of a batch), a group lies in one read or straddles one boundary (read_len >= 16)
-// and every cycle is in the table.  Same LDS tables (packed 16-bit counters, cycle slots permuted against bank
-// conflicts) and same result as k_tally.  MAP = false: the plan is the identity (slot = quality for the values below
-// n_slots: the usual FASTQ range), no slot lookup; MAP = true: slot from the plan's table in LDS.  A quality without a
-// slot goes to the histograms directly.
-template <bool MAP>
-__global__ void __launch_bounds__(1024) k_tally_uniform(ReadsDev R, HistDev H, const uint32_t *err_bits, const uint32_t *patch,
-                                                         int ccap, int minscore, unsigned long long inv_len, TallyPlan P) {
-    extern __shared__ uint32_t lds[];
-    const int ns = P.n_slots;
-    const int L = (int)R.read_len;
-    const int cyc_words = (2 * ccap * ns + 1) / 2, cstep = ccap >> 4;
-    uint32_t *t_err = lds + cyc_words, *t_di = lds + 2 * cyc_words, *t_die = t_di + ns * 16;
-    const int lds_words = 2 * cyc_words + 2 * ns * 16;
-    uint8_t *l_qslot = reinterpret_cast<uint8_t *>(lds + lds_words);
-    for (int i = threadIdx.x; i < lds_words; i += blockDim.x) lds[i] = 0;
-    if (MAP && threadIdx.x < 256) l_qslot[threadIdx.x] = P.qslot[threadIdx.x];
-    __syncthreads();
-    auto count = [&](int second, int q, int cyc, int er, bool dinuc_ok, int d) {
-        const int sl = MAP ? (int)l_qslot[q] : q;
-        if (MAP ? sl != 255 : sl < ns) {
-            const int idx = (second * ns + sl) * ccap + (cyc & 15) * cstep + (cyc >> 4);
-            const uint32_t one = 1u << (16 * (idx & 1));
-            atomicAdd(&lds[idx >> 1], one);
-            if (er) atomicAdd(&t_err[idx >> 1], one);
-            if (dinuc_ok) {
-                atomicAdd(&t_di[sl * 16 + d], 1u);
-                if (er) atomicAdd(&t_die[sl * 16 + d], 1u);
-            }
-        } else {
-            atomicAdd(&H.cycle[cyc_index(H, 0, q, second, cyc) + 1], 1ULL);
-            if (er) atomicAdd(&H.cycle[cyc_index(H, 0, q, second, cyc)], 1ULL);
-            if (dinuc_ok) {
-                atomicAdd(&H.dinuc[((uint64_t)q * 16 + d) * 2 + 1], 1ULL);
-                if (er) atomicAdd(&H.dinuc[((uint64_t)q * 16 + d) * 2], 1ULL);
-            }
-        }
-    };
-    auto flush = [&]() {
-        for (int w = threadIdx.x; w < cyc_words; w += blockDim.x) {
-            const uint32_t v = lds[w], ve = t_err[w];
-            if (!v) continue;
-            lds[w] = 0;
-            t_err[w] = 0;
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t cnt = (v >> (16 * h)) & 0xFFFFu, cne = (ve >> (16 * h)) & 0xFFFFu;
-                if (!cnt) continue;
-                const int idx = 2 * w + h;
-                const int slot = idx % ccap, rest = idx / ccap;
-                const int q = MAP ? (int)P.qof[rest % ns] : rest % ns, sec = rest / ns;
-                const int c = (slot % cstep) * 16 + slot / cstep;
-                if (c < H.n_cycle) {
-                    atomicAdd(&H.cycle[cyc_index(H, 0, q, sec, c) + 1], (unsigned long long)cnt);
-                    if (cne) atomicAdd(&H.cycle[cyc_index(H, 0, q, sec, c)], (unsigned long long)cne);
-                }
-            }
-        }
-        for (int w = threadIdx.x; w < ns * 16; w += blockDim.x) {
-            const uint32_t v = t_di[w], ve = t_die[w];
-            const uint64_t cell = (uint64_t)(MAP ? (int)P.qof[w >> 4] : (w >> 4)) * 16 + (w & 15);
-            if (v) { t_di[w] = 0; atomicAdd(&H.dinuc[cell * 2 + 1], (unsigned long long)v); }
-            if (ve) { t_die[w] = 0; atomicAdd(&H.dinuc[cell * 2], (unsigned long long)ve); }
-        }
-    };
-    const uint64_t n_groups = (R.n_bases + 15) / 16;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t iters = (n_groups + stride - 1) / stride;
-    // a read adds at most one to a 16-bit counter; a block touches at most 16384 / L + 2 reads per iteration
-    const uint64_t flush_every = max((uint64_t)1, (uint64_t)40000 / ((uint64_t)16384 / (uint64_t)L + 2));
-    for (uint64_t it = 0; it < iters; ++it) {
-        const uint64_t g0 = (it * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-        if (g0 + 16 <= R.n_bases) {
-            const uint32_t r = (uint32_t)__umul64hi((unsigned long long)g0, inv_len);
-            const int c0 = (int)(g0 - (uint64_t)r * (uint64_t)L);
-            const int bpos = L - c0 < 16 ? L - c0 : 16;      // first base of the next read inside the group
-            const uint4 qv4 = *reinterpret_cast<const uint4 *>(R.qual + g0);
-            uint8_t qv[16];
-            memcpy(qv, &qv4, 16);
-            const uint32_t bw = (uint32_t)(R.bases[g0 >> 5] >> ((g0 & 31) * 2));
-            const uint32_t nw = (uint32_t)(R.nmask[g0 >> 6] >> (g0 & 63)) & 0xFFFFu;
-            const uint32_t ew = (err_bits[g0 >> 5] >> (g0 & 31)) & 0xFFFFu;
-            int prev_b = 0, prev_n = 1;
-            if (g0 > 0) {
-                const uint64_t gp = g0 - 1;
-                prev_b = (int)((R.bases[gp >> 5] >> ((gp & 31) * 2)) & 3);
-                prev_n = (int)((R.nmask[gp >> 6] >> (gp & 63)) & 1);
-            }
-            const bool two = bpos < 16;
-            const bool mine1 = !R.rg || R.rg[r] == 0, mine2 = !two || !R.rg || R.rg[r + 1] == 0;
-            const int sec1 = R.flags ? (R.flags[r] & 1) : 0;
-            const int sec2 = two && R.flags ? (R.flags[r + 1] & 1) : 0;
-            const uint32_t pt1 = patch ? patch[r] : 0u, pt2 = two && patch ? patch[r + 1] : 0u;
-            const int pp1 = (pt1 >> 31) ? patch_at(pt1) : -2, pp2 = (pt2 >> 31) ? patch_at(pt2) : -2;
-            if (pp1 >= 0 && pp1 == c0 - 1) { prev_b = (int)(pt1 & 3); prev_n = 0; }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const bool in2 = i >= bpos;
-                const int cyc = c0 + i - (in2 ? L : 0);
-                int b = (int)((bw >> (2 * i)) & 3), nn = (int)((nw >> i) & 1);
-                if (cyc == (in2 ? pp2 : pp1)) { b = (int)((in2 ? pt2 : pt1) & 3); nn = 0; }
-                const int q = qv[i];
-                if (in2 ? mine2 : mine1)
-                    count(in2 ? sec2 : sec1, q, cyc, (int)((ew >> i) & 1u), cyc >= 1 && q >= minscore && !(nn | prev_n), (prev_b << 2) | b);
-                prev_b = b;
-                prev_n = nn;
-            }
-        } else if (g0 < R.n_bases) {
-            // the batch's last, partial group: base by base, everything looked up afresh
-            for (uint64_t g = g0; g < R.n_bases; ++g) {
-                const uint64_t r = g / (uint64_t)L;
-                const int cyc = (int)(g - r * (uint64_t)L);
-                const uint32_t pt = patch ? patch[r] : 0u;
-                const int pp = (pt >> 31) ? patch_at(pt) : -2;
-                auto base_at = [&](uint64_t x, int cx, int &bb, int &nb) {
-                    bb = (int)((R.bases[x >> 5] >> ((x & 31) * 2)) & 3);
-                    nb = (int)((R.nmask[x >> 6] >> (x & 63)) & 1);
-                    if (cx == pp) { bb = (int)(pt & 3); nb = 0; }
-                };
-                int b, nn, pb = 0, pn = 1;
-                base_at(g, cyc, b, nn);
-                if (cyc >= 1) base_at(g - 1, cyc - 1, pb, pn);
-                const int q = R.qual[g];
-                const int er = (int)((err_bits[g >> 5] >> (g & 31)) & 1u);
-                if (!R.rg || R.rg[r] == 0)
-                    count(R.flags ? (R.flags[r] & 1) : 0, q, cyc, er, cyc >= 1 && q >= minscore && !(nn | pn), (pb << 2) | b);
-            }
-        }
-        if ((it + 1) % flush_every == 0 || it + 1 == iters) {      // block-uniform
-            __syncthreads();
-            flush();
-            __syncthreads();
-        }
-    }
-}
-
-// quality values of a batch that was not seen by pass 2 (--fixed mode, pass 3 on its own): 256 bits, the same set k_infer leaves
-__global__ void __launch_bounds__(256) k_qpresence(const uint8_t *qual, uint64_t n_bases, uint32_t *qpresent) {
-    __shared__ uint32_t qseen[8];
-    if (threadIdx.x < 8) qseen[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_bases; i += (uint64_t)gridDim.x * blockDim.x)
-        qseen_note(qseen, qual[i]);
-    __syncthreads();
-    if (threadIdx.x < 8 && qseen[threadIdx.x]) atomicOr(&qpresent[threadIdx.x], qseen[threadIdx.x]);
-}
-
-// ---- pass 4: delta-Q apply -------------------------------------------------------
-// CReadData::recalibrate (readutils.cc:572-595).  One lane per 16 consecutive
-// bases of the batch: 16-byte quality load and store, 4-byte base load.
-struct DqDev {
-    const int16_t *base;   // [n_rg][256]  meanq + rgdq + qscoredq
-    const int8_t *cycle;   // [n_rg][256][2][n_cycle]
-    const int8_t *dinuc;   // [n_rg][256][16]
-    const uint8_t *qslot;  // [256] slot of a quality in the LDS tables (255 = it has no cycle / dinucleotide delta anywhere)
-    int n_rg, n_cycle, n_slots;
-};
-
-__global__ void __launch_bounds__(1024) k_recalibrate(ReadsDev R, DqDev D, uint8_t *out, int minqual, int vec_ok, int lds_rgs,
-                                                       const uint32_t *read_index, uint64_t base0, uint64_t base1) {
-    // The delta-Q tables of the first `lds_rgs` read groups sit in LDS, compacted over the quality axis: only the
-    // D.n_slots quality values that have a non-zero cycle or dinucleotide delta anywhere get a slot (D.qslot; a
-    // handful for binned qualities, so a dozen read groups fit), holding per (slot, second, cycle) one int16 with
-    // meanq + rg + q delta-Q + cycle delta-Q already summed and the int8 dinucleotide delta-Q; every other
-    // quality only needs its base value.  Two or three dependent LDS reads per base instead of three global ones.
-    extern __shared__ uint8_t l_tab[];
-    uint8_t *l_qslot = l_tab;                                   // [256]: slot of a quality, 255 = none
-    const int ns = D.n_slots;
-    const int cyc_cells = ns * 2 * D.n_cycle, di_bytes = ns * 16, base_bytes = KBBQ_NQ * 2;
-    const int cyc_bytes = 2 * cyc_cells;
-    const int per_rg = (cyc_bytes + di_bytes + base_bytes + 3) & ~3;
-    uint8_t *l_rg = l_tab + 256;
-    if (threadIdx.x < 256) l_qslot[threadIdx.x] = D.qslot[threadIdx.x];
-    __syncthreads();
-    for (int i = threadIdx.x; i < lds_rgs * KBBQ_NQ; i += blockDim.x) {
-        const int rg = i / KBBQ_NQ, q = i % KBBQ_NQ;
-        reinterpret_cast<int16_t *>(l_rg + (size_t)rg * per_rg + cyc_bytes + di_bytes)[q] = D.base[rg * KBBQ_NQ + q];
-        const int sl = l_qslot[q];
-        if (sl != 255) {
-            int16_t *tc = reinterpret_cast<int16_t *>(l_rg + (size_t)rg * per_rg) + sl * 2 * D.n_cycle;
-            const int8_t *src = D.cycle + ((size_t)rg * KBBQ_NQ + q) * 2 * D.n_cycle;
-            for (int c = 0; c < 2 * D.n_cycle; ++c) tc[c] = (int16_t)(D.base[rg * KBBQ_NQ + q] + src[c]);
-            for (int x = 0; x < 16; ++x) l_rg[(size_t)rg * per_rg + cyc_bytes + sl * 16 + x] = (uint8_t)D.dinuc[((size_t)rg * KBBQ_NQ + q) * 16 + x];
-        }
-    }
-    __syncthreads();
-    // persistent blocks: the table load above is paid once per block, not once per 4 KB of qualities
-    // (the launch covers the bases [base0, base1) of the batch: a host batch may arrive in pieces)
-    for (uint64_t g0 = base0 + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; g0 < base1;
-         g0 += (uint64_t)gridDim.x * blockDim.x * 16) {
-    // read containing g0
-    uint64_t r, start, end;
-    if (R.offsets) {
-        find_read(R, read_index, g0, r, start, end);
-    } else {
-        r = g0 / R.read_len;
-        start = r * R.read_len;
-        end = start + R.read_len;
-    }
-    const int n = (int)min((uint64_t)16, R.n_bases - g0);
-    uint8_t qv[16];
-    if (n == 16 && vec_ok) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(R.qual + g0);
-        memcpy(qv, &v, 16);
-    } else {
-        for (int i = 0; i < 16; ++i) qv[i] = i < n ? R.qual[g0 + i] : 0;
-    }
-    const uint32_t bw = (uint32_t)(R.bases[g0 >> 5] >> ((g0 & 31) * 2));
-    const uint32_t nw = (uint32_t)(R.nmask[g0 >> 6] >> (g0 & 63)) & 0xFFFFu;
-    int prev_b = 0, prev_n = 1;
-    if (g0 > 0) {
-        const uint64_t gp = g0 - 1;
-        prev_b = (int)((R.bases[gp >> 5] >> ((gp & 31) * 2)) & 3);
-        prev_n = (int)((R.nmask[gp >> 6] >> (gp & 63)) & 1);
-    }
-    int rg = R.rg ? (int)R.rg[r] : 0;
-    int second = R.flags ? (R.flags[r] & 1) : 0;
-    uint8_t res[16];
-    // A group of 16 bases lies in one read or straddles one boundary (reads of 16 bases or more): handled
-    // without a branch per base -- the read a base belongs to is a select on its index.  Everything else (a
-    // second boundary inside the group, a read group whose tables are not in LDS, the batch's last group)
-    // takes the general loop below.
-    const int bpos = end - g0 < 16 ? (int)(end - g0) : 16;      // first base of the next read inside the group
-    int rg2 = rg, second2 = second;
-    uint64_t end2 = end;
-    if (bpos < 16 && r + 1 < R.n_reads) {
-        rg2 = R.rg ? (int)R.rg[r + 1] : 0;
-        second2 = R.flags ? (R.flags[r + 1] & 1) : 0;
-        end2 = R.offsets ? R.offsets[r + 2] : end + R.read_len;
-    }
-    const int c0 = (int)(g0 - start);
-    const bool plain = n == 16 && rg < lds_rgs && rg2 < lds_rgs && (bpos == 16 || (r + 1 < R.n_reads && end2 >= g0 + 16)) &&
-                       c0 + bpos <= D.n_cycle && 16 - bpos <= D.n_cycle;
-    if (plain) {
-        const int16_t *ta = reinterpret_cast<const int16_t *>(l_rg + rg * per_rg) + second * D.n_cycle + c0;
-        const int16_t *tb = reinterpret_cast<const int16_t *>(l_rg + rg2 * per_rg) + second2 * D.n_cycle - bpos;
-        const int8_t *da = reinterpret_cast<const int8_t *>(l_rg + rg * per_rg + cyc_bytes);
-        const int8_t *db = reinterpret_cast<const int8_t *>(l_rg + rg2 * per_rg + cyc_bytes);
-        const int16_t *ba = reinterpret_cast<const int16_t *>(l_rg + rg * per_rg + cyc_bytes + di_bytes);
-        const int16_t *bb = reinterpret_cast<const int16_t *>(l_rg + rg2 * per_rg + cyc_bytes + di_bytes);
-        const int qstride = 2 * D.n_cycle;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const bool in2 = i >= bpos;
-            const int b = (int)((bw >> (2 * i)) & 3), nn = (int)((nw >> i) & 1);
-            const int q = qv[i];
-            int v = q;
-            if (q >= minqual) {
-                const int sl = l_qslot[q];
-                if (sl != 255) {
-                    v = (in2 ? tb : ta)[sl * qstride + i];
-                    const bool first = in2 ? i == bpos : c0 + i == 0;        // cycle 0 has no dinucleotide context
-                    if (!first && !(nn | prev_n)) v += (in2 ? db : da)[sl * 16 + ((prev_b << 2) | b)];
-                } else {
-                    v = (in2 ? bb : ba)[q];      // no cycle or dinucleotide delta anywhere for this quality
-                }
-            }
-            res[i] = (uint8_t)(v < 0 ? 0 : (v > KBBQ_MAXQ ? KBBQ_MAXQ : v));
-            prev_b = b;
-            prev_n = nn;
-        }
-    } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const uint64_t g = g0 + i;
-        if (i < n) {
-            while (g >= end) {
-                ++r; start = end;
-                end = R.offsets ? R.offsets[r + 1] : end + R.read_len;
-                rg = R.rg ? (int)R.rg[r] : 0;
-                second = R.flags ? (R.flags[r] & 1) : 0;
-            }
-        }
-        const int cyc = (int)(g - start);
-        const int b = (int)((bw >> (2 * i)) & 3), nn = (int)((nw >> i) & 1);
-        const int q = qv[i];
-        int v = q;
-        if (i < n && q >= minqual && rg < D.n_rg && cyc < D.n_cycle) {
-            const int cell = rg * KBBQ_NQ + q;
-            const bool use_di = cyc > 0 && !nn && !prev_n;
-            if (rg < lds_rgs) {
-                const uint8_t *t = l_rg + rg * per_rg;
-                const int sl = l_qslot[q];
-                if (sl != 255) {
-                    v = reinterpret_cast<const int16_t *>(t)[(sl * 2 + second) * D.n_cycle + cyc];
-                    if (use_di) v += (int8_t)t[cyc_bytes + sl * 16 + ((prev_b << 2) | b)];
-                } else {
-                    v = reinterpret_cast<const int16_t *>(t + cyc_bytes + di_bytes)[q];
-                }
-            } else {
-                v = D.base[cell] + D.cycle[((uint64_t)cell * 2 + second) * D.n_cycle + cyc];
-                if (use_di) v += D.dinuc[cell * 16 + ((prev_b << 2) | b)];
-            }
-        }
-        res[i] = (uint8_t)(v < 0 ? 0 : (v > KBBQ_MAXQ ? KBBQ_MAXQ : v));
-        prev_b = b;
-        prev_n = nn;
-    }
-    }
-    if (n == 16 && vec_ok) {
-        uint4 v;
-        memcpy(&v, res, 16);
-        *reinterpret_cast<uint4 *>(out + g0) = v;
-    } else {
-        for (int i = 0; i < n; ++i) out[g0 + i] = res[i];
-    }
-    }
-}
+#include "tally.h"            // pass 3c: k_rg_presence, k_tally, k_tally_uniform, k_qpresence
+#include "recalibrate.h"      // pass 4: k_recalibrate
 
 // ---- helpers ----------------------------------------------------------------------
 __global__ void k_or_words(uint64_t *dst, const uint64_t *src, uint64_t n) {

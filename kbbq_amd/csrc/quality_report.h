@@ -4,8 +4,8 @@
 // writes nothing but its tables.  Compiled into engine.hip alone.
 //
 // A lane takes 16 consecutive bases: one 16-byte load of either array when both are 16-byte aligned, byte loads otherwise,
-// nothing outside [base0, base1).  The read of the first base comes from the coarse read index (find_read) as in
-// k_recalibrate; the lane steps over read boundaries from there, so any number of boundaries may fall into a group.
+// nothing outside [base0, base1).  The read of the first base comes from the coarse read index (base_groups.h: group_read)
+// as in k_recalibrate; the lane steps over read boundaries from there, so any number of boundaries may fall into a group.
 //
 // Hot counters are in LDS, for the first `lds_rgs` read groups:
 //   transfer  [94][94] u32 per group: cell (in, min(out, 93)); a lane merges a run of equal (group, in, out) among its 16
@@ -213,13 +213,7 @@ k_quality_report(ReadsDev R, const uint8_t *out, ReportDev T, int vec_ok, int ld
         const uint64_t g0 = base0 + (((uint64_t)it * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x) * 16;
         if (g0 < base1) {
             uint64_t r, start, end;
-            if (R.offsets) {
-                find_read(R, read_index, g0, r, start, end);
-            } else {
-                r = g0 / R.read_len;
-                start = r * R.read_len;
-                end = start + R.read_len;
-            }
+            group_read(R, read_index, g0, r, start, end);
             const int n = (int)min((uint64_t)16, base1 - g0);
             uint8_t qi[16], qo[16];
             if (n == 16 && vec_ok) {
@@ -229,8 +223,8 @@ k_quality_report(ReadsDev R, const uint8_t *out, ReportDev T, int vec_ok, int ld
             } else {
                 for (int i = 0; i < 16; ++i) { qi[i] = i < n ? R.qual[g0 + i] : 0; qo[i] = i < n ? out[g0 + i] : 0; }
             }
-            int rg = R.rg ? (int)R.rg[r] : 0;
-            int second = R.flags ? (R.flags[r] & 1) : 0;
+            int rg, second;
+            read_fields(R, r, rg, second);
             // the run of equal (group, in, out) being gathered: key < 0 = none
             int run_key = -1, run_rg = 0;
             uint32_t run_len = 0;
@@ -241,12 +235,7 @@ k_quality_report(ReadsDev R, const uint8_t *out, ReportDev T, int vec_ok, int ld
             for (int i = 0; i < 16; ++i) {
                 if (i < n) {
                     const uint64_t g = g0 + i;
-                    while (g >= end) {      // (g < n_bases: a read that holds it exists)
-                        ++r; start = end;
-                        end = R.offsets ? R.offsets[r + 1] : end + R.read_len;
-                        rg = R.rg ? (int)R.rg[r] : 0;
-                        second = R.flags ? (R.flags[r] & 1) : 0;
-                    }
+                    while (g >= end) next_read(R, r, start, end, rg, second);      // (g < n_bases: a read that holds it exists)
                     const uint64_t cyc = g - start;
                     const int in = qi[i], o = qo[i], key = in << 8 | o;
                     if (key == run_key && rg == run_rg) {

@@ -1,10 +1,10 @@
 """Pass 3's tally (k_tally_uniform, k_tally) and pass 4's apply (k_recalibrate) against the plain references of
 tests/plain_ref.py, over the branches the oracle-sized parity inputs never reach: mid-loop flushes of the 16-bit LDS
 counters near their bound, mapped and identity quality plans, qualities without an LDS slot, read groups split over
-launches, cycle windows, unaligned quality / output pointers, delta-Q tables beyond the LDS and the clamps, and the
-range check of kbbq_set_dq.  Every comparison is exact.
+launches, cycle windows, unaligned quality / output pointers, delta-Q tables beyond the LDS and the clamps, every place
+a read boundary takes in a 16-base group, and the range check of kbbq_set_dq.  Every comparison is exact.
 
-Each case states the engine rule that sends it down its branch (engine_pass3.h, engine_pass4.h / kernels.h, cited) as a check of its
+Each case states the engine rule that sends it down its branch (engine_pass3.h, engine_pass4.h / tally.h, recalibrate.h, cited) as a check of its
 own, and test_engine_rules_are_the_ones_the_cases_rely_on fails loudly if one of those rules is no longer in the sources."""
 import ctypes
 import os
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import common
+import plain_report_ref
 from kbbq_amd import _lib, synth
 from kbbq_amd.engine import Engine, device_tensor
 from kbbq_amd.reads import ReadBatch, pack_bits
@@ -31,21 +32,27 @@ CSRC = os.path.join(common.ROOT, "kbbq_amd", "csrc")
 RULES = (
     ("engine_pass3.h", "const int ccap = std::min(((max_len + 31) / 32) * 32, 192);"),             # run_tally: cycles per window
     ("engine_pass3.h", "constexpr int kTallyMaxWindows = 24;"),                                    # above: direct cycle counts
-    ("engine_pass3.h", "const size_t per_slot = (direct_cycles ? 0 : (size_t)8 * ccap) + 128;"),
+    ("engine_pass3.h", "const size_t per_slot = (size_t)tally_rg_words(1, ccap, direct_cycles) * 4;"),
+    ("tally.h", "return direct ? 0 : (2 * ccap * ns + 1) / 2;"),                                    # tally_cycle_words: 4 * ccap bytes a slot
+    ("tally.h", "return 2 * tally_cycle_words(ns, ccap, direct) + 2 * ns * 16;"),                   # tally_rg_words: twice that + 128
+    ("tally.h", "return n_rgs * rg_words + (counts_reads ? 1 : 0);"),                               # tally_qslot_word
+    ("tally.h", "return (size_t)tally_qslot_word(n_rgs, rg_words, true) * 4 + 256 + 4;"),           # tally_lds_bytes: + 264
+    ("engine_pass3.h", "const size_t lds = tally_lds_bytes(per_launch, rg_words);"),
     ("engine_pass3.h", "plan_tally_slots(P, e->qpresent, (int)((152 * 1024 - 512) / per_slot), n_rg);"),
     ("engine_pass3.h", "if (top >= 0 && top + 1 <= max_slots && (n_rg <= 1 || 2 * distinct >= top + 1)) {"),
     ("engine_pass3.h", "const size_t budget = (size_t)n_rg * per_rg <= 70 * 1024 ? 70 * 1024 : 140 * 1024;"),
     ("engine_pass3.h", "const int blocks = (int)std::min<uint64_t>((groups + 1023) / 1024, lds <= 76 * 1024 ? 512 : 256);"),
     ("engine_pass3.h", "if (!e->opt.tally_general && !R.offsets && n_rg == 1 && n_windows == 1 && R.read_len >= 16 && (int)R.read_len <= ccap && R.n_bases < (1ULL << 32) && vec_ok &&"),
-    ("kernels.h", "const uint64_t flush_every = max((uint64_t)1, (uint64_t)40000 / ((uint64_t)16384 / (uint64_t)L + 2));"),
-    ("kernels.h", "const bool flush = (direct ? (it & 0xFFFF) == 0xFFFF : *l_reads >= 40000u) || it + 1 == iters;"),
-    ("engine_pass4.h", "const int per_rg = (D.n_slots * (4 * D.n_cycle + 16) + KBBQ_NQ * 2 + 3) & ~3;"),
+    ("tally.h", "const uint64_t flush_every = max((uint64_t)1, (uint64_t)40000 / ((uint64_t)16384 / (uint64_t)L + 2));"),
+    ("tally.h", "const bool flush = (tab.direct ? (it & 0xFFFF) == 0xFFFF : *tab.reads >= 40000u) || it + 1 == iters;"),
+    ("recalibrate.h", "return (n_slots * (4 * n_cycle + 16) + KBBQ_NQ * 2 + 3) & ~3;"),             # recal_rg_bytes
+    ("engine_pass4.h", "const int per_rg = recal_rg_bytes(D.n_slots, D.n_cycle);"),
     ("engine_pass4.h", "const int budget = per_rg + 256 <= 64 * 1024 ? 64 * 1024 - 256 : 152 * 1024 - 256;"),
     ("engine_pass4.h", "const int lds_rgs = D.n_slots > 255 ? 0 : std::max(0, std::min(D.n_rg, budget / per_rg));"),
 )
-UNIFORM_FLUSH_READS = 40000      # kernels.h, k_tally_uniform's flush_every
-GENERAL_FLUSH_READS = 40000      # kernels.h, k_tally's l_reads bound
-BASES_PER_BLOCK_ITER = 16384     # 1024 lanes x 16 bases (kernels.h: one lane per 16 bases)
+UNIFORM_FLUSH_READS = 40000      # tally.h, k_tally_uniform's flush_every
+GENERAL_FLUSH_READS = 40000      # tally.h, k_tally's reads-touched bound
+BASES_PER_BLOCK_ITER = 16384     # 1024 lanes x 16 bases (base_groups.h: one lane per 16 bases)
 # include/kbbq_engine.h: what kbbq_set_dq accepts
 DELTA_MIN, DELTA_MAX, BASE_MIN, BASE_MAX = -128, 127, -32640, 32640
 
@@ -491,7 +498,7 @@ BOUNDS = {      # name: (table, index, last accepted value, first refused value)
 def test_set_dq_bounds(bound, monkeypatch):
     """kbbq_set_dq takes every value the device tables hold exactly and refuses the first one past it (KBBQ_EINVAL, the
     table named), keeping the tables it had.  At the base bounds, a cycle delta of the same sign pushes the apply
-    kernel's int16 pre-sum (kernels.h, k_recalibrate's LDS tables) to exactly INT16_MAX / INT16_MIN."""
+    kernel's int16 pre-sum (recalibrate.h, k_recalibrate's LDS tables) to exactly INT16_MAX / INT16_MIN."""
     key, idx, ok, past = BOUNDS[bound]
     R, C = 1, 150
     rng = np.random.RandomState(len(bound))
@@ -518,6 +525,58 @@ def test_set_dq_bounds(bound, monkeypatch):
         assert ex.value.code == -22 and ("cycledq" if key == "cycle" else "dinucdq" if key == "dinuc" else "qdq") in str(ex.value)
         assert np.array_equal(e.recalibrate(host_batch(d, True)), want), "a refused table changed the engine's tables"
         assert np.array_equal(e.dq()[key], edge[key])
+
+
+# ---- every place a read boundary takes in a 16-base group, through the three passes that walk the batch by such groups -
+BOUNDARY_BATCHES = {"L16": 16, "L17": 17, "L23": 23, "L31": 31, "L33": 33, "ragged_0_20": None}
+BOUNDARY_READS = 67
+
+
+def first_boundaries(L, n_reads):
+    """Where the first read boundary falls inside the whole 16-base groups of a uniform batch (1..15; none: not in the set)."""
+    return {L - g0 % L for g0 in range(0, n_reads * L - 15, 16) if L - g0 % L < 16}
+
+
+@pytest.mark.parametrize("batch", list(BOUNDARY_BATCHES))
+def test_group_boundaries_through_tally_apply_and_report(batch, monkeypatch):
+    """A few thousand bases, two read groups, pair flags, 5 % N.  Uniform reads of 16, 17, 23, 31 and 33 bases: between them
+    the first boundary of a group takes every place 1..15, and for the odd lengths the batch ends in a partial group.  Ragged
+    reads whose lengths cycle 0..20: several boundaries in a group, empty reads.  Each batch through k_tally (two read
+    groups), k_recalibrate and behind it k_quality_report; the uniform ones, as one read group, also through
+    k_tally_uniform and through k_tally forced in its place.  Everything exact against the plain references."""
+    L = BOUNDARY_BATCHES[batch]
+    uniform = L is not None
+    assert set().union(*(first_boundaries(x, BOUNDARY_READS) for x in BOUNDARY_BATCHES.values() if x)) == set(range(1, 16))
+    rng = np.random.RandomState(1000 + (L or 0))
+    lens = np.full(BOUNDARY_READS, L) if uniform else np.arange(21 * 12) % 21
+    C = int(lens.max())
+    d = make_reads(rng, lens, QSETS["mapped"], n_frac=0.05, n_rg=2, paired=True)
+    nb = len(d["qual"])
+    assert (nb % 16 != 0) == (batch != "L16") and d["nflag"].any() and d["second"].any() and len(set(d["rg"])) == 2
+    err = (rng.rand(nb) < 0.3).astype(np.uint8)
+    dq = adversarial_dq(rng, 2, C, (6, 25, 37, 255))
+    assert recal_lds_rgs(4, C, 2) == 2 and not uniform_kernel_taken(C, 2, not uniform, True)
+    with engine(2, C, monkeypatch) as e:
+        e.tally(host_batch(d, uniform), pack_bits(err))
+        assert_cov_equal(e.covariates(), ref_of(d, err, 2, C, uniform), "k_tally, two read groups")
+        e.set_dq(dq)
+        e.report_enable(True)
+        e.report(reset=True)
+        got = e.recalibrate(host_batch(d, uniform))
+        rep = e.report(reset=True)
+    want = want_of(d, uniform, dq)
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, "k_recalibrate: %d bases differ, first at %s: %s != %s" % (len(bad), bad[:5], got[bad[:5]], want[bad[:5]])
+    assert (want != d["qual"]).any()
+    plain_report_ref.assert_same(rep, plain_report_ref.report(d["qual"], want, d["off"], d["rg"], d["second"], 2, C), nb)
+    if uniform:
+        one = dict(d, rg=np.zeros(BOUNDARY_READS, np.uint16))
+        want_cov = ref_of(one, err, 1, L, True)
+        for general in (False, True):
+            assert uniform_kernel_taken(L, 1, False, True, general) == (not general)
+            with engine(1, L, monkeypatch, general) as e:
+                e.tally(host_batch(one, True), pack_bits(err))
+                assert_cov_equal(e.covariates(), want_cov, "k_tally" if general else "k_tally_uniform")
 
 
 # ---- end to end at scale: tally -> model -> apply against tally_ref -> oracle model -> apply_ref ---------------------
